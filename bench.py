@@ -14,6 +14,9 @@ all-reduces over RCCL/xGMI through torch.distributed.
 
 Rank 0 prints ONE JSON line with the driver's contract plus "roofline" (dominant kernel), "kernels" (per-phase
 rooflines) and, at N = 1, "cpu_baseline" (the CPU oracle timed on this box's host cores on a bounded sample).
+The timed run must complete exactly K steps.  --dump-outputs DIR writes what it computed -- the scene after its last
+step and the error after every step -- as DIR/<name>.npy (float64), so that two builds can be compared on the same seeded
+inputs.
 """
 import argparse
 import json
@@ -54,7 +57,14 @@ def parse():
     ap.add_argument("--no-dense-probe", action="store_true")
     ap.add_argument("--rcs", choices=["chunks", "skyline", "dense"], default="chunks",
                     help="reduced-camera-system solver: exploit the covisibility skyline (exact) or treat it as dense")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed run computed (scene after its last step, error per step) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:  # max_iterations = 0 would mean "until convergence" to the library
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def algorithmic_bytes(N, M, O, ld, rcs_fill=1.0):
@@ -67,6 +77,26 @@ def algorithmic_bytes(N, M, O, ld, rcs_fill=1.0):
     k5 = O * 240 + N * (72 + 24 + 24) + M * 80
     k4_flops = n ** 3 / 3.0
     return dict(jacobian=k2, error=k1, schur=k3, backsub=k5, solve_flops=k4_flops, solve_bytes=n * n * 8)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` as out_dir/<name>.npy (float64), at most DUMP_LIMIT_BYTES in all.  Over the limit, the rows of
+    "points" are replaced by a fixed, seeded sample (their indices go to points_index.npy)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    budget = DUMP_LIMIT_BYTES - 128 * (len(arrays) + 1)  # less one .npy header per file
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        pts = arrays["points"]
+        keep = max(1, (budget - (total - pts.nbytes)) // (pts.itemsize * (pts.shape[1] + 1)))  # + its index
+        idx = np.sort(np.random.RandomState(0).choice(pts.shape[0], size=min(keep, pts.shape[0]), replace=False))
+        arrays["points"] = pts[idx]
+        arrays["points_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _oracle_scene(orc, sc):
@@ -408,6 +438,23 @@ def main():
         dt = float(t.item())
     err_final = ba.report.err_final
     err_initial = ba.report.err_initial
+    if iterations != args.steps:
+        raise SystemExit(f"bench.py: the timed run stopped after {iterations} of {args.steps} steps "
+                         f"(status '{ba.OptimizationStatusString()}')")
+    if args.dump_outputs:
+        # outside the timed region, before any later run overwrites the handle's scene: what a caller of the timed path
+        # receives (srk_ba_download_scene of the normalised scene it uploaded; at N > 1 the shards in landmark order)
+        got = ba.download(shard.copy(), revert_normalization=False)
+        points = got.points
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, points)
+            points = np.concatenate(parts)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {
+                "points": points, "cam_R": got.cam_R, "cam_T": got.cam_T,
+                "err_by_step": iter_log["err"],
+                "report": np.array([err_initial, err_final, iterations, attempts_timed], dtype=np.float64)})
 
     # outside the timed region: the first iteration alone (one attempt on the synthetic scenes), for reference
     torch.cuda.synchronize()

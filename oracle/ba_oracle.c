@@ -3,7 +3,7 @@
  *
  * Plain C99 restatement of whigg/surikatoko's Kanatani bundle adjustment.  Every function
  * cites the reference text it follows; citations are relative to
- * /root/reference/cpp_impl/suriko-engine/ ("BA" = src/bundle-adj-kanatani.cpp,
+ * the reference tree's cpp_impl/suriko-engine/ ("BA" = src/bundle-adj-kanatani.cpp,
  * "OG" = src/obs-geom.cpp).  Arithmetic is kept in the reference's evaluation order
  * (frames-outer / points-inner accumulation for frame blocks, points-outer for point
  * blocks) so that results agree with the reference's Python prototype to the last bits.

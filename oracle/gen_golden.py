@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Generate golden vectors for the BA hot path by importing the reference's Python prototype.
 
-TEST INFRASTRUCTURE.  Run in the build container only (needs /root/reference):
+TEST INFRASTRUCTURE.  Needs a checkout of the reference project; pass its py_proto directory:
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py <reference>/py_proto
 
 Writes tests/golden/pyproto_*.npz (inputs + the prototype's outputs).  Only data is
 committed; no reference source or bytecode travels.  The prototype functions used:
@@ -21,7 +21,9 @@ import sys
 
 import numpy as np
 
-REF = "/root/reference/py_proto"
+if len(sys.argv) != 2:
+    raise SystemExit("usage: gen_golden.py <reference>/py_proto")
+REF = sys.argv[1]
 sys.path.insert(0, REF)
 sys.dont_write_bytecode = True
 

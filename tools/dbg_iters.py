@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import surikatoko_amd as sa, torch
 spec = sa.CONFIGS["C3_1kcam_100kpt"]; sc = sa.generate_scene(spec)
 ba = sa.BundleAdjustmentKanatani(0); ba.set_profile(0)

@@ -1,5 +1,5 @@
-import time, numpy as np, sys
-sys.path.insert(0,'/root/repo')
+import os, time, numpy as np, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import surikatoko_amd as sa, torch
 spec = sa.SceneSpec(n_frames=29, grid_nx=40, grid_ny=30, vis_window=4, f0=1.0)
 sc0 = sa.generate_scene(spec)

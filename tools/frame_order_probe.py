@@ -3,7 +3,7 @@
 loop (20-frame tracks, 20 000 landmarks).  For each: srk_ba_set_frame_reordering 0 (the caller's numbering) against the
 default; 5 + 10 LM iterations, ms / iteration, chunks of the solver plan, skyline fill, the derivative kernel chosen."""
 import json, os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import surikatoko_amd as sa, torch
 

@@ -1,6 +1,6 @@
 """GPU box: derivative phase time by kernel selection (srk_ba_set_jacobian_mode) on C2, C2 with dropped observations, C1, C3."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import surikatoko_amd as sa, torch
 def scene(name, drop):
     sc = sa.config_scene(name)

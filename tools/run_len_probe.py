@@ -1,7 +1,7 @@
 """GPU box, development library (SRK_BA_LIBRARY=surikatoko_amd/libsrk_ba_dev.so): Schur phase and LM iteration time by the
 number of equal parts the Schur kernels' landmark runs are cut into (SRK_SCHUR_RUN_SPLIT; unset = the product's rule) on small and mid-size scenes."""
 import os, subprocess, sys, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SCENES = {  # name -> (config name | SceneSpec arguments, observations dropped)
     "C1_dino_standin": ("C1_dino_standin", 0), "C1_drop10": ("C1_dino_standin", 0.1),

@@ -1,7 +1,7 @@
 """GPU box: host + device time of srk_ba_upload_scene by stage (SRK_DEBUG trace), first and second upload of a handle."""
 import os, sys, time
 os.environ["SRK_DEBUG"] = "1"
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import surikatoko_amd as sa
 name = sys.argv[1] if len(sys.argv) > 1 else "C3_1kcam_100kpt"
 if name == "all_visible_60":
