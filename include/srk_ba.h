@@ -220,20 +220,20 @@ int srk_ba_phase_accept(srk_ba*);                           /* trial scene becom
 
 /* copies of device buffers for the parity tests, expanded to the oracle's layouts */
 enum srk_buffer {
-    SRK_BUF_GRAD = 0,        /* [3N + 10M] gradE */
+    SRK_BUF_GRAD = 0,        /* [3N + FV M] gradE; FV = srk_ba_frame_vars: 10, or 6 */
     SRK_BUF_POINT_BLOCKS,    /* [N][3][3] */
-    SRK_BUF_FRAME_BLOCKS,    /* [M][10][10] */
-    SRK_BUF_POINT_FRAME,     /* [O][3][10] */
-    SRK_BUF_RCS,             /* [10M][10M] padded reduced camera system (fixed variables: identity rows) */
-    SRK_BUF_RCS_RHS,         /* [10M] */
-    SRK_BUF_CORRECTIONS,     /* [3N + 10M] corrections with zero gaps */
+    SRK_BUF_FRAME_BLOCKS,    /* [M][FV][FV] */
+    SRK_BUF_POINT_FRAME,     /* [O][3][FV] */
+    SRK_BUF_RCS,             /* [FV M][FV M] padded reduced camera system (fixed variables: identity rows) */
+    SRK_BUF_RCS_RHS,         /* [FV M] */
+    SRK_BUF_CORRECTIONS,     /* [3N + FV M] corrections with zero gaps */
     SRK_BUF_POINTS,          /* [N][3] current (normalised) points */
     SRK_BUF_CAM_R,           /* [M][9] */
     SRK_BUF_CAM_T            /* [M][3] */
 };
 int64_t srk_ba_buffer_size(srk_ba*, int which);                 /* doubles; negative on error */
 int srk_ba_download(srk_ba*, int which, double* dst, int64_t count);
-/* selected rows of the padded reduced camera system (SRK_BUF_RCS is 12.8 GB at 4000 frames): dst[n_rows][10M], row
+/* selected rows of the padded reduced camera system (SRK_BUF_RCS is 12.8 GB at 4000 frames): dst[n_rows][FV M], row
  * rows[k] of the system with its columns <= the row filled (the lower triangle is authoritative), zeros right of it */
 int srk_ba_download_rcs_rows(srk_ba*, const int64_t* rows, int64_t n_rows, double* dst);
 
@@ -347,6 +347,24 @@ int srk_ba_set_storage_precision(srk_ba*, int f32);
  * blocks, the factorisation and everything else stay fp64.  Default 0 = the reference's fp64 arithmetic (the only
  * mode the parity tests and the benchmark's headline use). */
 int srk_ba_set_schur_precision(srk_ba*, int fp32);
+
+/* Calibrated bundle adjustment (an extension; the reference declares the intrinsic variable count as "0 if K is shared for
+ * all frames; 3 ...; 4", bundle-adj-kanatani.h:113-118, but only wires up 10, and ApplyCorrections adds the intrinsic
+ * corrections to a copy of K that is thrown away, bundle-adj-kanatani.cpp:2025-2033): on = 1 makes the intrinsics constants.
+ * Each frame then has the 6 pose variables [Tx Ty Tz Wx Wy Wz] (variables 4..9 of the default layout, same gauge), the
+ * reduced camera system is 6M wide, and every step is the Gauss-Newton / LM step of the problem actually solved -- the
+ * 10-variable damped system restricted to the pose and point variables.  K is never changed.  Takes effect at the next
+ * upload (srk_ba_compute_inplace included); the staged API and the downloads then use the compact layout: SRK_BUF_GRAD and
+ * SRK_BUF_CORRECTIONS [3N + 6M], SRK_BUF_FRAME_BLOCKS [M][6][6], SRK_BUF_POINT_FRAME [O][3][6], SRK_BUF_RCS [6M][6M],
+ * SRK_BUF_RCS_RHS [6M], srk_ba_download_rcs_rows rows of 6M.  Refused with SRK_E_ARGS (and a srk_ba_last_error text) by
+ * whichever call comes second: deterministic mode, f32 storage, fp32 Schur accumulation, more than one rank.  Default 0. */
+int srk_ba_set_fixed_intrinsics(srk_ba*, int on);
+/* variables per frame: 6 with fixed intrinsics, else 10 (of the uploaded scene; before an upload, of the next one) */
+int srk_ba_frame_vars(srk_ba*);
+/* landmarks of the uploaded scene whose Schur terms take the per-landmark kernel (fp64 atomics) instead of the run-based
+ * kernels: with fixed intrinsics every landmark outside the runs of <= 20 frames k_schur_mm takes (wider runs, long tracks);
+ * otherwise the tracks too long for the long-track kernel.  0 on the circle-grid bench scenes; negative without a scene. */
+int64_t srk_ba_schur_fallback_landmarks(srk_ba*);
 
 /* device-time instrumentation of srk_ba_optimize / srk_ba_compute_inplace: 0 = none (default; report.ms_* stay 0
  * except ms_total), 1 = one HIP event pair per phase (fills report.ms_*), 2 = additionally event pairs around

@@ -149,7 +149,15 @@ public:
 
     size_t PointsCount() const { return points_count_; }
     size_t FramesCount() const { return frames_count_; }
-    size_t VarsCount() const { return 3 * points_count_ + 10 * frames_count_; }
+    /// EXTENSION (the reference class has no such method): calibrated bundle adjustment from the next ComputeInplace on --
+    /// the intrinsics are constants and each frame has the 6 pose variables (srk_ba_set_fixed_intrinsics,
+    /// bundle-adj-kanatani.h:113-118).  Throws std::invalid_argument where the library refuses the combination.
+    void SetFixedIntrinsics(bool on) {
+        int rc = srk_ba_set_fixed_intrinsics(h_, on ? 1 : 0);
+        if (rc < 0) Raise(rc);
+    }
+
+    size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
     const srk_ba_report& Report() const { return report_; }

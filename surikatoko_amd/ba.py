@@ -256,7 +256,7 @@ class BundleAdjustmentKanatani:
         return self._scene.M
 
     def VarsCount(self):
-        return 3 * self._scene.N + 10 * self._scene.M
+        return 3 * self._scene.N + self.frame_vars() * self._scene.M
 
     def NormalizedVarsCount(self):
         return self.VarsCount() - 7
@@ -371,6 +371,26 @@ class BundleAdjustmentKanatani:
         """W stored as float (next upload); arithmetic stays fp64 -- see include/srk_ba.h"""
         self._raise(self._lib.srk_ba_set_storage_precision(C.c_void_p(self._h), C.c_int(int(bool(f32)))))
 
+    def set_fixed_intrinsics(self, on=True):
+        """Calibrated BA (next upload): the intrinsics are constants, each frame has the 6 pose variables [Tx Ty Tz Wx Wy Wz]
+        and the reduced camera system is 6M wide -- see include/srk_ba.h.  Not with deterministic mode, f32 storage, fp32
+        Schur sums or more than one rank (ValueError)."""
+        self._raise(self._lib.srk_ba_set_fixed_intrinsics(C.c_void_p(self._h), C.c_int(int(bool(on)))))
+
+    def frame_vars(self):
+        """variables per frame of the uploaded scene (before an upload: of the next one): 10, or 6 with fixed intrinsics"""
+        n = int(self._lib.srk_ba_frame_vars(C.c_void_p(self._h)))
+        self._raise(n)
+        return n
+
+    def schur_fallback_landmarks(self):
+        """landmarks of the uploaded scene that take the per-landmark Schur kernel (srk_ba_schur_fallback_landmarks)"""
+        fn = self._lib.srk_ba_schur_fallback_landmarks
+        fn.restype = C.c_int64
+        n = int(fn(C.c_void_p(self._h)))
+        self._raise(n)
+        return n
+
     def set_schur_precision(self, fp32=False):
         """Opt-in mixed precision: fp32 run sums in the grouped Schur kernel (everything else stays fp64)."""
         self._raise(self._lib.srk_ba_set_schur_precision(C.c_void_p(self._h), C.c_int(int(bool(fp32)))))
@@ -455,6 +475,7 @@ class BundleAdjustmentKanatani:
         self._raise(self._lib.srk_ba_phase_accept(C.c_void_p(self._h)))
 
     def buffer(self, which):
+        """flat download of a staged buffer; its layout follows frame_vars() (include/srk_ba.h SRK_BUF_*)"""
         n = self._lib.srk_ba_buffer_size(C.c_void_p(self._h), int(which))
         if n < 0:
             self._raise(int(n))
@@ -463,9 +484,9 @@ class BundleAdjustmentKanatani:
         return out
 
     def rcs_rows(self, rows):
-        """rows of the padded reduced camera system (full frame-variable indexing, columns <= row filled)"""
+        """rows of the padded reduced camera system (full frame-variable indexing, columns <= row filled); frame_vars() * M wide"""
         rows = np.ascontiguousarray(rows, dtype=np.int64)
-        out = np.zeros((len(rows), 10 * self._scene.M))
+        out = np.zeros((len(rows), self.frame_vars() * self._scene.M))
         self._raise(self._lib.srk_ba_download_rcs_rows(C.c_void_p(self._h), rows.ctypes.data_as(C.c_void_p),
                                                        C.c_int64(len(rows)), _p(out)))
         return out

@@ -67,6 +67,8 @@ struct srk_ba {
     std::vector<int32_t> frame_order_given; // srk_ba_set_frame_order: the numbering to use (several ranks: the same on every rank)
     bool frame_order_supplied = false;      // the uploaded scene uses frame_order_given
     DevBuf grp_first, grp_count, grp_nf, grp_frames, obs_slot, pt_mask, gen_list, wg_jmin;
+    DevBuf cal_list;      // fixed intrinsics: the landmarks outside the runs k_schur_mm takes (per-landmark kernel)
+    int64_t n_cal_list = 0;
     // long tracks (more than SRK_GRP_MAXNF_HOST frames): runs over frame-block pairs, k_schur_long
     DevBuf lg_item, lg_np, lg_nf, lg_pts, lg_frames, lg_obs_off, lg_obs;
     int64_t n_long_items = 0, n_long_runs = 0;
@@ -166,6 +168,7 @@ struct srk_ba {
     std::vector<hipEvent_t> chol_ev;
     bool schur_fp32 = false; // opt-in mixed precision: fp32 run sums in the grouped Schur kernel
     bool store_f32 = false;  // opt-in: the point-frame blocks W are STORED as float (next upload); arithmetic stays fp64
+    bool fixed_k = false;    // opt-in: calibrated BA, six pose variables per frame (next upload; srk_ba_set_fixed_intrinsics)
     int profile_level = 0; // 0 = no events, 1 = phase events (report.ms_*), 2 = + event pairs around the MFMA updates
     bool chol_fused = true; // the solve's outer steps as one launch each (k_step256); srk_ba_set_solver_fusion
     // what the caller asked for.  A hand-off timeout switches chol_fused off for the rest of that call; the next upload /
@@ -352,7 +355,7 @@ void srk_ba_destroy(srk_ba* h)
     DevBuf* all[] = { &h->K, &h->pts0, &h->camR0, &h->camT0, &h->row_ptr,
                       &h->obs_frame, &h->obs_pt, &h->obs_uv, &h->col_ptr, &h->fobs_pt, &h->fobs_uv, &h->W, &h->Vg, &h->Ug,
                       &h->scratch, &h->grp_first, &h->grp_count, &h->grp_nf, &h->grp_frames, &h->obs_slot, &h->pt_mask,
-                      &h->gen_list, &h->env_col, &h->env_off, &h->wg_jmin, &h->band_col, &h->band_off,
+                      &h->gen_list, &h->cal_list, &h->env_col, &h->env_off, &h->wg_jmin, &h->band_col, &h->band_off,
                       &h->dj_ptr, &h->dj_ent, &h->dj_stage, &h->ds_pair_ptr, &h->ds_pair_fa, &h->ds_pair_fb, &h->ds_pair_ent, &h->ds_f_ptr, &h->ds_f_ent,
                       &h->jd_nf, &h->jd_frames, &h->jd_mask,
                       &h->jr_first, &h->jr_count, &h->jr_jmin, &h->jr_group, &h->lg_item, &h->lg_np, &h->lg_nf, &h->lg_pts, &h->lg_frames,
@@ -415,9 +418,28 @@ static bool exchange_after_reordered_upload(srk_ba* h, int world_size)
     return true;
 }
 
+// fixed intrinsics (srk_ba_set_fixed_intrinsics) are built for one rank, fp64 storage and fp64 Schur sums, not deterministic
+// mode: the combination is refused by whichever call makes it (a setter, or the upload).  Returns the text, or NULL when fine.
+static const char* fixed_k_conflict(bool fixed_k, bool deterministic, bool store_f32, bool schur_fp32, int world)
+{
+    if (!fixed_k) return nullptr;
+    if (deterministic) return "fixed intrinsics: not available in deterministic mode";
+    if (store_f32) return "fixed intrinsics: not available with f32 storage of the point-frame blocks";
+    if (schur_fp32) return "fixed intrinsics: not available with fp32 Schur accumulation";
+    if (world > 1) return "fixed intrinsics: not available with more than one rank";
+    return nullptr;
+}
+static bool refuse_fixed_k(srk_ba* h, bool fixed_k, bool deterministic, bool store_f32, bool schur_fp32, int world)
+{
+    const char* e = fixed_k_conflict(fixed_k, deterministic, store_f32, schur_fp32, world);
+    if (e) h->last_error = e;
+    return e != nullptr;
+}
+
 int srk_ba_set_allreduce(srk_ba* h, srk_allreduce_fn fn, void* ctx, int rank, int world_size)
 {
     if (!h || world_size < 1 || rank < 0 || rank >= world_size) return SRK_E_ARGS;
+    if (refuse_fixed_k(h, h->fixed_k, h->deterministic, h->store_f32, h->schur_fp32, world_size)) return SRK_E_ARGS;
     if (exchange_after_reordered_upload(h, world_size)) return SRK_E_STATE;
     // either exchange replaces the other: exchange() prefers a communicator, so a callback set after srk_ba_rccl_init
     // would never be called unless the communicators are detached here
@@ -449,6 +471,10 @@ int srk_ba_rccl_get_unique_id(void* id128)
 }
 static int rccl_attach(srk_ba* h, ncclComm_t comm, bool owned, int rank, int world_size)
 {
+    if (refuse_fixed_k(h, h->fixed_k, h->deterministic, h->store_f32, h->schur_fp32, world_size)) {
+        if (owned) rccl().CommDestroy(comm);
+        return SRK_E_ARGS;
+    }
     if (exchange_after_reordered_upload(h, world_size)) {
         if (owned) rccl().CommDestroy(comm);
         return SRK_E_STATE;
@@ -726,7 +752,7 @@ static int build_chunk_plan(srk_ba* h)
     // the same skyline as the plan in place was built for (a scene uploaded again, the next call of a caller that adjusts the
     // same tracks): keep plan and buffers -- freeing and allocating them again costs ~9 ms a slot at 1000 frames -- and
     // bring the buffers that must be zero outside what a solve writes back to zero
-    std::vector<int64_t> sig = { d.ld, h->use_envelope ? 1 : 0, h->use_chunks ? 1 : 0 };
+    std::vector<int64_t> sig = { d.ld, d.fv, h->use_envelope ? 1 : 0, h->use_chunks ? 1 : 0 };
     sig.insert(sig.end(), h->min_cv.begin(), h->min_cv.end());
     if (!h->A->plan_sig.empty() && sig == h->A->plan_sig) {
         for (size_t i = 0; i < h->A->plan_bufs.size(); ++i)
@@ -742,7 +768,7 @@ static int build_chunk_plan(srk_ba* h)
     h->A->plan_children.clear();
     if (!h->use_envelope || !h->use_chunks) return SRK_OK;
     int64_t maxdist = 0;
-    for (int32_t j = 0; j < d.M; ++j) maxdist = std::max<int64_t>(maxdist, 10 * (int64_t)(j - h->min_cv[(size_t)j]) + 9);
+    for (int32_t j = 0; j < d.M; ++j) maxdist = std::max<int64_t>(maxdist, d.fv * (int64_t)(j - h->min_cv[(size_t)j]) + d.fv - 1);
     // separators at least one bandwidth wide, in units of the 256-column outer panel (k_bwd_border stages 2 sepw values)
     const int64_t sepw = (maxdist + SRK_CHOL_NB - 1) / SRK_CHOL_NB * SRK_CHOL_NB;
     if (sepw > SRK_MAX_SEPW) return SRK_OK;
@@ -762,7 +788,7 @@ static int build_envelope(srk_ba* h)
         int64_t r0 = 128 * t, r1 = 128 * t + 127;
         int64_t fc = r0; // padding rows and the diagonal itself
         if (h->use_envelope) {
-            for (int64_t j = r0 / 10; j <= r1 / 10 && j < d.M; ++j) fc = std::min<int64_t>(fc, 10 * (int64_t)h->min_cv[(size_t)j]);
+            for (int64_t j = r0 / d.fv; j <= r1 / d.fv && j < d.M; ++j) fc = std::min<int64_t>(fc, d.fv * (int64_t)h->min_cv[(size_t)j]);
         } else {
             fc = 0;
         }
@@ -793,7 +819,7 @@ static int build_envelope(srk_ba* h)
         std::vector<int64_t> bc((size_t)d.ld), bo((size_t)d.ld + 1, 0);
         for (int64_t r = 0; r < d.ld; ++r) {
             int64_t c0 = r; // padding rows: the diagonal only
-            if (r < 10 * (int64_t)d.M) c0 = h->use_envelope ? 10 * (int64_t)h->min_cv[(size_t)(r / 10)] : 0;
+            if (r < d.fv * (int64_t)d.M) c0 = h->use_envelope ? d.fv * (int64_t)h->min_cv[(size_t)(r / d.fv)] : 0;
             bc[(size_t)r] = c0;
             bo[(size_t)r + 1] = bo[(size_t)r] + (r - c0 + 1);
         }
@@ -986,6 +1012,7 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     };
     int rc = validate_scene(h, f0, N, pts_in, M, cam_R_in, cam_T_in, K_in, row_ptr, obs_frame, obs_uv);
     if (rc != SRK_OK) return rc;
+    if (refuse_fixed_k(h, h->fixed_k, h->deterministic, h->store_f32, h->schur_fp32, h->world)) return SRK_E_ARGS;
     rearm_fusion(h);
     stage("validate");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1344,7 +1371,8 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     if (d.Os == 0) d.Os = 64;
     d.Ns = ((N + 63) / 64) * 64;
     if (d.Ns == 0) d.Ns = 64;
-    d.ld = ((10 * (int64_t)M + SRK_CHOL_NB - 1) / SRK_CHOL_NB) * SRK_CHOL_NB;
+    d.fv = h->fixed_k ? 6 : 10;
+    d.ld = ((d.fv * (int64_t)M + SRK_CHOL_NB - 1) / SRK_CHOL_NB) * SRK_CHOL_NB;
     d.comp = 1;
     d.g0 = g0;
     d.g1 = g1;
@@ -1652,7 +1680,7 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     ALLOC(h->fobs_uv, 8 * fobs_uv.size());
     ALLOC(h->W, (d.w_f32 ? 4 : 8) * SRK_WF_PLANES * d.Os); // the 21 rank-2 factors of every point-frame block, fp64 or (opt-in) float
     ALLOC(h->Vg, 8 * 9 * d.Ns);
-    ALLOC(h->Ug, 8 * SRK_UG * (int64_t)M);
+    ALLOC(h->Ug, 8 * SRK_UGS(d.fv) * (int64_t)M); // the frame sums: 65 a frame, 27 with fixed intrinsics
     select_attempt(h, 0);
     for (int sl = 0; sl < SRK_SLOTS; ++sl) {
         srk_ba::Attempt& a = h->att[sl];
@@ -1680,6 +1708,19 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         a.sync.flags = P<unsigned>(a.sync_flags);
         a.sync.fused = h->chol_fused;
     }
+    // fixed intrinsics: k_schur_mm sums the runs of at most SRK_WS_NF_HOST frames on 6-wide blocks; every other landmark (wider
+    // runs, long tracks, the generic list) takes the per-landmark kernel
+    std::vector<int32_t> cal_list;
+    if (d.fv == 6) {
+        std::vector<char> in_mm((size_t)N, 0);
+        for (size_t r = 0; r < grp_first.size(); ++r)
+            if (std::abs(grp_nf[r]) <= SRK_WS_NF_HOST)
+                for (int32_t k = 0; k < grp_count[r]; ++k) in_mm[(size_t)(grp_first[r] + k)] = 1;
+        for (int64_t i = 0; i < N; ++i)
+            if (!in_mm[(size_t)i] && rp[(size_t)i + 1] > rp[(size_t)i]) cal_list.push_back((int32_t)i);
+    }
+    h->n_cal_list = (int64_t)cal_list.size();
+    ALLOC(h->cal_list, 4 * cal_list.size());
     ALLOC(h->grp_first, 4 * grp_first.size());
     ALLOC(h->grp_count, 4 * grp_count.size());
     ALLOC(h->grp_nf, 4 * grp_nf.size());
@@ -1760,6 +1801,7 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     H2D(h->obs_slot, obs_slot.data(), obs_slot.size());
     H2D(h->pt_mask, pt_mask.data(), 4 * pt_mask.size());
     H2D(h->gen_list, gen_list.data(), 4 * gen_list.size());
+    H2D(h->cal_list, cal_list.data(), 4 * cal_list.size());
     H2D(h->lg_item, lg_item.data(), 4 * lg_item.size());
     H2D(h->lg_np, lg_np.data(), 4 * lg_np.size());
     H2D(h->lg_nf, lg_nf.data(), 4 * lg_nf.size());
@@ -2019,7 +2061,7 @@ static int phase_derivatives(srk_ba* h)
     hipStream_t s = h->stream;
     int c = h->cur;
     HIPCHK(h, hipMemsetAsync(h->Vg.p, 0, 8 * 9 * d.Ns, s));
-    HIPCHK(h, hipMemsetAsync(h->Ug.p, 0, 8 * SRK_UG * (int64_t)d.M, s));
+    HIPCHK(h, hipMemsetAsync(h->Ug.p, 0, 8 * SRK_UGS(d.fv) * (int64_t)d.M, s));
     if (h->profile_level >= 1) HIPCHK(h, hipEventRecord(h->ev[12], s));
     const SrkDetJac detj{ P<double>(h->dj_stage), P<int32_t>(h->dj_ptr), P<int32_t>(h->dj_ent) };
     if (h->jac_runs) {
@@ -2080,16 +2122,28 @@ static int phase_schur(srk_ba* h, double c, bool local_only)
     srk_launch_env_zero(s, d.ld, P<int64_t>(h->env_col), P<double>(h->A->S), P<double>(h->A->rhs), P<int32_t>(h->A->irr)); // S band, rhs, hand-back counter
     const SrkDetSchur dets{ P<double>(h->A->det_stage), P<double>(h->A->det_rhs), P<int32_t>(h->ds_pair_ptr), P<int32_t>(h->ds_pair_fa),
                             P<int32_t>(h->ds_pair_fb), P<int32_t>(h->ds_pair_ent), h->ds_n_pairs, P<int32_t>(h->ds_f_ptr), P<int32_t>(h->ds_f_ent) };
-    srk_launch_schur_grouped(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_pt), P<uint8_t>(h->obs_slot),
-                             P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(h->A->S),
-                             P<double>(h->A->rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
-                             P<int32_t>(h->grp_frames), h->n_groups, h->n_groups_wide, h->n_groups_mid, h->schur_fp32 ? 1 : 0,
-                             P<int32_t>(h->A->irr), h->n_mm_uniform, h->n_mm_ragged, h->det_active ? &dets : nullptr);
-    srk_launch_schur_long(s, d, c, P<double>(h->W), P<double>(h->Vg), P<double>(h->A->S), P<double>(h->A->rhs),
-                          P<int32_t>(h->lg_item), h->n_long_items, P<int32_t>(h->lg_np), P<int32_t>(h->lg_nf), P<int32_t>(h->lg_pts),
-                          P<int32_t>(h->lg_frames), P<int64_t>(h->lg_obs_off), P<int32_t>(h->lg_obs), h->long_fb);
-    srk_launch_schur(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg),
-                     P<double>(h->A->S), P<double>(h->A->rhs), P<int32_t>(h->gen_list), h->n_generic);
+    if (d.fv == 6) {
+        // fixed intrinsics: the runs of at most SRK_WS_NF_HOST frames through k_schur_mm on 6-wide blocks, every other landmark
+        // through the per-landmark kernel
+        srk_launch_schur_grouped(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_pt), P<uint8_t>(h->obs_slot),
+                                 P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(h->A->S),
+                                 P<double>(h->A->rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
+                                 P<int32_t>(h->grp_frames), h->n_groups, h->n_groups_wide, h->n_groups_mid, 0,
+                                 P<int32_t>(h->A->irr), h->n_mm_uniform, h->n_mm_ragged, nullptr);
+        srk_launch_schur(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg),
+                         P<double>(h->A->S), P<double>(h->A->rhs), P<int32_t>(h->cal_list), h->n_cal_list);
+    } else {
+        srk_launch_schur_grouped(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_pt), P<uint8_t>(h->obs_slot),
+                                 P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(h->A->S),
+                                 P<double>(h->A->rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
+                                 P<int32_t>(h->grp_frames), h->n_groups, h->n_groups_wide, h->n_groups_mid, h->schur_fp32 ? 1 : 0,
+                                 P<int32_t>(h->A->irr), h->n_mm_uniform, h->n_mm_ragged, h->det_active ? &dets : nullptr);
+        srk_launch_schur_long(s, d, c, P<double>(h->W), P<double>(h->Vg), P<double>(h->A->S), P<double>(h->A->rhs),
+                              P<int32_t>(h->lg_item), h->n_long_items, P<int32_t>(h->lg_np), P<int32_t>(h->lg_nf), P<int32_t>(h->lg_pts),
+                              P<int32_t>(h->lg_frames), P<int64_t>(h->lg_obs_off), P<int32_t>(h->lg_obs), h->long_fb);
+        srk_launch_schur(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg),
+                         P<double>(h->A->S), P<double>(h->A->rhs), P<int32_t>(h->gen_list), h->n_generic);
+    }
     HIPCHK(h, hipGetLastError());
     // G (frame blocks, damped) and the frame gradients are linear in this rank's landmarks as well, so they are added
     // before the exchange; the identity diagonal of fixed / padding variables comes from rank 0 alone
@@ -2115,7 +2169,7 @@ static void launch_solve(srk_ba* h, SrkSolveProf* prof)
                                P<int64_t>(h->env_col), P<int>(h->A->info), prof, &h->A->sync);
     else
         srk_chol_solve(h->stream, d.ld, P<double>(h->A->S), P<double>(h->A->rhs), P<double>(h->A->wy), P<double>(h->A->dc),
-                       P<int>(h->A->info), h->row_end_h.data(), h->col_begin_h.data(), P<double>(h->A->dinv), prof, &h->A->sync, 10 * (int64_t)d.M);
+                       P<int>(h->A->info), h->row_end_h.data(), h->col_begin_h.data(), P<double>(h->A->dinv), prof, &h->A->sync, d.fv * (int64_t)d.M);
 }
 
 static int phase_solve(srk_ba* h, bool profile)
@@ -2164,7 +2218,7 @@ static int phase_cam_apply(srk_ba* h)
 {
     int cur = h->cur, tr = h->A->trial;
     srk_launch_cam_apply(h->stream, h->d.M, P<double>(h->camR[cur]), P<double>(h->camT[cur]), P<double>(h->A->dc),
-                         P<double>(h->camR[tr]), P<double>(h->camT[tr]), P<double>(h->K), h->f0, P<double>(h->cam[tr]));
+                         P<double>(h->camR[tr]), P<double>(h->camT[tr]), P<double>(h->K), h->f0, P<double>(h->cam[tr]), h->d.fv);
     HIPCHK(h, hipGetLastError());
     return SRK_OK;
 }
@@ -2757,6 +2811,7 @@ static int score_scene(srk_ba* h, double f0, int64_t N, const double* pts, int32
     for (int32_t j = 0; j < M; ++j) std::memcpy(&Kexp[9 * (size_t)j], shared_k ? K : K + 9 * (int64_t)j, 72);
     SrkDims d{};
     d.O = O;
+    d.fv = 10;
     const int32_t np = srk_error_partials(d);
     struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
         { &h->sc_pts, pts, (size_t)(24 * N) },          { &h->sc_R, cam_R, (size_t)(72 * (int64_t)M) },
@@ -3008,13 +3063,13 @@ int64_t srk_ba_buffer_size(srk_ba* h, int which)
     if (!h || !h->have_scene) return SRK_E_STATE;
     const SrkDims& d = h->d;
     switch (which) {
-    case SRK_BUF_GRAD: return 3 * d.N + 10 * (int64_t)d.M;
+    case SRK_BUF_GRAD: return 3 * d.N + d.fv * (int64_t)d.M;
     case SRK_BUF_POINT_BLOCKS: return 9 * d.N;
-    case SRK_BUF_FRAME_BLOCKS: return 100 * (int64_t)d.M;
-    case SRK_BUF_POINT_FRAME: return 30 * d.O;
-    case SRK_BUF_RCS: return 100 * (int64_t)d.M * d.M;
-    case SRK_BUF_RCS_RHS: return 10 * (int64_t)d.M;
-    case SRK_BUF_CORRECTIONS: return 3 * d.N + 10 * (int64_t)d.M;
+    case SRK_BUF_FRAME_BLOCKS: return d.fv * d.fv * (int64_t)d.M;
+    case SRK_BUF_POINT_FRAME: return 3 * d.fv * d.O;
+    case SRK_BUF_RCS: return d.fv * d.fv * (int64_t)d.M * d.M;
+    case SRK_BUF_RCS_RHS: return d.fv * (int64_t)d.M;
+    case SRK_BUF_CORRECTIONS: return 3 * d.N + d.fv * (int64_t)d.M;
     case SRK_BUF_POINTS: return 3 * d.N;
     case SRK_BUF_CAM_R: return 9 * (int64_t)d.M;
     case SRK_BUF_CAM_T: return 3 * (int64_t)d.M;
@@ -3056,27 +3111,30 @@ int srk_ba_download(srk_ba* h, int which, double* dst, int64_t count)
         }
         for (int64_t i = 0; i < d.N; ++i)
             for (int e = 0; e < 3; ++e) dst[3 * h->perm[(size_t)i] + e] = vg[(size_t)((6 + e) * d.Ns + i)];
-        std::vector<double> ug((size_t)(SRK_UG * (int64_t)d.M));
+        const int ugs = SRK_UGS(d.fv), ut = d.fv * (d.fv + 1) / 2; // Ug: block upper triangle, then the gradient
+        std::vector<double> ug((size_t)(ugs * (int64_t)d.M));
         if ((rc = d2h(ug.data(), h->Ug.p, ug.size() * 8)) != SRK_OK) return rc;
         for (int32_t j = 0; j < d.M; ++j)
-            for (int e = 0; e < 10; ++e) dst[3 * d.N + 10 * (int64_t)j + e] = ug[(size_t)(SRK_UG * (int64_t)j + 55 + e)];
-        frames_to_user(h, dst + 3 * d.N, 10);
+            for (int e = 0; e < d.fv; ++e) dst[3 * d.N + d.fv * (int64_t)j + e] = ug[(size_t)(ugs * (int64_t)j + ut + e)];
+        frames_to_user(h, dst + 3 * d.N, d.fv);
         return SRK_OK;
     }
     case SRK_BUF_FRAME_BLOCKS: {
-        std::vector<double> ug((size_t)(SRK_UG * (int64_t)d.M));
+        const int fv = d.fv, ugs = SRK_UGS(fv);
+        std::vector<double> ug((size_t)(ugs * (int64_t)d.M));
         if ((rc = d2h(ug.data(), h->Ug.p, ug.size() * 8)) != SRK_OK) return rc;
         for (int32_t j = 0; j < d.M; ++j)
-            for (int v1 = 0; v1 < 10; ++v1)
-                for (int v2 = 0; v2 < 10; ++v2) {
+            for (int v1 = 0; v1 < fv; ++v1)
+                for (int v2 = 0; v2 < fv; ++v2) {
                     int a = v1 < v2 ? v1 : v2, b = v1 < v2 ? v2 : v1;
-                    dst[100 * (int64_t)j + 10 * v1 + v2] = ug[(size_t)(SRK_UG * (int64_t)j + a * 10 - a * (a - 1) / 2 + (b - a))];
+                    dst[fv * fv * (int64_t)j + fv * v1 + v2] = ug[(size_t)(ugs * (int64_t)j + a * fv - a * (a - 1) / 2 + (b - a))];
                 }
-        frames_to_user(h, dst, 100);
+        frames_to_user(h, dst, fv * fv);
         return SRK_OK;
     }
     case SRK_BUF_POINT_FRAME: {
-        std::vector<double> w((size_t)(30 * d.Os));
+        const int fv3 = 3 * d.fv, off = 10 - d.fv;
+        std::vector<double> w((size_t)(fv3 * d.Os));
         {
             // the library keeps the rank-2 factors (srk_dev.hpp SRK_WF_*; as floats in the f32 storage mode): the products are formed here
             std::vector<double> f((size_t)(SRK_WF_PLANES * d.Os));
@@ -3088,10 +3146,10 @@ int srk_ba_download(srk_ba* h, int which, double* dst, int64_t count)
             auto F = [&](int plane, int64_t o) { return plane >= 0 ? f[(size_t)(plane * d.Os + o)] : 0.0; };
             for (int64_t o = 0; o < d.O; ++o)
                 for (int pv = 0; pv < 3; ++pv)
-                    for (int fv = 0; fv < 10; ++fv) {
+                    for (int fv = off; fv < 10; ++fv) {
                         const int pa = fv >= 4 ? SRK_WF_AF4 + fv - 4 : (fv == 0 ? SRK_WF_AF0 : (fv == 2 ? SRK_WF_G : -1));
                         const int pb = fv >= 4 ? SRK_WF_BF4 + fv - 4 : (fv == 1 ? SRK_WF_BF1 : (fv == 3 ? SRK_WF_G : -1));
-                        w[(size_t)((10 * pv + fv) * d.Os + o)] = F(SRK_WF_AP + pv, o) * F(pa, o) + F(SRK_WF_BP + pv, o) * F(pb, o);
+                        w[(size_t)((d.fv * pv + fv - off) * d.Os + o)] = F(SRK_WF_AP + pv, o) * F(pa, o) + F(SRK_WF_BP + pv, o) * F(pb, o);
                     }
         }
         for (int64_t i = 0; i < d.N; ++i) {
@@ -3099,15 +3157,15 @@ int srk_ba_download(srk_ba* h, int which, double* dst, int64_t count)
             int64_t cnt = h->row_ptr_int[(size_t)i + 1] - oi;
             for (int64_t a = 0; a < cnt; ++a) { // the caller's observation ou + a: internal place obs_rank inside its landmark
                 const int64_t ai = h->obs_rank.empty() ? a : h->obs_rank[(size_t)(ou + a)];
-                for (int k = 0; k < 30; ++k) dst[30 * (ou + a) + k] = w[(size_t)(k * d.Os + oi + ai)];
+                for (int k = 0; k < fv3; ++k) dst[fv3 * (ou + a) + k] = w[(size_t)(k * d.Os + oi + ai)];
             }
         }
         return SRK_OK;
     }
     case SRK_BUF_RCS: {
-        int64_t n = 10 * (int64_t)d.M;
+        const int64_t fv = d.fv, n = fv * (int64_t)d.M;
         std::vector<double> row((size_t)d.ld);
-        auto uvar = [&](int64_t v) { return h->frame_user.empty() ? v : 10 * (int64_t)h->frame_user[(size_t)(v / 10)] + v % 10; };
+        auto uvar = [&](int64_t v) { return h->frame_user.empty() ? v : fv * (int64_t)h->frame_user[(size_t)(v / fv)] + v % fv; };
         for (int64_t r = 0; r < n; ++r) {
             if ((rc = d2h(row.data(), P<double>(h->A->S) + r * d.ld, (size_t)(8 * n))) != SRK_OK) return rc;
             const int64_t ur = uvar(r);
@@ -3120,15 +3178,15 @@ int srk_ba_download(srk_ba* h, int which, double* dst, int64_t count)
         return SRK_OK;
     }
     case SRK_BUF_RCS_RHS:
-        if ((rc = d2h(dst, h->A->rhs.p, (size_t)(80 * (int64_t)d.M))) != SRK_OK) return rc;
-        frames_to_user(h, dst, 10);
+        if ((rc = d2h(dst, h->A->rhs.p, (size_t)(8 * d.fv * (int64_t)d.M))) != SRK_OK) return rc;
+        frames_to_user(h, dst, d.fv);
         return SRK_OK;
     case SRK_BUF_CORRECTIONS: {
         std::vector<double> tmp((size_t)(3 * d.N));
         if ((rc = d2h(tmp.data(), h->A->dx.p, (size_t)(24 * d.N))) != SRK_OK) return rc;
         for (int64_t i = 0; i < d.N; ++i) std::memcpy(dst + 3 * h->perm[(size_t)i], &tmp[(size_t)(3 * i)], 24);
-        if ((rc = d2h(dst + 3 * d.N, h->A->dc.p, (size_t)(80 * (int64_t)d.M))) != SRK_OK) return rc;
-        frames_to_user(h, dst + 3 * d.N, 10);
+        if ((rc = d2h(dst + 3 * d.N, h->A->dc.p, (size_t)(8 * d.fv * (int64_t)d.M))) != SRK_OK) return rc;
+        frames_to_user(h, dst + 3 * d.N, d.fv);
         return SRK_OK;
     }
     case SRK_BUF_POINTS: {
@@ -3156,7 +3214,7 @@ int srk_ba_download_rcs_rows(srk_ba* h, const int64_t* rows, int64_t n_rows, dou
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int sl = 1; sl < SRK_SLOTS; ++sl) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
     const SrkDims& d = h->d;
-    const int64_t n = 10 * (int64_t)d.M;
+    const int64_t fv = d.fv, n = fv * (int64_t)d.M;
     const double* S = P<double>(h->att[h->last_slot].S);
     std::vector<double> rowi, coli;
     for (int64_t k = 0; k < n_rows; ++k) {
@@ -3169,14 +3227,14 @@ int srk_ba_download_rcs_rows(srk_ba* h, const int64_t* rows, int64_t n_rows, dou
         }
         // reordered frames: the caller's row r is internal row ri; its entries left of the diagonal in the CALLER's order
         // lie in internal row ri (internal columns <= ri) and in internal column ri (rows > ri)
-        const int64_t ri = 10 * (int64_t)h->frame_int[(size_t)(r / 10)] + r % 10;
+        const int64_t ri = fv * (int64_t)h->frame_int[(size_t)(r / fv)] + r % fv;
         rowi.assign((size_t)n, 0.0);
         coli.assign((size_t)n, 0.0);
         HIPCHK(h, hipMemcpy(rowi.data(), S + ri * d.ld, (size_t)(8 * (ri + 1)), hipMemcpyDeviceToHost));
         if (ri + 1 < n)
             HIPCHK(h, hipMemcpy2D(coli.data() + ri + 1, 8, S + (ri + 1) * d.ld + ri, (size_t)(8 * d.ld), 8, (size_t)(n - ri - 1), hipMemcpyDeviceToHost));
         for (int64_t ci = 0; ci < n; ++ci) {
-            const int64_t c = 10 * (int64_t)h->frame_user[(size_t)(ci / 10)] + ci % 10;
+            const int64_t c = fv * (int64_t)h->frame_user[(size_t)(ci / fv)] + ci % fv;
             if (c <= r) dst[k * n + c] = ci <= ri ? rowi[(size_t)ci] : coli[(size_t)ci];
         }
     }
@@ -3329,6 +3387,7 @@ int srk_ba_solver_fusion(srk_ba* h) { return h ? (h->chol_fused ? 1 : 0) : -1; }
 int srk_ba_set_deterministic(srk_ba* h, int on)
 {
     if (!h) return SRK_E_ARGS;
+    if (refuse_fixed_k(h, h->fixed_k, on != 0, h->store_f32, h->schur_fp32, h->world)) return SRK_E_ARGS;
     h->deterministic = on != 0;
     return SRK_OK;
 }
@@ -3411,6 +3470,7 @@ int srk_ba_jacobian_kernel(srk_ba* h) { return (h && h->have_scene) ? (h->jac_ru
 int srk_ba_set_storage_precision(srk_ba* h, int f32)
 {
     if (!h || (f32 != 0 && f32 != 1)) return SRK_E_ARGS;
+    if (refuse_fixed_k(h, h->fixed_k, h->deterministic, f32 != 0, h->schur_fp32, h->world)) return SRK_E_ARGS;
     h->store_f32 = f32 != 0;
     return SRK_OK;
 }
@@ -3418,8 +3478,29 @@ int srk_ba_set_storage_precision(srk_ba* h, int f32)
 int srk_ba_set_schur_precision(srk_ba* h, int fp32)
 {
     if (!h || (fp32 != 0 && fp32 != 1)) return SRK_E_ARGS;
+    if (refuse_fixed_k(h, h->fixed_k, h->deterministic, h->store_f32, fp32 != 0, h->world)) return SRK_E_ARGS;
     h->schur_fp32 = fp32 != 0;
     return SRK_OK;
+}
+
+// calibrated bundle adjustment: the intrinsics are constants, six variables per frame (bundle-adj-kanatani.h:113-118);
+// next upload.  1 = on, 0 = the reference's ten variables (default)
+int srk_ba_set_fixed_intrinsics(srk_ba* h, int on)
+{
+    if (!h || (on != 0 && on != 1)) return SRK_E_ARGS;
+    if (refuse_fixed_k(h, on != 0, h->deterministic, h->store_f32, h->schur_fp32, h->world)) return SRK_E_ARGS;
+    h->fixed_k = on != 0;
+    return SRK_OK;
+}
+int srk_ba_frame_vars(srk_ba* h)
+{
+    if (!h) return SRK_E_ARGS;
+    return h->have_scene ? h->d.fv : (h->fixed_k ? 6 : 10);
+}
+int64_t srk_ba_schur_fallback_landmarks(srk_ba* h)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    return h->d.fv == 6 ? h->n_cal_list : h->n_generic;
 }
 
 // knob for bench.py: event pairs around every MFMA trailing-update launch (report.ms_solve_syrk)

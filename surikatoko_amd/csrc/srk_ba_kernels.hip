@@ -14,12 +14,25 @@
 
 #define WAVE 64
 
+// FV = variables per frame: 10 [fx fy u0 v0 Tx Ty Tz Wx Wy Wz], or 6 [Tx Ty Tz Wx Wy Wz] with fixed intrinsics
+// (srk_ba_set_fixed_intrinsics); compact frame variable v is the full variable v + SRK_FV_OFF(FV)
+#define SRK_FV_OFF(FV) (10 - (FV))
 __device__ __forceinline__ bool srk_is_fixed_var(int64_t var, const SrkDims& d)
 {
     // bundle-adj-kanatani.cpp:539-563: frame-local 4..9 of frame 0 and 14+comp (frame 1's 4+comp) are removed by the gauge;
     // d.g0, d.g1: where the caller's frames 0 and 1 sit in the internal frame order (0 and 1 unless the frames were reordered)
     const int64_t b0 = 10 * (int64_t)d.g0;
     return (var >= b0 + 4 && var <= b0 + 9) || (var == 10 * (int64_t)d.g1 + 4 + d.comp);
+}
+// the same for FV frame variables (the kernels templated on FV; srk_is_fixed_var above is kept as it was for the others)
+template <int FV>
+__device__ __forceinline__ bool srk_is_fixed_var_fv(int64_t var, const SrkDims& d)
+{
+    // bundle-adj-kanatani.cpp:539-563: frame-local 4..9 of frame 0 and 14+comp (frame 1's 4+comp) are removed by the gauge;
+    // d.g0, d.g1: where the caller's frames 0 and 1 sit in the internal frame order (0 and 1 unless the frames were reordered)
+    constexpr int off = SRK_FV_OFF(FV);
+    const int64_t b0 = FV * (int64_t)d.g0;
+    return (var >= b0 + 4 - off && var <= b0 + 9 - off) || (var == FV * (int64_t)d.g1 + 4 - off + d.comp);
 }
 
 // ------------------------------------------------------------------ camera pack
@@ -80,17 +93,28 @@ template <typename WT> __device__ __forceinline__ double w_entry(const WT* __res
     const double af = pa >= 0 ? (double)W[(int64_t)pa * Os + o] : 0.0, bf = pb >= 0 ? (double)W[(int64_t)pb * Os + o] : 0.0;
     return (double)W[(int64_t)(SRK_WF_AP + pv) * Os + o] * af + (double)W[(int64_t)(SRK_WF_BP + pv) * Os + o] * bf;
 }
+// entry k = FV pv + fv for FV frame variables (fv compact: the full frame variable is fv + SRK_FV_OFF(FV))
+template <typename WT, int FV> __device__ __forceinline__ double w_entry_fv(const WT* __restrict__ W, int64_t Os, int64_t o, int k)
+{
+    const int pv = k / FV, fv = k - FV * pv + SRK_FV_OFF(FV);
+    const int pa = srk_wf_af_plane(fv), pb = srk_wf_bf_plane(fv);
+    const double af = pa >= 0 ? (double)W[(int64_t)pa * Os + o] : 0.0, bf = pb >= 0 ? (double)W[(int64_t)pb * Os + o] : 0.0;
+    return (double)W[(int64_t)(SRK_WF_AP + pv) * Os + o] * af + (double)W[(int64_t)(SRK_WF_BP + pv) * Os + o] * bf;
+}
 // the block of observation o from factors scaled so that W = Ap Af + Bp Bf
-template <typename WT>
+// (FV = 6, fixed intrinsics: the 18 planes Ap, Bp, Af[4..9], Bf[4..9]; planes AF0, G and BF1 are neither written nor read)
+template <typename WT, int FV = 10>
 __device__ __forceinline__ void w_store(WT* __restrict__ W, int64_t Os, int64_t o, const double (&Ap)[3], const double (&Bp)[3],
                                         const double (&Af)[10], const double (&Bf)[10])
 {
     WT* wp = W + o;
 #pragma unroll
     for (int v = 0; v < 3; ++v) { wp[(int64_t)(SRK_WF_AP + v) * Os] = (WT)Ap[v]; wp[(int64_t)(SRK_WF_BP + v) * Os] = (WT)Bp[v]; }
-    wp[(int64_t)SRK_WF_AF0 * Os] = (WT)Af[0];
-    wp[(int64_t)SRK_WF_G * Os] = (WT)Af[2];
-    wp[(int64_t)SRK_WF_BF1 * Os] = (WT)Bf[1];
+    if constexpr (FV == 10) {
+        wp[(int64_t)SRK_WF_AF0 * Os] = (WT)Af[0];
+        wp[(int64_t)SRK_WF_G * Os] = (WT)Af[2];
+        wp[(int64_t)SRK_WF_BF1 * Os] = (WT)Bf[1];
+    }
 #pragma unroll
     for (int v = 4; v < 10; ++v) { wp[(int64_t)(SRK_WF_AF4 + v - 4) * Os] = (WT)Af[v]; wp[(int64_t)(SRK_WF_BF4 + v - 4) * Os] = (WT)Bf[v]; }
 }
@@ -166,7 +190,7 @@ __device__ __forceinline__ void frame_ab(const double* __restrict__ c, const Obs
 // One thread per observation.  Writes the 3x10 point-frame block (SoA, lane-contiguous 8-byte stores) and
 // reduces the point block V (6 unique) + point gradient (3) over the landmark's observations with a
 // wavefront segmented reduction; one atomic per (wave, landmark) segment.
-template <typename WT> // storage type of the point-frame blocks W: double, or float (srk_ba_set_storage_precision)
+template <typename WT, int FV = 10> // storage type of the point-frame blocks W: double, or float (srk_ba_set_storage_precision)
 __global__ __launch_bounds__(256) void k_jac_points(SrkDims d, const double* __restrict__ pts,
                                                     const double* __restrict__ cam,
                                                     const int32_t* __restrict__ obs_frame,
@@ -200,7 +224,7 @@ __global__ __launch_bounds__(256) void k_jac_points(SrkDims d, const double* __r
             for (int v = 0; v < 3; ++v) { Aps[v] = Ap[v] * sc; Bps[v] = Bp[v] * sc; }
 #pragma unroll
             for (int v = 0; v < 10; ++v) { Afs[v] = Af[v] * sc; Bfs[v] = Bf[v] * sc; }
-            w_store<WT>(W, d.Os, o, Aps, Bps, Afs, Bfs);
+            w_store<WT, FV>(W, d.Os, o, Aps, Bps, Afs, Bfs);
         }
         acc[0] = (Ap[0] * Ap[0] + Bp[0] * Bp[0]) * g.s2;
         acc[1] = (Ap[0] * Ap[1] + Bp[0] * Bp[1]) * g.s2;
@@ -250,7 +274,7 @@ __device__ __forceinline__ double jf_rcp(double d)
     return r;
 }
 
-template <typename WT>
+template <typename WT, int FV = 10>
 __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __restrict__ pts,
                                                    const double* __restrict__ cam,
                                                    const int32_t* __restrict__ obs_frame,
@@ -259,7 +283,8 @@ __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __re
                                                    double* __restrict__ Vg, double* __restrict__ Ug,
                                                    const int32_t* __restrict__ wg_jmin)
 {
-    __shared__ double sU[SRK_JF_SLOTS][SRK_UG + 1];                              // frame blocks + frame gradients
+    constexpr int UGS = SRK_UGS(FV), UT = FV * (FV + 1) / 2, off = SRK_FV_OFF(FV);
+    __shared__ double sU[SRK_JF_SLOTS][UGS + 1];                              // frame blocks + frame gradients
     __shared__ __attribute__((aligned(16))) double sCam[SRK_JF_SLOTS][SRK_CAM_PACK]; // camera packs of the frame range
     __shared__ double sV[9][SRK_JF_PMAX];                                        // point blocks + point gradients
     __shared__ int sTouched[SRK_JF_SLOTS];
@@ -269,7 +294,7 @@ __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __re
     const int64_t o_last = (o_first + SRK_JF_OBS < d.O ? o_first + SRK_JF_OBS : d.O) - 1;
     const int32_t pmin = obs_pt[o_first], pmax = obs_pt[o_last];
     const int npts = pmax - pmin + 1;
-    for (int t = threadIdx.x; t < SRK_JF_SLOTS * (SRK_UG + 1); t += 256) (&sU[0][0])[t] = 0.0;
+    for (int t = threadIdx.x; t < SRK_JF_SLOTS * (UGS + 1); t += 256) (&sU[0][0])[t] = 0.0;
     for (int t = threadIdx.x; t < 9 * SRK_JF_PMAX; t += 256) (&sV[0][0])[t] = 0.0;
     if (threadIdx.x < SRK_JF_SLOTS) sTouched[threadIdx.x] = 0;
     {
@@ -341,7 +366,7 @@ __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __re
                 for (int v = 0; v < 3; ++v) { Apq[v] = Ap[v] * sc; Bpq[v] = Bp[v] * sc; }
 #pragma unroll
                 for (int v = 0; v < 10; ++v) { Afq[v] = Af[v] * sc; Bfq[v] = Bf[v] * sc; }
-                w_store<WT>(W, d.Os, o, Apq, Bpq, Afq, Bfq);
+                w_store<WT, FV>(W, d.Os, o, Apq, Bpq, Afq, Bfq);
             }
             acc[0] = Aps[0] * Ap[0] + Bps[0] * Bp[0];
             acc[1] = Aps[0] * Ap[1] + Bps[0] * Bp[1];
@@ -357,14 +382,14 @@ __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __re
             sTouched[js] = 1;
             int idx = 0;
 #pragma unroll
-            for (int v1 = 0; v1 < 10; ++v1)
+            for (int v1 = off; v1 < 10; ++v1)
 #pragma unroll
                 for (int v2 = v1; v2 < 10; ++v2) {
                     atomicAdd(&su[idx], Afs[v1] * Af[v2] + Bfs[v1] * Bf[v2]);
                     ++idx;
                 }
 #pragma unroll
-            for (int v = 0; v < 10; ++v) atomicAdd(&su[55 + v], ex1 * Af[v] + ey1 * Bf[v]);
+            for (int v = off; v < 10; ++v) atomicAdd(&su[UT + v - off], ex1 * Af[v] + ey1 * Bf[v]);
         }
         // point block + gradient: wavefront segmented reduction over the landmark's (contiguous) observations, then
         // one LDS add per (wave, landmark) -- 20 lanes adding to one LDS word would serialise (measured slower)
@@ -394,9 +419,9 @@ __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __re
         if (ps == 0 || ps == npts - 1) atomicAdd(dst, v);
         else *dst = v;
     }
-    for (int t = threadIdx.x; t < SRK_JF_SLOTS * SRK_UG; t += 256) {
-        int slot = t / SRK_UG, k = t - slot * SRK_UG;
-        if (sTouched[slot]) atomicAdd(&Ug[(int64_t)(jmin + slot) * SRK_UG + k], sU[slot][k]);
+    for (int t = threadIdx.x; t < SRK_JF_SLOTS * UGS; t += 256) {
+        int slot = t / UGS, k = t - slot * UGS;
+        if (sTouched[slot]) atomicAdd(&Ug[(int64_t)(jmin + slot) * UGS + k], sU[slot][k]);
     }
 }
 
@@ -406,7 +431,10 @@ void srk_launch_jac_fused(hipStream_t s, const SrkDims& d, const double* pts, co
 {
     if (d.O == 0) return;
     int64_t blocks = (d.O + SRK_JF_OBS - 1) / SRK_JF_OBS;
-    if (d.w_f32)
+    if (d.fv == 6)
+        hipLaunchKernelGGL((k_jac_fused<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+                           W, Vg, Ug, wg_jmin);
+    else if (d.w_f32)
         hipLaunchKernelGGL(k_jac_fused<float>, dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
                            reinterpret_cast<float*>(W), Vg, Ug, wg_jmin);
     else
@@ -442,7 +470,7 @@ void srk_launch_jac_fused(hipStream_t s, const SrkDims& d, const double* pts, co
 // (landmark m of the step, frame slot f of the union): the cell's observation is the landmark's first one plus the number of
 // mask bits below the slot; a cell the landmark does not see computes nothing and adds zeros to the landmark's sums.  A lane
 // still stays on one frame for the whole task.  The landmarks' first observations and masks sit in a per-wave LDS table.
-template <typename WT, bool MASKED, bool DET = false>
+template <typename WT, bool MASKED, bool DET = false, int FV = 10>
 __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __restrict__ pts,
                                                      const double* __restrict__ cam,
                                                      const int64_t* __restrict__ row_ptr,
@@ -456,15 +484,18 @@ __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __
                                                      const int32_t* __restrict__ grp_frames, const uint32_t* __restrict__ pt_mask,
                                                      double* __restrict__ det_stage /* DET: [task][64][SRK_UG] */, int frames_stride)
 {
+    // FV = 6 (fixed intrinsics): 21 + 6 frame sums (the pose block and gradient), 18 stored factor planes
+    constexpr int UGS = SRK_UGS(FV), UT = FV * (FV + 1) / 2, off = SRK_FV_OFF(FV);
+    static_assert(!DET || FV == 10, "deterministic mode is built for ten frame variables");
     __shared__ int32_t sTOff[MASKED ? 4 : 1][MASKED ? SRK_JR_TASK_PTS_MAX_HOST : 1];
     __shared__ uint32_t sTMask[MASKED ? 4 : 1][MASKED ? SRK_JR_TASK_PTS_MAX_HOST : 1];
-    __shared__ double sU[SRK_JF_SLOTS][SRK_UG + 1];                                  // frame blocks + frame gradients
+    __shared__ double sU[SRK_JF_SLOTS][UGS + 1];                                  // frame blocks + frame gradients
     __shared__ __attribute__((aligned(16))) double sCam[SRK_JF_SLOTS][SRK_CAM_PACK]; // camera packs of the frame window
     __shared__ double sR[4][9 * SRK_JR_RSTRIDE];                                     // per-wave landmark reduction
     __shared__ int sTouched[SRK_JF_SLOTS];
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
     const int jmin = wg_jmin[blockIdx.x];
-    for (int t = threadIdx.x; t < SRK_JF_SLOTS * (SRK_UG + 1); t += 256) (&sU[0][0])[t] = 0.0;
+    for (int t = threadIdx.x; t < SRK_JF_SLOTS * (UGS + 1); t += 256) (&sU[0][0])[t] = 0.0;
     if (threadIdx.x < SRK_JF_SLOTS) sTouched[threadIdx.x] = 0;
     {
         int nfr = d.M - jmin < SRK_JF_SLOTS ? d.M - jmin : SRK_JF_SLOTS;
@@ -507,9 +538,9 @@ __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __
         };
         const double* c = sCam[js];
         double* sr = sR[wv];
-        double acc[SRK_UG];
+        double acc[UGS];
 #pragma unroll
-        for (int k = 0; k < SRK_UG; ++k) acc[k] = 0;
+        for (int k = 0; k < UGS; ++k) acc[k] = 0;
         // software pipeline: the next iteration's observation and landmark are loaded while this one is computed
         double2 uv_n = make_double2(0, 0);
         double Xn0 = 0, Xn1 = 0, Xn2 = 0;
@@ -578,7 +609,7 @@ __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __
                 const double t0 = X0 - c[30], t1 = X1 - c[31], t2 = X2 - c[32];
                 Af[7] = a1[1] * t2 - a1[2] * t1; Af[8] = a1[2] * t0 - a1[0] * t2; Af[9] = a1[0] * t1 - a1[1] * t0;
                 Bf[7] = b1[1] * t2 - b1[2] * t1; Bf[8] = b1[2] * t0 - b1[0] * t2; Bf[9] = b1[0] * t1 - b1[1] * t0;
-                w_store<WT>(W, d.Os, o, Ap, Bp, Af, Bf); // the 21 factors (as floats in the f32 storage mode)
+                w_store<WT, FV>(W, d.Os, o, Ap, Bp, Af, Bf); // the 21 (FV = 6: 18) factors (as floats in the f32 storage mode)
                 v9[0] = Ap[0] * Ap[0] + Bp[0] * Bp[0];
                 v9[1] = Ap[0] * Ap[1] + Bp[0] * Bp[1];
                 v9[2] = Ap[0] * Ap[2] + Bp[0] * Bp[2];
@@ -590,14 +621,14 @@ __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __
                 v9[8] = exs * Ap[2] + eys * Bp[2];
                 int idx = 0;
 #pragma unroll
-                for (int v1 = 0; v1 < 10; ++v1)
+                for (int v1 = off; v1 < 10; ++v1)
 #pragma unroll
                     for (int v2 = v1; v2 < 10; ++v2) {
                         acc[idx] = fma(Af[v1], Af[v2], fma(Bf[v1], Bf[v2], acc[idx]));
                         ++idx;
                     }
 #pragma unroll
-                for (int v = 0; v < 10; ++v) acc[55 + v] = fma(exs, Af[v], fma(eys, Bf[v], acc[55 + v]));
+                for (int v = off; v < 10; ++v) acc[UT + v - off] = fma(exs, Af[v], fma(eys, Bf[v], acc[UT + v - off]));
             }
             // point block + gradient of the g landmarks of this iteration: every lane parks its nine terms in the wave's
             // scratch, lane (k, mm) adds landmark mm's nf terms of entry k in frame order and stores the sum.  LDS
@@ -630,7 +661,7 @@ __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __
             // tasks' sums per frame in task order.
             for (int m2 = 1; m2 < g; ++m2) {
 #pragma unroll
-                for (int k = 0; k < SRK_UG; ++k) {
+                for (int k = 0; k < UGS; ++k) {
                     const double o = __shfl(acc[k], f + m2 * nf, WAVE);
                     if (m == 0) acc[k] += o; // (the other lanes keep their own sums: they are read in the steps behind)
                 }
@@ -638,21 +669,21 @@ __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __
             if (on && m == 0) {
                 double* dst = det_stage + ((int64_t)task * WAVE + f) * SRK_UG;
 #pragma unroll
-                for (int k = 0; k < SRK_UG; ++k) dst[k] = acc[k];
+                for (int k = 0; k < UGS; ++k) dst[k] = acc[k];
             }
         } else if (on) {
             double* su = sU[js];
             sTouched[js] = 1;
 #pragma unroll
-            for (int k = 0; k < SRK_UG; ++k) atomicAdd(&su[k], acc[k]);
+            for (int k = 0; k < UGS; ++k) atomicAdd(&su[k], acc[k]);
         }
     }
     }
     if (DET) return;
     __syncthreads();
-    for (int t = threadIdx.x; t < SRK_JF_SLOTS * SRK_UG; t += 256) {
-        int slot = t / SRK_UG, k = t - slot * SRK_UG;
-        if (sTouched[slot]) atomicAdd(&Ug[(int64_t)(jmin + slot) * SRK_UG + k], sU[slot][k]);
+    for (int t = threadIdx.x; t < SRK_JF_SLOTS * UGS; t += 256) {
+        int slot = t / UGS, k = t - slot * UGS;
+        if (sTouched[slot]) atomicAdd(&Ug[(int64_t)(jmin + slot) * UGS + k], sU[slot][k]);
     }
 }
 
@@ -686,7 +717,10 @@ void srk_launch_jac_runs(hipStream_t s, const SrkDims& d, const double* pts, con
             else hipLaunchKernelGGL((k_jac_runs<double, MASKED, false>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));                         \
         }                                                                                                                             \
     } while (0)
-    if (task_group) SRK_JR_LAUNCH(true); // tasks over unions of frame lists (ragged tracks)
+    if (d.fv == 6) { // fixed intrinsics: fp64 storage, never deterministic
+        if (task_group) hipLaunchKernelGGL((k_jac_runs<double, true, false, 6>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));
+        else hipLaunchKernelGGL((k_jac_runs<double, false, false, 6>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));
+    } else if (task_group) SRK_JR_LAUNCH(true); // tasks over unions of frame lists (ragged tracks)
     else SRK_JR_LAUNCH(false);
 #undef SRK_JR_LAUNCH
 #undef SRK_JR_ARGS
@@ -699,7 +733,10 @@ void srk_launch_jac_points(hipStream_t s, const SrkDims& d, const double* pts, c
 {
     if (d.O == 0) return;
     int64_t blocks = (d.O + 255) / 256;
-    if (d.w_f32)
+    if (d.fv == 6)
+        hipLaunchKernelGGL((k_jac_points<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+                           W, Vg);
+    else if (d.w_f32)
         hipLaunchKernelGGL(k_jac_points<float>, dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
                            reinterpret_cast<float*>(W), Vg);
     else
@@ -719,22 +756,24 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+template <int FV = 10>
 __global__ __launch_bounds__(256) void k_jac_frames(SrkDims d, const double* __restrict__ pts,
                                                     const double* __restrict__ cam,
                                                     const int64_t* __restrict__ col_ptr,
                                                     const int32_t* __restrict__ fobs_pt,
                                                     const double* __restrict__ fobs_uv, double* __restrict__ Ug)
 {
-    __shared__ double red[4][SRK_UG];
+    constexpr int UGS = SRK_UGS(FV), UT = FV * (FV + 1) / 2, off = SRK_FV_OFF(FV); // FV = 6: the pose block and gradient
+    __shared__ double red[4][UGS];
     int j = blockIdx.y;
     int64_t begin = col_ptr[j] + (int64_t)blockIdx.x * SRK_FCHUNK;
     int64_t end = col_ptr[j + 1];
     if (begin >= end) return;
     if (end > begin + SRK_FCHUNK) end = begin + SRK_FCHUNK;
     const double* c = cam + (int64_t)SRK_CAM_PACK * j;
-    double acc[SRK_UG];
+    double acc[UGS];
 #pragma unroll
-    for (int k = 0; k < SRK_UG; ++k) acc[k] = 0;
+    for (int k = 0; k < UGS; ++k) acc[k] = 0;
     for (int64_t k = begin + threadIdx.x; k < end; k += 256) {
         int32_t pt = fobs_pt[k];
         double2 uv = reinterpret_cast<const double2*>(fobs_uv)[k];
@@ -746,25 +785,25 @@ __global__ __launch_bounds__(256) void k_jac_frames(SrkDims d, const double* __r
         frame_ab(c, g, X0, X1, X2, Af, Bf);
         int idx = 0;
 #pragma unroll
-        for (int v1 = 0; v1 < 10; ++v1)
+        for (int v1 = off; v1 < 10; ++v1)
 #pragma unroll
             for (int v2 = v1; v2 < 10; ++v2) {
                 acc[idx] += (Af[v1] * Af[v2] + Bf[v1] * Bf[v2]) * g.s2;
                 ++idx;
             }
 #pragma unroll
-        for (int v = 0; v < 10; ++v) acc[55 + v] += (g.ex * Af[v] + g.ey * Bf[v]) * g.s1;
+        for (int v = off; v < 10; ++v) acc[UT + v - off] += (g.ex * Af[v] + g.ey * Bf[v]) * g.s1;
     }
     int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < SRK_UG; ++k) {
+    for (int k = 0; k < UGS; ++k) {
         double v = wave_sum(acc[k]);
         if (lane == 0) red[wave][k] = v;
     }
     __syncthreads();
-    if (threadIdx.x < SRK_UG) {
+    if (threadIdx.x < UGS) {
         double v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        atomicAdd(&Ug[(int64_t)j * SRK_UG + threadIdx.x], v);
+        atomicAdd(&Ug[(int64_t)j * UGS + threadIdx.x], v);
     }
 }
 
@@ -774,8 +813,12 @@ void srk_launch_jac_frames(hipStream_t s, const SrkDims& d, int64_t max_frame_ob
 {
     if (d.O == 0 || max_frame_obs == 0) return;
     int64_t chunks = (max_frame_obs + SRK_FCHUNK - 1) / SRK_FCHUNK;
-    hipLaunchKernelGGL(k_jac_frames, dim3((unsigned)chunks, (unsigned)d.M), dim3(256), 0, s, d, pts, cam, col_ptr,
-                       fobs_pt, fobs_uv, Ug);
+    if (d.fv == 6)
+        hipLaunchKernelGGL(k_jac_frames<6>, dim3((unsigned)chunks, (unsigned)d.M), dim3(256), 0, s, d, pts, cam, col_ptr,
+                           fobs_pt, fobs_uv, Ug);
+    else
+        hipLaunchKernelGGL(k_jac_frames<10>, dim3((unsigned)chunks, (unsigned)d.M), dim3(256), 0, s, d, pts, cam, col_ptr,
+                           fobs_pt, fobs_uv, Ug);
 }
 
 // expand the packed per-frame accumulators to the oracle's [M][10][10] + [M][10] layout (tests / downloads)
@@ -874,7 +917,7 @@ struct SchurLmScratch {
     double sYb[SRK_SCH][30];
     int32_t sFa[SRK_SCH], sFb[SRK_SCH];
 };
-template <typename WT>
+template <typename WT, int FV = 10>
 __device__ __forceinline__ void schur_one_landmark(const SrkDims& d, double c, const int64_t* __restrict__ row_ptr,
                                                    const int32_t* __restrict__ obs_frame, const WT* __restrict__ W,
                                                    const double* __restrict__ Vg, double* __restrict__ S,
@@ -897,18 +940,18 @@ __device__ __forceinline__ void schur_one_landmark(const SrkDims& d, double c, c
         int a0 = ca * SRK_SCH;
         int na = n - a0 < SRK_SCH ? n - a0 : SRK_SCH;
         __syncthreads();
-        for (int t = threadIdx.x; t < na * 30; t += 256) {
+        for (int t = threadIdx.x; t < na * 3 * FV; t += 256) {
             int k = t / na, a = t - k * na;
-            sWa[a][k] = w_entry<WT>(W, d.Os, o0 + a0 + a, k);
+            sWa[a][k] = w_entry_fv<WT, FV>(W, d.Os, o0 + a0 + a, k);
         }
         if (threadIdx.x < na) sFa[threadIdx.x] = obs_frame[o0 + a0 + threadIdx.x];
         __syncthreads();
         // rhs += F^T E^-1 g   (:1895-1897)
-        for (int t = threadIdx.x; t < na * 10; t += 256) {
-            int a = t / 10, r = t - a * 10;
-            int64_t row = 10 * (int64_t)sFa[a] + r;
-            if (!srk_is_fixed_var(row, d)) {
-                double v = sWa[a][r] * Eg[0] + sWa[a][10 + r] * Eg[1] + sWa[a][20 + r] * Eg[2];
+        for (int t = threadIdx.x; t < na * FV; t += 256) {
+            int a = t / FV, r = t - a * FV;
+            int64_t row = FV * (int64_t)sFa[a] + r;
+            if (!srk_is_fixed_var_fv<FV>(row, d)) {
+                double v = sWa[a][r] * Eg[0] + sWa[a][FV + r] * Eg[1] + sWa[a][2 * FV + r] * Eg[2];
                 atomicAdd(&rhs[row], v);
             }
         }
@@ -916,26 +959,26 @@ __device__ __forceinline__ void schur_one_landmark(const SrkDims& d, double c, c
             int b0 = cb * SRK_SCH;
             int nb = n - b0 < SRK_SCH ? n - b0 : SRK_SCH;
             __syncthreads();
-            for (int t = threadIdx.x; t < nb * 10; t += 256) {
+            for (int t = threadIdx.x; t < nb * FV; t += 256) {
                 int fv = t / nb, b = t - fv * nb;
                 int64_t ob = o0 + b0 + b;
-                double w0 = w_entry<WT>(W, d.Os, ob, fv), w1 = w_entry<WT>(W, d.Os, ob, 10 + fv), w2 = w_entry<WT>(W, d.Os, ob, 20 + fv);
-                // Y = E^-1 W  (3 x 10)
+                double w0 = w_entry_fv<WT, FV>(W, d.Os, ob, fv), w1 = w_entry_fv<WT, FV>(W, d.Os, ob, FV + fv), w2 = w_entry_fv<WT, FV>(W, d.Os, ob, 2 * FV + fv);
+                // Y = E^-1 W  (3 x FV)
                 sYb[b][fv] = Einv[0] * w0 + Einv[1] * w1 + Einv[2] * w2;
-                sYb[b][10 + fv] = Einv[3] * w0 + Einv[4] * w1 + Einv[5] * w2;
-                sYb[b][20 + fv] = Einv[6] * w0 + Einv[7] * w1 + Einv[8] * w2;
+                sYb[b][FV + fv] = Einv[3] * w0 + Einv[4] * w1 + Einv[5] * w2;
+                sYb[b][2 * FV + fv] = Einv[6] * w0 + Einv[7] * w1 + Einv[8] * w2;
             }
             if (threadIdx.x < nb) sFb[threadIdx.x] = obs_frame[o0 + b0 + threadIdx.x];
             __syncthreads();
-            int total = na * nb * 100;
+            int total = na * nb * FV * FV;
             for (int t = threadIdx.x; t < total; t += 256) {
-                int e = t % 100, pr = t / 100;
+                int e = t % (FV * FV), pr = t / (FV * FV);
                 int b = pr % nb, a = pr / nb;
                 if (ca == cb && b > a) continue; // lower block triangle only (frames ascend inside a landmark)
-                int r = e / 10, cc = e - r * 10;
-                int64_t row = 10 * (int64_t)sFa[a] + r, col = 10 * (int64_t)sFb[b] + cc;
-                if (srk_is_fixed_var(row, d) || srk_is_fixed_var(col, d)) continue;
-                double v = sWa[a][r] * sYb[b][cc] + sWa[a][10 + r] * sYb[b][10 + cc] + sWa[a][20 + r] * sYb[b][20 + cc];
+                int r = e / FV, cc = e - r * FV;
+                int64_t row = FV * (int64_t)sFa[a] + r, col = FV * (int64_t)sFb[b] + cc;
+                if (srk_is_fixed_var_fv<FV>(row, d) || srk_is_fixed_var_fv<FV>(col, d)) continue;
+                double v = sWa[a][r] * sYb[b][cc] + sWa[a][FV + r] * sYb[b][FV + cc] + sWa[a][2 * FV + r] * sYb[b][2 * FV + cc];
                 atomicAdd(&S[row * d.ld + col], -v); // S = G - sum F^T E^-1 F  (:1891-1892)
             }
         }
@@ -943,7 +986,7 @@ __device__ __forceinline__ void schur_one_landmark(const SrkDims& d, double c, c
     __syncthreads(); // the scratch is free for the next landmark
 }
 
-template <typename WT>
+template <typename WT, int FV = 10>
 __global__ __launch_bounds__(256) void k_schur(SrkDims d, double c, const int64_t* __restrict__ row_ptr,
                                                const int32_t* __restrict__ obs_frame, const WT* __restrict__ W,
                                                const double* __restrict__ Vg, double* __restrict__ S,
@@ -952,7 +995,7 @@ __global__ __launch_bounds__(256) void k_schur(SrkDims d, double c, const int64_
 {
     __shared__ SchurLmScratch sm;
     for (int64_t li = blockIdx.x; li < n_list; li += gridDim.x)
-        schur_one_landmark<WT>(d, c, row_ptr, obs_frame, W, Vg, S, rhs, pt_list ? pt_list[li] : li, sm);
+        schur_one_landmark<WT, FV>(d, c, row_ptr, obs_frame, W, Vg, S, rhs, pt_list ? pt_list[li] : li, sm);
 }
 
 void srk_launch_schur(hipStream_t s, const SrkDims& d, double c, const int64_t* row_ptr, const int32_t* obs_frame,
@@ -961,7 +1004,10 @@ void srk_launch_schur(hipStream_t s, const SrkDims& d, double c, const int64_t* 
 {
     if (n_list <= 0) return;
     int64_t blocks = n_list < 65536 ? n_list : 65536;
-    if (d.w_f32)
+    if (d.fv == 6) // fixed intrinsics (fp64 storage only: srk_ba_set_fixed_intrinsics)
+        hipLaunchKernelGGL((k_schur<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, c, row_ptr, obs_frame, W, Vg, S, rhs,
+                           pt_list, n_list);
+    else if (d.w_f32)
         hipLaunchKernelGGL(k_schur<float>, dim3((unsigned)blocks), dim3(256), 0, s, d, c, row_ptr, obs_frame,
                            reinterpret_cast<const float*>(W), Vg, S, rhs, pt_list, n_list);
     else
@@ -1561,6 +1607,32 @@ __device__ __forceinline__ void schur_mm_steps(srk_double4 (&acc)[SRK_MM_SLOTS],
     load(a1, b1, 5); mac(a0, b0, 4);
     mac(a1, b1, 5);
 }
+// the same for a wave with only NS live slots (6-wide frame blocks: a run of at most 20 frames is at most 36 tiles, three for
+// each of the 12 multiplying waves): NS MFMAs a K step instead of eight, idle slots u >= n_tiles multiply tile (0, 0) and are
+// not flushed; operand sets per K step, the next one's reads in flight
+template <int NS>
+__device__ __forceinline__ void schur_mm_steps_n(srk_double4 (&acc)[SRK_MM_SLOTS], const double* bw, const int (&ta)[SRK_MM_SLOTS],
+                                                 const int (&tb)[SRK_MM_SLOTS], int lbase)
+{
+    static_assert(NS <= SRK_MM_SLOTS, "slots");
+    struct Ops { double a[NS], b[NS]; };
+    auto load = [&](Ops& o, int ks) {
+        int lb = lbase;
+        asm volatile("" : "+v"(lb));
+        const int ko = ks * 4 * SRK_MM_LDW;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) { o.a[s] = bw[ko + lb + ta[s]]; o.b[s] = bw[ko + lb + tb[s]]; }
+    };
+    auto mac = [&](const Ops& o) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[s], o.b[s], acc[s], 0, 0, 0);
+    };
+    Ops o0, o1;
+    load(o0, 0);
+    load(o1, 1); mac(o0);
+    load(o0, 2); mac(o1);
+    mac(o0);
+}
 // the same for a wave whose eight tiles are a 2 x 4 BLOCK of the tile grid (tiles 0 .. 3: row ta[0], columns tb[0 .. 3];
 // tiles 4 .. 7: row ta[4], the same columns): two A and four B operands serve the eight MFMAs of a K step -- 6 LDS reads
 // instead of 16 -- and the operand sets are per K step (the next one's reads in flight under eight MFMAs)
@@ -1680,7 +1752,7 @@ __device__ __forceinline__ void schur_mm_steps_row(srk_double4 (&acc)[SRK_MM_SLO
 // What was measured on the way (DESIGN sections 5 and 8): the helpers' instructions do not overlap with the MFMA streams of
 // their SIMD, so what counts is how FEW instructions both sides issue; latency hiding on the helper side, barrier-free
 // progress words, leaner block-wave address arithmetic each made it slower.
-template <typename WT, int KIND, bool DET = false>
+template <typename WT, int KIND, bool DET = false, int FV = 10>
 __global__ __launch_bounds__(SRK_MM_THREADS) void k_schur_mm(
     SrkDims d, double c, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ obs_pt,
     const uint8_t* __restrict__ obs_slot, const uint32_t* __restrict__ pt_mask, const WT* __restrict__ W,
@@ -1700,6 +1772,10 @@ __global__ __launch_bounds__(SRK_MM_THREADS) void k_schur_mm(
     constexpr bool masked = KIND == 1;
     constexpr int NV = SRK_WF_PLANES; // values of an observation a row lane keeps in flight: its 21 factors
     static_assert(SRK_WS_NF * 10 <= LDW && KR % 4 == 0, "round buffers");
+    // FV = 6 (fixed intrinsics): a cell is the 6 pose columns of the frame slot, a 20-frame run 120 columns (8 x 8 tile grid,
+    // dealt out row-major like every grid but the full 13 x 13 one); the deterministic mode is not built for it
+    static_assert((FV == 10 || FV == 6) && (!DET || FV == 10), "frame variables");
+    constexpr int FH = FV / 2; // 16-byte LDS stores of a cell row
     static_assert(SRK_MM_CW * SRK_MM_SLOTS >= 13 * 14 / 2, "tiles do not fit the multiplying waves");
     static_assert((SRK_GRP_MAXPTS + PB - 1) / PB < 64, "a run's row_ptr entries do not fit a wave");
     static_assert(3 * QMAX <= NH && 2 * 3 * QMAX <= SRK_MM_THREADS, "row lanes");
@@ -1733,13 +1809,13 @@ __global__ __launch_bounds__(SRK_MM_THREADS) void k_schur_mm(
     if (KIND == 0 && nfu < 0) return; // (never launched on such a scene)
     const int nf = nfu < 0 ? -nfu : nfu;
     if (nf > SRK_WS_NF) return; // k_schur_grouped takes the wider runs
-    if (tid < nf * 10) {
+    if (tid < nf * FV) {
         sRhs[tid] = 0.0;
-        const int64_t var = 10 * (int64_t)grp_frames[(int64_t)blockIdx.x * SRK_GRP_MAXNF + tid / 10] + tid % 10;
-        sVar[tid] = srk_is_fixed_var(var, d) ? -1 : (int)var;
+        const int64_t var = FV * (int64_t)grp_frames[(int64_t)blockIdx.x * SRK_GRP_MAXNF + tid / FV] + tid % FV;
+        sVar[tid] = srk_is_fixed_var_fv<FV>(var, d) ? -1 : (int)var;
     }
     const int R = (np + PB - 1) / PB;
-    const int nf10 = nf * 10;
+    const int nf10 = nf * FV; // columns of the sum
     const int64_t o0 = row_ptr[p0];
     // LDS column of cell (staged landmark pl, frame slot a), Z row k = 3 pl + m:  (3 pl + m) LDW + 10 a + i
     // (masked) the cell (landmark pidx of the run, frame slot a): which observation, if any -- a landmark's observations are
@@ -1765,17 +1841,19 @@ __global__ __launch_bounds__(SRK_MM_THREADS) void k_schur_mm(
         for (int k = 0; k < SRK_WF_PLANES; ++k) v[k] = (double)(W + (int64_t)k * d.Os)[voff];
     };
     // row m of Z = L^-1 W from those values and the landmark's sE row E; returns hm = (L^-1 g)[m]
-    auto z_row = [&](const double (&v)[NV], const double* E, int m, double (&z)[10]) -> double {
+    auto z_row = [&](const double (&v)[NV], const double* E, int m, double (&z)[FV]) -> double {
         const int r3 = m * (m + 1) / 2; // row m of the lower triangle of L^-1: 1, 2 or 3 entries
         const double li0 = E[r3], li1 = m >= 1 ? E[r3 + 1] : 0.0, li2 = m >= 2 ? E[r3 + 2] : 0.0;
         const double am = li0 * v[SRK_WF_AP] + li1 * v[SRK_WF_AP + 1] + li2 * v[SRK_WF_AP + 2];
         const double bm = li0 * v[SRK_WF_BP] + li1 * v[SRK_WF_BP + 1] + li2 * v[SRK_WF_BP + 2];
-        z[0] = am * v[SRK_WF_AF0];
-        z[1] = bm * v[SRK_WF_BF1];
-        z[2] = am * v[SRK_WF_G];
-        z[3] = bm * v[SRK_WF_G];
+        if constexpr (FV == 10) {
+            z[0] = am * v[SRK_WF_AF0];
+            z[1] = bm * v[SRK_WF_BF1];
+            z[2] = am * v[SRK_WF_G];
+            z[3] = bm * v[SRK_WF_G];
+        }
 #pragma unroll
-        for (int i = 4; i < 10; ++i) z[i] = am * v[SRK_WF_AF4 + i - 4] + bm * v[SRK_WF_BF4 + i - 4];
+        for (int i = 4; i < 10; ++i) z[i - SRK_FV_OFF(FV)] = am * v[SRK_WF_AF4 + i - 4] + bm * v[SRK_WF_BF4 + i - 4];
         return E[6 + m];
     };
     {
@@ -1810,19 +1888,19 @@ __global__ __launch_bounds__(SRK_MM_THREADS) void k_schur_mm(
             if (st == 2) irr[1 + atomicAdd(&irr[0], 1)] = (int32_t)(p0 + tid);
         }
         __syncthreads(); // sE; sRhs is zeroed
-        double2* wp = reinterpret_cast<double2*>(sBuf + rd * WB + (3 * pl + sm) * LDW + 10 * a);
+        double2* wp = reinterpret_cast<double2*>(sBuf + rd * WB + (3 * pl + sm) * LDW + FV * a);
         if (row_on) {
-            double z[10];
+            double z[FV];
             const double hm = z_row(v, sE[rd * PB + pl], sm, z);
 #pragma unroll
-            for (int i = 0; i < 5; ++i) wp[i] = make_double2(z[2 * i], z[2 * i + 1]);
+            for (int i = 0; i < FH; ++i) wp[i] = make_double2(z[2 * i], z[2 * i + 1]);
             if (!DET) {
 #pragma unroll
-                for (int i = 0; i < 10; ++i) atomicAdd(&sRhs[10 * a + i], z[i] * hm);
+                for (int i = 0; i < FV; ++i) atomicAdd(&sRhs[FV * a + i], z[i] * hm);
             }
         } else if (masked && cell) {
 #pragma unroll
-            for (int i = 0; i < 5; ++i) wp[i] = make_double2(0.0, 0.0);
+            for (int i = 0; i < FH; ++i) wp[i] = make_double2(0.0, 0.0);
         }
     }
     const int nt = (nf10 + 15) >> 4; // tile rows of the sum
@@ -1851,11 +1929,11 @@ __global__ __launch_bounds__(SRK_MM_THREADS) void k_schur_mm(
         // for its two scalars and two for each of its ten entries, and its ten entries leave as five 16-byte LDS writes: ~40.
         const int sm = h / QMAX, sq = h - sm * QMAX;
         const int pl = sq / nf, a = sq - pl * nf;
-        const int dst = (3 * pl + sm) * LDW + 10 * a;
-        double v[NV], racc[10];
+        const int dst = (3 * pl + sm) * LDW + FV * a;
+        double v[NV], racc[FV];
         bool row_on = false, cell = false;
 #pragma unroll
-        for (int i = 0; i < 10; ++i) racc[i] = 0;
+        for (int i = 0; i < FV; ++i) racc[i] = 0;
         auto load_round = [&](int r) { // global loads of round r (left in flight)
             unsigned voff;
             if constexpr (masked) {
@@ -1872,17 +1950,17 @@ __global__ __launch_bounds__(SRK_MM_THREADS) void k_schur_mm(
         auto stage_round = [&](int r, double* bw) {
             const int pb = r * PB;
             const int nb = np - pb < PB ? np - pb : PB;
-            double2* wp = reinterpret_cast<double2*>(bw + dst); // (3 pl + m) LDW + 10 a: 16-byte aligned
+            double2* wp = reinterpret_cast<double2*>(bw + dst); // (3 pl + m) LDW + FV a: 16-byte aligned
             if (row_on) {
-                double z[10];
+                double z[FV];
                 const double hm = z_row(v, sE[pb + pl], sm, z);
 #pragma unroll
-                for (int i = 0; i < 5; ++i) wp[i] = make_double2(z[2 * i], z[2 * i + 1]);
+                for (int i = 0; i < FH; ++i) wp[i] = make_double2(z[2 * i], z[2 * i + 1]);
 #pragma unroll
-                for (int i = 0; i < 10; ++i) racc[i] = fma(z[i], hm, racc[i]);
+                for (int i = 0; i < FV; ++i) racc[i] = fma(z[i], hm, racc[i]);
             } else if (masked && cell) { // the landmark does not see this frame (or the round is short): a block of zeros
 #pragma unroll
-                for (int i = 0; i < 5; ++i) wp[i] = make_double2(0.0, 0.0);
+                for (int i = 0; i < FH; ++i) wp[i] = make_double2(0.0, 0.0);
             }
             // a short last round: the k rows of the landmarks it does not have must not carry an earlier round's data
             if (nb < PB)
@@ -1922,10 +2000,10 @@ __global__ __launch_bounds__(SRK_MM_THREADS) void k_schur_mm(
         if (sm < 3 && pl < PB) {
             if (DET) { // every product is done (the loop's last barrier): the arena's first round buffer takes the lanes' sums
 #pragma unroll
-                for (int i = 0; i < 10; ++i) sBuf[dst + i] = racc[i];
+                for (int i = 0; i < FV; ++i) sBuf[dst + i] = racc[i];
             } else {
 #pragma unroll
-                for (int i = 0; i < 10; ++i) atomicAdd(&sRhs[10 * a + i], racc[i]);
+                for (int i = 0; i < FV; ++i) atomicAdd(&sRhs[FV * a + i], racc[i]);
             }
         }
     } else {
@@ -2005,6 +2083,10 @@ __global__ __launch_bounds__(SRK_MM_THREADS) void k_schur_mm(
             else if (wvu == 10) double_rounds([&](const double* bw) { schur_mm_steps_row<1>(acc, bw, lbase); });
             else double_rounds([&](const double* bw) { schur_mm_steps_row<2>(acc, bw, lbase); });
 #endif
+        } else if constexpr (FV == 6) {
+            // at most 8 x 8 tiles (120 columns): the row-major deal gives every wave slots 0 .. 2 at most
+            static_assert(SRK_WS_NF * 6 <= 8 * 16 && 8 * 9 / 2 <= 3 * SRK_MM_CW, "6-wide grid");
+            double_rounds([&](const double* bw) { schur_mm_steps_n<3>(acc, bw, ta, tb, lbase); });
         } else {
             double_rounds([&](const double* bw) { schur_mm_steps(acc, bw, bw, ta, tb, lbase); }); // idle slots multiply tile (0, 0)
         }
@@ -2297,6 +2379,19 @@ void srk_launch_schur_grouped(hipStream_t s, const SrkDims& d, double c, const i
                               int fp32_accumulate, int32_t* irr, int64_t n_mm_uniform, int64_t n_mm_ragged, const SrkDetSchur* det)
 {
     if (n_groups <= 0) return;
+    if (d.fv == 6) {
+        // fixed intrinsics (fp64 storage and sums only, never deterministic): the runs over at most SRK_WS_NF frames on 6-wide
+        // blocks; the host hands every other landmark to the per-landmark kernel (srk_launch_schur)
+        if (n_mm_uniform + n_mm_ragged > 0) {
+            if (n_mm_ragged > 0)
+                hipLaunchKernelGGL((k_schur_mm<double, 1, false, 6>), dim3((unsigned)n_groups), dim3(SRK_MM_THREADS), 0, s, d, c, row_ptr,
+                                   obs_pt, obs_slot, pt_mask, W, Vg, S, rhs, grp_first, grp_count, grp_nf, grp_frames, irr, nullptr, nullptr);
+            else
+                hipLaunchKernelGGL((k_schur_mm<double, 0, false, 6>), dim3((unsigned)n_groups), dim3(SRK_MM_THREADS), 0, s, d, c, row_ptr,
+                                   obs_pt, obs_slot, pt_mask, W, Vg, S, rhs, grp_first, grp_count, grp_nf, grp_frames, irr, nullptr, nullptr);
+        }
+        return;
+    }
     // runs over at most SRK_WS_NF frames go to the MFMA kernel, fp64 only (the opt-in fp32 accumulation keeps the packed
     // FMA register-tile kernel).  SRK_SCHUR_NO_WS / SRK_SCHUR_VALU: development switches back to the register-tile kernels.
 #ifdef SRK_DEV
@@ -2362,46 +2457,47 @@ void srk_launch_schur_grouped(hipStream_t s, const SrkDims& d, double c, const i
 // The last SRK_ASM_TAIL workgroups serve the landmarks k_schur_mm's SYRK form handed back (a point block that passes the
 // determinant check without positive pivots; irr[0] = how many, normally none): the per-landmark inverse path.
 #define SRK_ASM_TAIL 8
-template <typename WT>
+template <typename WT, int FV = 10>
 __global__ __launch_bounds__(256) void k_assemble(SrkDims d, double c, const double* __restrict__ Ug, double* __restrict__ S,
                                                   double* __restrict__ rhs, double ident, const int64_t* __restrict__ row_ptr,
                                                   const int32_t* __restrict__ obs_frame, const WT* __restrict__ W,
                                                   const double* __restrict__ Vg, const int32_t* __restrict__ irr)
 {
+    constexpr int UGS = SRK_UGS(FV), UT = FV * (FV + 1) / 2; // Ug: FV (FV + 1) / 2 block entries + FV gradient entries a frame
     if (blockIdx.x >= gridDim.x - SRK_ASM_TAIL) {
         const int n = irr ? irr[0] : 0;
         if (n <= 0) return;
         __shared__ SchurLmScratch sm;
         for (int li = (int)(blockIdx.x - (gridDim.x - SRK_ASM_TAIL)); li < n; li += SRK_ASM_TAIL)
-            schur_one_landmark<WT>(d, c, row_ptr, obs_frame, W, Vg, S, rhs, irr[1 + li], sm);
+            schur_one_landmark<WT, FV>(d, c, row_ptr, obs_frame, W, Vg, S, rhs, irr[1 + li], sm);
         return;
     }
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t nblk = (int64_t)d.M * 110;
+    int64_t nblk = (int64_t)d.M * (FV * FV + FV);
     if (t < nblk) {
-        int64_t j = t / 110;
-        int e = (int)(t - j * 110);
-        const double* u = Ug + j * SRK_UG;
-        if (e < 100) {
-            int v1 = e / 10, v2 = e - v1 * 10;
-            int64_t row = 10 * j + v1, col = 10 * j + v2;
-            bool fr = srk_is_fixed_var(row, d), fc = srk_is_fixed_var(col, d);
+        int64_t j = t / (FV * FV + FV);
+        int e = (int)(t - j * (FV * FV + FV));
+        const double* u = Ug + j * UGS;
+        if (e < FV * FV) {
+            int v1 = e / FV, v2 = e - v1 * FV;
+            int64_t row = FV * j + v1, col = FV * j + v2;
+            bool fr = srk_is_fixed_var_fv<FV>(row, d), fc = srk_is_fixed_var_fv<FV>(col, d);
             if (fr || fc) {
                 if (v1 == v2) S[row * d.ld + col] = ident;
             } else {
                 int a = v1 < v2 ? v1 : v2, b = v1 < v2 ? v2 : v1;
-                double val = u[a * 10 - a * (a - 1) / 2 + (b - a)];
+                double val = u[a * FV - a * (a - 1) / 2 + (b - a)];
                 if (v1 == v2) val *= 1 + c;
                 S[row * d.ld + col] += val;
             }
         } else {
-            int v = e - 100;
-            int64_t row = 10 * j + v;
-            if (srk_is_fixed_var(row, d)) rhs[row] = 0.0;
-            else rhs[row] -= u[55 + v];
+            int v = e - FV * FV;
+            int64_t row = FV * j + v;
+            if (srk_is_fixed_var_fv<FV>(row, d)) rhs[row] = 0.0;
+            else rhs[row] -= u[UT + v];
         }
     } else {
-        int64_t p = 10 * (int64_t)d.M + (t - nblk);
+        int64_t p = FV * (int64_t)d.M + (t - nblk);
         if (p < d.ld) {
             S[p * d.ld + p] = ident;
             rhs[p] = 0.0;
@@ -2412,9 +2508,12 @@ __global__ __launch_bounds__(256) void k_assemble(SrkDims d, double c, const dou
 void srk_launch_assemble(hipStream_t s, const SrkDims& d, double c, const double* Ug, double* S, double* rhs, double ident,
                          const int64_t* row_ptr, const int32_t* obs_frame, const double* W, const double* Vg, const int32_t* irr)
 {
-    int64_t n = (int64_t)d.M * 110 + (d.ld - 10 * (int64_t)d.M);
+    const int fv = d.fv == 6 ? 6 : 10;
+    int64_t n = (int64_t)d.M * (fv * fv + fv) + (d.ld - fv * (int64_t)d.M);
     const dim3 grid((unsigned)((n + 255) / 256 + SRK_ASM_TAIL));
-    if (d.w_f32)
+    if (fv == 6)
+        hipLaunchKernelGGL((k_assemble<double, 6>), grid, dim3(256), 0, s, d, c, Ug, S, rhs, ident, row_ptr, obs_frame, W, Vg, irr);
+    else if (d.w_f32)
         hipLaunchKernelGGL(k_assemble<float>, grid, dim3(256), 0, s, d, c, Ug, S, rhs, ident, row_ptr, obs_frame,
                            reinterpret_cast<const float*>(W), Vg, irr);
     else hipLaunchKernelGGL(k_assemble<double>, grid, dim3(256), 0, s, d, c, Ug, S, rhs, ident, row_ptr, obs_frame, W, Vg, irr);
@@ -2434,7 +2533,7 @@ void srk_launch_symmetrize(hipStream_t s, int64_t n, int64_t ld, double* S)
 
 // ------------------------------------------------------------------ K5: back-substitution + landmark update
 // thread per observation: t = W_ij dc_j (3-vector), segmented wave reduction by landmark, one atomic per segment
-template <typename WT>
+template <typename WT, int FV = 10>
 __global__ __launch_bounds__(256) void k_backsub_obs(SrkDims d, const int32_t* __restrict__ obs_frame,
                                                      const int32_t* __restrict__ obs_pt, const WT* __restrict__ W,
                                                      const double* __restrict__ dc, double* __restrict__ acc)
@@ -2445,18 +2544,27 @@ __global__ __launch_bounds__(256) void k_backsub_obs(SrkDims d, const int32_t* _
     double t[3] = { 0, 0, 0 };
     if (o < d.O) {
         pt = obs_pt[o];
-        const double* x = dc + 10 * (int64_t)obs_frame[o];
+        constexpr int off = SRK_FV_OFF(FV); // FV = 6: the frame's corrections are [Tx Ty Tz Wx Wy Wz], the intrinsic ones absent
+        const double* x = dc + FV * (int64_t)obs_frame[o];
         double xv[10];
 #pragma unroll
-        for (int fv = 0; fv < 10; ++fv) xv[fv] = x[fv];
+        for (int fv = off; fv < 10; ++fv) xv[fv] = x[fv - off];
         {
             // W x = Ap (Af . x) + Bp (Bf . x): 21 loads and 22 multiply-adds instead of 30 and 30
             const WT* wp = W + o;
-            const double gq = wp[(int64_t)SRK_WF_G * d.Os];
-            double sa = wp[(int64_t)SRK_WF_AF0 * d.Os] * xv[0] + gq * xv[2];
-            double sb = wp[(int64_t)SRK_WF_BF1 * d.Os] * xv[1] + gq * xv[3];
+            double sa = 0, sb = 0;
+            if (FV == 10) {
+                const double gq = wp[(int64_t)SRK_WF_G * d.Os];
+                sa = wp[(int64_t)SRK_WF_AF0 * d.Os] * xv[0] + gq * xv[2];
+                sb = wp[(int64_t)SRK_WF_BF1 * d.Os] * xv[1] + gq * xv[3];
+            }
 #pragma unroll
             for (int fv = 4; fv < 10; ++fv) {
+                if (FV == 6 && fv == 4) {
+                    sa = wp[(int64_t)SRK_WF_AF4 * d.Os] * xv[4];
+                    sb = wp[(int64_t)SRK_WF_BF4 * d.Os] * xv[4];
+                    continue;
+                }
                 sa += wp[(int64_t)(SRK_WF_AF4 + fv - 4) * d.Os] * xv[fv];
                 sb += wp[(int64_t)(SRK_WF_BF4 + fv - 4) * d.Os] * xv[fv];
             }
@@ -2516,7 +2624,9 @@ void srk_launch_backsub(hipStream_t s, const SrkDims& d, double c, const int32_t
     // the int right behind acc
     if (d.O > 0) {
         int64_t blocks = (d.O + 255) / 256;
-        if (d.w_f32)
+        if (d.fv == 6)
+            hipLaunchKernelGGL((k_backsub_obs<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, obs_frame, obs_pt, W, dc, acc);
+        else if (d.w_f32)
             hipLaunchKernelGGL(k_backsub_obs<float>, dim3((unsigned)blocks), dim3(256), 0, s, d, obs_frame, obs_pt,
                                reinterpret_cast<const float*>(W), dc, acc);
         else
@@ -2530,7 +2640,9 @@ void srk_launch_backsub(hipStream_t s, const SrkDims& d, double c, const int32_t
 }
 
 // ------------------------------------------------------------------ K6: camera update
-// T_direct += dT ; R_direct <- Rodrigues(dW) R_direct unless |dW| ~ 0 ; store the inverse pose (:2021-2062, :59-92)
+// T_direct += dT ; R_direct <- Rodrigues(dW) R_direct unless |dW| ~ 0 ; store the inverse pose (:2021-2062, :59-92).
+// The intrinsic corrections are never applied (:2025-2033 adds them to a copy of K), so FV = 6 reads the pose part alone.
+template <int FV = 10>
 __global__ void k_cam_apply(int32_t M, const double* __restrict__ R, const double* __restrict__ T,
                             const double* __restrict__ dc, double* __restrict__ Rn, double* __restrict__ Tn,
                             const double* __restrict__ K, double f0, double* __restrict__ pack /* of the new pose, or null */)
@@ -2539,13 +2651,14 @@ __global__ void k_cam_apply(int32_t M, const double* __restrict__ R, const doubl
     if (j >= M) return;
     const double* r = R + 9 * (int64_t)j;
     const double* t = T + 3 * (int64_t)j;
-    const double* x = dc + 10 * (int64_t)j;
+    constexpr int off = SRK_FV_OFF(FV);
+    const double* x = dc + FV * (int64_t)j; // T corrections at x[4 - off], W corrections at x[7 - off]
     double Rd[9], Td[3];
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) Rd[3 * a + b] = r[3 * b + a];
     for (int a = 0; a < 3; ++a) Td[a] = -(Rd[3 * a] * t[0] + Rd[3 * a + 1] * t[1] + Rd[3 * a + 2] * t[2]);
-    Td[0] += x[4]; Td[1] += x[5]; Td[2] += x[6];
-    double w0 = x[7], w1 = x[8], w2 = x[9];
+    Td[0] += x[4 - off]; Td[1] += x[5 - off]; Td[2] += x[6 - off];
+    double w0 = x[7 - off], w1 = x[8 - off], w2 = x[9 - off];
     double ang = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
     double Rnew[9];
     // IsClose(0, ang): |ang| <= 1e-8 + 1e-5 * |max(0, ang)|  (approx-alg.h:8-16, obs-geom.cpp:555-556)
@@ -2580,9 +2693,10 @@ __global__ void k_cam_apply(int32_t M, const double* __restrict__ R, const doubl
 }
 
 void srk_launch_cam_apply(hipStream_t s, int32_t M, const double* R, const double* T, const double* dc, double* Rn,
-                          double* Tn, const double* K, double f0, double* pack)
+                          double* Tn, const double* K, double f0, double* pack, int fv)
 {
-    hipLaunchKernelGGL(k_cam_apply, dim3((M + 63) / 64), dim3(64), 0, s, M, R, T, dc, Rn, Tn, K, f0, pack);
+    if (fv == 6) hipLaunchKernelGGL(k_cam_apply<6>, dim3((M + 63) / 64), dim3(64), 0, s, M, R, T, dc, Rn, Tn, K, f0, pack);
+    else hipLaunchKernelGGL(k_cam_apply<10>, dim3((M + 63) / 64), dim3(64), 0, s, M, R, T, dc, Rn, Tn, K, f0, pack);
 }
 
 // ------------------------------------------------------------------ K1: reprojection error

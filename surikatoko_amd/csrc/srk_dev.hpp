@@ -12,8 +12,11 @@
 //            f32 storage mode: the same 21 planes as floats ([21][Os], plane k of observation o at W[k*Os + o]); widened on load
 //   Vg       [9][Ns]   per point: V00 V01 V02 V11 V12 V22 g0 g1 g2 (SoA, Ns = N rounded up to 64)
 //   Ug       [M][65]   per frame: 55 upper-triangle entries of the 10x10 block (row-major order) + 10 gradient
+//            (fixed intrinsics, fv = 6: [M][27], 21 entries of the 6x6 pose block + 6 gradient; W then carries 18 planes:
+//            AF0, G and BF1 are not written)
 //   S        [ld][ld]  padded reduced camera system, row-major, LOWER triangle authoritative;
-//            variable index = 10*frame + var; the 7 gauge-fixed variables and the padding rows
+//            variable index = fv*frame + var (fv = 10, or 6 = [Tx Ty Tz Wx Wy Wz] with fixed intrinsics: SrkDims::fv);
+//            the 7 gauge-fixed variables and the padding rows
 //            carry an identity diagonal and zero rhs, so their correction is exactly 0
 //   rhs,dc   [ld]
 #pragma once
@@ -23,6 +26,9 @@
 
 #define SRK_CAM_PACK 48
 #define SRK_UG 65
+// frame sums a frame keeps in Ug for FV frame variables: the upper triangle of the FV x FV block (row-major) + FV gradient
+// entries -- 65 for the reference's ten, 21 + 6 = 27 with fixed intrinsics (SrkDims::fv = 6)
+#define SRK_UGS(FV) ((FV) * ((FV) + 1) / 2 + (FV))
 // fp64 storage of the point-frame blocks: the rank-2 factors of W[pv][fv] = Ap[pv] Af[fv] + Bp[pv] Bf[fv] as SoA planes
 // (srk_ba_kernels.hip: "storage of the point-frame blocks"); Af[1] = Af[3] = Bf[0] = Bf[2] = 0, Af[2] = Bf[3] = G
 #define SRK_WF_AP 0   // planes 0..2   Ap[0..2]
@@ -37,6 +43,8 @@
 struct SrkDims {
     int64_t N, O, Os, Ns;
     int32_t M;
+    int32_t fv;          // variables per frame in the reduced camera system: 10, or 6 with fixed intrinsics (variable = fv*frame + var);
+                         // in the padding behind M, so the struct keeps its size and layout
     int64_t ld;          // padded RCS dimension (multiple of SRK_CHOL_NB)
     int32_t comp;        // unity_t1_comp_ind (gauge), 1 by default
     int32_t w_f32;       // 1: the point-frame blocks W are stored as float (W then points at floats), arithmetic stays fp64
@@ -133,7 +141,8 @@ void srk_launch_backsub(hipStream_t s, const SrkDims& d, double c, const int32_t
                         const double* W, const double* Vg, const double* dc, double* acc, const double* pts,
                         double* pts_trial, double* dx);
 void srk_launch_cam_apply(hipStream_t s, int32_t M, const double* R, const double* T, const double* dc, double* Rn,
-                          double* Tn, const double* K, double f0, double* pack /* camera packs of the new poses, or NULL */);
+                          double* Tn, const double* K, double f0, double* pack /* camera packs of the new poses, or NULL */,
+                          int fv /* dc holds fv corrections per frame: 10, or 6 (pose only) */);
 void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                       const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* partial,
                       int32_t n_partial, double* err_out,
