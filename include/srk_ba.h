@@ -211,7 +211,7 @@ int srk_ba_download_scene(srk_ba*, double* points_xyz, double* cam_R, double* ca
 int srk_ba_reset_scene(srk_ba*);
 
 /* single phases on the resident scene (parity tests and per-kernel timing) */
-int srk_ba_phase_error(srk_ba*, double* err, int64_t* seen);
+int srk_ba_phase_error(srk_ba*, double* err, int64_t* seen); /* err = E = sum rho(s) when a robust loss is set */
 int srk_ba_phase_derivatives(srk_ba*);
 int srk_ba_phase_schur(srk_ba*, double hessian_factor);
 int srk_ba_phase_solve(srk_ba*);                            /* 0 ok, 1 non-finite / not positive definite */
@@ -365,6 +365,29 @@ int srk_ba_frame_vars(srk_ba*);
  * kernels: with fixed intrinsics every landmark outside the runs of <= 20 frames k_schur_mm takes (wider runs, long tracks);
  * otherwise the tracks too long for the long-track kernel.  0 on the circle-grid bench scenes; negative without a scene. */
 int64_t srk_ba_schur_fallback_landmarks(srk_ba*);
+
+/* ---- robust bundle adjustment (EXTENSION) ----
+ * Observation o has the residual (ex, ey) = (p/r - u/f0, q/r - v/f0) and s = ex^2 + ey^2 in the (pix/f0)^2 units of
+ * srk_ba_report::err_initial.  With a loss set, LM minimises E = sum_o rho(s_o) instead of sum_o s_o:
+ *   kind 1, Huber:   rho(s) = s for s <= d^2, 2 d sqrt(s) - d^2 above;   weight w = rho'(s) = min(1, d / sqrt(s))
+ *   kind 2, Cauchy:  rho(s) = d^2 log(1 + s / d^2);                      weight w = 1 / (1 + s / d^2)
+ * with d = delta_pixels / f0.  Every derivative pass (the speculative one included) weights each observation's Gauss-Newton
+ * blocks and gradient terms by its w at the current scene (first-order IRLS, no second-order correction); the weighted
+ * gradient is the exact gradient of E.  E is what the accept / reject test, the relative-change termination,
+ * err_initial / err_final, srk_ba_iteration_log and srk_ba_phase_error report.  srk_ba_reproj_error and
+ * srk_ba_reproj_error_mvf never apply a loss.  Works with every mode the library accepts (fixed intrinsics,
+ * deterministic, f32 storage, fp32 Schur, every Jacobian mode, frame reordering, several ranks).
+ * Takes effect at the next optimise / phase call (srk_ba_compute_inplace and srk_ba_compute_inplace_f32 included); no
+ * re-upload is needed.  kind 0 = none: the reference's plain least squares (default).  SRK_E_ARGS (and a
+ * srk_ba_last_error text) for an unknown kind or, with kind != 0, a delta that is not finite and positive. */
+int srk_ba_set_robust_loss(srk_ba*, int kind /* 0 none, 1 Huber, 2 Cauchy */, double delta_pixels);
+/* the loss set on the handle: kind and delta in pixels (0 with kind 0); either pointer may be NULL */
+int srk_ba_robust_loss(srk_ba*, int* kind, double* delta_pixels);
+/* the IRLS weights w of the resident scene's observations (current scene: after srk_ba_optimize, the result), in the
+ * caller's observation order (the CSR order of the upload; internal landmark and frame orders undone); count = the number
+ * of observations (of this rank's shard with several ranks).  All 1 without a loss.  Observations with w < 1 lie beyond
+ * the threshold: the outliers of a robust solve. */
+int srk_ba_observation_weights(srk_ba*, double* w, int64_t count);
 
 /* device-time instrumentation of srk_ba_optimize / srk_ba_compute_inplace: 0 = none (default; report.ms_* stay 0
  * except ms_total), 1 = one HIP event pair per phase (fills report.ms_*), 2 = additionally event pairs around

@@ -157,6 +157,13 @@ public:
         if (rc < 0) Raise(rc);
     }
 
+    /// EXTENSION: robust bundle adjustment from the next ComputeInplace on (srk_ba_set_robust_loss): kind 0 none, 1 Huber,
+    /// 2 Cauchy, delta in pixels.  Throws std::invalid_argument for an unknown kind or a delta that is not finite and positive.
+    void SetRobustLoss(int kind, Scalar delta) {
+        int rc = srk_ba_set_robust_loss(h_, kind, (double)delta);
+        if (rc < 0) Raise(rc);
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }

@@ -383,6 +383,35 @@ class BundleAdjustmentKanatani:
         self._raise(n)
         return n
 
+    _LOSSES = {None: 0, "none": 0, "huber": 1, "cauchy": 2}
+
+    def set_robust_loss(self, kind=None, delta=1.0):
+        """Robust bundle adjustment: kind "huber", "cauchy" or None (plain least squares, the
+        default) with the scale delta in pixels.  Takes effect at the next optimise / phase call; ValueError for an unknown
+        kind or a delta that is not finite and positive."""
+        k = kind.lower() if isinstance(kind, str) else kind
+        if k not in self._LOSSES:
+            raise ValueError(f"unknown robust loss {kind!r}: 'huber', 'cauchy' or None")
+        code = self._LOSSES[k]
+        self._raise(self._lib.srk_ba_set_robust_loss(C.c_void_p(self._h), C.c_int(code), C.c_double(delta if code else 0.0)))
+
+    def robust_loss(self):
+        """(kind, delta_pixels): kind "huber", "cauchy" or None"""
+        k, dl = C.c_int(0), C.c_double(0)
+        self._raise(self._lib.srk_ba_robust_loss(C.c_void_p(self._h), C.byref(k), C.byref(dl)))
+        return {0: None, 1: "huber", 2: "cauchy"}[k.value], dl.value
+
+    def observation_weights(self):
+        """IRLS weights w = rho'(s) of the resident scene's observations, in the caller's observation order (all 1 without
+        a loss); outliers of a robust solve have w < 1"""
+        size = int(self._lib.srk_ba_buffer_size(C.c_void_p(self._h), C.c_int(BUF_POINT_FRAME)))
+        self._raise(size)
+        n = size // (3 * self.frame_vars())  # observations of the resident scene (of this rank's shard)
+        w = np.empty(n, dtype=np.float64)
+        self._raise(self._lib.srk_ba_observation_weights(C.c_void_p(self._h), w.ctypes.data_as(C.POINTER(C.c_double)),
+                                                         C.c_int64(n)))
+        return w
+
     def schur_fallback_landmarks(self):
         """landmarks of the uploaded scene that take the per-landmark Schur kernel (srk_ba_schur_fallback_landmarks)"""
         fn = self._lib.srk_ba_schur_fallback_landmarks

@@ -169,6 +169,8 @@ struct srk_ba {
     bool schur_fp32 = false; // opt-in mixed precision: fp32 run sums in the grouped Schur kernel
     bool store_f32 = false;  // opt-in: the point-frame blocks W are STORED as float (next upload); arithmetic stays fp64
     bool fixed_k = false;    // opt-in: calibrated BA, six pose variables per frame (next upload; srk_ba_set_fixed_intrinsics)
+    int loss_kind = SRK_LOSS_NONE; // opt-in: robust loss (srk_ba_set_robust_loss); takes effect at the next optimise / phase call
+    double loss_delta_pix = 0;     // its scale in pixels; the kernels get delta / f0 (robust_loss below)
     int profile_level = 0; // 0 = no events, 1 = phase events (report.ms_*), 2 = + event pairs around the MFMA updates
     bool chol_fused = true; // the solve's outer steps as one launch each (k_step256); srk_ba_set_solver_fusion
     // what the caller asked for.  A hand-off timeout switches chol_fused off for the rest of that call; the next upload /
@@ -2036,15 +2038,27 @@ static int coll_group(srk_ba* h, int op, int G, double* const* ptrs, const int64
 
 // with_status: {solver info, point-update finite flag (lives behind acc)} are packed next to the error scalar and
 // summed over the ranks with it, so every rank takes the same accept / reject decision
+// the robust loss for the kernels: NULL when none is set, so the plain least-squares kernels run
+static const SrkLoss* robust_loss(const srk_ba* h, SrkLoss& L)
+{
+    if (h->loss_kind == SRK_LOSS_NONE) return nullptr;
+    L.kind = h->loss_kind;
+    L.d = h->loss_delta_pix / h->f0;
+    L.d2 = L.d * L.d;
+    return &L;
+}
+
 static int phase_error(srk_ba* h, int which, double* err_host, bool with_status = false, bool no_exchange = false)
 {
     const SrkDims& d = h->d;
     hipStream_t s = h->stream;
     int32_t np = srk_error_partials(d);
+    SrkLoss L;
     srk_launch_error(s, d, P<double>(h->pts[which]), P<double>(h->cam[which]), P<int32_t>(h->obs_frame),
                      P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(h->A->err_partial), np, h->A->err_dst,
                      h->jac_fused ? P<int32_t>(h->wg_jmin) : nullptr, with_status ? P<int>(h->A->info) : nullptr,
-                     with_status ? reinterpret_cast<int*>(reinterpret_cast<char*>(h->A->acc.p) + 8 * 3 * d.Ns) : nullptr);
+                     with_status ? reinterpret_cast<int*>(reinterpret_cast<char*>(h->A->acc.p) + 8 * 3 * d.Ns) : nullptr,
+                     robust_loss(h, L));
     HIPCHK(h, hipGetLastError());
     int rc = no_exchange ? SRK_OK : exchange(h, h->A->err_dst, with_status ? 3 : 1);
     if (rc != SRK_OK) return rc;
@@ -2064,6 +2078,8 @@ static int phase_derivatives(srk_ba* h)
     HIPCHK(h, hipMemsetAsync(h->Ug.p, 0, 8 * SRK_UGS(d.fv) * (int64_t)d.M, s));
     if (h->profile_level >= 1) HIPCHK(h, hipEventRecord(h->ev[12], s));
     const SrkDetJac detj{ P<double>(h->dj_stage), P<int32_t>(h->dj_ptr), P<int32_t>(h->dj_ent) };
+    SrkLoss Ls;
+    const SrkLoss* L = robust_loss(h, Ls); // the IRLS weights, recomputed in every derivative pass
     if (h->jac_runs) {
         srk_launch_jac_runs(s, d, P<double>(h->pts[c]), P<double>(h->cam[c]), P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame),
                             P<double>(h->obs_uv), P<double>(h->W), P<double>(h->Vg), P<double>(h->Ug), P<int32_t>(h->jr_first),
@@ -2072,19 +2088,19 @@ static int phase_derivatives(srk_ba* h)
                             h->jr_own_runs ? P<int32_t>(h->jd_nf) : P<int32_t>(h->grp_nf),
                             h->jr_own_runs ? P<int32_t>(h->jd_frames) : P<int32_t>(h->grp_frames),
                             h->jr_own_runs ? P<uint32_t>(h->jd_mask) : P<uint32_t>(h->pt_mask), h->det_active ? &detj : nullptr,
-                            h->jr_own_runs ? 32 : SRK_GRP_MAXNF_HOST);
+                            h->jr_own_runs ? 32 : SRK_GRP_MAXNF_HOST, L);
         if (h->profile_level >= 1) HIPCHK(h, hipEventRecord(h->ev[13], s));
     } else if (h->jac_fused) {
         srk_launch_jac_fused(s, d, P<double>(h->pts[c]), P<double>(h->cam[c]), P<int32_t>(h->obs_frame),
                              P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(h->W), P<double>(h->Vg),
-                             P<double>(h->Ug), P<int32_t>(h->wg_jmin));
+                             P<double>(h->Ug), P<int32_t>(h->wg_jmin), L);
         if (h->profile_level >= 1) HIPCHK(h, hipEventRecord(h->ev[13], s));
     } else {
         srk_launch_jac_points(s, d, P<double>(h->pts[c]), P<double>(h->cam[c]), P<int32_t>(h->obs_frame),
-                              P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(h->W), P<double>(h->Vg));
+                              P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(h->W), P<double>(h->Vg), L);
         if (h->profile_level >= 1) HIPCHK(h, hipEventRecord(h->ev[13], s));
         srk_launch_jac_frames(s, d, h->max_frame_obs, P<double>(h->pts[c]), P<double>(h->cam[c]),
-                              P<int64_t>(h->col_ptr), P<int32_t>(h->fobs_pt), P<double>(h->fobs_uv), P<double>(h->Ug));
+                              P<int64_t>(h->col_ptr), P<int32_t>(h->fobs_pt), P<double>(h->fobs_uv), P<double>(h->Ug), L);
     }
     HIPCHK(h, hipGetLastError());
     // landmark shards: Ug stays this rank's partial sum; it enters the reduced camera system before that is summed
@@ -3501,6 +3517,67 @@ int64_t srk_ba_schur_fallback_landmarks(srk_ba* h)
 {
     if (!h || !h->have_scene) return SRK_E_STATE;
     return h->d.fv == 6 ? h->n_cal_list : h->n_generic;
+}
+
+// robust loss: 0 none (plain least squares, the reference's objective), 1 Huber, 2 Cauchy, with the
+// scale delta in pixels.  Takes effect at the next optimise / phase call; the scene, skyline and plan stay as they are.
+int srk_ba_set_robust_loss(srk_ba* h, int kind, double delta_pixels)
+{
+    if (!h) return SRK_E_ARGS;
+    if (kind < SRK_LOSS_NONE || kind > SRK_LOSS_CAUCHY) { h->last_error = "set_robust_loss: unknown loss kind"; return SRK_E_ARGS; }
+    if (kind != SRK_LOSS_NONE && !(std::isfinite(delta_pixels) && delta_pixels > 0)) {
+        h->last_error = "set_robust_loss: delta must be finite and positive";
+        return SRK_E_ARGS;
+    }
+    h->loss_kind = kind;
+    h->loss_delta_pix = kind == SRK_LOSS_NONE ? 0.0 : delta_pixels;
+    return SRK_OK;
+}
+int srk_ba_robust_loss(srk_ba* h, int* kind, double* delta_pixels)
+{
+    if (!h) return SRK_E_ARGS;
+    if (kind) *kind = h->loss_kind;
+    if (delta_pixels) *delta_pixels = h->loss_delta_pix;
+    return SRK_OK;
+}
+// the IRLS weights of the resident scene's observations in the caller's order (the CSR order of the upload); all 1
+// without a loss.  Scene of this rank: count = its observations.
+int srk_ba_observation_weights(srk_ba* h, double* w, int64_t count)
+{
+    if (!h || !h->have_scene || !w) return SRK_E_STATE;
+    const SrkDims& d = h->d;
+    if (count != d.O) { h->last_error = "observation_weights: count must be the number of observations"; return SRK_E_ARGS; }
+    if (d.O == 0) return SRK_OK;
+    SrkLoss Ls;
+    const SrkLoss* L = robust_loss(h, Ls);
+    if (!L) {
+        std::fill(w, w + d.O, 1.0);
+        return SRK_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    HIPCHK(h, hipStreamSynchronize(s));
+    DevBuf wd;
+    int rc = dev_alloc(h, wd, (size_t)(8 * d.O));
+    if (rc != SRK_OK) return rc;
+    std::vector<double> wi((size_t)d.O);
+    srk_launch_obs_weights(s, d, P<double>(h->pts[h->cur]), P<double>(h->cam[h->cur]), P<int32_t>(h->obs_frame),
+                           P<int32_t>(h->obs_pt), P<double>(h->obs_uv), *L, P<double>(wd));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(wi.data(), wd.p, (size_t)(8 * d.O), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    dev_free(wd);
+    HIPCHK(h, e);
+    // internal order -> the caller's: landmark perm, observation rank inside the landmark (as SRK_BUF_POINT_FRAME)
+    for (int64_t i = 0; i < d.N; ++i) {
+        const int64_t oi = h->row_ptr_int[(size_t)i], ou = h->row_ptr_user[(size_t)h->perm[(size_t)i]];
+        const int64_t cnt = h->row_ptr_int[(size_t)i + 1] - oi;
+        for (int64_t a = 0; a < cnt; ++a) {
+            const int64_t ai = h->obs_rank.empty() ? a : h->obs_rank[(size_t)(ou + a)];
+            w[ou + a] = wi[(size_t)(oi + ai)];
+        }
+    }
+    return SRK_OK;
 }
 
 // knob for bench.py: event pairs around every MFMA trailing-update launch (report.ms_solve_syrk)

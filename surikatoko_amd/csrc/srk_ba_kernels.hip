@@ -145,6 +145,38 @@ __device__ __forceinline__ void obs_pqr(const double* __restrict__ c, double X0,
     g.s2 = g.s1 * ir2;
 }
 
+// ------------------------------------------------------------------ robust loss (srk_ba_set_robust_loss)
+// The derivative kernels end in a parameter pack `Loss...`: empty, it is the plain least-squares kernel (signature and
+// device code as without the pack); one SrkLoss, the robust instantiation (the loss kind and threshold are runtime values).
+template <typename... Loss> struct SrkRobust {
+    static_assert(sizeof...(Loss) == 0 || (sizeof...(Loss) == 1 && (std::is_same_v<Loss, SrkLoss> && ...)), "Loss: none or one SrkLoss");
+    static constexpr bool on = sizeof...(Loss) == 1;
+};
+template <typename... Loss> __device__ __forceinline__ const SrkLoss& srk_loss(const Loss&... L) { return (L, ...); }
+
+// (w, rho) of one observation from its residual: s = ex^2 + ey^2, rho(s) its term of the objective, w = rho'(s) its IRLS
+// weight.  Every robust kernel that forms an observation's contribution calls this once, so V, U, W and the gradient all
+// see the same w.  Below the threshold (Huber s <= d^2) w is exactly 1 and rho is s itself: the kernels fold w (and
+// sqrt(w)) into scale factors they multiply anyway, and a multiply by 1.0 is exact, so a threshold above every residual
+// reproduces the plain kernels' values bit for bit.
+__device__ __forceinline__ void srk_robust_wr(double ex, double ey, const SrkLoss& L, double& w, double& rho)
+{
+    const double s = ex * ex + ey * ey;
+    w = 1.0;
+    rho = s;
+    if (L.kind == SRK_LOSS_HUBER) {
+        if (s > L.d2) {
+            const double rs = sqrt(s);
+            w = L.d / rs;
+            rho = 2.0 * L.d * rs - L.d2;
+        }
+    } else if (L.kind == SRK_LOSS_CAUCHY) {
+        const double t = s / L.d2;
+        w = 1.0 / (1.0 + t);
+        rho = L.d2 * log1p(t);
+    }
+}
+
 // A_v = r p'_v - p r'_v , B_v = r q'_v - q r'_v for the three landmark variables (:1450-1455)
 __device__ __forceinline__ void point_ab(const double* __restrict__ c, const ObsGeom& g, double A[3], double B[3])
 {
@@ -190,13 +222,14 @@ __device__ __forceinline__ void frame_ab(const double* __restrict__ c, const Obs
 // One thread per observation.  Writes the 3x10 point-frame block (SoA, lane-contiguous 8-byte stores) and
 // reduces the point block V (6 unique) + point gradient (3) over the landmark's observations with a
 // wavefront segmented reduction; one atomic per (wave, landmark) segment.
-template <typename WT, int FV = 10> // storage type of the point-frame blocks W: double, or float (srk_ba_set_storage_precision)
+// Loss (one SrkLoss: robust): every term carries the observation's weight w -- sqrt(w) on the stored factors, w on the sums
+template <typename WT, int FV = 10, typename... Loss> // WT: storage type of the point-frame blocks W: double, or float (srk_ba_set_storage_precision)
 __global__ __launch_bounds__(256) void k_jac_points(SrkDims d, const double* __restrict__ pts,
                                                     const double* __restrict__ cam,
                                                     const int32_t* __restrict__ obs_frame,
                                                     const int32_t* __restrict__ obs_pt,
                                                     const double* __restrict__ obs_uv, WT* __restrict__ W,
-                                                    double* __restrict__ Vg)
+                                                    double* __restrict__ Vg, Loss... L)
 {
     int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int lane = threadIdx.x & (WAVE - 1);
@@ -218,7 +251,16 @@ __global__ __launch_bounds__(256) void k_jac_points(SrkDims d, const double* __r
         point_ab(c, g, Ap, Bp);
         frame_ab(c, g, X0, X1, X2, Af, Bf);
         {
-            const double sc = 0.7071067811865476 * g.s1; // sqrt(2 / r^4): both sides of every product carry it once
+            double sc = 0.7071067811865476 * g.s1; // sqrt(2 / r^4): both sides of every product carry it once
+            if constexpr (SrkRobust<Loss...>::on) {
+                double w, rho;
+                srk_robust_wr(g.ex, g.ey, srk_loss(L...), w, rho);
+                if (w != 1.0) { // (an inlier's w is exactly 1: nothing to scale, no square root)
+                    sc *= sqrt(w);
+                    g.s1 *= w;
+                    g.s2 *= w;
+                }
+            }
             double Aps[3], Bps[3], Afs[10], Bfs[10];
 #pragma unroll
             for (int v = 0; v < 3; ++v) { Aps[v] = Ap[v] * sc; Bps[v] = Bp[v] * sc; }
@@ -274,14 +316,14 @@ __device__ __forceinline__ double jf_rcp(double d)
     return r;
 }
 
-template <typename WT, int FV = 10>
+template <typename WT, int FV = 10, typename... Loss>
 __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __restrict__ pts,
                                                    const double* __restrict__ cam,
                                                    const int32_t* __restrict__ obs_frame,
                                                    const int32_t* __restrict__ obs_pt,
                                                    const double* __restrict__ obs_uv, WT* __restrict__ W,
                                                    double* __restrict__ Vg, double* __restrict__ Ug,
-                                                   const int32_t* __restrict__ wg_jmin)
+                                                   const int32_t* __restrict__ wg_jmin, Loss... L)
 {
     constexpr int UGS = SRK_UGS(FV), UT = FV * (FV + 1) / 2, off = SRK_FV_OFF(FV);
     __shared__ double sU[SRK_JF_SLOTS][UGS + 1];                              // frame blocks + frame gradients
@@ -326,7 +368,13 @@ __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __re
             const double q = c[15] * xc0 + c[16] * xc1 + c[17] * xc2;
             const double r = c[18] * xc0 + c[19] * xc1 + c[20] * xc2;
             const double ir = jf_rcp(r), ir2 = ir * ir;
-            const double s1 = 2 * ir2, s2 = s1 * ir2; // 2 / r^2 , 2 / r^4
+            double s1 = 2 * ir2, s2 = s1 * ir2; // 2 / r^2 , 2 / r^4 (robust: both times w; sc below then carries sqrt(w))
+            if constexpr (SrkRobust<Loss...>::on) {
+                double w, rho;
+                srk_robust_wr(p * ir - uv.x * c[46], q * ir - uv.y * c[46], srk_loss(L...), w, rho);
+                s1 *= w;
+                s2 *= w;
+            }
             const double ex1 = (p * ir - uv.x * c[46]) * s1, ey1 = (q * ir - uv.y * c[46]) * s1;
             // A_v = r p'_v - p r'_v , B_v = r q'_v - q r'_v
             double Ap[3], Bp[3], Af[10], Bf[10];
@@ -427,10 +475,23 @@ __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __re
 
 void srk_launch_jac_fused(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                           const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* W,
-                          double* Vg, double* Ug, const int32_t* wg_jmin)
+                          double* Vg, double* Ug, const int32_t* wg_jmin, const SrkLoss* loss)
 {
     if (d.O == 0) return;
     int64_t blocks = (d.O + SRK_JF_OBS - 1) / SRK_JF_OBS;
+    if (loss && loss->kind != SRK_LOSS_NONE) {
+        const dim3 grid((unsigned)blocks);
+        if (d.fv == 6)
+            hipLaunchKernelGGL((k_jac_fused<double, 6, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W, Vg,
+                               Ug, wg_jmin, *loss);
+        else if (d.w_f32)
+            hipLaunchKernelGGL((k_jac_fused<float, 10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+                               reinterpret_cast<float*>(W), Vg, Ug, wg_jmin, *loss);
+        else
+            hipLaunchKernelGGL((k_jac_fused<double, 10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W,
+                               Vg, Ug, wg_jmin, *loss);
+        return;
+    }
     if (d.fv == 6)
         hipLaunchKernelGGL((k_jac_fused<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
                            W, Vg, Ug, wg_jmin);
@@ -470,7 +531,7 @@ void srk_launch_jac_fused(hipStream_t s, const SrkDims& d, const double* pts, co
 // (landmark m of the step, frame slot f of the union): the cell's observation is the landmark's first one plus the number of
 // mask bits below the slot; a cell the landmark does not see computes nothing and adds zeros to the landmark's sums.  A lane
 // still stays on one frame for the whole task.  The landmarks' first observations and masks sit in a per-wave LDS table.
-template <typename WT, bool MASKED, bool DET = false, int FV = 10>
+template <typename WT, bool MASKED, bool DET = false, int FV = 10, typename... Loss>
 __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __restrict__ pts,
                                                      const double* __restrict__ cam,
                                                      const int64_t* __restrict__ row_ptr,
@@ -482,7 +543,8 @@ __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __
                                                      const int32_t* __restrict__ wg_jmin,
                                                      const int32_t* __restrict__ task_group, const int32_t* __restrict__ grp_nf,
                                                      const int32_t* __restrict__ grp_frames, const uint32_t* __restrict__ pt_mask,
-                                                     double* __restrict__ det_stage /* DET: [task][64][SRK_UG] */, int frames_stride)
+                                                     double* __restrict__ det_stage /* DET: [task][64][SRK_UG] */, int frames_stride,
+                                                     Loss... L)
 {
     // FV = 6 (fixed intrinsics): 21 + 6 frame sums (the pose block and gradient), 18 stored factor planes
     constexpr int UGS = SRK_UGS(FV), UT = FV * (FV + 1) / 2, off = SRK_FV_OFF(FV);
@@ -582,8 +644,18 @@ __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __
                 // A's and B's scaled by sqrt(2) / r^2 once, the blocks are plain products and the gradient terms carry
                 // sqrt(2) ex, sqrt(2) ey (no second, pre-scaled copy of the 26 values: they would not fit the registers
                 // beside the 65 frame sums).
-                const double sc = 1.4142135623730951 * ir2;
-                const double exs = (p * ir - uv.x * c[46]) * 1.4142135623730951, eys = (q * ir - uv.y * c[46]) * 1.4142135623730951;
+                double sc = 1.4142135623730951 * ir2;
+                double exs = (p * ir - uv.x * c[46]) * 1.4142135623730951, eys = (q * ir - uv.y * c[46]) * 1.4142135623730951;
+                if constexpr (SrkRobust<Loss...>::on) { // sqrt(w) on both sides of every product
+                    double w, rho;
+                    srk_robust_wr(p * ir - uv.x * c[46], q * ir - uv.y * c[46], srk_loss(L...), w, rho);
+                    if (w != 1.0) { // (an inlier's w is exactly 1: nothing to scale, no square root)
+                        const double sw = sqrt(w);
+                        sc *= sw;
+                        exs *= sw;
+                        eys *= sw;
+                    }
+                }
                 const double rs = r * sc, ps = p * sc, qs = q * sc;
                 double Ap[3], Bp[3], Af[10], Bf[10];
 #pragma unroll
@@ -702,7 +774,7 @@ void srk_launch_jac_runs(hipStream_t s, const SrkDims& d, const double* pts, con
                          const int32_t* obs_frame, const double* obs_uv, double* W, double* Vg, double* Ug,
                          const int32_t* task_first, const int32_t* task_count, int32_t n_tasks, const int32_t* wg_jmin,
                          const int32_t* task_group, const int32_t* grp_nf, const int32_t* grp_frames, const uint32_t* pt_mask,
-                         const SrkDetJac* det, int frames_stride)
+                         const SrkDetJac* det, int frames_stride, const SrkLoss* loss)
 {
     if (n_tasks <= 0) return;
     const dim3 grid((unsigned)((n_tasks + 3) / 4));
@@ -717,11 +789,30 @@ void srk_launch_jac_runs(hipStream_t s, const SrkDims& d, const double* pts, con
             else hipLaunchKernelGGL((k_jac_runs<double, MASKED, false>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));                         \
         }                                                                                                                             \
     } while (0)
+    // the robust instantiations: the same choices, the loss behind the last argument
+#define SRK_JR_LAUNCH_ROBUST(MASKED)                                                                                                  \
+    do {                                                                                                                              \
+        if (det) {                                                                                                                    \
+            if (d.w_f32) hipLaunchKernelGGL((k_jac_runs<float, MASKED, true, 10, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(reinterpret_cast<float*>(W)), *loss); \
+            else hipLaunchKernelGGL((k_jac_runs<double, MASKED, true, 10, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);     \
+        } else {                                                                                                                      \
+            if (d.w_f32) hipLaunchKernelGGL((k_jac_runs<float, MASKED, false, 10, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(reinterpret_cast<float*>(W)), *loss); \
+            else hipLaunchKernelGGL((k_jac_runs<double, MASKED, false, 10, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);    \
+        }                                                                                                                             \
+    } while (0)
+    const bool robust = loss && loss->kind != SRK_LOSS_NONE;
     if (d.fv == 6) { // fixed intrinsics: fp64 storage, never deterministic
-        if (task_group) hipLaunchKernelGGL((k_jac_runs<double, true, false, 6>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));
+        if (robust) {
+            if (task_group) hipLaunchKernelGGL((k_jac_runs<double, true, false, 6, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);
+            else hipLaunchKernelGGL((k_jac_runs<double, false, false, 6, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);
+        } else if (task_group) hipLaunchKernelGGL((k_jac_runs<double, true, false, 6>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));
         else hipLaunchKernelGGL((k_jac_runs<double, false, false, 6>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));
+    } else if (robust) {
+        if (task_group) SRK_JR_LAUNCH_ROBUST(true);
+        else SRK_JR_LAUNCH_ROBUST(false);
     } else if (task_group) SRK_JR_LAUNCH(true); // tasks over unions of frame lists (ragged tracks)
     else SRK_JR_LAUNCH(false);
+#undef SRK_JR_LAUNCH_ROBUST
 #undef SRK_JR_LAUNCH
 #undef SRK_JR_ARGS
     if (det) hipLaunchKernelGGL(k_jac_det_gather, dim3((unsigned)d.M), dim3(128), 0, s, d.M, det->ptr, det->ent, det->stage, Ug);
@@ -729,10 +820,23 @@ void srk_launch_jac_runs(hipStream_t s, const SrkDims& d, const double* pts, con
 
 void srk_launch_jac_points(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                            const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* W,
-                           double* Vg)
+                           double* Vg, const SrkLoss* loss)
 {
     if (d.O == 0) return;
     int64_t blocks = (d.O + 255) / 256;
+    if (loss && loss->kind != SRK_LOSS_NONE) {
+        const dim3 grid((unsigned)blocks);
+        if (d.fv == 6)
+            hipLaunchKernelGGL((k_jac_points<double, 6, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W, Vg,
+                               *loss);
+        else if (d.w_f32)
+            hipLaunchKernelGGL((k_jac_points<float, 10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+                               reinterpret_cast<float*>(W), Vg, *loss);
+        else
+            hipLaunchKernelGGL((k_jac_points<double, 10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W,
+                               Vg, *loss);
+        return;
+    }
     if (d.fv == 6)
         hipLaunchKernelGGL((k_jac_points<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
                            W, Vg);
@@ -756,12 +860,12 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-template <int FV = 10>
+template <int FV = 10, typename... Loss>
 __global__ __launch_bounds__(256) void k_jac_frames(SrkDims d, const double* __restrict__ pts,
                                                     const double* __restrict__ cam,
                                                     const int64_t* __restrict__ col_ptr,
                                                     const int32_t* __restrict__ fobs_pt,
-                                                    const double* __restrict__ fobs_uv, double* __restrict__ Ug)
+                                                    const double* __restrict__ fobs_uv, double* __restrict__ Ug, Loss... L)
 {
     constexpr int UGS = SRK_UGS(FV), UT = FV * (FV + 1) / 2, off = SRK_FV_OFF(FV); // FV = 6: the pose block and gradient
     __shared__ double red[4][UGS];
@@ -781,6 +885,12 @@ __global__ __launch_bounds__(256) void k_jac_frames(SrkDims d, const double* __r
         double X0 = X[0], X1 = X[1], X2 = X[2];
         ObsGeom g;
         obs_pqr(c, X0, X1, X2, uv.x, uv.y, g);
+        if constexpr (SrkRobust<Loss...>::on) {
+            double w, rho;
+            srk_robust_wr(g.ex, g.ey, srk_loss(L...), w, rho);
+            g.s1 *= w;
+            g.s2 *= w;
+        }
         double Af[10], Bf[10];
         frame_ab(c, g, X0, X1, X2, Af, Bf);
         int idx = 0;
@@ -809,10 +919,18 @@ __global__ __launch_bounds__(256) void k_jac_frames(SrkDims d, const double* __r
 
 void srk_launch_jac_frames(hipStream_t s, const SrkDims& d, int64_t max_frame_obs, const double* pts,
                            const double* cam, const int64_t* col_ptr, const int32_t* fobs_pt, const double* fobs_uv,
-                           double* Ug)
+                           double* Ug, const SrkLoss* loss)
 {
     if (d.O == 0 || max_frame_obs == 0) return;
     int64_t chunks = (max_frame_obs + SRK_FCHUNK - 1) / SRK_FCHUNK;
+    if (loss && loss->kind != SRK_LOSS_NONE) {
+        const dim3 grid((unsigned)chunks, (unsigned)d.M);
+        if (d.fv == 6)
+            hipLaunchKernelGGL((k_jac_frames<6, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, col_ptr, fobs_pt, fobs_uv, Ug, *loss);
+        else
+            hipLaunchKernelGGL((k_jac_frames<10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, col_ptr, fobs_pt, fobs_uv, Ug, *loss);
+        return;
+    }
     if (d.fv == 6)
         hipLaunchKernelGGL(k_jac_frames<6>, dim3((unsigned)chunks, (unsigned)d.M), dim3(256), 0, s, d, pts, cam, col_ptr,
                            fobs_pt, fobs_uv, Ug);
@@ -2779,6 +2897,103 @@ __global__ __launch_bounds__(256) void k_error_staged(SrkDims d, const double* _
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// ---- robust loss: the sum of rho(s) instead of s, same partial sums and fixed-order final sum.
+// (Kernels of their own rather than a pack on k_error / k_error_staged, whose names carry no template.)
+// the residual of one observation as k_error forms it (divisions, not the derivative kernels' reciprocal)
+__device__ __forceinline__ void err_residual(const double* c /* R T K: 0..20 */, double f0, const double* __restrict__ X,
+                                             double2 uv, double& ex, double& ey)
+{
+    double X0 = X[0], X1 = X[1], X2 = X[2];
+    double xc0 = c[0] * X0 + c[1] * X1 + c[2] * X2 + c[9];
+    double xc1 = c[3] * X0 + c[4] * X1 + c[5] * X2 + c[10];
+    double xc2 = c[6] * X0 + c[7] * X1 + c[8] * X2 + c[11];
+    double p = c[12] * xc0 + c[13] * xc1 + c[14] * xc2;
+    double q = c[15] * xc0 + c[16] * xc1 + c[17] * xc2;
+    double r = c[18] * xc0 + c[19] * xc1 + c[20] * xc2;
+    ex = p / r - uv.x / f0;
+    ey = q / r - uv.y / f0;
+}
+
+__global__ __launch_bounds__(256) void k_error_robust(SrkDims d, const double* __restrict__ pts,
+                                                      const double* __restrict__ cam, const int32_t* __restrict__ obs_frame,
+                                                      const int32_t* __restrict__ obs_pt, const double* __restrict__ obs_uv,
+                                                      double* __restrict__ partial, SrkLoss L)
+{
+    __shared__ double red[4];
+    double sum = 0;
+    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < d.O; o += (int64_t)gridDim.x * 256) {
+        const double* c = cam + (int64_t)SRK_CAM_PACK * obs_frame[o];
+        double ex, ey, w, rho;
+        err_residual(c, c[47], pts + 3 * (int64_t)obs_pt[o], reinterpret_cast<const double2*>(obs_uv)[o], ex, ey);
+        srk_robust_wr(ex, ey, L, w, rho);
+        sum += rho;
+    }
+    sum = wave_sum(sum);
+    int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = sum;
+    lds_barrier();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void k_error_staged_robust(SrkDims d, const double* __restrict__ pts,
+                                                             const double* __restrict__ cam, const int32_t* __restrict__ obs_frame,
+                                                             const int32_t* __restrict__ obs_pt, const double* __restrict__ obs_uv,
+                                                             const int32_t* __restrict__ wg_jmin, double* __restrict__ partial,
+                                                             SrkLoss L)
+{
+    __shared__ double sCam[SRK_JF_SLOTS][23]; // as k_error_staged
+    __shared__ double red[4];
+    const int jmin = wg_jmin[blockIdx.x];
+    {
+        const int nfr = d.M - jmin < SRK_JF_SLOTS ? d.M - jmin : SRK_JF_SLOTS;
+        for (int t = threadIdx.x; t < nfr * 22; t += 256) {
+            const int js = t / 22, e = t - js * 22;
+            sCam[js][e] = cam[(int64_t)SRK_CAM_PACK * (jmin + js) + (e < 21 ? e : 47)];
+        }
+    }
+    lds_barrier();
+    const int64_t o_first = (int64_t)blockIdx.x * SRK_JF_OBS;
+    double sum = 0;
+#pragma unroll
+    for (int ch = 0; ch < SRK_JF_CHUNKS; ++ch) {
+        const int64_t o = o_first + ch * 256 + threadIdx.x;
+        if (o >= d.O) break;
+        const double* c = sCam[obs_frame[o] - jmin];
+        double ex, ey, w, rho;
+        err_residual(c, c[21], pts + 3 * (int64_t)obs_pt[o], reinterpret_cast<const double2*>(obs_uv)[o], ex, ey);
+        srk_robust_wr(ex, ey, L, w, rho);
+        sum += rho;
+    }
+    sum = wave_sum(sum);
+    int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = sum;
+    lds_barrier();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// the IRLS weight of every observation of the resident scene, internal order (srk_ba_observation_weights maps it back to the
+// caller's order): the residual as the error pass forms it
+__global__ __launch_bounds__(256) void k_obs_weights(SrkDims d, const double* __restrict__ pts, const double* __restrict__ cam,
+                                                     const int32_t* __restrict__ obs_frame, const int32_t* __restrict__ obs_pt,
+                                                     const double* __restrict__ obs_uv, SrkLoss L, double* __restrict__ w_out)
+{
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= d.O) return;
+    const double* c = cam + (int64_t)SRK_CAM_PACK * obs_frame[o];
+    double ex, ey, w, rho;
+    err_residual(c, c[47], pts + 3 * (int64_t)obs_pt[o], reinterpret_cast<const double2*>(obs_uv)[o], ex, ey);
+    srk_robust_wr(ex, ey, L, w, rho);
+    w_out[o] = w;
+}
+
+void srk_launch_obs_weights(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int32_t* obs_frame,
+                            const int32_t* obs_pt, const double* obs_uv, const SrkLoss& loss, double* w)
+{
+    if (d.O == 0) return;
+    hipLaunchKernelGGL(k_obs_weights, dim3((unsigned)((d.O + 255) / 256)), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+                       loss, w);
+}
+
 // scoring variant (MultiViewIterativeFactorizer::ReprojError, multi-view-factorization.cpp:415-475): observations whose
 // homogeneous image point has |z| <= z_tol are skipped (:455-457) and the summands are counted; z_tol < 0 keeps all.
 // partial[0 .. grid) = error sums, partial[grid .. 2 grid) = counts.
@@ -2854,17 +3069,26 @@ int64_t srk_error_partials_staged(const SrkDims& d) { return d.O > 0 ? (d.O + SR
 
 void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                       const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* partial,
-                      int32_t n_partial, double* err_out, const int32_t* wg_jmin, int* info, int* info2)
+                      int32_t n_partial, double* err_out, const int32_t* wg_jmin, int* info, int* info2, const SrkLoss* loss)
 {
+    const bool robust = loss && loss->kind != SRK_LOSS_NONE;
     if (wg_jmin && d.O > 0) { // staged cameras: one partial sum per run of SRK_JF_OBS observations
         const int64_t nb = srk_error_partials_staged(d);
-        hipLaunchKernelGGL(k_error_staged, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, wg_jmin,
-                           partial);
+        if (robust)
+            hipLaunchKernelGGL(k_error_staged_robust, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+                               wg_jmin, partial, *loss);
+        else
+            hipLaunchKernelGGL(k_error_staged, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, wg_jmin,
+                               partial);
         hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, (int32_t)nb, partial, err_out, info, info2);
         return;
     }
-    hipLaunchKernelGGL(k_error, dim3((unsigned)n_partial), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                       partial);
+    if (robust)
+        hipLaunchKernelGGL(k_error_robust, dim3((unsigned)n_partial), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+                           partial, *loss);
+    else
+        hipLaunchKernelGGL(k_error, dim3((unsigned)n_partial), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+                           partial);
     hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, n_partial, partial, err_out, info, info2);
 }
 

@@ -72,19 +72,31 @@ struct SrkDetSchur {
     const int32_t *f_ptr, *f_ent; // per frame: run | slot << 20
 };
 
+// ---- robust loss (srk_ba_set_robust_loss): observation o with squared residual s = ex^2 + ey^2 ((pix/f0)^2) enters the
+// objective as rho(s) and the normal equations with the IRLS weight w = rho'(s).  Kinds: SRK_LOSS_HUBER rho = s for s <= d^2,
+// 2 d sqrt(s) - d^2 above; SRK_LOSS_CAUCHY rho = d^2 log(1 + s / d^2).  d = delta_pixels / f0.  The launchers below take a
+// loss pointer: NULL (or kind 0) launches the plain least-squares kernels, anything else their robust instantiations.
+#define SRK_LOSS_NONE 0
+#define SRK_LOSS_HUBER 1
+#define SRK_LOSS_CAUCHY 2
+struct SrkLoss {
+    int32_t kind; // SRK_LOSS_*
+    double d, d2; // threshold in normalised units (pix / f0) and its square
+};
+
 // ---- BA kernels (srk_ba_kernels.hip) ----
 void srk_launch_cam_pack(hipStream_t s, int32_t M, const double* R, const double* T, const double* K, double f0,
                          double* pack);
 void srk_launch_jac_points(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                            const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* W,
-                           double* Vg);
+                           double* Vg, const SrkLoss* loss = nullptr);
 // fused single pass (point blocks + frame blocks); usable when every workgroup's frame range fits SRK_JF_SLOTS_HOST
 #define SRK_JF_OBS_HOST 1024
 #define SRK_JF_SLOTS_HOST 48
 #define SRK_JF_PMAX_HOST 448
 void srk_launch_jac_fused(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                           const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* W,
-                          double* Vg, double* Ug, const int32_t* wg_jmin);
+                          double* Vg, double* Ug, const int32_t* wg_jmin, const SrkLoss* loss = nullptr);
 // run-based single pass: one wave per task = consecutive landmarks with identical frame lists (nf <= 64 frames), about
 // SRK_JR_TASK_PTS_MIN_HOST .. MAX_HOST of them; four consecutive tasks (one workgroup) must touch fewer than
 // SRK_JF_SLOTS_HOST consecutive frames
@@ -96,10 +108,11 @@ void srk_launch_jac_runs(hipStream_t s, const SrkDims& d, const double* pts, con
                          const int32_t* task_group /* NULL: uniform runs; else the Schur run (grp_*) each task is a piece of */,
                          const int32_t* grp_nf, const int32_t* grp_frames, const uint32_t* pt_mask,
                          const SrkDetJac* det = nullptr /* deterministic mode */,
-                         int frames_stride = 24 /* row length of grp_frames: SRK_GRP_MAXNF_HOST (the Schur runs) or 32 (the derivative kernel's own) */);
+                         int frames_stride = 24 /* row length of grp_frames: SRK_GRP_MAXNF_HOST (the Schur runs) or 32 (the derivative kernel's own) */,
+                         const SrkLoss* loss = nullptr);
 void srk_launch_jac_frames(hipStream_t s, const SrkDims& d, int64_t max_frame_obs, const double* pts,
                            const double* cam, const int64_t* col_ptr, const int32_t* fobs_pt, const double* fobs_uv,
-                           double* Ug);
+                           double* Ug, const SrkLoss* loss = nullptr);
 void srk_launch_schur(hipStream_t s, const SrkDims& d, double c, const int64_t* row_ptr, const int32_t* obs_frame,
                       const double* W, const double* Vg, double* S, double* rhs, const int32_t* pt_list,
                       int64_t n_list);
@@ -147,7 +160,11 @@ void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const 
                       const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* partial,
                       int32_t n_partial, double* err_out,
                       const int32_t* wg_jmin /* fused-Jacobian frame windows, or NULL: gather the cameras */,
-                      int* info = nullptr, int* info2 = nullptr /* given: packed into err_out[1..2] and cleared */);
+                      int* info = nullptr, int* info2 = nullptr /* given: packed into err_out[1..2] and cleared */,
+                      const SrkLoss* loss = nullptr /* given (kind != 0): the sum of rho(s) instead of s */);
+// the IRLS weights w = rho'(s) of the resident scene, one per observation in the internal order (srk_ba_observation_weights)
+void srk_launch_obs_weights(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int32_t* obs_frame,
+                            const int32_t* obs_pt, const double* obs_uv, const SrkLoss& loss, double* w);
 int32_t srk_error_partials(const SrkDims& d);
 int64_t srk_error_partials_staged(const SrkDims& d); // partial sums written when wg_jmin is given
 void srk_launch_error_score(hipStream_t s, int64_t O, const double* pts, const double* cam, const int32_t* obs_frame,
