@@ -1437,11 +1437,32 @@ const char* orc_status_string(int status)
     }
 }
 
+/* per-attempt record of orc_compute_inplace_log (test instrumentation: observes the loop, never steers it) */
+typedef struct {
+    int64_t cap, n;
+    int64_t* iteration;
+    double *factor, *err_trial, *err_value;
+    int32_t* outcome;
+} orc_attempt_log;
+
+static void log_attempt(orc_attempt_log* lg, int64_t iteration, double factor, double err_trial, double err_value,
+                        int32_t outcome)
+{
+    if (!lg) return;
+    int64_t k = lg->n++;
+    if (k >= lg->cap) return;
+    if (lg->iteration) lg->iteration[k] = iteration;
+    if (lg->factor) lg->factor[k] = factor;
+    if (lg->err_trial) lg->err_trial[k] = err_trial;
+    if (lg->err_value) lg->err_value[k] = err_value;
+    if (lg->outcome) lg->outcome[k] = outcome;
+}
+
 /* BA:617-718 ComputeInplace + BA:720-893 ComputeOnNormalizedWorld */
-int orc_compute_inplace(double f0, int64_t N, double* points, int32_t M, double* cam_R, double* cam_T,
-                        const double* K, int32_t shared_k, const int64_t* row_ptr, const int32_t* obs_frame,
-                        const double* obs_uv, const double* allowed_err_change, const double* max_hessian_factor,
-                        int64_t max_iterations, int32_t dense_literal, orc_report* rep)
+static int compute_inplace_impl(double f0, int64_t N, double* points, int32_t M, double* cam_R, double* cam_T,
+                                const double* K, int32_t shared_k, const int64_t* row_ptr, const int32_t* obs_frame,
+                                const double* obs_uv, const double* allowed_err_change, const double* max_hessian_factor,
+                                int64_t max_iterations, int32_t dense_literal, orc_report* rep, orc_attempt_log* lg)
 {
     orc_report local;
     if (!rep) rep = &local;
@@ -1502,23 +1523,41 @@ int orc_compute_inplace(double f0, int64_t N, double* points, int32_t M, double*
             rep->attempts += 1;
             int suc = orc_two_phase(N, M, row_ptr, obs_frame, gradE, Vpp, Uff, Wpf, hessian_factor, comp, dense_literal,
                                     corr, NULL, NULL, &rep->sec_schur, &rep->sec_solve, &rep->sec_backsub);
-            if (!suc) { decrease = 2; break; } /* :807-808 */
+            if (!suc) { /* :807-808 */
+                log_attempt(lg, rep->iterations, hessian_factor, NAN, err_value, ORC_ATTEMPT_SOLVE_FAILED);
+                decrease = 2;
+                break;
+            }
             tt = now_sec();
             orc_apply_corrections(N, points, M, cam_R, cam_T, corr);
             rep->sec_apply += now_sec() - tt;
             tt = now_sec();
             err_new = orc_reproj_error(f0, N, points, M, cam_R, cam_T, K, shared_k, row_ptr, obs_frame, obs_uv, NULL);
             rep->sec_error += now_sec() - tt;
-            if (err_new - err_value < 0) { decrease = 1; break; } /* :816-819 */
+            if (err_new - err_value < 0) { /* :816-819 */
+                log_attempt(lg, rep->iterations, hessian_factor, err_new, err_value, ORC_ATTEMPT_ACCEPTED);
+                decrease = 1;
+                break;
+            }
             memcpy(points, pts_bak, sizeof(double) * (size_t)(3 * N)); /* :823-826 */
             memcpy(cam_R, R_bak, sizeof(double) * (size_t)(9 * (int64_t)M));
             memcpy(cam_T, T_bak, sizeof(double) * (size_t)(3 * (int64_t)M));
             if (have_prev && allowed_err_change) { /* :828-838 */
                 double change = err_new - err_new_prev;
-                if (fabs(change) < *allowed_err_change) { decrease = 3; break; }
+                if (fabs(change) < *allowed_err_change) {
+                    log_attempt(lg, rep->iterations, hessian_factor, err_new, err_value, ORC_ATTEMPT_CONVERGED);
+                    decrease = 3;
+                    break;
+                }
             }
+            const double factor_used = hessian_factor;
             hessian_factor *= 10; /* :841 */
-            if (max_hessian_factor && hessian_factor > *max_hessian_factor) { decrease = 2; break; } /* :843-847 */
+            if (max_hessian_factor && hessian_factor > *max_hessian_factor) { /* :843-847 */
+                log_attempt(lg, rep->iterations, factor_used, err_new, err_value, ORC_ATTEMPT_CAP_OVERFLOW);
+                decrease = 2;
+                break;
+            }
+            log_attempt(lg, rep->iterations, factor_used, err_new, err_value, ORC_ATTEMPT_REJECTED);
             err_new_prev = err_new;
             have_prev = 1;
         }
@@ -1543,4 +1582,27 @@ int orc_compute_inplace(double f0, int64_t N, double* points, int32_t M, double*
     orc_revert_normalization(N, points, M, cam_R, cam_T, &nrm); /* :706 */
     free(gradE); free(Vpp); free(Uff); free(Wpf); free(corr); free(pts_bak); free(R_bak); free(T_bak);
     return result_true ? 0 : 1;
+}
+
+int orc_compute_inplace(double f0, int64_t N, double* points, int32_t M, double* cam_R, double* cam_T,
+                        const double* K, int32_t shared_k, const int64_t* row_ptr, const int32_t* obs_frame,
+                        const double* obs_uv, const double* allowed_err_change, const double* max_hessian_factor,
+                        int64_t max_iterations, int32_t dense_literal, orc_report* rep)
+{
+    return compute_inplace_impl(f0, N, points, M, cam_R, cam_T, K, shared_k, row_ptr, obs_frame, obs_uv,
+                                allowed_err_change, max_hessian_factor, max_iterations, dense_literal, rep, NULL);
+}
+
+int orc_compute_inplace_log(double f0, int64_t N, double* points, int32_t M, double* cam_R, double* cam_T,
+                            const double* K, int32_t shared_k, const int64_t* row_ptr, const int32_t* obs_frame,
+                            const double* obs_uv, const double* allowed_err_change, const double* max_hessian_factor,
+                            int64_t max_iterations, int32_t dense_literal, orc_report* rep, int64_t log_cap,
+                            int64_t* log_iteration, double* log_factor, double* log_err_trial, double* log_err_value,
+                            int32_t* log_outcome, int64_t* log_n)
+{
+    orc_attempt_log lg = { log_cap, 0, log_iteration, log_factor, log_err_trial, log_err_value, log_outcome };
+    int rc = compute_inplace_impl(f0, N, points, M, cam_R, cam_T, K, shared_k, row_ptr, obs_frame, obs_uv,
+                                  allowed_err_change, max_hessian_factor, max_iterations, dense_literal, rep, &lg);
+    if (log_n) *log_n = lg.n;
+    return rc;
 }

@@ -224,13 +224,33 @@ def apply_corrections(sc, corr):
     lib().orc_apply_corrections(C.c_int64(sc.N), _d(sc.points), C.c_int32(sc.M), _d(sc.cam_R), _d(sc.cam_T), _d(corr))
 
 
-def compute_inplace(f0, sc, allowed_err_change=None, max_hessian_factor=None, max_iterations=0, dense_literal=False):
+def compute_inplace(f0, sc, allowed_err_change=None, max_hessian_factor=None, max_iterations=0, dense_literal=False,
+                    want_log=False):
+    """(rc, report) of ComputeInplace; with want_log (rc, report, log): log = one entry per attempt, a dict of arrays
+    iteration, factor, err_trial, err_value, outcome (orc_compute_inplace_log; the format of tests/lm_trajectory.py)"""
     rep = Report()
     a = C.byref(C.c_double(allowed_err_change)) if allowed_err_change is not None else None
     m = C.byref(C.c_double(max_hessian_factor)) if max_hessian_factor is not None else None
-    rc = lib().orc_compute_inplace(C.c_double(f0), *sc._args(), a, m, C.c_int64(max_iterations),
-                                   C.c_int32(int(dense_literal)), C.byref(rep))
-    return rc, rep
+    if not want_log:
+        rc = lib().orc_compute_inplace(C.c_double(f0), *sc._args(), a, m, C.c_int64(max_iterations),
+                                       C.c_int32(int(dense_literal)), C.byref(rep))
+        return rc, rep
+    cap = 1 << 12
+    while True:
+        bak = sc.copy()
+        it, fac, et, ev = np.zeros(cap, dtype=np.int64), np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        out, n = np.zeros(cap, dtype=np.int32), C.c_int64(0)
+        rc = lib().orc_compute_inplace_log(C.c_double(f0), *sc._args(), a, m, C.c_int64(max_iterations),
+                                           C.c_int32(int(dense_literal)), C.byref(rep), C.c_int64(cap), _i64(it), _d(fac),
+                                           _d(et), _d(ev), _i32(out), C.byref(n))
+        if n.value <= cap:
+            break
+        for k in ("points", "cam_R", "cam_T"):  # the log did not fit: the same run again from the same scene
+            getattr(sc, k)[:] = getattr(bak, k)
+        cap = int(n.value)
+    n = int(n.value)
+    log = {"iteration": it[:n], "factor": fac[:n], "err_trial": et[:n], "err_value": ev[:n], "outcome": out[:n]}
+    return rc, rep, log
 
 
 def fd_point(f0, sc, pi, eps=1e-5):

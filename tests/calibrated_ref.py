@@ -9,6 +9,8 @@ The LM loop restates bundle-adj-kanatani.cpp:720-893 with the decisions of orc_c
 """
 import numpy as np
 
+import lm_trajectory as lt
+
 FV = 6
 INTR = slice(0, 4)  # [fx fy u0 v0] of the 10-variable layout
 
@@ -100,6 +102,8 @@ def compute_inplace(orc, f0, so, allowed_err_change=None, max_hessian_factor=Non
     rep = Report()
     rep.status, rep.iterations, rep.attempts = 0, 0, 0
     rep.attempts_per_iteration = []
+    rep.log = lt.AttemptLog().arrays()
+    log = lt.AttemptLog()
     ok, nrm = orc.normalize(so)
     if not ok:
         return 1, rep
@@ -127,21 +131,27 @@ def compute_inplace(orc, f0, so, allowed_err_change=None, max_hessian_factor=Non
             else:
                 suc, corr = orc.two_phase(so, g, V, Ur, Wr, hessian_factor)
             if not suc:
+                log.add(rep.iterations, hessian_factor, np.nan, err_value, lt.SOLVE_FAILED)
                 decrease = 2
                 break
             orc.apply_corrections(so, corr)
             err_new, _ = orc.reproj_error(f0, so)
             if err_new - err_value < 0:
+                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.ACCEPTED)
                 decrease = 1
                 break
             so.points[:], so.cam_R[:], so.cam_T[:] = bak
             if have_prev and allowed_err_change is not None and abs(err_new - err_new_prev) < allowed_err_change:
+                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.CONVERGED)
                 decrease = 3
                 break
+            used = hessian_factor
             hessian_factor *= 10
             if max_hessian_factor is not None and hessian_factor > max_hessian_factor:
+                log.add(rep.iterations, used, err_new, err_value, lt.CAP_OVERFLOW)
                 decrease = 2
                 break
+            log.add(rep.iterations, used, err_new, err_value, lt.REJECTED)
             err_new_prev, have_prev = err_new, True
         rep.attempts_per_iteration.append(n_att)
         if decrease != 1:
@@ -157,5 +167,6 @@ def compute_inplace(orc, f0, so, allowed_err_change=None, max_hessian_factor=Non
         err_value = err_new
         hessian_factor /= 10
     rep.hessian_factor = hessian_factor
+    rep.log = log.arrays()
     orc.revert(so, nrm)
     return (0 if result_true else 1), rep

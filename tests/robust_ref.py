@@ -10,6 +10,8 @@ two_phase / two_phase_skyline on those blocks; the LM loop restates bundle-adj-k
 """
 import numpy as np
 
+import lm_trajectory as lt
+
 import calibrated_ref as cref
 
 NONE, HUBER, CAUCHY = 0, 1, 2
@@ -191,6 +193,8 @@ def compute_inplace(orc, f0, so, kind=NONE, delta=None, allowed_err_change=None,
     rep = Report()
     rep.status, rep.iterations, rep.attempts = 0, 0, 0
     rep.attempts_per_iteration, rep.errors = [], []
+    rep.log = lt.AttemptLog().arrays()
+    log = lt.AttemptLog()
     nrm = None
     if normalize:
         ok, nrm = orc.normalize(so)
@@ -221,21 +225,27 @@ def compute_inplace(orc, f0, so, kind=NONE, delta=None, allowed_err_change=None,
             else:
                 suc, corr = orc.two_phase(so, gradE, V, U, W, hessian_factor)
             if not suc:
+                log.add(rep.iterations, hessian_factor, np.nan, err_value, lt.SOLVE_FAILED)
                 decrease = 2
                 break
             orc.apply_corrections(so, corr)
             err_new = energy(f0, so, kind, delta)
             if err_new - err_value < 0:
+                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.ACCEPTED)
                 decrease = 1
                 break
             so.points[:], so.cam_R[:], so.cam_T[:] = bak
             if have_prev and allowed_err_change is not None and abs(err_new - err_new_prev) < allowed_err_change:
+                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.CONVERGED)
                 decrease = 3
                 break
+            used = hessian_factor
             hessian_factor *= 10
             if max_hessian_factor is not None and hessian_factor > max_hessian_factor:
+                log.add(rep.iterations, used, err_new, err_value, lt.CAP_OVERFLOW)
                 decrease = 2
                 break
+            log.add(rep.iterations, used, err_new, err_value, lt.REJECTED)
             err_new_prev, have_prev = err_new, True
         rep.attempts_per_iteration.append(n_att)
         if decrease != 1:
@@ -252,6 +262,7 @@ def compute_inplace(orc, f0, so, kind=NONE, delta=None, allowed_err_change=None,
         err_value = err_new
         hessian_factor /= 10
     rep.hessian_factor = hessian_factor
+    rep.log = log.arrays()
     if nrm is not None:
         orc.revert(so, nrm)
     return (0 if result_true else 1), rep

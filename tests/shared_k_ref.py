@@ -11,6 +11,8 @@ library and this yardstick work on every frame's K scaled by f0 / K(2,2) (the sa
 """
 import numpy as np
 
+import lm_trajectory as lt
+
 import calibrated_ref as cref
 import robust_ref as rref
 
@@ -135,6 +137,8 @@ def compute_inplace(orc, f0, so, groups, allowed_err_change=None, max_hessian_fa
     rep = Report()
     rep.status, rep.iterations, rep.attempts = 0, 0, 0
     rep.attempts_per_iteration = []
+    rep.log = lt.AttemptLog().arrays()
+    log = lt.AttemptLog()
     ok, nrm = orc.normalize(so)
     if not ok:
         return 1, rep
@@ -158,22 +162,28 @@ def compute_inplace(orc, f0, so, groups, allowed_err_change=None, max_hessian_fa
             n_att += 1
             out = step(orc, f0, so, groups, hessian_factor)
             if not out["ok"] or not np.all(np.isfinite(out["corr"])):
+                log.add(rep.iterations, hessian_factor, np.nan, err_value, lt.SOLVE_FAILED)
                 decrease = 2
                 break
             orc.apply_corrections(so, out["corr10"])
             so.K[:] = apply_k(so.K, out["dc"], M, groups)
             err_new, _ = orc.reproj_error(f0, so)
             if err_new - err_value < 0:
+                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.ACCEPTED)
                 decrease = 1
                 break
             so.points[:], so.cam_R[:], so.cam_T[:], so.K[:] = bak
             if have_prev and allowed_err_change is not None and abs(err_new - err_new_prev) < allowed_err_change:
+                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.CONVERGED)
                 decrease = 3
                 break
+            used = hessian_factor
             hessian_factor *= 10
             if max_hessian_factor is not None and hessian_factor > max_hessian_factor:
+                log.add(rep.iterations, used, err_new, err_value, lt.CAP_OVERFLOW)
                 decrease = 2
                 break
+            log.add(rep.iterations, used, err_new, err_value, lt.REJECTED)
             err_new_prev, have_prev = err_new, True
         rep.attempts_per_iteration.append(n_att)
         if decrease != 1:
@@ -189,5 +199,6 @@ def compute_inplace(orc, f0, so, groups, allowed_err_change=None, max_hessian_fa
         err_value = err_new
         hessian_factor /= 10
     rep.hessian_factor = hessian_factor
+    rep.log = log.arrays()
     orc.revert(so, nrm)
     return (0 if result_true else 1), rep

@@ -13,6 +13,7 @@ import pytest
 import surikatoko_amd as sa
 from surikatoko_amd import ba as B
 from conftest import load_golden, rel_err, sym_scaled_err, class_rel_err
+import lm_trajectory as lt
 
 pytestmark = pytest.mark.gpu
 
@@ -453,6 +454,7 @@ def test_ragged_tracks_end_to_end(orc, gpu):
     rc_o, rep_o, so, ok, rep, sg = _end_to_end(orc, gpu, sc, spec.f0, allowed=1e-7, max_factor=1e6, max_iterations=5)
     assert ok == (rc_o == 0)
     assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts)
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts)
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6)
     assert np.abs(sg.points - so.points).max() < 1e-6
 
@@ -507,6 +509,7 @@ def test_failed_solve_is_hessian_overflow_as_in_the_reference_and_leaves_no_resi
     assert rc_o == 1 and orc.status_string(rep_o.status) == "hessian overflow"
     assert not ok and sa.status_string(rep.status) == "hessian overflow"
     assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts) == (0, 1)
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts)
     assert rep.err_final == rep.err_initial == pytest.approx(rep_o.err_initial, rel=1e-12)
     # the scene is handed back unchanged (up to the normalise / revert round trip), as the reference restores its backup
     assert np.abs(sg.points - bad.points).max() < 1e-9 and np.abs(sg.cam_T - bad.cam_T).max() < 1e-9
@@ -517,6 +520,7 @@ def test_failed_solve_is_hessian_overflow_as_in_the_reference_and_leaves_no_resi
     rc_o, rep_o, so, ok, rep, sg = _end_to_end(orc, gpu, good, spec.f0, allowed=1e-12, max_factor=1e6, max_iterations=30)
     assert ok == (rc_o == 0) and sa.status_string(rep.status) == orc.status_string(rep_o.status)
     assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts)
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts, err_abs=1e-18)
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6, abs=1e-18)
     assert np.abs(sg.points - so.points).max() < 1e-6
 
@@ -557,6 +561,7 @@ def test_failed_solve_on_a_loop_closure_scene_then_reset(orc, gpu):
     rc_o, rep_o, so, ok, rep, sg = _end_to_end(orc, gpu, loop, spec.f0, allowed=1e-10, max_factor=1e6, max_iterations=6)
     assert ok == (rc_o == 0) and sa.status_string(rep.status) == orc.status_string(rep_o.status)
     assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts) and rep.iterations >= 1
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts, err_abs=1e-18)
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6, abs=1e-18)
     assert np.abs(sg.points - so.points).max() < 1e-6
 
@@ -592,7 +597,7 @@ def test_shared_k_mode(orc, gpu):
 
 def _end_to_end(orc, gpu, sc, f0, allowed=None, max_factor=None, max_iterations=0):
     so = _orc_scene(orc, sc)
-    rc_o, rep_o = orc.compute_inplace(f0, so, allowed, max_factor, max_iterations)
+    rc_o, rep_o, rep_o.log = orc.compute_inplace(f0, so, allowed, max_factor, max_iterations, want_log=True)
     crit = sa.BundleAdjustmentKanataniTermCriteria()
     crit.AllowedReprojErrRelativeChange(allowed)
     crit.MaxHessianFactor(max_factor)
@@ -614,6 +619,7 @@ def test_compute_inplace_matches_oracle(orc, gpu, name, allowed, max_it):
     assert rep.err_initial == pytest.approx(rep_o.err_initial, rel=1e-12)
     # identical accept / reject sequence (a fork on a near tie would show here)
     assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts)
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts, err_abs=1e-18)
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6, abs=1e-18)
     assert np.abs(sg.points - so.points).max() < 1e-6
     assert np.abs(sg.cam_R - so.cam_R).max() < 1e-6
@@ -632,6 +638,7 @@ def test_compute_inplace_iteration_cap_and_report(orc, gpu):
     assert not ok and rc_o == 1
     assert sa.status_string(rep.status) == "max iterations" == orc.status_string(rep_o.status)
     assert rep.iterations == 2 == rep_o.iterations and rep.attempts == rep_o.attempts
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts)
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6)
     assert rep.ms_jacobian > 0 and rep.ms_schur > 0 and rep.ms_solve > 0
     assert np.abs(sg.points - so.points).max() < 1e-6
@@ -701,7 +708,7 @@ def test_c1_dino_standin_end_to_end_vs_oracle(orc, gpu, dense_literal):
     sc = sa.config_scene("C1_dino_standin")
     assert (sc.M, sc.N, sc.O) == (36, 4983, 16432)
     so = _orc_scene(orc, sc)
-    rc_o, rep_o = orc.compute_inplace(600.0, so, 4.56e-8, None, 0, dense_literal=dense_literal)
+    rc_o, rep_o, rep_o.log = orc.compute_inplace(600.0, so, 4.56e-8, None, 0, dense_literal=dense_literal, want_log=True)
     crit = sa.BundleAdjustmentKanataniTermCriteria()
     crit.AllowedReprojErrRelativeChange(4.56e-8)
     sg = sc.copy()
@@ -712,6 +719,7 @@ def test_c1_dino_standin_end_to_end_vs_oracle(orc, gpu, dense_literal):
     assert rep.seen == rep_o.seen == 16432
     assert rep.err_initial == pytest.approx(rep_o.err_initial, rel=1e-12)
     assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts)
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts)
     assert rep.iterations >= 10
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6)
     assert np.abs(sg.points - so.points).max() < 1e-6
@@ -732,6 +740,7 @@ def test_c2_full_size_blocks_system_and_one_iteration_vs_oracle(orc, gpu):
     rc_o, rep_o, so, ok, rep, sg = _end_to_end(orc, gpu, sc, spec.f0, max_iterations=1)
     assert not ok and rc_o == 1 and sa.status_string(rep.status) == "max iterations"
     assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts) and rep.iterations == 1
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts)
     assert rep.err_initial == pytest.approx(rep_o.err_initial, rel=1e-12)
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6)
     assert np.abs(sg.points - so.points).max() < 1e-6
@@ -758,6 +767,7 @@ def test_c2_ten_iterations_end_to_end_vs_the_oracle_loop(orc, gpu):
     assert not ok and rc_o == 1 and sa.status_string(rep.status) == orc.status_string(rep_o.status) == "max iterations"
     assert rep.iterations == rep_o.iterations == 10
     assert rep.attempts == rep_o.attempts and rep.attempts > rep.iterations      # some attempts were rejected on the way
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts)
     assert rep.err_initial == pytest.approx(rep_o.err_initial, rel=1e-12)
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6)
     assert np.abs(sg.points - so.points).max() < 1e-6
@@ -821,6 +831,7 @@ def test_c2_all_visible_full_size_blocks_system_and_corrections_vs_oracle(orc, g
         orc.set_solver(1)
         rc_o, rep_o, so2, ok2, rep, sg = _end_to_end(orc, gpu, sc, spec.f0, max_iterations=1)
         assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts) and rep.iterations == 1
+        lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts)
         assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6)
         assert np.abs(sg.points - so2.points).max() < 1e-6 and np.abs(sg.cam_T - so2.cam_T).max() < 1e-6
     finally:
@@ -834,7 +845,8 @@ def test_c3_full_size_blocks_and_reduced_system_vs_oracle(orc, gpu):
     dense solve (the oracle's Householder QR of the 9993^2 system would take hours): reprojection error, gradient,
     point / frame / point-frame blocks (rel 1e-12, gradient 1e-10), and the whole reduced camera system and right-hand
     side (rel 1e-10) -- 800 MB each side; the solve itself is covered at this size by
-    test_c3_solver_modes_agree_at_bench_size (three factorisations of the same system agree)."""
+    test_c3_solver_modes_agree_at_bench_size (three factorisations of the same system agree), and the corrections of the
+    step against the oracle's skyline Cholesky of the same system (point and frame parts rel 1e-8, as for C5)."""
     spec = sa.CONFIGS["C3_1kcam_100kpt"]
     sc = sa.config_scene("C3_1kcam_100kpt")
     so = _orc_scene(orc, sc)
@@ -854,10 +866,17 @@ def test_c3_full_size_blocks_and_reduced_system_vs_oracle(orc, gpu):
     dU = _check_blocks_by_class(Vg_, V, Ug_, U, Wg, W, gg_, gradE, eo)  # every entry on the scale of its variable class
     del Wg
     orc.set_skip_solve(True)   # the system is formed, the QR is not run
+    threads = orc.get_threads()
     try:
         _, _, S, rhs = orc.two_phase(so, gradE, V, U, W, 1e-4, want_system=True)
     finally:
         orc.set_skip_solve(False)
+    try:  # the step itself: the oracle's skyline Cholesky of the same system
+        orc.set_threads(min(16, os.cpu_count() or 1))
+        ok_o, corr_o = orc.two_phase_skyline(so, gradE, V, U, W, 1e-4)
+        assert ok_o
+    finally:
+        orc.set_threads(threads)
     del W
     gpu.phase_schur(1e-4)
     M = sc.M
@@ -878,6 +897,12 @@ def test_c3_full_size_blocks_and_reduced_system_vs_oracle(orc, gpu):
     assert worst_scaled < 1e-10                   # rows / columns on the scale of their variable (1 / sqrt(diag U))
     gs = 2.0 * np.sqrt(eo)
     assert float((np.abs(rg[keep] - rhs) / (dk * gs)).max()) < 1e-10
+    del S, Sg
+    assert gpu.phase_solve()
+    gpu.phase_backsub(1e-4)
+    corr_g = gpu.buffer(B.BUF_CORRECTIONS)
+    assert rel_err(corr_g[3 * sc.N:], corr_o[3 * sc.N:]) < 1e-8
+    assert rel_err(corr_g[:3 * sc.N], corr_o[:3 * sc.N]) < 1e-8
     gpu.upload(SCENES["tiny"].f0, sa.generate_scene(SCENES["tiny"]))  # release the large buffers
 
 
@@ -1032,7 +1057,7 @@ def test_native_rccl_exchange_world_size_1(orc):
     try:
         ba.rccl_init(ba.rccl_unique_id(), 0, 1)
         so = _orc_scene(orc, sc)
-        rc_o, rep_o = orc.compute_inplace(spec.f0, so, 1e-7, 1e6, 40)
+        rc_o, rep_o, rep_o.log = orc.compute_inplace(spec.f0, so, 1e-7, 1e6, 40, want_log=True)
         crit = sa.BundleAdjustmentKanataniTermCriteria()
         crit.AllowedReprojErrRelativeChange(1e-7)
         crit.MaxHessianFactor(1e6)
@@ -1041,6 +1066,7 @@ def test_native_rccl_exchange_world_size_1(orc):
         rep = ba.report
         assert ok == (rc_o == 0) and sa.status_string(rep.status) == orc.status_string(rep_o.status)
         assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts)
+        lt.assert_same_trajectory(ba.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts, err_abs=1e-18)
         assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6, abs=1e-18)
         assert np.abs(sg.points - so.points).max() < 1e-6
     finally:
@@ -1058,7 +1084,7 @@ def test_native_rccl_two_communicators_keep_the_attempt_pairs_world_size_1(orc):
         ba.rccl_init(ba.rccl_unique_id(), 0, 1)
         ba.rccl_init_second(ba.rccl_unique_id())
         so = _orc_scene(orc, sc)
-        rc_o, rep_o = orc.compute_inplace(spec.f0, so, 1e-7, 1e6, 40)
+        rc_o, rep_o, rep_o.log = orc.compute_inplace(spec.f0, so, 1e-7, 1e6, 40, want_log=True)
         crit = sa.BundleAdjustmentKanataniTermCriteria()
         crit.AllowedReprojErrRelativeChange(1e-7)
         crit.MaxHessianFactor(1e6)
@@ -1067,6 +1093,7 @@ def test_native_rccl_two_communicators_keep_the_attempt_pairs_world_size_1(orc):
         rep = ba.report
         assert ok == (rc_o == 0) and sa.status_string(rep.status) == orc.status_string(rep_o.status)
         assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts)
+        lt.assert_same_trajectory(ba.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts, err_abs=1e-18)
         assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6, abs=1e-18)
         assert np.abs(sg.points - so.points).max() < 1e-6
         assert ba.solver_sync_timeouts() == 0
@@ -1095,7 +1122,7 @@ def test_damping_parallel_schedule_world_size_1(orc, native, monkeypatch):
             hook = ALLREDUCE_FN(lambda ctx, ptr, n: calls.append(n) or 0)
             ba.set_allreduce(hook, 0, 1)
         so = _orc_scene(orc, sc)
-        rc_o, rep_o = orc.compute_inplace(spec.f0, so, 1e-7, 1e6, 40)
+        rc_o, rep_o, rep_o.log = orc.compute_inplace(spec.f0, so, 1e-7, 1e6, 40, want_log=True)
         crit = sa.BundleAdjustmentKanataniTermCriteria()
         crit.AllowedReprojErrRelativeChange(1e-7)
         crit.MaxHessianFactor(1e6)
@@ -1104,6 +1131,7 @@ def test_damping_parallel_schedule_world_size_1(orc, native, monkeypatch):
         rep = ba.report
         assert ok == (rc_o == 0) and sa.status_string(rep.status) == orc.status_string(rep_o.status)
         assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts)
+        lt.assert_same_trajectory(ba.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts, err_abs=1e-18)
         assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6, abs=1e-18)
         assert np.abs(sg.points - so.points).max() < 1e-6
         assert np.abs(sg.cam_T - so.cam_T).max() < 1e-6
@@ -1624,6 +1652,7 @@ def test_f32_storage_mode_tolerance_table(orc, name):
             assert rel_err(out["S_g"][np.ix_(keep, keep)], out["S_o"]) < (1e-9 if f32 else 1e-10)
             rc_o, rep_o, so, ok, rep, sg = _end_to_end(orc, gpu, sc, spec.f0, allowed=1e-9, max_factor=1e6, max_iterations=6)
             assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts)
+            lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts)
             assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6)
             res[f32] = (out["S_g"].copy(), out["corr_g"].copy(), rep.err_final, out["W_g"].copy())
     finally:
@@ -1672,7 +1701,7 @@ def test_f32_modes_against_the_reference_float_build(orc, name):
                     f32["K"].astype(np.float64), sc.shared_k, sc.row_ptr, sc.obs_frame, f32["obs_uv"].astype(np.float64))
     # fp64 oracle (skyline Cholesky on C1's 353 variables: the QR's own rounding is not the subject here)
     so = _orc_scene(orc, sc64)
-    rc_o, rep_o = orc.compute_inplace(f0, so, None, None, iters)
+    rc_o, rep_o, log_o = orc.compute_inplace(f0, so, None, None, iters, want_log=True)
     # the reference's float build
     s32 = o32.SceneF32(sc64)
     rc_f, rep_f = o32.compute_inplace(f0, s32, None, None, iters)
@@ -1690,6 +1719,7 @@ def test_f32_modes_against_the_reference_float_build(orc, name):
         gpu.ComputeInplaceF32(spec.f0, a["points"], a["cam_R"], a["cam_T"], a["K"], sc.shared_k, sc.row_ptr, sc.obs_frame,
                               a["obs_uv"], None, iters)
         rep_a = (gpu.report.iterations, gpu.report.attempts, gpu.report.err_final)
+        log_a = gpu.iteration_log()
 
         class _S:  # (points, cam_T, cam_R holder for _scene_distance)
             pass
@@ -1715,6 +1745,7 @@ def test_f32_modes_against_the_reference_float_build(orc, name):
     assert d_err_b <= max(d_err_ref, floor_err) and d_scene_b <= max(d_scene_ref, floor_scene), (d_err_b, d_scene_b)
     # ... and the LM loop of the fp64 pipeline takes the fp64 oracle's decisions (the float build may fork: it is reported above)
     assert (rep_a[0], rep_a[1]) == (rep_o.iterations, rep_o.attempts)
+    lt.assert_same_trajectory(log_a, log_o, max(d_err_ref, floor_err), gpu_attempts=rep_a[1])
 
 
 # ------------------------------------------------------------------ deterministic mode (srk_ba_set_deterministic)
@@ -1822,7 +1853,7 @@ def test_speculative_attempts_follow_the_sequential_loop(orc, name):
             s2 = sc.copy()
             ok = h.ComputeInplace(spec.f0, s2, crit, 12)
             r = h.report
-            out[spec_on] = (ok, r.iterations, r.attempts, r.status, r.err_final, r.hessian_factor, s2)
+            out[spec_on] = (ok, r.iterations, r.attempts, r.status, r.err_final, r.hessian_factor, s2, h.iteration_log())
         finally:
             h.close()
     a, b = out[True], out[False]
@@ -1830,8 +1861,10 @@ def test_speculative_attempts_follow_the_sequential_loop(orc, name):
     assert a[4] == pytest.approx(b[4], rel=1e-9) and a[5] == pytest.approx(b[5])
     assert np.abs(a[6].points - b[6].points).max() < 1e-8 and np.abs(a[6].cam_T - b[6].cam_T).max() < 1e-8
     so = _orc_scene(orc, sc)
-    rc_o, rep_o = orc.compute_inplace(spec.f0, so, 1e-9, None, 12)
+    rc_o, rep_o, log_o = orc.compute_inplace(spec.f0, so, 1e-9, None, 12, want_log=True)
     assert (a[1], a[2]) == (rep_o.iterations, rep_o.attempts) and a[0] == (rc_o == 0)
+    for r in (a, b):  # each mode, iteration by iteration: a pair that counts its second slot in the wrong iteration fails here
+        lt.assert_same_trajectory(r[7], log_o, 1e-6, gpu_attempts=r[2])
 
 
 # ------------------------------------------------------------------ frames in another order than time (srk_ba_set_frame_reordering)
@@ -1877,6 +1910,7 @@ def test_compute_inplace_with_renumbered_frames_matches_oracle(orc, gpu, name):
     assert gpu.frame_order() is not None
     assert ok == (rc_o == 0) and sa.status_string(rep.status) == orc.status_string(rep_o.status)
     assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts) and rep.iterations >= 1
+    lt.assert_same_trajectory(gpu.iteration_log(), rep_o.log, 1e-6, gpu_attempts=rep.attempts, err_abs=1e-18)
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6, abs=1e-18)
     assert np.abs(sg.points - so.points).max() < 1e-6
     assert np.abs(sg.cam_R - so.cam_R).max() < 1e-6
@@ -1915,3 +1949,152 @@ def test_renumbering_gives_an_unordered_400_frame_scene_its_chunked_solve_back()
             ba.set_covisibility(sa.ba.covisibility(sc))
     finally:
         ba.close()
+
+
+# ------------------------------------------------------------------ the benchmarked run, attempt by attempt
+
+_C3_ORACLE = {}
+
+
+def _c3_normalized():
+    """the bench's scene: C3, gauge-normalised once on the host (bench.py)"""
+    sc = sa.config_scene("C3_1kcam_100kpt")
+    ok, _ = sa.normalize_scene_inplace(sc)
+    assert ok
+    return sc
+
+
+def _c3_oracle_run(orc):
+    """the oracle's loop on the bench's normalised C3 scene, 20 iterations, skyline Cholesky, min(16, cpus) threads (once
+    per module): (log, report, final scene, seconds)"""
+    if not _C3_ORACLE:
+        import time
+        so = _orc_scene(orc, _c3_normalized())
+        threads = orc.get_threads()
+        orc.set_solver(1)
+        orc.set_threads(min(16, os.cpu_count() or 1))
+        try:
+            t0 = time.perf_counter()
+            rc, rep, log = orc.compute_inplace(sa.CONFIGS["C3_1kcam_100kpt"].f0, so, None, None, 20, want_log=True)
+            sec = time.perf_counter() - t0
+        finally:
+            orc.set_solver(0)
+            orc.set_threads(threads)
+        assert rc == 1 and orc.status_string(rep.status) == "max iterations" and rep.iterations == 20
+        lt.check_log_consistent(log, rep)
+        print(f"C3 oracle loop: {sec:.1f} s at {min(16, os.cpu_count() or 1)} threads, {rep.attempts} attempts, per iteration "
+              f"{lt.fold(log)['attempts'].tolist()}")
+        _C3_ORACLE.update(log=log, rep=rep, scene=so, sec=sec)
+    return _C3_ORACLE
+
+
+def _bench_shape_run(sc, deterministic, speculation=True, warm_up=5, groups=None, f0=None):
+    """bench.py's timed region on a fresh handle: upload(already_normalized=True), optimize(warm_up), reset(), optimize(20);
+    warm_up = 0: no warm-up and no reset.  Returns (report, iteration log, downloaded scene (normalised), K of the groups)"""
+    f0 = sa.CONFIGS["C3_1kcam_100kpt"].f0 if f0 is None else f0
+    h = sa.BundleAdjustmentKanatani(0)
+    try:
+        h.set_profile(0)
+        h.set_deterministic(deterministic)
+        h.set_speculation(speculation)
+        if groups is not None:
+            h.set_intrinsic_groups(groups)
+        assert h.upload(f0, sc, already_normalized=True)
+        if warm_up:
+            h.optimize(None, max_iterations=warm_up)
+            assert h.report.iterations == warm_up
+            h.reset()
+        h.optimize(None, max_iterations=20)
+        rep = h.report
+        s2 = sc.copy()
+        h.download(s2, revert_normalization=False)
+        K = h.download_intrinsics() if groups is not None else None
+        return rep, h.iteration_log(), s2, K
+    finally:
+        h.close()
+
+
+def test_c3_bench_run_vs_the_oracle_loop_attempt_by_attempt(orc):
+    """The benchmarked run (bench.py: C3 normalised on the host, upload(already_normalized=True), a 5-iteration warm-up,
+    reset(), optimize(20)) in deterministic mode against the oracle's loop on the same normalised scene (skyline Cholesky):
+    20 iterations, "max iterations", every accepted iteration with the oracle's attempt count and damping factor, err_final
+    rel 1e-6, scene abs 1e-6.  The oracle normalises the scene it is given once more; on an already normalised C3 scene
+    that moves the points by 1.2e-14, cam_T by 2e-14 and cam_R by 7e-16 (world scale 1 + 1e-15), so both loops start
+    from the same scene to rounding.
+    Past the converging phase (iterations 1..11) the run sits at the noise floor: the oracle accepts iterations 12..20 by
+    margins of 2e-13 and rejects their first attempts by 3e-13 .. 6e-11.  A fork there is allowed only at a decision on a
+    margin below 1e-10 (lm_trajectory.TIE_MARGIN); DESIGN 2 records what the GPU does there."""
+    o = _c3_oracle_run(orc)
+    rep, log, s2, _ = _bench_shape_run(_c3_normalized(), deterministic=True)
+    print(f"C3 deterministic bench run: {rep.attempts} attempts, per iteration {log['attempts'].tolist()}; oracle "
+          f"{o['rep'].attempts}")
+    assert rep.iterations == 20 and sa.status_string(rep.status) == "max iterations"
+    fork = lt.assert_same_trajectory(log, o["log"], 1e-6, gpu_attempts=None, allow_tie_fork=True)
+    if fork is None:
+        assert rep.attempts == o["rep"].attempts
+    else:
+        print(f"deterministic run parts from the oracle at a tie in iteration {fork + 1}: margin "
+              f"{lt.decisive_margin(log, o['log'], fork):+.3e}")
+        assert fork >= 11
+    assert rep.err_final == pytest.approx(o["rep"].err_final, rel=1e-6)
+    so = o["scene"]
+    assert np.abs(s2.points - so.points).max() < 1e-6
+    assert np.abs(s2.cam_R - so.cam_R).max() < 1e-6 and np.abs(s2.cam_T - so.cam_T).max() < 1e-6
+
+
+def test_c3_default_mode_bench_run_vs_the_oracle_loop(orc):
+    """The same run in the default mode (speculative pairs, fp64 atomics: what the bench line measures): the converging
+    phase (the first 11 iterations, bench.py's converging_phase) matches the oracle iteration by iteration with the error
+    rel 1e-9; after it the first place the attempts differ, if any, must be a tie (oracle margin < 1e-10)."""
+    o = _c3_oracle_run(orc)
+    rep, log, s2, _ = _bench_shape_run(_c3_normalized(), deterministic=False)
+    print(f"C3 default-mode bench run: {rep.attempts} attempts, per iteration {log['attempts'].tolist()}")
+    assert rep.iterations == 20 and sa.status_string(rep.status) == "max iterations"
+    lt.assert_same_trajectory(log, o["log"], 1e-9, n_iter=11)
+    fork = lt.assert_same_trajectory(log, o["log"], 1e-6, allow_tie_fork=True)
+    if fork is not None:
+        print(f"default-mode run parts from the oracle at a tie in iteration {fork + 1}: margin "
+              f"{lt.decisive_margin(log, o['log'], fork):+.3e}")
+
+
+@pytest.mark.parametrize("speculation", [True, False])
+def test_reset_after_a_warm_up_reproduces_a_fresh_run(speculation):
+    """reset() is the bench's state machine: after a 5-iteration warm-up, reset() and optimize(20) must give, bit for bit in
+    deterministic mode, what a fresh handle's first optimize(20) gives -- iteration log, report and scene: the current /
+    trial slot swap, the attempt slots and the damping factor start over."""
+    sc = _c3_normalized()
+    a = _bench_shape_run(sc, deterministic=True, speculation=speculation, warm_up=5)
+    b = _bench_shape_run(sc, deterministic=True, speculation=speculation, warm_up=0)
+    _assert_same_run(a, b)
+
+
+def _assert_same_run(a, b):
+    (ra, la, sa_, Ka), (rb, lb, sb, Kb) = a, b
+    assert (ra.iterations, ra.attempts, ra.status, ra.err_initial, ra.err_final, ra.hessian_factor) == \
+        (rb.iterations, rb.attempts, rb.status, rb.err_initial, rb.err_final, rb.hessian_factor)
+    for k in ("attempts", "err", "hessian_factor"):
+        assert np.array_equal(la[k], lb[k]), k
+    for k in ("points", "cam_R", "cam_T"):
+        assert np.array_equal(getattr(sa_, k), getattr(sb, k)), k
+    if Ka is not None:
+        assert np.array_equal(Ka, Kb)
+
+
+def test_reset_restores_the_uploaded_intrinsics_in_shared_k_mode():
+    """Shared intrinsics on C1 (one group, K off by 3 % and 5 px): the warm-up moves K; reset() must restore the uploaded K,
+    so that warm-up + reset + 20 iterations equals a fresh handle's 20 iterations, K included (deterministic mode)."""
+    f0 = sa.CONFIGS["C1_dino_standin"].f0
+    sc = sa.config_scene("C1_dino_standin")
+    K = sc.K.reshape(-1, 9).copy()
+    K[:, 0] *= 1.03
+    K[:, 4] *= 1.03
+    K[:, 2] += 5.0 * K[:, 8] / f0
+    K[:, 5] += 5.0 * K[:, 8] / f0
+    sc = sa.Scene(sc.points, sc.cam_R, sc.cam_T, K, sc.shared_k, sc.row_ptr, sc.obs_frame, sc.obs_uv)
+    ok, _ = sa.normalize_scene_inplace(sc)
+    assert ok
+    groups = np.zeros(sc.M, dtype=np.int32)
+    a = _bench_shape_run(sc, deterministic=True, warm_up=5, groups=groups, f0=f0)
+    b = _bench_shape_run(sc, deterministic=True, warm_up=0, groups=groups, f0=f0)
+    assert not np.array_equal(a[3], K.reshape(-1, 3, 3)[:1])   # K moved
+    _assert_same_run(a, b)

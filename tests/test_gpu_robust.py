@@ -19,6 +19,7 @@ import surikatoko_amd as sa
 from surikatoko_amd import ba as B
 from conftest import load_golden, rel_err, sym_scaled_err, class_rel_err
 import calibrated_ref as cref
+import lm_trajectory as lt
 import robust_ref as rr
 
 pytestmark = pytest.mark.gpu
@@ -168,6 +169,7 @@ def _same_as_yardstick(orc, gpu, sc, f0, kind, delta=2.0, skyline=False, fv=10, 
     assert list(log["attempts"]) == rep_o.attempts_per_iteration[:rep.iterations]
     err_tol, scene_tol = (1e-10, 1e-8) if fv == 6 else (1e-8, 1e-7)
     assert np.allclose(log["err"], rep_o.errors, rtol=err_tol, atol=0)
+    lt.assert_same_trajectory(log, rep_o.log, err_tol, gpu_attempts=rep.attempts)
     assert rep.err_initial == pytest.approx(rep_o.err_initial, rel=1e-12)
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=err_tol)
     scale = max(1.0, float(np.abs(so.points).max()))

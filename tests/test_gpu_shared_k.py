@@ -13,6 +13,7 @@ from surikatoko_amd import ba as B
 from surikatoko_amd import _lib
 from conftest import load_golden, rel_err
 import shared_k_ref as kref
+import lm_trajectory as lt
 import robust_ref as rref
 import dataclasses
 
@@ -229,6 +230,7 @@ def _same_as_yardstick(orc, gpu, sc, f0, groups, **kw):
     assert (rep.iterations, rep.attempts) == (rep_o.iterations, rep_o.attempts)
     assert list(log["attempts"]) == rep_o.attempts_per_iteration[:rep.iterations]
     assert rep.err_final == pytest.approx(rep_o.err_final, rel=1e-6, abs=1e-18)
+    lt.assert_same_trajectory(log, rep_o.log, 1e-6, gpu_attempts=rep.attempts, err_abs=1e-18)
     assert np.abs(sg.points - so.points).max() < 1e-6
     assert np.abs(sg.cam_R - so.cam_R).max() < 1e-6
     assert np.abs(sg.cam_T - so.cam_T).max() < 1e-6
