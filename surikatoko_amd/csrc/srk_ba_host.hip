@@ -23,7 +23,6 @@
 #include <iterator>
 #include <memory>
 #include <vector>
-#include <functional>
 #include <unordered_set>
 #include <thread>
 
@@ -40,7 +39,6 @@ struct DevBuf {
 #define SRK_SLOTS 3 // attempt slots: two on one GPU (speculative pairs), up to three with several ranks (one damping factor each)
 struct srk_ba {
     int device = 0;
-    hipStream_t stream = nullptr;
     bool own_stream = true;
     std::string last_error;
 
@@ -123,10 +121,10 @@ struct srk_ba {
         hipEvent_t ev_a = nullptr, ev_b = nullptr; // cross-stream hand-offs of the damping-parallel schedule
         double* err_dst = nullptr;   // {error, solver info, point-update info} of this slot: 8 doubles inside srk_ba::status_all
         int trial = 1;               // index of this slot's trial scene buffers
+        int slot = 0;                // its index in att (slot 1's all-reduces take comm2 when there is one: exchange)
         bool allocated = false;
     };
     Attempt att[SRK_SLOTS];
-    Attempt* A = &att[0]; // the slot the phase functions work on (select_attempt)
     hipStream_t main_stream = nullptr; // = att[0].stream
     hipEvent_t ev_jac = nullptr;       // derivatives done (the second slot's stream waits for it)
     bool speculate = true;             // single rank, instrumentation off: run two damping factors side by side
@@ -308,11 +306,10 @@ srk_ba* srk_ba_create(int device_id)
     if (hipSetDevice(device_id) != hipSuccess) return nullptr;
     srk_ba* h = new srk_ba();
     h->device = device_id;
-    if (hipStreamCreate(&h->stream) != hipSuccess) {
+    if (hipStreamCreate(&h->main_stream) != hipSuccess) {
         delete h;
         return nullptr;
     }
-    h->main_stream = h->stream;
 #ifdef SRK_DEV // development switches (tools/): the default build reads no environment but SRK_DEBUG (the trace)
     if (const char* e = getenv("SRK_CHOL_FUSED")) h->chol_fused = h->chol_fused_wanted = e[0] != '0'; // the unfused launch sequence
     if (const char* e = getenv("SRK_MULTI_SPECULATION")) h->spec_multi = e[0] != '0';
@@ -321,7 +318,7 @@ srk_ba* srk_ba_create(int device_id)
         h->dp_force = std::strcmp(e, "dp_force") == 0;
     }
 #endif
-    h->att[0].stream = h->stream;
+    h->att[0].stream = h->main_stream;
     bool ok = hipEventCreateWithFlags(&h->ev_jac, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&h->ev_comm, hipEventDisableTiming) == hipSuccess &&
               hipStreamCreateWithFlags(&h->comm_stream, hipStreamNonBlocking) == hipSuccess &&
@@ -330,6 +327,7 @@ srk_ba* srk_ba_create(int device_id)
     if (ok) h->status_all.bytes = 64 * SRK_SLOTS, ok = hipMemset(h->status_all.p, 0, 64 * SRK_SLOTS) == hipSuccess;
     for (int sl = 0; sl < SRK_SLOTS; ++sl) {
         auto& a = h->att[sl];
+        a.slot = sl;
         a.trial = sl + 1;
         a.err_dst = ok ? P<double>(h->status_all) + 8 * sl : nullptr;
         if (sl > 0) ok = ok && hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking) == hipSuccess;
@@ -346,18 +344,11 @@ srk_ba* srk_ba_create(int device_id)
     return h;
 }
 
-// the phase functions work on h->A and enqueue on h->stream: point both at one attempt slot
-static void select_attempt(srk_ba* h, int slot)
-{
-    h->A = &h->att[slot];
-    h->stream = h->A->stream;
-}
-
 void srk_ba_destroy(srk_ba* h)
 {
     if (!h) return;
     hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
+    if (h->main_stream) hipStreamSynchronize(h->main_stream);
     for (int sl = 1; sl < SRK_SLOTS; ++sl)
         if (h->att[sl].stream) hipStreamSynchronize(h->att[sl].stream);
     if (h->comm_stream) hipStreamSynchronize(h->comm_stream);
@@ -375,7 +366,7 @@ void srk_ba_destroy(srk_ba* h)
                       &h->dj_ptr, &h->dj_ent, &h->dj_stage, &h->ds_pair_ptr, &h->ds_pair_fa, &h->ds_pair_fb, &h->ds_pair_ent, &h->ds_f_ptr, &h->ds_f_ent,
                       &h->jd_nf, &h->jd_frames, &h->jd_mask,
                       &h->jr_first, &h->jr_count, &h->jr_jmin, &h->jr_group, &h->lg_item, &h->lg_np, &h->lg_nf, &h->lg_pts, &h->lg_frames,
-                      &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env };
+                      &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk };
     for (DevBuf* b : all) dev_free(*b);
     for (auto& a : h->att) {
         for (DevBuf* b : { &a.S, &a.rhs, &a.wy, &a.dc, &a.acc, &a.dx, &a.err_partial, &a.info, &a.dinv, &a.packed, &a.sync_flags, &a.irr, &a.det_stage, &a.det_rhs,
@@ -419,10 +410,9 @@ int srk_ba_set_stream(srk_ba* h, void* hip_stream)
 {
     if (!h) return SRK_E_ARGS;
     hipSetDevice(h->device);
-    select_attempt(h, 0);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-    h->stream = h->main_stream = h->att[0].stream = reinterpret_cast<hipStream_t>(hip_stream);
+    if (h->main_stream) hipStreamSynchronize(h->main_stream);
+    if (h->own_stream && h->main_stream) hipStreamDestroy(h->main_stream);
+    h->main_stream = h->att[0].stream = reinterpret_cast<hipStream_t>(hip_stream);
     h->own_stream = false;
     return SRK_OK;
 }
@@ -473,7 +463,7 @@ int srk_ba_set_allreduce(srk_ba* h, srk_allreduce_fn fn, void* ctx, int rank, in
     // would never be called unless the communicators are detached here
     if (h->comm || h->comm2) {
         hipSetDevice(h->device);
-        if (h->stream) hipStreamSynchronize(h->stream);
+        if (h->main_stream) hipStreamSynchronize(h->main_stream);
         for (int sl = 1; sl < SRK_SLOTS; ++sl)
             if (h->att[sl].stream) hipStreamSynchronize(h->att[sl].stream);
         if (h->comm_stream) hipStreamSynchronize(h->comm_stream);
@@ -659,7 +649,7 @@ static int validate_scene(srk_ba* h, double f0, int64_t N, const double* pts, in
 static double* kbuf(srk_ba* h, int w);
 static int compute_cam_packs(srk_ba* h, int which)
 {
-    srk_launch_cam_pack(h->stream, h->d.M, P<double>(h->camR[which]), P<double>(h->camT[which]), kbuf(h, which),
+    srk_launch_cam_pack(h->main_stream, h->d.M, P<double>(h->camR[which]), P<double>(h->camT[which]), kbuf(h, which),
                         h->f0, P<double>(h->cam[which]));
     HIPCHK(h, hipGetLastError());
     return SRK_OK;
@@ -690,7 +680,7 @@ static double plan_cost(int64_t ld, int64_t sepw, int64_t unit, int* best_P)
 }
 
 // row_end (per 256 block, multiple of 128) / col_begin (per 64 tile): the skyline of the system to be chunked
-static int make_plan(srk_ba* h, SrkChunkPlan& pl, int64_t ld, int64_t sepw, int64_t unit,
+static int make_plan(srk_ba* h, srk_ba::Attempt& a, hipStream_t s, SrkChunkPlan& pl, int64_t ld, int64_t sepw, int64_t unit,
                      const std::vector<int64_t>& row_end, const std::vector<int64_t>& col_begin)
 {
     pl.P = 0;
@@ -707,11 +697,11 @@ static int make_plan(srk_ba* h, SrkChunkPlan& pl, int64_t ld, int64_t sepw, int6
     std::vector<int64_t> sep_start((size_t)(P - 1));
     int64_t pos = 0;
     auto alloc = [&](size_t bytes, bool zero) -> void* {
-        h->A->plan_bufs.emplace_back();
-        h->A->plan_zeroed.push_back(zero ? 1 : 0);
-        if (dev_alloc(h, h->A->plan_bufs.back(), bytes) != SRK_OK) return nullptr;
-        if (zero) hipMemsetAsync(h->A->plan_bufs.back().p, 0, bytes, h->stream);
-        return h->A->plan_bufs.back().p;
+        a.plan_bufs.emplace_back();
+        a.plan_zeroed.push_back(zero ? 1 : 0);
+        if (dev_alloc(h, a.plan_bufs.back(), bytes) != SRK_OK) return nullptr;
+        if (zero) hipMemsetAsync(a.plan_bufs.back().p, 0, bytes, s);
+        return a.plan_bufs.back().p;
     };
     for (int c = 0; c < P; ++c) {
         int64_t nb = blocks / P + (c < blocks % P ? 1 : 0);
@@ -748,7 +738,7 @@ static int make_plan(srk_ba* h, SrkChunkPlan& pl, int64_t ld, int64_t sepw, int6
     pl.d_sep_start = (int64_t*)alloc((size_t)(8 * (P - 1)), false);
     pl.d_sep_env = (int64_t*)alloc((size_t)(8 * (lds / 128)), false);
     if (!pl.Cs || !pl.ws || !pl.ys || !pl.xs || !pl.dinvs || !pl.d_sep_start || !pl.d_sep_env) return SRK_E_NOMEM;
-    HIPCHK(h, hipMemcpyAsync(pl.d_sep_start, sep_start.data(), (size_t)(8 * (P - 1)), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(pl.d_sep_start, sep_start.data(), (size_t)(8 * (P - 1)), hipMemcpyHostToDevice, s));
     // separators only couple with their neighbours (through the chunk between them): block tridiagonal skyline
     pl.s_row_end.assign((size_t)(lds / SRK_CHOL_NB), 0);
     for (int64_t K = 0; K < lds / SRK_CHOL_NB; ++K) {
@@ -762,47 +752,47 @@ static int make_plan(srk_ba* h, SrkChunkPlan& pl, int64_t ld, int64_t sepw, int6
     }
     std::vector<int64_t> sep_env((size_t)(lds / 128));
     for (int64_t t = 0; t < lds / 128; ++t) sep_env[(size_t)t] = pl.s_col_begin[(size_t)(2 * t)];
-    HIPCHK(h, hipMemcpyAsync(pl.d_sep_env, sep_env.data(), (size_t)(8 * (lds / 128)), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(pl.d_sep_env, sep_env.data(), (size_t)(8 * (lds / 128)), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));
     // the separator system, chunked again when that shortens its chain
-    h->A->plan_children.emplace_back(new SrkChunkPlan());
-    SrkChunkPlan* child = h->A->plan_children.back().get();
-    int rc = make_plan(h, *child, lds, sepw, sepw, pl.s_row_end, pl.s_col_begin);
+    a.plan_children.emplace_back(new SrkChunkPlan());
+    SrkChunkPlan* child = a.plan_children.back().get();
+    int rc = make_plan(h, a, s, *child, lds, sepw, sepw, pl.s_row_end, pl.s_col_begin);
     if (rc != SRK_OK) return rc;
     pl.child = child->P >= 2 ? child : nullptr;
     pl.P = P;
     return SRK_OK;
 }
 
-static int build_chunk_plan(srk_ba* h)
+static int build_chunk_plan(srk_ba* h, srk_ba::Attempt& a, hipStream_t s)
 {
     const SrkDims& d = h->d;
-    SrkChunkPlan& pl = h->A->plan;
+    SrkChunkPlan& pl = a.plan;
     // the same skyline as the plan in place was built for (a scene uploaded again, the next call of a caller that adjusts the
     // same tracks): keep plan and buffers -- freeing and allocating them again costs ~9 ms a slot at 1000 frames -- and
     // bring the buffers that must be zero outside what a solve writes back to zero
     std::vector<int64_t> sig = { d.ld, d.fv, h->use_envelope ? 1 : 0, h->use_chunks ? 1 : 0, h->shk_G };
     sig.insert(sig.end(), h->min_cv.begin(), h->min_cv.end());
-    if (!h->A->plan_sig.empty() && sig == h->A->plan_sig) {
-        for (size_t i = 0; i < h->A->plan_bufs.size(); ++i)
-            if (h->A->plan_zeroed[i]) HIPCHK(h, hipMemsetAsync(h->A->plan_bufs[i].p, 0, h->A->plan_bufs[i].bytes, h->stream));
+    if (!a.plan_sig.empty() && sig == a.plan_sig) {
+        for (size_t i = 0; i < a.plan_bufs.size(); ++i)
+            if (a.plan_zeroed[i]) HIPCHK(h, hipMemsetAsync(a.plan_bufs[i].p, 0, a.plan_bufs[i].bytes, s));
         return SRK_OK;
     }
-    h->A->plan_sig = sig;
+    a.plan_sig = sig;
     pl.P = 0;
     pl.child = nullptr;
-    for (DevBuf& b : h->A->plan_bufs) dev_free(b);
-    h->A->plan_bufs.clear();
-    h->A->plan_zeroed.clear();
-    h->A->plan_children.clear();
+    for (DevBuf& b : a.plan_bufs) dev_free(b);
+    a.plan_bufs.clear();
+    a.plan_zeroed.clear();
+    a.plan_children.clear();
     if (!h->use_envelope || !h->use_chunks || h->shk_G > 0) return SRK_OK; // shared intrinsics: one chain with the border
     int64_t maxdist = 0;
     for (int32_t j = 0; j < d.M; ++j) maxdist = std::max<int64_t>(maxdist, d.fv * (int64_t)(j - h->min_cv[(size_t)j]) + d.fv - 1);
     // separators at least one bandwidth wide, in units of the 256-column outer panel (k_bwd_border stages 2 sepw values)
     const int64_t sepw = (maxdist + SRK_CHOL_NB - 1) / SRK_CHOL_NB * SRK_CHOL_NB;
     if (sepw > SRK_MAX_SEPW) return SRK_OK;
-    const int rc = make_plan(h, pl, d.ld, sepw, SRK_CHOL_NB, h->row_end_h, h->col_begin_h);
-    if (rc != SRK_OK) h->A->plan_sig.clear();
+    const int rc = make_plan(h, a, s, pl, d.ld, sepw, SRK_CHOL_NB, h->row_end_h, h->col_begin_h);
+    if (rc != SRK_OK) a.plan_sig.clear();
     return rc;
 }
 
@@ -850,8 +840,8 @@ static int build_envelope(srk_ba* h)
     int rc;
     if ((rc = dev_alloc(h, h->env_col, (size_t)(8 * nt))) != SRK_OK) return rc;
     if ((rc = dev_alloc(h, h->env_off, (size_t)(8 * (nt + 1)))) != SRK_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->env_col.p, h->env_col_h.data(), (size_t)(8 * nt), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->env_off.p, h->env_off_h.data(), (size_t)(8 * (nt + 1)), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->env_col.p, h->env_col_h.data(), (size_t)(8 * nt), hipMemcpyHostToDevice, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(h->env_off.p, h->env_off_h.data(), (size_t)(8 * (nt + 1)), hipMemcpyHostToDevice, h->main_stream));
     // exchange format of the assembled system (landmark shards): the exact pre-factorisation band of every row
     {
         std::vector<int64_t> bc((size_t)d.ld), bo((size_t)d.ld + 1, 0);
@@ -864,18 +854,15 @@ static int build_envelope(srk_ba* h)
         h->band_packed = bo[(size_t)d.ld];
         if ((rc = dev_alloc(h, h->band_col, (size_t)(8 * d.ld))) != SRK_OK) return rc;
         if ((rc = dev_alloc(h, h->band_off, (size_t)(8 * (d.ld + 1)))) != SRK_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->band_col.p, bc.data(), (size_t)(8 * d.ld), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->band_off.p, bo.data(), (size_t)(8 * (d.ld + 1)), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream)); // bc / bo are locals
+        HIPCHK(h, hipMemcpyAsync(h->band_col.p, bc.data(), (size_t)(8 * d.ld), hipMemcpyHostToDevice, h->main_stream));
+        HIPCHK(h, hipMemcpyAsync(h->band_off.p, bo.data(), (size_t)(8 * (d.ld + 1)), hipMemcpyHostToDevice, h->main_stream));
+        HIPCHK(h, hipStreamSynchronize(h->main_stream)); // bc / bo are locals
     }
     for (int sl = 0; sl < SRK_SLOTS; ++sl) { // every allocated attempt slot: its own zeroed system and solver plan
-        select_attempt(h, 0);
         if (!h->att[sl].allocated) continue;
-        HIPCHK(h, hipMemsetAsync(h->att[sl].S.p, 0, (size_t)(8 * d.ld * d.ld), h->stream)); // outside the skyline stays 0
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->A = &h->att[sl]; // plan buffers of slot sl, allocated and zeroed on the main stream
-        rc = build_chunk_plan(h);
-        h->A = &h->att[0];
+        HIPCHK(h, hipMemsetAsync(h->att[sl].S.p, 0, (size_t)(8 * d.ld * d.ld), h->main_stream)); // outside the skyline stays 0
+        HIPCHK(h, hipStreamSynchronize(h->main_stream));
+        rc = build_chunk_plan(h, h->att[sl], h->main_stream); // plan buffers of slot sl, allocated and zeroed on the main stream
         if (rc != SRK_OK) return rc;
     }
     return SRK_OK;
@@ -911,7 +898,7 @@ static int build_shared_k(srk_ba* h)
     if ((rc = dev_alloc(h, h->shk_mptr, 4 * ((size_t)G + 1))) != SRK_OK) return rc;
     if ((rc = dev_alloc(h, h->shk_mem, 4 * (size_t)M)) != SRK_OK) return rc;
     if ((rc = dev_alloc(h, h->shk_env, 8 * env.size())) != SRK_OK) return rc;
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     HIPCHK(h, hipMemcpyAsync(h->shk_grp.p, h->shk_grp_h.data(), 4 * (size_t)M, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->shk_lo.p, lo.data(), 4 * (size_t)M, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->shk_hi.p, hi.data(), 4 * (size_t)M, hipMemcpyHostToDevice, s));
@@ -935,7 +922,7 @@ static int build_shared_k(srk_ba* h)
     return SRK_OK;
 }
 
-static SrkShk shk_args(const srk_ba* h)
+static SrkShk shk_args(const srk_ba* h, const srk_ba::Attempt& a)
 {
     SrkShk k;
     k.M = h->d.M;
@@ -949,7 +936,7 @@ static SrkShk shk_args(const srk_ba* h)
     k.mem_ptr = P<int32_t>(h->shk_mptr);
     k.mem = P<int32_t>(h->shk_mem);
     k.env_sh = P<int64_t>(h->shk_env);
-    k.T = P<double>(h->A->Tsh);
+    k.T = P<double>(a.Tsh);
     return k;
 }
 // the intrinsics of scene buffer set w: its own copy with shared intrinsics (the trial K of an attempt), else the uploaded K
@@ -1824,7 +1811,6 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     ALLOC(h->W, (d.w_f32 ? 4 : 8) * SRK_WF_PLANES * d.Os); // the 21 rank-2 factors of every point-frame block, fp64 or (opt-in) float
     ALLOC(h->Vg, 8 * 9 * d.Ns);
     ALLOC(h->Ug, 8 * SRK_UGS(d.fv) * (int64_t)M); // the frame sums: 65 a frame, 27 with fixed intrinsics
-    select_attempt(h, 0);
     for (int sl = 0; sl < SRK_SLOTS; ++sl) {
         srk_ba::Attempt& a = h->att[sl];
         a.allocated = sl < n_slots;
@@ -1843,7 +1829,7 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         ALLOC(a.info, 64);
         ALLOC(a.dinv, 8 * 64 * d.ld);
         ALLOC(a.irr, 4 * (N + 2));
-        HIPCHK(h, hipMemsetAsync(a.irr.p, 0, 4, h->stream));
+        HIPCHK(h, hipMemsetAsync(a.irr.p, 0, 4, h->main_stream));
         if (!a.sync_flags.p) { // flag words of the fused outer-step kernel: zeroed ONCE (they hold launch epochs)
             ALLOC(a.sync_flags, 4 * SRK_SYNC_WORDS);
             HIPCHK(h, hipMemset(a.sync_flags.p, 0, 4 * SRK_SYNC_WORDS));
@@ -1902,7 +1888,7 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         ALLOC(h->jd_mask, 4 * jd_mask.size());
     }
 #undef ALLOC
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     stage("device allocations");
 #define H2D(buf, src, bytes)                                                                               \
     do {                                                                                                   \
@@ -2006,6 +1992,13 @@ static void rearm_fusion(srk_ba* h)
     h->chol_fused = true;
     for (auto& a : h->att) a.sync.fused = true;
 }
+// a hand-off of the fused solve timed out: the unfused launch sequence for the rest of this call (see chol_fused_wanted)
+static void fusion_off(srk_ba* h)
+{
+    ++h->sync_timeouts;
+    h->chol_fused = false;
+    for (auto& a : h->att) a.sync.fused = false;
+}
 
 // after a failed solve: every slot's system and zero-initialised plan buffers back to zeros (see srk_ba::poisoned)
 static int clear_poison(srk_ba* h)
@@ -2050,8 +2043,7 @@ extern "C" int srk_ba_reset_scene(srk_ba* h)
 {
     if (!h || !h->have_scene) return SRK_E_STATE;
     HIPCHK(h, hipSetDevice(h->device));
-    select_attempt(h, 0);
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     for (int sl = 1; sl < SRK_SLOTS; ++sl) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream)); // a speculative attempt may still read the current scene
     {
         int rcp = clear_poison(h);
@@ -2070,7 +2062,7 @@ extern "C" int srk_ba_download_scene(srk_ba* h, double* pts, double* cam_R, doub
 {
     if (!h || !h->have_scene) return SRK_E_STATE;
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     int c = h->cur;
     std::vector<double> tmp((size_t)(3 * h->d.N));
     if (h->d.N > 0) HIPCHK(h, hipMemcpyAsync(tmp.data(), h->pts[c].p, 24 * h->d.N, hipMemcpyDeviceToHost, s));
@@ -2086,11 +2078,11 @@ extern "C" int srk_ba_download_scene(srk_ba* h, double* pts, double* cam_R, doub
 
 // ------------------------------------------------------------------ phases
 
-static int exchange(srk_ba* h, double* dev_ptr, int64_t count)
+static int exchange(srk_ba* h, srk_ba::Attempt& a, double* dev_ptr, int64_t count)
 {
     if (h->comm) { // RCCL on this attempt's stream: ordered behind the kernels that filled the buffer, nothing waits on the host
-        ncclComm_t comm = (h->A == &h->att[1] && h->comm2) ? h->comm2 : h->comm; // the second slot's own communicator
-        ncclResult_t r = rccl().AllReduce(dev_ptr, dev_ptr, (size_t)count, ncclDouble, ncclSum, comm, h->stream);
+        ncclComm_t comm = (a.slot == 1 && h->comm2) ? h->comm2 : h->comm; // the second slot's own communicator
+        ncclResult_t r = rccl().AllReduce(dev_ptr, dev_ptr, (size_t)count, ncclDouble, ncclSum, comm, a.stream);
         if (r != ncclSuccess) {
             h->last_error = std::string("ncclAllReduce: ") + rccl().GetErrorString(r);
             return SRK_E_DEVICE;
@@ -2100,7 +2092,7 @@ static int exchange(srk_ba* h, double* dev_ptr, int64_t count)
     if (!h->allreduce) return SRK_OK;
     // the hook reduces on its own (RCCL) stream: everything queued on ours must have landed first, and the hook
     // returns only after the reduced values are visible
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(a.stream));
     int rc = h->allreduce(h->allreduce_ctx, dev_ptr, count);
     if (rc != 0) {
         h->last_error = "allreduce hook failed";
@@ -2204,22 +2196,22 @@ static const SrkLoss* robust_loss(const srk_ba* h, SrkLoss& L)
     return &L;
 }
 
-static int phase_error(srk_ba* h, int which, double* err_host, bool with_status = false, bool no_exchange = false)
+static int phase_error(srk_ba* h, srk_ba::Attempt& a, int which, double* err_host, bool with_status = false, bool no_exchange = false)
 {
     const SrkDims& d = h->d;
-    hipStream_t s = h->stream;
+    hipStream_t s = a.stream;
     int32_t np = srk_error_partials(d);
     SrkLoss L;
     srk_launch_error(s, d, P<double>(h->pts[which]), P<double>(h->cam[which]), P<int32_t>(h->obs_frame),
-                     P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(h->A->err_partial), np, h->A->err_dst,
-                     h->jac_fused ? P<int32_t>(h->wg_jmin) : nullptr, with_status ? P<int>(h->A->info) : nullptr,
-                     with_status ? reinterpret_cast<int*>(reinterpret_cast<char*>(h->A->acc.p) + 8 * 3 * d.Ns) : nullptr,
+                     P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(a.err_partial), np, a.err_dst,
+                     h->jac_fused ? P<int32_t>(h->wg_jmin) : nullptr, with_status ? P<int>(a.info) : nullptr,
+                     with_status ? reinterpret_cast<int*>(reinterpret_cast<char*>(a.acc.p) + 8 * 3 * d.Ns) : nullptr,
                      robust_loss(h, L));
     HIPCHK(h, hipGetLastError());
-    int rc = no_exchange ? SRK_OK : exchange(h, h->A->err_dst, with_status ? 3 : 1);
+    int rc = no_exchange ? SRK_OK : exchange(h, a, a.err_dst, with_status ? 3 : 1);
     if (rc != SRK_OK) return rc;
     if (err_host) {
-        HIPCHK(h, hipMemcpyAsync(err_host, h->A->err_dst, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(err_host, a.err_dst, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
     }
     return SRK_OK;
@@ -2228,7 +2220,7 @@ static int phase_error(srk_ba* h, int which, double* err_host, bool with_status 
 static int phase_derivatives(srk_ba* h)
 {
     const SrkDims& d = h->d;
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     int c = h->cur;
     HIPCHK(h, hipMemsetAsync(h->Vg.p, 0, 8 * 9 * d.Ns, s));
     HIPCHK(h, hipMemsetAsync(h->Ug.p, 0, 8 * SRK_UGS(d.fv) * (int64_t)d.M, s));
@@ -2263,106 +2255,106 @@ static int phase_derivatives(srk_ba* h)
     return SRK_OK;
 }
 
-static int phase_schur(srk_ba* h, double c, bool local_only = false);
+static int phase_schur(srk_ba* h, srk_ba::Attempt& a, double c, bool local_only = false);
 // the reduced camera system of this rank's landmarks, packed for an exchange: band + right-hand side behind it
-static int schur_pack(srk_ba* h)
+static int schur_pack(srk_ba* h, srk_ba::Attempt& a)
 {
     const SrkDims& d = h->d;
-    hipStream_t s = h->stream;
+    hipStream_t s = a.stream;
     int rc;
-    if ((rc = dev_alloc(h, h->A->packed, (size_t)(8 * (h->band_packed + d.ld)))) != SRK_OK) return rc;
-    double* tail = P<double>(h->A->packed) + h->band_packed;
-    srk_launch_band_pack(s, d.ld, P<int64_t>(h->band_col), P<int64_t>(h->band_off), P<double>(h->A->S), P<double>(h->A->packed), 0);
-    HIPCHK(h, hipMemcpyAsync(tail, h->A->rhs.p, (size_t)(8 * d.ld), hipMemcpyDeviceToDevice, s));
+    if ((rc = dev_alloc(h, a.packed, (size_t)(8 * (h->band_packed + d.ld)))) != SRK_OK) return rc;
+    double* tail = P<double>(a.packed) + h->band_packed;
+    srk_launch_band_pack(s, d.ld, P<int64_t>(h->band_col), P<int64_t>(h->band_off), P<double>(a.S), P<double>(a.packed), 0);
+    HIPCHK(h, hipMemcpyAsync(tail, a.rhs.p, (size_t)(8 * d.ld), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipGetLastError());
     return SRK_OK;
 }
-static int schur_unpack(srk_ba* h)
+static int schur_unpack(srk_ba* h, srk_ba::Attempt& a)
 {
     const SrkDims& d = h->d;
-    hipStream_t s = h->stream;
-    double* tail = P<double>(h->A->packed) + h->band_packed;
-    srk_launch_band_pack(s, d.ld, P<int64_t>(h->band_col), P<int64_t>(h->band_off), P<double>(h->A->S), P<double>(h->A->packed), 1);
-    HIPCHK(h, hipMemcpyAsync(h->A->rhs.p, tail, (size_t)(8 * d.ld), hipMemcpyDeviceToDevice, s));
+    hipStream_t s = a.stream;
+    double* tail = P<double>(a.packed) + h->band_packed;
+    srk_launch_band_pack(s, d.ld, P<int64_t>(h->band_col), P<int64_t>(h->band_off), P<double>(a.S), P<double>(a.packed), 1);
+    HIPCHK(h, hipMemcpyAsync(a.rhs.p, tail, (size_t)(8 * d.ld), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipGetLastError());
     return SRK_OK;
 }
-static int phase_schur(srk_ba* h, double c, bool local_only)
+static int phase_schur(srk_ba* h, srk_ba::Attempt& a, double c, bool local_only)
 {
     const SrkDims& d = h->d;
-    hipStream_t s = h->stream;
-    srk_launch_env_zero(s, d.ld, P<int64_t>(h->env_col), P<double>(h->A->S), P<double>(h->A->rhs), P<int32_t>(h->A->irr)); // S band, rhs, hand-back counter
-    const SrkDetSchur dets{ P<double>(h->A->det_stage), P<double>(h->A->det_rhs), P<int32_t>(h->ds_pair_ptr), P<int32_t>(h->ds_pair_fa),
+    hipStream_t s = a.stream;
+    srk_launch_env_zero(s, d.ld, P<int64_t>(h->env_col), P<double>(a.S), P<double>(a.rhs), P<int32_t>(a.irr)); // S band, rhs, hand-back counter
+    const SrkDetSchur dets{ P<double>(a.det_stage), P<double>(a.det_rhs), P<int32_t>(h->ds_pair_ptr), P<int32_t>(h->ds_pair_fa),
                             P<int32_t>(h->ds_pair_fb), P<int32_t>(h->ds_pair_ent), h->ds_n_pairs, P<int32_t>(h->ds_f_ptr), P<int32_t>(h->ds_f_ent) };
     if (d.fv == 6) {
         // fixed intrinsics: the runs of at most SRK_WS_NF_HOST frames through k_schur_mm on 6-wide blocks, every other landmark
         // through the per-landmark kernel
         srk_launch_schur_grouped(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_pt), P<uint8_t>(h->obs_slot),
-                                 P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(h->A->S),
-                                 P<double>(h->A->rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
+                                 P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(a.S),
+                                 P<double>(a.rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
                                  P<int32_t>(h->grp_frames), h->n_groups, h->n_groups_wide, h->n_groups_mid, 0,
-                                 P<int32_t>(h->A->irr), h->n_mm_uniform, h->n_mm_ragged, nullptr);
+                                 P<int32_t>(a.irr), h->n_mm_uniform, h->n_mm_ragged, nullptr);
         srk_launch_schur(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg),
-                         P<double>(h->A->S), P<double>(h->A->rhs), P<int32_t>(h->cal_list), h->n_cal_list);
+                         P<double>(a.S), P<double>(a.rhs), P<int32_t>(h->cal_list), h->n_cal_list);
     } else {
         srk_launch_schur_grouped(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_pt), P<uint8_t>(h->obs_slot),
-                                 P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(h->A->S),
-                                 P<double>(h->A->rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
+                                 P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(a.S),
+                                 P<double>(a.rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
                                  P<int32_t>(h->grp_frames), h->n_groups, h->n_groups_wide, h->n_groups_mid, h->schur_fp32 ? 1 : 0,
-                                 P<int32_t>(h->A->irr), h->n_mm_uniform, h->n_mm_ragged, h->det_active ? &dets : nullptr);
-        srk_launch_schur_long(s, d, c, P<double>(h->W), P<double>(h->Vg), P<double>(h->A->S), P<double>(h->A->rhs),
+                                 P<int32_t>(a.irr), h->n_mm_uniform, h->n_mm_ragged, h->det_active ? &dets : nullptr);
+        srk_launch_schur_long(s, d, c, P<double>(h->W), P<double>(h->Vg), P<double>(a.S), P<double>(a.rhs),
                               P<int32_t>(h->lg_item), h->n_long_items, P<int32_t>(h->lg_np), P<int32_t>(h->lg_nf), P<int32_t>(h->lg_pts),
                               P<int32_t>(h->lg_frames), P<int64_t>(h->lg_obs_off), P<int32_t>(h->lg_obs), h->long_fb);
         srk_launch_schur(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg),
-                         P<double>(h->A->S), P<double>(h->A->rhs), P<int32_t>(h->gen_list), h->n_generic);
+                         P<double>(a.S), P<double>(a.rhs), P<int32_t>(h->gen_list), h->n_generic);
     }
     HIPCHK(h, hipGetLastError());
     // G (frame blocks, damped) and the frame gradients are linear in this rank's landmarks as well, so they are added
     // before the exchange; the identity diagonal of fixed / padding variables comes from rank 0 alone
-    srk_launch_assemble(s, d, c, P<double>(h->Ug), P<double>(h->A->S), P<double>(h->A->rhs), h->rank == 0 ? 1.0 : 0.0,
-                        P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg), P<int32_t>(h->A->irr));
+    srk_launch_assemble(s, d, c, P<double>(h->Ug), P<double>(a.S), P<double>(a.rhs), h->rank == 0 ? 1.0 : 0.0,
+                        P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg), P<int32_t>(a.irr));
     HIPCHK(h, hipGetLastError());
     if (h->shk_G > 0) { // shared intrinsics: S_sh = P^T S10 P, rhs_sh = P^T rhs10 (one rank only)
-        srk_launch_rcs_fold(s, shk_args(h), P<double>(h->A->S), P<double>(h->A->rhs), P<double>(h->A->Ssh), P<double>(h->A->rsh));
+        srk_launch_rcs_fold(s, shk_args(h, a), P<double>(a.S), P<double>(a.rhs), P<double>(a.Ssh), P<double>(a.rsh));
         HIPCHK(h, hipGetLastError());
     }
     h->last_hessian_factor = c;
     if ((h->allreduce || h->comm) && !local_only) { // landmark shards: ONE exchange per attempt; only the band travels, the rhs rides behind it
-        int rc = schur_pack(h);
-        if (rc == SRK_OK) rc = exchange(h, P<double>(h->A->packed), h->band_packed + d.ld);
-        if (rc == SRK_OK) rc = schur_unpack(h);
+        int rc = schur_pack(h, a);
+        if (rc == SRK_OK) rc = exchange(h, a, P<double>(a.packed), h->band_packed + d.ld);
+        if (rc == SRK_OK) rc = schur_unpack(h, a);
         if (rc != SRK_OK) return rc;
     }
     return SRK_OK;
 }
 
 // one solve of the reduced camera system in the current mode; prof may be NULL
-static int launch_solve(srk_ba* h, SrkSolveProf* prof)
+static int launch_solve(srk_ba* h, srk_ba::Attempt& a, SrkSolveProf* prof)
 {
     const SrkDims& d = h->d;
     if (h->shk_G > 0) { // (rhs_sh stays for the downloads: the solve consumes a copy)
         const bool sky = h->use_envelope;
-        double* w = P<double>(h->A->ysh);
-        if (!(prof && prof->dry)) HIPCHK(h, hipMemcpyAsync(w, h->A->rsh.p, (size_t)(8 * h->shk_ldb), hipMemcpyDeviceToDevice, h->stream));
-        srk_chol_solve_bordered(h->stream, h->shk_ncols, h->shk_ldb, P<double>(h->A->Ssh), w, w + h->shk_ldb,
-                                P<double>(h->A->dcsh), P<double>(h->A->dinvsh), P<int>(h->A->info), sky ? h->shk_row_end.data() : nullptr,
-                                sky ? h->shk_col_begin.data() : nullptr, 6 * (int64_t)d.M, 4 * (int64_t)h->shk_G, prof, &h->A->sync);
-    } else if (h->A->plan.P >= 2)
-        srk_chol_solve_chunked(h->stream, h->A->plan, d.ld, P<double>(h->A->S), P<double>(h->A->rhs), P<double>(h->A->dc),
-                               P<int64_t>(h->env_col), P<int>(h->A->info), prof, &h->A->sync);
+        double* w = P<double>(a.ysh);
+        if (!(prof && prof->dry)) HIPCHK(h, hipMemcpyAsync(w, a.rsh.p, (size_t)(8 * h->shk_ldb), hipMemcpyDeviceToDevice, a.stream));
+        srk_chol_solve_bordered(a.stream, h->shk_ncols, h->shk_ldb, P<double>(a.Ssh), w, w + h->shk_ldb,
+                                P<double>(a.dcsh), P<double>(a.dinvsh), P<int>(a.info), sky ? h->shk_row_end.data() : nullptr,
+                                sky ? h->shk_col_begin.data() : nullptr, 6 * (int64_t)d.M, 4 * (int64_t)h->shk_G, prof, &a.sync);
+    } else if (a.plan.P >= 2)
+        srk_chol_solve_chunked(a.stream, a.plan, d.ld, P<double>(a.S), P<double>(a.rhs), P<double>(a.dc),
+                               P<int64_t>(h->env_col), P<int>(a.info), prof, &a.sync);
     else
-        srk_chol_solve(h->stream, d.ld, P<double>(h->A->S), P<double>(h->A->rhs), P<double>(h->A->wy), P<double>(h->A->dc),
-                       P<int>(h->A->info), h->row_end_h.data(), h->col_begin_h.data(), P<double>(h->A->dinv), prof, &h->A->sync, d.fv * (int64_t)d.M);
+        srk_chol_solve(a.stream, d.ld, P<double>(a.S), P<double>(a.rhs), P<double>(a.wy), P<double>(a.dc),
+                       P<int>(a.info), h->row_end_h.data(), h->col_begin_h.data(), P<double>(a.dinv), prof, &a.sync, d.fv * (int64_t)d.M);
     return SRK_OK;
 }
 
-static int phase_solve(srk_ba* h, bool profile)
+static int phase_solve(srk_ba* h, srk_ba::Attempt& a, bool profile)
 {
     const SrkDims& d = h->d;
     // inside the LM loop the status words and the point accumulators are left cleared by the kernels that consume them
     // (k_error_final, k_point_update); the step-wise entry points clear them here
-    if (!h->lean_resets) HIPCHK(h, hipMemsetAsync(h->A->info.p, 0, 4, h->stream));
-    h->A->solve_prof = SrkSolveProf{};
+    if (!h->lean_resets) HIPCHK(h, hipMemsetAsync(a.info.p, 0, 4, a.stream));
+    a.solve_prof = SrkSolveProf{};
     if (profile) {
         size_t need = (size_t)(2 * (2 * (d.ld / SRK_CHOL_NB) + 64)); // every level of a nested plan included
         while (h->chol_ev.size() < need) {
@@ -2370,41 +2362,41 @@ static int phase_solve(srk_ba* h, bool profile)
             HIPCHK(h, hipEventCreate(&e));
             h->chol_ev.push_back(e);
         }
-        h->A->solve_prof.ev = h->chol_ev.data();
-        h->A->solve_prof.cap = h->chol_ev.size();
+        a.solve_prof.ev = h->chol_ev.data();
+        a.solve_prof.cap = h->chol_ev.size();
     }
-    const int rc = launch_solve(h, profile ? &h->A->solve_prof : nullptr);
+    const int rc = launch_solve(h, a, profile ? &a.solve_prof : nullptr);
     if (rc != SRK_OK) return rc;
     HIPCHK(h, hipGetLastError());
     return SRK_OK;
 }
 
-static int read_info(srk_ba* h, int* info_host)
+static int read_info(srk_ba* h, srk_ba::Attempt& a, int* info_host)
 {
-    HIPCHK(h, hipMemcpyAsync(info_host, h->A->info.p, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(info_host, a.info.p, 4, hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(h, hipStreamSynchronize(a.stream));
     return SRK_OK;
 }
 
-static int phase_backsub_apply(srk_ba* h, double c)
+static int phase_backsub_apply(srk_ba* h, srk_ba::Attempt& a, double c)
 {
     const SrkDims& d = h->d;
-    hipStream_t s = h->stream;
-    int cur = h->cur, tr = h->A->trial;
-    if (!h->lean_resets) HIPCHK(h, hipMemsetAsync(h->A->acc.p, 0, 8 * 3 * d.Ns + 64, s));
+    hipStream_t s = a.stream;
+    int cur = h->cur, tr = a.trial;
+    if (!h->lean_resets) HIPCHK(h, hipMemsetAsync(a.acc.p, 0, 8 * 3 * d.Ns + 64, s));
     if (h->shk_G > 0) // shared intrinsics: dc10 = P dc_sh, and the trial K of every frame
-        srk_launch_rcs_expand(s, shk_args(h), P<double>(h->A->dcsh), P<double>(h->A->dc), kbuf(h, cur), kbuf(h, tr));
+        srk_launch_rcs_expand(s, shk_args(h, a), P<double>(a.dcsh), P<double>(a.dc), kbuf(h, cur), kbuf(h, tr));
     srk_launch_backsub(s, d, c, P<int32_t>(h->obs_frame), P<int32_t>(h->obs_pt), P<double>(h->W), P<double>(h->Vg),
-                       P<double>(h->A->dc), P<double>(h->A->acc), P<double>(h->pts[cur]), P<double>(h->pts[tr]),
-                       P<double>(h->A->dx));
+                       P<double>(a.dc), P<double>(a.acc), P<double>(h->pts[cur]), P<double>(h->pts[tr]),
+                       P<double>(a.dx));
     HIPCHK(h, hipGetLastError());
     return SRK_OK;
 }
 
-static int phase_cam_apply(srk_ba* h)
+static int phase_cam_apply(srk_ba* h, srk_ba::Attempt& a)
 {
-    int cur = h->cur, tr = h->A->trial;
-    srk_launch_cam_apply(h->stream, h->d.M, P<double>(h->camR[cur]), P<double>(h->camT[cur]), P<double>(h->A->dc),
+    int cur = h->cur, tr = a.trial;
+    srk_launch_cam_apply(a.stream, h->d.M, P<double>(h->camR[cur]), P<double>(h->camT[cur]), P<double>(a.dc),
                          P<double>(h->camR[tr]), P<double>(h->camT[tr]), kbuf(h, tr), h->f0, P<double>(h->cam[tr]), h->d.fv);
     HIPCHK(h, hipGetLastError());
     return SRK_OK;
@@ -2417,7 +2409,7 @@ int srk_ba_phase_error(srk_ba* h, double* err, int64_t* seen)
     if (!h || !h->have_scene) return SRK_E_STATE;
     HIPCHK(h, hipSetDevice(h->device));
     if (seen) *seen = h->d.O;
-    return phase_error(h, h->cur, err);
+    return phase_error(h, h->att[0], h->cur, err);
 }
 int srk_ba_phase_derivatives(srk_ba* h)
 {
@@ -2425,51 +2417,48 @@ int srk_ba_phase_derivatives(srk_ba* h)
     HIPCHK(h, hipSetDevice(h->device));
     int rc = phase_derivatives(h);
     if (rc != SRK_OK) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
     return SRK_OK;
 }
 int srk_ba_phase_schur(srk_ba* h, double c)
 {
     if (!h || !h->have_scene) return SRK_E_STATE;
     HIPCHK(h, hipSetDevice(h->device));
-    select_attempt(h, 0); // the staged calls always work on attempt slot 0
+    srk_ba::Attempt& a = h->att[0]; // the staged calls always work on attempt slot 0
     h->last_slot = 0;
     int rc = clear_poison(h);
     if (rc != SRK_OK) return rc;
-    rc = phase_schur(h, c);
+    rc = phase_schur(h, a, c);
     if (rc != SRK_OK) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(a.stream));
     return SRK_OK;
 }
 int srk_ba_phase_solve(srk_ba* h)
 {
     if (!h || !h->have_scene) return SRK_E_STATE;
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = phase_solve(h, false);
+    srk_ba::Attempt& a = h->att[0];
+    int rc = phase_solve(h, a, false);
     if (rc != SRK_OK) return rc;
     int info = 0;
-    rc = read_info(h, &info);
+    rc = read_info(h, a, &info);
     if (rc != SRK_OK) return rc;
     if (info && srk_debug()) fprintf(stderr, "srk_ba_phase_solve: info=%d (1 = pivot, 4 = non-finite solution, 8 = hand-off timeout of the fused solve)\n", info);
-    if ((info & 8) && h->A->plan.P >= 2) {
+    if ((info & 8) && a.plan.P >= 2) {
         // a hand-off of the fused outer step timed out: a scheduling event, not a numerical failure.  The chunked solve works
         // on copies (the system itself is intact): the plan's buffers back to zero, fusion off for good, once more unfused.
-        ++h->sync_timeouts;
-        h->chol_fused = false;
-        for (auto& a : h->att) a.sync.fused = false;
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (size_t i = 0; i < h->A->plan_bufs.size(); ++i)
-            if (h->A->plan_zeroed[i]) HIPCHK(h, hipMemsetAsync(h->A->plan_bufs[i].p, 0, h->A->plan_bufs[i].bytes, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->A->info.p, 0, 4, h->stream));
-        rc = phase_solve(h, false);
+        fusion_off(h);
+        HIPCHK(h, hipStreamSynchronize(a.stream));
+        for (size_t i = 0; i < a.plan_bufs.size(); ++i)
+            if (a.plan_zeroed[i]) HIPCHK(h, hipMemsetAsync(a.plan_bufs[i].p, 0, a.plan_bufs[i].bytes, a.stream));
+        HIPCHK(h, hipMemsetAsync(a.info.p, 0, 4, a.stream));
+        rc = phase_solve(h, a, false);
         if (rc != SRK_OK) return rc;
-        rc = read_info(h, &info);
+        rc = read_info(h, a, &info);
         if (rc != SRK_OK) return rc;
     } else if (info & 8) {
         // (the single-chain / dense solve factorises the system in place: nothing to repeat from; the caller builds it again)
-        ++h->sync_timeouts;
-        h->chol_fused = false;
-        for (auto& a : h->att) a.sync.fused = false;
+        fusion_off(h);
         h->last_error = "a hand-off of the fused solve timed out; the system was factorised in place: call srk_ba_phase_schur again "
                         "(the unfused launch sequence is selected from now on)";
     }
@@ -2480,11 +2469,12 @@ int srk_ba_phase_backsub(srk_ba* h, double c)
 {
     if (!h || !h->have_scene) return SRK_E_STATE;
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = phase_backsub_apply(h, c);
+    srk_ba::Attempt& a = h->att[0];
+    int rc = phase_backsub_apply(h, a, c);
     if (rc != SRK_OK) return rc;
-    rc = phase_cam_apply(h);
+    rc = phase_cam_apply(h, a);
     if (rc != SRK_OK) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(a.stream));
     return SRK_OK;
 }
 int srk_ba_phase_accept(srk_ba* h)
@@ -2494,337 +2484,420 @@ int srk_ba_phase_accept(srk_ba* h)
     return SRK_OK;
 }
 
+} // extern "C"
+
 // ------------------------------------------------------------------ the LM loop (bundle-adj-kanatani.cpp:720-893)
 
-int srk_ba_optimize(srk_ba* h, const double* allowed_err_change, const double* max_hessian_factor,
-                    int64_t max_iterations, srk_ba_report* rep)
-{
-    srk_ba_report local;
-    if (!rep) rep = &local;
-    std::memset(rep, 0, sizeof *rep);
-    if (!h || !h->have_scene) return SRK_E_STATE;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    const SrkDims& d = h->d;
-    auto t_begin = std::chrono::steady_clock::now();
-    h->iter_log.clear();
-    rep->world_scale = h->nrm.world_scale;
-    rearm_fusion(h);
-    {
-        int rcp = clear_poison(h);
-        if (rcp != SRK_OK) return rcp;
-    }
+namespace {
 
-    auto fail_device = [&](int rc) {
+// One srk_ba_optimize call: the reference's LM control flow, the speculative-pair schedule, the damping-parallel schedule of
+// several ranks and the repeat after a hand-off timeout.  begin(), then iterate() for as long as it returns Again, then
+// finish(); a negative return value is an error code and ends the call at once.
+struct LmRun {
+    enum { Done = 0, Again = 1 };
+    enum class Decrease { Undecided, Accepted, Overflow, Converged };
+
+    srk_ba* const h;
+    srk_ba_report* const rep;
+    const double* const allowed_err_change; // the two optional criteria
+    const double* const max_hessian_factor;
+    const int64_t max_iterations;
+    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    double hessian_factor = (double)0.0001f; // :723 (float literal)
+    double err_value = 0;
+    bool result_true = false, spec_wanted = false, spec_drain = false;
+    int64_t prev_attempts = 0; // attempts the previous iteration needed
+    // state of one iteration (iterate() resets it)
+    Decrease decrease = Decrease::Undecided;
+    bool have_prev = false, jac_timed = false, dp_mode = false;
+    double err_new_prev = 0, err_new = 0;
+    int accepted_slot = 0, round = 0;
+    unsigned spec_in_flight = 0; // slots whose speculative attempt has been enqueued and not judged
+    std::chrono::steady_clock::time_point t_iter; // SRK_DEBUG trace only
+
+    bool undecided() const { return decrease == Decrease::Undecided; }
+    int fail_device(int rc)
+    {
         rep->status = SRK_STATUS_DEVICE_ERROR;
         rep->optimized = 0;
         return rc;
-    };
-    auto ev_ms = [&](int a, int b) {
+    }
+    double ev_ms(int a, int b) const
+    {
         float ms = 0;
         if (h->profile_level < 1 || hipEventElapsedTime(&ms, h->ev[a], h->ev[b]) != hipSuccess) return 0.0;
         return (double)ms;
-    };
-#define EVREC(i) do { if (h->profile_level >= 1) HIPCHK(h, hipEventRecord(h->ev[i], s)); } while (0)
-
-    // clear the status words and point accumulators of every slot once; from here on the kernels keep them clear
-    for (auto& a : h->att)
-        if (a.allocated) {
-            HIPCHK(h, hipMemsetAsync(a.info.p, 0, 4, s));
-            HIPCHK(h, hipMemsetAsync(a.acc.p, 0, 8 * 3 * d.Ns + 64, s));
-        }
-    HIPCHK(h, hipStreamSynchronize(s)); // the second slot's stream starts after this
-    struct LeanGuard {
-        srk_ba* h;
-        explicit LeanGuard(srk_ba* hh) : h(hh) { h->lean_resets = true; }
-        ~LeanGuard() { h->lean_resets = false; }
-    } lean_guard(h);
-    double hessian_factor = (double)0.0001f; // :723 (float literal)
-    // seen_points_count over all shards (:483, :726)
-    // once per uploaded scene: it does not change between optimise calls
-    if (h->seen_global < 0) {
-        double seen_d = (double)d.O;
-        if (h->allreduce || h->comm) {
-            HIPCHK(h, hipMemcpyAsync(h->A->err_dst, &seen_d, 8, hipMemcpyHostToDevice, s));
-            int rc = exchange(h, h->A->err_dst, 1);
-            if (rc != SRK_OK) return fail_device(rc);
-            HIPCHK(h, hipMemcpyAsync(&seen_d, h->A->err_dst, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipStreamSynchronize(s));
-        }
-        h->seen_global = (int64_t)seen_d;
     }
-    const double seen_d = (double)h->seen_global;
-    rep->seen = (int64_t)seen_d;
-
-    double err_initial = 0;
-    EVREC(0);
-    int rc = phase_error(h, h->cur, nullptr);
-    if (rc != SRK_OK) return fail_device(rc);
-    EVREC(1);
-    HIPCHK(h, hipMemcpyAsync(&err_initial, h->A->err_dst, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    rep->ms_error += ev_ms(0, 1);
-    rep->err_initial = rep->err_final = err_initial;
-
-    bool result_true = false;
-    bool done = false;
-    if (allowed_err_change && err_initial < *allowed_err_change) { // :749-753
-        rep->status = SRK_STATUS_ABS_ERR_THRESHOLD;
-        result_true = true;
-        done = true;
+    int mark(int i) // phase event i on the main stream; nothing at profile level 0
+    {
+        if (h->profile_level >= 1) HIPCHK(h, hipEventRecord(h->ev[i], h->main_stream));
+        return SRK_OK;
     }
-    double err_value = err_initial;
-    bool spec_wanted = false, spec_drain = false;
-    int64_t prev_attempts = 0; // attempts the previous iteration needed
-    while (!done) {
-        if (max_iterations > 0 && rep->iterations >= max_iterations) {
-            rep->status = SRK_STATUS_MAX_ITERATIONS;
-            result_true = false;
-            break;
+
+    int begin()
+    {
+        hipStream_t s = h->main_stream;
+        const SrkDims& d = h->d;
+        srk_ba::Attempt& a0 = h->att[0];
+        h->iter_log.clear();
+        rep->world_scale = h->nrm.world_scale;
+        rearm_fusion(h);
+        int rc = clear_poison(h);
+        if (rc != SRK_OK) return rc;
+        // clear the status words and point accumulators of every slot once; from here on the kernels keep them clear
+        for (auto& a : h->att)
+            if (a.allocated) {
+                HIPCHK(h, hipMemsetAsync(a.info.p, 0, 4, s));
+                HIPCHK(h, hipMemsetAsync(a.acc.p, 0, 8 * 3 * d.Ns + 64, s));
+            }
+        HIPCHK(h, hipStreamSynchronize(s)); // the second slot's stream starts after this
+        // seen_points_count over all shards (:483, :726)
+        // once per uploaded scene: it does not change between optimise calls
+        if (h->seen_global < 0) {
+            double seen_d = (double)d.O;
+            if (h->allreduce || h->comm) {
+                HIPCHK(h, hipMemcpyAsync(a0.err_dst, &seen_d, 8, hipMemcpyHostToDevice, s));
+                rc = exchange(h, a0, a0.err_dst, 1);
+                if (rc != SRK_OK) return fail_device(rc);
+                HIPCHK(h, hipMemcpyAsync(&seen_d, a0.err_dst, 8, hipMemcpyDeviceToHost, s));
+                HIPCHK(h, hipStreamSynchronize(s));
+            }
+            h->seen_global = (int64_t)seen_d;
         }
-        // ComputeCloseFormReprErrorDerivatives (:759)
-        EVREC(0);
-        rc = phase_derivatives(h);
+        rep->seen = h->seen_global;
+
+        double err_initial = 0;
+        if ((rc = mark(0)) != SRK_OK) return rc;
+        rc = phase_error(h, a0, h->cur, nullptr);
         if (rc != SRK_OK) return fail_device(rc);
-        EVREC(1);
-        rep->jacobian_launches += 2;
-        bool jac_timed = false;
+        if ((rc = mark(1)) != SRK_OK) return rc;
+        HIPCHK(h, hipMemcpyAsync(&err_initial, a0.err_dst, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        rep->ms_error += ev_ms(0, 1);
+        rep->err_initial = rep->err_final = err_value = err_initial;
+        if (allowed_err_change && err_initial < *allowed_err_change) { // :749-753
+            rep->status = SRK_STATUS_ABS_ERR_THRESHOLD;
+            result_true = true;
+            return Done;
+        }
+        return Again;
+    }
 
-        HIPCHK(h, hipEventRecord(h->ev_jac, s));
-        const auto t_iter = std::chrono::steady_clock::now(); // SRK_DEBUG trace only
+    // one attempt, enqueued on slot sl's stream without waiting for it, in two parts so that a pair can put both
+    // Schur sums (which fill the chip one after the other) in front of both solves
+    int enqueue_schur(int sl, double c)
+    {
+        srk_ba::Attempt& a = h->att[sl];
+        int r2 = SRK_OK, e;
+        if (sl >= 1 && hipStreamWaitEvent(a.stream, h->ev_jac, 0) != hipSuccess) r2 = SRK_E_DEVICE;
+        if (sl == 0 && (e = mark(2)) != SRK_OK) return e;
+        if (r2 == SRK_OK) r2 = phase_schur(h, a, c);
+        if (sl == 0 && (e = mark(3)) != SRK_OK) return e;
+        return r2;
+    }
+    int enqueue_rest(int sl, double c)
+    {
+        srk_ba::Attempt& a = h->att[sl];
+        int e, r2 = phase_solve(h, a, h->profile_level >= 2);
+        if (sl == 0 && (e = mark(4)) != SRK_OK) return e;
+        if (r2 == SRK_OK) r2 = phase_backsub_apply(h, a, c);
+        if (sl == 0 && (e = mark(5)) != SRK_OK) return e;
+        if (r2 == SRK_OK) r2 = phase_cam_apply(h, a);
+        if (sl == 0 && (e = mark(6)) != SRK_OK) return e;
+        if (r2 == SRK_OK) r2 = phase_error(h, a, a.trial, nullptr, true);
+        if (sl == 0 && (e = mark(7)) != SRK_OK) return e;
+        // one read-back per attempt into pinned host memory: {error, solver info, point-update info}
+        if (r2 == SRK_OK && hipMemcpyAsync(a.host_back, a.err_dst, 24, hipMemcpyDeviceToHost, a.stream) != hipSuccess)
+            r2 = SRK_E_DEVICE;
+        if (r2 == SRK_OK && hipEventRecord(a.done, a.stream) != hipSuccess) r2 = SRK_E_DEVICE;
+        return r2;
+    }
+    // repeats one attempt after a hand-off timeout
+    int redo_unfused(int sl, double c)
+    {
+        fusion_off(h);
+        if (srk_debug()) fprintf(stderr, "srk_ba[rank %d]: hand-off timeout in the fused solve (slot %d); repeating unfused\n", h->rank, sl);
+        h->poisoned = true;
+        int r2 = clear_poison(h); // waits for both slots' streams, re-zeroes systems, plans, status words, accumulators
+        if (r2 == SRK_OK) r2 = enqueue_schur(sl, c);
+        if (r2 == SRK_OK) r2 = enqueue_rest(sl, c);
+        return r2;
+    }
 
-        // try_decrease_targ_fun (:764-852): the backup is the untouched `cur` buffer set, every attempt slot has a trial
-        // set of its own.  With two slots the NEXT damping factor (x10) is tried speculatively beside the current one on
-        // a second stream: the solve is a latency chain that leaves most of the chip idle, so the pair costs little more
-        // than one attempt, and a rejected first attempt finds its successor already done.  Attempts are still judged
-        // strictly in the reference's order; a speculative result that is not needed is dropped unseen.
-        bool have_prev = false;
-        double err_new_prev = 0, err_new = std::nan("");
-        int decrease = 0; // 1 success, 2 hessian overflow, 3 converged
-        int accepted_slot = 0;
-        // one attempt, enqueued on slot sl's stream without waiting for it, in two parts so that a pair can put both
-        // Schur sums (which fill the chip one after the other) in front of both solves
-        auto enqueue_schur = [&](int sl, double c) -> int {
-            select_attempt(h, sl);
-            hipStream_t st = h->stream;
-            int r2 = SRK_OK;
-            if (sl >= 1 && hipStreamWaitEvent(st, h->ev_jac, 0) != hipSuccess) r2 = SRK_E_DEVICE;
-            if (sl == 0) EVREC(2);
-            if (r2 == SRK_OK) r2 = phase_schur(h, c);
-            if (sl == 0) EVREC(3);
-            select_attempt(h, 0);
-            return r2;
-        };
-        auto enqueue_rest = [&](int sl, double c) -> int {
-            select_attempt(h, sl);
-            hipStream_t st = h->stream;
-            int r2 = phase_solve(h, h->profile_level >= 2);
-            if (sl == 0) EVREC(4);
-            if (r2 == SRK_OK) r2 = phase_backsub_apply(h, c);
-            if (sl == 0) EVREC(5);
-            if (r2 == SRK_OK) r2 = phase_cam_apply(h);
-            if (sl == 0) EVREC(6);
-            if (r2 == SRK_OK) r2 = phase_error(h, h->A->trial, nullptr, true);
-            if (sl == 0) EVREC(7);
-            // one read-back per attempt into pinned host memory: {error, solver info, point-update info}
-            if (r2 == SRK_OK && hipMemcpyAsync(h->A->host_back, h->A->err_dst, 24, hipMemcpyDeviceToHost, st) != hipSuccess)
-                r2 = SRK_E_DEVICE;
-            if (r2 == SRK_OK && hipEventRecord(h->A->done, st) != hipSuccess) r2 = SRK_E_DEVICE;
-            select_attempt(h, 0);
-            return r2;
-        };
-        // several ranks, damping-parallel schedule (instrumentation off): see dp_round below
-        bool dp_mode = (h->allreduce || h->comm) && (h->world >= 2 || h->dp_force) && h->dp_schedule &&
-                       h->profile_level == 0 && h->att[1].allocated;
-        // wait for slot sl's attempt and judge it exactly as the reference judges the attempt with factor `hessian_factor`
-        std::function<int(int, double)> redo_unfused; // (defined below: repeats one attempt after a hand-off timeout)
-        auto judge_attempt = [&](int sl) -> int {
+    // wait for slot sl's attempt and judge it exactly as the reference judges the attempt with factor `hessian_factor`
+    int judge(int sl)
+    {
+        if (hipStreamSynchronize(h->att[sl].stream) != hipSuccess) return SRK_E_DEVICE;
+        const double* hb = h->att[sl].host_back;
+        // (several ranks: the status words are SUMMED over the ranks, so bit 8 cannot be told from two ranks' bit 4; any
+        // non-zero status of a fused solve is then taken for a possible timeout -- every rank sees the same sum and
+        // repeats, a genuine failure shows again without the fused kernels)
+        // (damping-parallel schedule: only the rank that solved a factor contributes its status word, bit 8 is exact, and
+        // the round loop has dealt with it before anything is judged)
+        const bool multi_rank = (h->allreduce || h->comm) && !dp_mode;
+        if (multi_rank ? ((int)hb[1] != 0 && h->att[sl].sync.fused) : (((int)hb[1] & 8) != 0 && !dp_mode)) {
+            // an in-launch hand-off of the fused solve timed out (srk_chol.hip: k_step256; its spins are bounded): the
+            // numbers of this attempt are void.  From now on the unfused launch sequence (the two agree to rounding);
+            // this attempt is repeated with the factor it stands for, which is `hessian_factor` at this point.
+            int r2 = redo_unfused(sl, hessian_factor);
+            if (r2 != SRK_OK) return r2;
             if (hipStreamSynchronize(h->att[sl].stream) != hipSuccess) return SRK_E_DEVICE;
-            const double* hb = h->att[sl].host_back;
-            // (several ranks: the status words are SUMMED over the ranks, so bit 8 cannot be told from two ranks' bit 4; any
-            // non-zero status of a fused solve is then taken for a possible timeout -- every rank sees the same sum and
-            // repeats, a genuine failure shows again without the fused kernels)
-            // (damping-parallel schedule: only the rank that solved a factor contributes its status word, bit 8 is exact, and
-            // the round loop has dealt with it before anything is judged)
-            const bool multi_rank = (h->allreduce || h->comm) && !dp_mode;
-            if (multi_rank ? ((int)hb[1] != 0 && h->att[sl].sync.fused) : (((int)hb[1] & 8) != 0 && !dp_mode)) {
-                // an in-launch hand-off of the fused solve timed out (srk_chol.hip: k_step256; its spins are bounded): the
-                // numbers of this attempt are void.  From now on the unfused launch sequence (bit-identical arithmetic);
-                // this attempt is repeated with the factor it stands for, which is `hessian_factor` at this point.
-                int r2 = redo_unfused(sl, hessian_factor);
-                if (r2 != SRK_OK) return r2;
-                if (hipStreamSynchronize(h->att[sl].stream) != hipSuccess) return SRK_E_DEVICE;
-            }
-            struct { double err; int info; } back{ hb[0], (int)hb[1] };
-            const int info2 = (int)hb[2];
-            rep->attempts += 1;
-            rep->schur_launches += 2;
-            h->last_slot = sl;
-            if (srk_debug())
-                fprintf(stderr, "srk_ba[rank %d] iteration %lld attempt %lld (slot %d, +%.3f ms): hessian_factor %.3g err %.17g -> "
-                                "%.17g, solver info %d, point-update info %d\n", h->rank, (long long)rep->iterations + 1,
-                        (long long)rep->attempts, sl,
-                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_iter).count(),
-                        hessian_factor, err_value, back.err, back.info, info2);
-            // Solve failed (:807-808, :1912-1913, :1953-1954).  The multiplicative damping keeps the diagonally scaled
-            // system's smallest eigenvalue >= c, so a Cholesky pivot can only fail where diag(G) holds an exact
-            // zero or a non-finite value -- exactly where the reference's Householder QR divides by a zero diagonal of R
-            // and returns non-finite numbers: both sides end with "hessian overflow".
-            if (back.info != 0 || info2 != 0) { h->poisoned = true; decrease = 2; return SRK_OK; }
-            err_new = back.err;
-            if (err_new - err_value < 0) { decrease = 1; accepted_slot = sl; return SRK_OK; } // :816-819
-            // restore = drop the trial buffers (:823-826)
-            if (have_prev && allowed_err_change) { // :828-838
-                double change = err_new - err_new_prev;
-                if (std::fabs(change) < *allowed_err_change) { decrease = 3; return SRK_OK; }
-            }
-            hessian_factor *= 10; // :841
-            if (max_hessian_factor && hessian_factor > *max_hessian_factor) { decrease = 2; return SRK_OK; } // :843-847
-            err_new_prev = err_new;
-            have_prev = true;
-            return SRK_OK;
-        };
-        redo_unfused = [&](int sl, double c) -> int {
-            ++h->sync_timeouts;
-            if (srk_debug()) fprintf(stderr, "srk_ba[rank %d]: hand-off timeout in the fused solve (slot %d); repeating unfused\n", h->rank, sl);
-            h->chol_fused = false;
-            for (auto& a : h->att) a.sync.fused = false;
-            h->poisoned = true;
-            int r2 = clear_poison(h); // waits for both slots' streams, re-zeroes systems, plans, status words, accumulators
-            if (r2 == SRK_OK) r2 = enqueue_schur(sl, c);
-            if (r2 == SRK_OK) r2 = enqueue_rest(sl, c);
-            return r2;
-        };
+        }
+        struct { double err; int info; } back{ hb[0], (int)hb[1] };
+        const int info2 = (int)hb[2];
+        rep->attempts += 1;
+        rep->schur_launches += 2;
+        h->last_slot = sl;
+        if (srk_debug())
+            fprintf(stderr, "srk_ba[rank %d] iteration %lld attempt %lld (slot %d, +%.3f ms): hessian_factor %.3g err %.17g -> "
+                            "%.17g, solver info %d, point-update info %d\n", h->rank, (long long)rep->iterations + 1,
+                    (long long)rep->attempts, sl,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_iter).count(),
+                    hessian_factor, err_value, back.err, back.info, info2);
+        // Solve failed (:807-808, :1912-1913, :1953-1954).  The multiplicative damping keeps the diagonally scaled
+        // system's smallest eigenvalue >= c, so a Cholesky pivot can only fail where diag(G) holds an exact
+        // zero or a non-finite value -- exactly where the reference's Householder QR divides by a zero diagonal of R
+        // and returns non-finite numbers: both sides end with "hessian overflow".
+        if (back.info != 0 || info2 != 0) { h->poisoned = true; decrease = Decrease::Overflow; return SRK_OK; }
+        err_new = back.err;
+        if (err_new - err_value < 0) { decrease = Decrease::Accepted; accepted_slot = sl; return SRK_OK; } // :816-819
+        // restore = drop the trial buffers (:823-826)
+        if (have_prev && allowed_err_change) { // :828-838
+            double change = err_new - err_new_prev;
+            if (std::fabs(change) < *allowed_err_change) { decrease = Decrease::Converged; return SRK_OK; }
+        }
+        hessian_factor *= 10; // :841
+        if (max_hessian_factor && hessian_factor > *max_hessian_factor) { decrease = Decrease::Overflow; return SRK_OK; } // :843-847
+        err_new_prev = err_new;
+        have_prev = true;
+        return SRK_OK;
+    }
+
+    // one round of the single-rank and the all-reduce schedule: the attempt with `hessian_factor` and, when a pair pays, its
+    // successor beside it
+    int pair_round()
+    {
         // several ranks: every rank takes the same decisions, so the two slots' exchanges are issued in the same order
         // everywhere; the native path wants the second slot's own communicator (srk_ba_rccl_init_second), the callback
         // serialises the exchanges on the host
         const bool multi = h->allreduce || h->comm;
         const bool can_speculate = h->speculate && h->att[1].allocated && h->profile_level == 0 &&
                                    (!multi || (h->spec_multi && (h->allreduce || h->comm2)));
-        unsigned spec_in_flight = 0; // slots whose speculative attempt has been enqueued and not judged
-        int round = 0;
-        const int64_t attempts_before = rep->attempts;
-        // ---- several ranks: one round = the next G damping factors c, 10c, (100c), one attempt slot each.
-        //   every rank: Schur sum of its landmarks for each factor (+ its share of the frame blocks), band packed;
-        //   band k REDUCED to rank k % world (a reduce, not an all-reduce: half the traffic, and one ncclGroup for all k);
-        //   rank k % world: unpack, factorise and solve factor k -- the G solves run at the same time on G GPUs;
-        //   corrections of factor k BROADCAST from its rank (80 KB at 1000 frames);
-        //   every rank: back-substitution, camera update and error of its shard for every factor;
-        //   ONE all-reduce of the G x {error, solver status, point-update status}; every rank judges the attempts in the
-        //   reference's order and takes the same decisions.  An iteration that needs <= G attempts costs about one solve.
-        auto dp_round = [&](int G, const double* cf) -> int {
-            double* ptrs[SRK_SLOTS];
-            int64_t counts[SRK_SLOTS];
-            int r2 = SRK_OK;
-            for (int k = 0; k < G && r2 == SRK_OK; ++k) {
-                select_attempt(h, k);
-                if (k > 0 && hipStreamWaitEvent(h->stream, h->ev_jac, 0) != hipSuccess) r2 = SRK_E_DEVICE;
-                if (r2 == SRK_OK) r2 = phase_schur(h, cf[k], true);
-                if (r2 == SRK_OK) r2 = schur_pack(h);
-                ptrs[k] = P<double>(h->A->packed);
-                counts[k] = h->band_packed + d.ld;
+        // speculate once this optimise call has seen a rejection (or from its second iteration on): the first
+        // iteration of a fresh scene is usually accepted at once -- and after a rejected pair the third attempt
+        // usually is the last one: it runs alone unless the previous iteration needed four or more (then the damping
+        // factor has a long way to climb and pairs pay again)
+        const bool pair_pays = round == 0 ? (spec_wanted || rep->iterations >= 1) : (round >= 2 || prev_attempts >= 4);
+        // (Round 3, measured and dropped: TRIPLES when the previous iteration needed three attempts -- late in a run on
+        // the circle-grid scenes 16 of 20 iterations reject c / 10 and c and accept 10 c.  Three solves side by side are
+        // slower than a pair plus a lone attempt, 299-302 against 331 it/s: one solve's fused outer steps hold ~200
+        // workgroups of 66 KB LDS, two solves fill the chip's LDS, the third waits for slots.  Holding the solves back
+        // until the last Schur sum is done: 325 against 331 it/s with pairs, 283-299 with triples.)
+        const int want = (can_speculate && pair_pays) ? 2 : 1;
+        int n_now = 1; // attempts enqueued this round: the factors hessian_factor * 10^k that the cap allows
+        for (double cc = hessian_factor * 10; n_now < want && !(max_hessian_factor && cc > *max_hessian_factor); cc *= 10) ++n_now;
+        const bool speculate_now = n_now >= 2;
+        ++round;
+        // one rank: all Schur sums first (a later one would otherwise wait behind ~0.6 ms of launch calls), then the
+        // solves.  Several ranks: a Schur phase ends in a blocking exchange, so slot 0's solve is enqueued before it
+        // and runs under slot 1's Schur sum and exchange.
+        double cfk[SRK_SLOTS];
+        for (int k = 0; k < SRK_SLOTS; ++k) cfk[k] = k == 0 ? hessian_factor : cfk[k - 1] * 10;
+        int rc = enqueue_schur(0, cfk[0]);
+        if (multi) {
+            if (rc == SRK_OK) rc = enqueue_rest(0, cfk[0]);
+            if (rc == SRK_OK && speculate_now) rc = enqueue_schur(1, cfk[1]);
+        } else {
+            for (int k = 1; k < n_now && rc == SRK_OK; ++k) rc = enqueue_schur(k, cfk[k]);
+            if (rc == SRK_OK) rc = enqueue_rest(0, cfk[0]);
+        }
+        for (int k = 1; k < n_now && rc == SRK_OK; ++k) rc = enqueue_rest(k, cfk[k]);
+        if (rc != SRK_OK) return fail_device(rc);
+        for (int k = 1; k < n_now; ++k) spec_in_flight |= 1u << k;
+        rc = judge(0);
+        if (rc != SRK_OK) return fail_device(rc);
+        if (!jac_timed) {
+            rep->ms_jacobian += ev_ms(0, 1);
+            rep->ms_jacobian_kernel += ev_ms(12, 13);
+            jac_timed = true;
+        }
+        rep->ms_schur += ev_ms(2, 3);
+        rep->ms_solve += ev_ms(3, 4);
+        rep->ms_backsub += ev_ms(4, 5);
+        rep->ms_apply += ev_ms(5, 6);
+        rep->ms_error += ev_ms(6, 7);
+        if (h->profile_level >= 2) {
+            for (size_t kb = 0; kb < h->att[0].solve_prof.n; ++kb) {
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, h->chol_ev[2 * kb], h->chol_ev[2 * kb + 1]) == hipSuccess)
+                    rep->ms_solve_syrk += ms;
             }
-            select_attempt(h, 0);
-            // first native round of this handle: every rooted collective is checked against a plain all-reduce of checksums
-            const bool verify = h->comm != nullptr && !h->dp_verified;
-            double expect[2 * SRK_SLOTS] = {}, bad = 0;
-            auto selfcheck_failed = [&](const char* what) {
-                h->dp_schedule = false;
-                h->dp_selfcheck_failed = true;
-                h->last_error = std::string("damping-parallel schedule: self-check of the first native round failed (") + what +
-                                "); this handle runs the all-reduce schedule";
-                if (srk_debug()) fprintf(stderr, "srk_ba[rank %d]: %s\n", h->rank, h->last_error.c_str());
-                return SRK_RETRY_ALLREDUCE;
-            };
-            if (verify && r2 == SRK_OK) { // what the sum over the ranks of band k must be
-                for (int k = 0; k < G && r2 == SRK_OK; ++k) r2 = dp_checksum(h, h->att[k].stream, ptrs[k], counts[k], expect + 2 * k);
-                if (r2 == SRK_OK) r2 = dp_allreduce_host(h, expect, 2 * G);
+            rep->solve_mfma_flops += h->att[0].solve_prof.flops;
+        }
+        if (undecided()) spec_wanted = true; // a rejection: from now on pairs pay
+        for (int k = 1; k < n_now && undecided(); ++k) { // the successors were computed meanwhile, with exactly these factors
+            rc = judge(k);
+            if (rc != SRK_OK) return fail_device(rc);
+            spec_in_flight &= ~(1u << k);
+        }
+        return SRK_OK;
+    }
+
+    // ---- several ranks: one round = the next G damping factors c, 10c, (100c), one attempt slot each.
+    //   every rank: Schur sum of its landmarks for each factor (+ its share of the frame blocks), band packed;
+    //   band k REDUCED to rank k % world (a reduce, not an all-reduce: half the traffic, and one ncclGroup for all k);
+    //   rank k % world: unpack, factorise and solve factor k -- the G solves run at the same time on G GPUs;
+    //   corrections of factor k BROADCAST from its rank (80 KB at 1000 frames);
+    //   every rank: back-substitution, camera update and error of its shard for every factor;
+    //   ONE all-reduce of the G x {error, solver status, point-update status}; every rank judges the attempts in the
+    //   reference's order and takes the same decisions.  An iteration that needs <= G attempts costs about one solve.
+    int dp_round(int G, const double* cf)
+    {
+        double* ptrs[SRK_SLOTS];
+        int64_t counts[SRK_SLOTS];
+        // first native round of this handle: every rooted collective is checked against a plain all-reduce of checksums
+        const bool verify = h->comm != nullptr && !h->dp_verified;
+        double expect[2 * SRK_SLOTS] = {}, rootv[2 * SRK_SLOTS] = {};
+        int r2 = dp_build_and_reduce(G, cf, ptrs, counts, verify ? expect : nullptr);
+        if (verify && (r2 = dp_verify_reduce(G, r2, ptrs, counts, expect)) == SRK_RETRY_ALLREDUCE) return r2;
+        if (r2 == SRK_OK) r2 = dp_solve_and_broadcast(G, ptrs, counts, verify ? rootv : nullptr);
+        if (verify && (r2 = dp_verify_broadcast(G, r2, ptrs, counts, rootv)) == SRK_RETRY_ALLREDUCE) return r2;
+        if (r2 == SRK_OK) r2 = dp_score(G, cf);
+        if (r2 == SRK_OK) r2 = dp_collect_status(G);
+        return r2;
+    }
+    // expect (first native round only): what the sum over the ranks of band k must be
+    int dp_build_and_reduce(int G, const double* cf, double** ptrs, int64_t* counts, double* expect)
+    {
+        int r2 = SRK_OK;
+        for (int k = 0; k < G && r2 == SRK_OK; ++k) {
+            srk_ba::Attempt& a = h->att[k];
+            if (k > 0 && hipStreamWaitEvent(a.stream, h->ev_jac, 0) != hipSuccess) r2 = SRK_E_DEVICE;
+            if (r2 == SRK_OK) r2 = phase_schur(h, a, cf[k], true);
+            if (r2 == SRK_OK) r2 = schur_pack(h, a);
+            ptrs[k] = P<double>(a.packed);
+            counts[k] = h->band_packed + h->d.ld;
+        }
+        if (expect && r2 == SRK_OK) {
+            for (int k = 0; k < G && r2 == SRK_OK; ++k) r2 = dp_checksum(h, h->att[k].stream, ptrs[k], counts[k], expect + 2 * k);
+            if (r2 == SRK_OK) r2 = dp_allreduce_host(h, expect, 2 * G);
+        }
+        if (r2 == SRK_OK) r2 = coll_group(h, SRK_COLL_REDUCE, G, ptrs, counts);
+        return r2;
+    }
+    // rootv (first native round only): the checksum of the corrections on the rank that solved them, known to everybody
+    int dp_solve_and_broadcast(int G, double** ptrs, int64_t* counts, double* rootv)
+    {
+        int r2 = SRK_OK;
+        for (int k = 0; k < G && r2 == SRK_OK; ++k) {
+            srk_ba::Attempt& a = h->att[k];
+            if (h->rank == k % h->world) {
+                r2 = schur_unpack(h, a);
+                if (r2 == SRK_OK) r2 = phase_solve(h, a, false);
             }
-            if (r2 == SRK_OK) r2 = coll_group(h, SRK_COLL_REDUCE, G, ptrs, counts);
-            if (verify) {
-                if (r2 == SRK_E_DEVICE) return selfcheck_failed("an RCCL call of the reduce group returned an error");
-                for (int k = 0; k < G && r2 == SRK_OK; ++k) {
-                    if (h->rank != k % h->world) continue;
-                    double got[2];
-                    r2 = dp_checksum(h, h->att[k].stream, ptrs[k], counts[k], got); // (the slot's stream waits for the group)
-                    if (!(std::fabs(got[0] - expect[2 * k]) <= 1e-9 * expect[2 * k + 1] + 1e-300)) bad += 1;
-                }
-#ifdef SRK_DEV
-                if (g_dp_corrupt == 1) bad += 1, g_dp_corrupt = 0;
-#endif
-                if (r2 == SRK_OK) r2 = dp_allreduce_host(h, &bad, 1);
-                if (r2 == SRK_OK && bad > 0) return selfcheck_failed("a reduced band does not sum to the all-reduced checksum");
+            ptrs[k] = P<double>(a.dc);
+            counts[k] = h->d.ld;
+        }
+        if (rootv && r2 == SRK_OK) {
+            for (int k = 0; k < G && r2 == SRK_OK; ++k)
+                if (h->rank == k % h->world) r2 = dp_checksum(h, h->att[k].stream, ptrs[k], counts[k], rootv + 2 * k);
+            if (r2 == SRK_OK) r2 = dp_allreduce_host(h, rootv, 2 * G);
+        }
+        if (r2 == SRK_OK) r2 = coll_group(h, SRK_COLL_BCAST, G, ptrs, counts);
+        return r2;
+    }
+    int dp_score(int G, const double* cf)
+    {
+        int r2 = SRK_OK;
+        for (int k = 0; k < G && r2 == SRK_OK; ++k) {
+            srk_ba::Attempt& a = h->att[k];
+            r2 = phase_backsub_apply(h, a, cf[k]);
+            if (r2 == SRK_OK) r2 = phase_cam_apply(h, a);
+            if (r2 == SRK_OK) r2 = phase_error(h, a, a.trial, nullptr, true, true);
+        }
+        return r2;
+    }
+    // the status words of all slots in one all-reduce, then one read-back
+    int dp_collect_status(int G)
+    {
+        if (h->comm) {
+            for (int k = 0; k < G; ++k) {
+                if (hipEventRecord(h->att[k].ev_b, h->att[k].stream) != hipSuccess ||
+                    hipStreamWaitEvent(h->comm_stream, h->att[k].ev_b, 0) != hipSuccess) return SRK_E_DEVICE;
             }
-            for (int k = 0; k < G && r2 == SRK_OK; ++k) {
-                select_attempt(h, k);
-                if (h->rank == k % h->world) {
-                    r2 = schur_unpack(h);
-                    if (r2 == SRK_OK) r2 = phase_solve(h, false);
-                }
-                ptrs[k] = P<double>(h->A->dc);
-                counts[k] = d.ld;
-            }
-            select_attempt(h, 0);
-            double rootv[2 * SRK_SLOTS] = {};
-            if (verify && r2 == SRK_OK) { // the checksum of the corrections on the rank that solved them, known to everybody
-                for (int k = 0; k < G && r2 == SRK_OK; ++k)
-                    if (h->rank == k % h->world) r2 = dp_checksum(h, h->att[k].stream, ptrs[k], counts[k], rootv + 2 * k);
-                if (r2 == SRK_OK) r2 = dp_allreduce_host(h, rootv, 2 * G);
-            }
-            if (r2 == SRK_OK) r2 = coll_group(h, SRK_COLL_BCAST, G, ptrs, counts);
-            if (verify) {
-                if (r2 == SRK_E_DEVICE) return selfcheck_failed("an RCCL call of the broadcast group returned an error");
-                bad = 0;
-                for (int k = 0; k < G && r2 == SRK_OK; ++k) {
-                    double got[2];
-                    r2 = dp_checksum(h, h->att[k].stream, ptrs[k], counts[k], got);
-                    // (a broadcast copies bits and the checksum has a fixed order: equal, not close; NaN corrections of a failed
-                    // solve compare unequal to themselves and are let through -- the status words deal with them)
-                    if (got[0] == got[0] && rootv[2 * k] == rootv[2 * k] && (got[0] != rootv[2 * k] || got[1] != rootv[2 * k + 1])) bad += 1;
-                }
-#ifdef SRK_DEV
-                if (g_dp_corrupt == 2) bad += 1, g_dp_corrupt = 0;
-#endif
-                if (r2 == SRK_OK) r2 = dp_allreduce_host(h, &bad, 1);
-                if (r2 == SRK_OK && bad > 0) return selfcheck_failed("broadcast corrections differ from the solving rank's");
-                if (r2 == SRK_OK) h->dp_verified = true;
-            }
-            for (int k = 0; k < G && r2 == SRK_OK; ++k) {
-                select_attempt(h, k);
-                r2 = phase_backsub_apply(h, cf[k]);
-                if (r2 == SRK_OK) r2 = phase_cam_apply(h);
-                if (r2 == SRK_OK) r2 = phase_error(h, h->A->trial, nullptr, true, true);
-            }
-            select_attempt(h, 0);
-            if (r2 != SRK_OK) return r2;
-            // the status words of all slots in one all-reduce, then one read-back
-            if (h->comm) {
-                for (int k = 0; k < G; ++k) {
-                    if (hipEventRecord(h->att[k].ev_b, h->att[k].stream) != hipSuccess ||
-                        hipStreamWaitEvent(h->comm_stream, h->att[k].ev_b, 0) != hipSuccess) return SRK_E_DEVICE;
-                }
-                ncclResult_t nr = rccl().AllReduce(h->status_all.p, h->status_all.p, (size_t)(8 * G), ncclDouble, ncclSum, h->comm, h->comm_stream);
-                if (nr != ncclSuccess) { h->last_error = std::string("ncclAllReduce: ") + rccl().GetErrorString(nr); return SRK_E_DEVICE; }
-                if (hipMemcpyAsync(h->dp_back, h->status_all.p, (size_t)(64 * G), hipMemcpyDeviceToHost, h->comm_stream) != hipSuccess ||
-                    hipStreamSynchronize(h->comm_stream) != hipSuccess) return SRK_E_DEVICE;
-            } else {
-                for (int k = 0; k < G; ++k)
-                    if (hipStreamSynchronize(h->att[k].stream) != hipSuccess) return SRK_E_DEVICE;
-                if (h->allreduce(h->allreduce_ctx, P<double>(h->status_all), 8 * G) != 0) { h->last_error = "allreduce hook failed"; return SRK_E_DEVICE; }
-                if (hipMemcpy(h->dp_back, h->status_all.p, (size_t)(64 * G), hipMemcpyDeviceToHost) != hipSuccess) return SRK_E_DEVICE;
-            }
+            ncclResult_t nr = rccl().AllReduce(h->status_all.p, h->status_all.p, (size_t)(8 * G), ncclDouble, ncclSum, h->comm, h->comm_stream);
+            if (nr != ncclSuccess) { h->last_error = std::string("ncclAllReduce: ") + rccl().GetErrorString(nr); return SRK_E_DEVICE; }
+            if (hipMemcpyAsync(h->dp_back, h->status_all.p, (size_t)(64 * G), hipMemcpyDeviceToHost, h->comm_stream) != hipSuccess ||
+                hipStreamSynchronize(h->comm_stream) != hipSuccess) return SRK_E_DEVICE;
+        } else {
             for (int k = 0; k < G; ++k)
-                for (int e = 0; e < 3; ++e) h->att[k].host_back[e] = h->dp_back[8 * k + e];
-            return SRK_OK;
-        };
-        while (dp_mode && !decrease) {
+                if (hipStreamSynchronize(h->att[k].stream) != hipSuccess) return SRK_E_DEVICE;
+            if (h->allreduce(h->allreduce_ctx, P<double>(h->status_all), 8 * G) != 0) { h->last_error = "allreduce hook failed"; return SRK_E_DEVICE; }
+            if (hipMemcpy(h->dp_back, h->status_all.p, (size_t)(64 * G), hipMemcpyDeviceToHost) != hipSuccess) return SRK_E_DEVICE;
+        }
+        for (int k = 0; k < G; ++k)
+            for (int e = 0; e < 3; ++e) h->att[k].host_back[e] = h->dp_back[8 * k + e];
+        return SRK_OK;
+    }
+    int dp_selfcheck_failed(const char* what)
+    {
+        h->dp_schedule = false;
+        h->dp_selfcheck_failed = true;
+        h->last_error = std::string("damping-parallel schedule: self-check of the first native round failed (") + what +
+                        "); this handle runs the all-reduce schedule";
+        if (srk_debug()) fprintf(stderr, "srk_ba[rank %d]: %s\n", h->rank, h->last_error.c_str());
+        return SRK_RETRY_ALLREDUCE;
+    }
+    // The two verdicts of the first native round on what the round has returned so far: r2 (SRK_OK: the round goes on) or
+    // SRK_RETRY_ALLREDUCE.
+    // TODO: advisor finding (medium): a failure local to one rank returns SRK_RETRY_ALLREDUCE while its peers enter the collective
+    int dp_verify_reduce(int G, int r2, double* const* ptrs, const int64_t* counts, const double* expect)
+    {
+        if (r2 == SRK_E_DEVICE) return dp_selfcheck_failed("an RCCL call of the reduce group returned an error");
+        double bad = 0;
+        for (int k = 0; k < G && r2 == SRK_OK; ++k) {
+            if (h->rank != k % h->world) continue;
+            double got[2];
+            r2 = dp_checksum(h, h->att[k].stream, ptrs[k], counts[k], got); // (the slot's stream waits for the group)
+            if (!(std::fabs(got[0] - expect[2 * k]) <= 1e-9 * expect[2 * k + 1] + 1e-300)) bad += 1;
+        }
+#ifdef SRK_DEV
+        if (g_dp_corrupt == 1) bad += 1, g_dp_corrupt = 0;
+#endif
+        if (r2 == SRK_OK) r2 = dp_allreduce_host(h, &bad, 1);
+        if (r2 == SRK_OK && bad > 0) return dp_selfcheck_failed("a reduced band does not sum to the all-reduced checksum");
+        return r2;
+    }
+    int dp_verify_broadcast(int G, int r2, double* const* ptrs, const int64_t* counts, const double* rootv)
+    {
+        if (r2 == SRK_E_DEVICE) return dp_selfcheck_failed("an RCCL call of the broadcast group returned an error");
+        double bad = 0;
+        for (int k = 0; k < G && r2 == SRK_OK; ++k) {
+            double got[2];
+            r2 = dp_checksum(h, h->att[k].stream, ptrs[k], counts[k], got);
+            // (a broadcast copies bits and the checksum has a fixed order: equal, not close; NaN corrections of a failed
+            // solve compare unequal to themselves and are let through -- the status words deal with them)
+            if (got[0] == got[0] && rootv[2 * k] == rootv[2 * k] && (got[0] != rootv[2 * k] || got[1] != rootv[2 * k + 1])) bad += 1;
+        }
+#ifdef SRK_DEV
+        if (g_dp_corrupt == 2) bad += 1, g_dp_corrupt = 0;
+#endif
+        if (r2 == SRK_OK) r2 = dp_allreduce_host(h, &bad, 1);
+        if (r2 == SRK_OK && bad > 0) return dp_selfcheck_failed("broadcast corrections differ from the solving rank's");
+        if (r2 == SRK_OK) h->dp_verified = true;
+        return r2;
+    }
+    // the damping-parallel rounds of one iteration: until an attempt decides it, or the schedule is given up
+    int dp_rounds()
+    {
+        while (dp_mode && undecided()) {
             double cf[SRK_SLOTS];
             int G = 0;
             for (double cc = hessian_factor; G < SRK_SLOTS && h->att[G].allocated; cc *= 10) {
                 if (G > 0 && max_hessian_factor && cc > *max_hessian_factor) break; // the reference stops before such an attempt (:843-847)
                 cf[G++] = cc;
             }
-            rc = dp_round(G, cf);
+            int rc = dp_round(G, cf);
             if (rc == SRK_RETRY_ALLREDUCE) { // the first native round failed its self-check (every rank saw the same verdict):
                 // nothing of it was judged; the systems are rebuilt and this iteration's attempts run through the all-reduce schedule
                 dp_mode = false;
@@ -2837,78 +2910,56 @@ int srk_ba_optimize(srk_ba* h, const double* allowed_err_change, const double* m
             bool timeout = false;
             for (int k = 0; k < G; ++k) timeout = timeout || (((int)h->att[k].host_back[1] & 8) != 0);
             if (timeout && h->chol_fused) { // a hand-off of the fused solve timed out on the rank that solved: the round again, unfused, everywhere
-                ++h->sync_timeouts;
-                h->chol_fused = false;
-                for (auto& a : h->att) a.sync.fused = false;
+                fusion_off(h);
                 h->poisoned = true;
                 rc = clear_poison(h);
                 if (rc != SRK_OK) return fail_device(rc);
                 continue;
             }
-            for (int k = 0; k < G && !decrease; ++k) {
-                rc = judge_attempt(k);
+            for (int k = 0; k < G && undecided(); ++k) {
+                rc = judge(k);
                 if (rc != SRK_OK) return fail_device(rc);
             }
         }
-        while (!decrease) {
-            // speculate once this optimise call has seen a rejection (or from its second iteration on): the first
-            // iteration of a fresh scene is usually accepted at once -- and after a rejected pair the third attempt
-            // usually is the last one: it runs alone unless the previous iteration needed four or more (then the damping
-            // factor has a long way to climb and pairs pay again)
-            const bool pair_pays = round == 0 ? (spec_wanted || rep->iterations >= 1) : (round >= 2 || prev_attempts >= 4);
-            // (Round 3, measured and dropped: TRIPLES when the previous iteration needed three attempts -- late in a run on
-            // the circle-grid scenes 16 of 20 iterations reject c / 10 and c and accept 10 c.  Three solves side by side are
-            // slower than a pair plus a lone attempt, 299-302 against 331 it/s: one solve's fused outer steps hold ~200
-            // workgroups of 66 KB LDS, two solves fill the chip's LDS, the third waits for slots.  Holding the solves back
-            // until the last Schur sum is done: 325 against 331 it/s with pairs, 283-299 with triples.)
-            const int want = (can_speculate && pair_pays) ? 2 : 1;
-            int n_now = 1; // attempts enqueued this round: the factors hessian_factor * 10^k that the cap allows
-            for (double cc = hessian_factor * 10; n_now < want && !(max_hessian_factor && cc > *max_hessian_factor); cc *= 10) ++n_now;
-            const bool speculate_now = n_now >= 2;
-            ++round;
-            // one rank: all Schur sums first (a later one would otherwise wait behind ~0.6 ms of launch calls), then the
-            // solves.  Several ranks: a Schur phase ends in a blocking exchange, so slot 0's solve is enqueued before it
-            // and runs under slot 1's Schur sum and exchange.
-            double cfk[SRK_SLOTS];
-            for (int k = 0; k < SRK_SLOTS; ++k) cfk[k] = k == 0 ? hessian_factor : cfk[k - 1] * 10;
-            rc = enqueue_schur(0, cfk[0]);
-            if (h->allreduce || h->comm) {
-                if (rc == SRK_OK) rc = enqueue_rest(0, cfk[0]);
-                if (rc == SRK_OK && speculate_now) rc = enqueue_schur(1, cfk[1]);
-            } else {
-                for (int k = 1; k < n_now && rc == SRK_OK; ++k) rc = enqueue_schur(k, cfk[k]);
-                if (rc == SRK_OK) rc = enqueue_rest(0, cfk[0]);
-            }
-            for (int k = 1; k < n_now && rc == SRK_OK; ++k) rc = enqueue_rest(k, cfk[k]);
-            if (rc != SRK_OK) return fail_device(rc);
-            for (int k = 1; k < n_now; ++k) spec_in_flight |= 1u << k;
-            rc = judge_attempt(0);
-            if (rc != SRK_OK) return fail_device(rc);
-            if (!jac_timed) {
-                rep->ms_jacobian += ev_ms(0, 1);
-                rep->ms_jacobian_kernel += ev_ms(12, 13);
-                jac_timed = true;
-            }
-            rep->ms_schur += ev_ms(2, 3);
-            rep->ms_solve += ev_ms(3, 4);
-            rep->ms_backsub += ev_ms(4, 5);
-            rep->ms_apply += ev_ms(5, 6);
-            rep->ms_error += ev_ms(6, 7);
-            if (h->profile_level >= 2) {
-                for (size_t kb = 0; kb < h->att[0].solve_prof.n; ++kb) {
-                    float ms = 0;
-                    if (hipEventElapsedTime(&ms, h->chol_ev[2 * kb], h->chol_ev[2 * kb + 1]) == hipSuccess)
-                        rep->ms_solve_syrk += ms;
-                }
-                rep->solve_mfma_flops += h->att[0].solve_prof.flops;
-            }
-            if (!decrease) spec_wanted = true; // a rejection: from now on pairs pay
-            for (int k = 1; k < n_now && !decrease; ++k) { // the successors were computed meanwhile, with exactly these factors
-                rc = judge_attempt(k);
-                if (rc != SRK_OK) return fail_device(rc);
-                spec_in_flight &= ~(1u << k);
-            }
+        return SRK_OK;
+    }
+
+    // one iteration: accepted (Again, unless a criterion ends the run) or the run's last
+    int iterate()
+    {
+        hipStream_t s = h->main_stream;
+        if (max_iterations > 0 && rep->iterations >= max_iterations) {
+            rep->status = SRK_STATUS_MAX_ITERATIONS;
+            result_true = false;
+            return Done;
         }
+        // ComputeCloseFormReprErrorDerivatives (:759)
+        int rc;
+        if ((rc = mark(0)) != SRK_OK) return rc;
+        rc = phase_derivatives(h);
+        if (rc != SRK_OK) return fail_device(rc);
+        if ((rc = mark(1)) != SRK_OK) return rc;
+        rep->jacobian_launches += 2;
+        HIPCHK(h, hipEventRecord(h->ev_jac, s));
+        t_iter = std::chrono::steady_clock::now();
+
+        // try_decrease_targ_fun (:764-852): the backup is the untouched `cur` buffer set, every attempt slot has a trial
+        // set of its own.  With two slots the NEXT damping factor (x10) is tried speculatively beside the current one on
+        // a second stream: the solve is a latency chain that leaves most of the chip idle, so the pair costs little more
+        // than one attempt, and a rejected first attempt finds its successor already done.  Attempts are still judged
+        // strictly in the reference's order; a speculative result that is not needed is dropped unseen.
+        decrease = Decrease::Undecided;
+        have_prev = jac_timed = false;
+        err_new_prev = 0, err_new = std::nan("");
+        accepted_slot = round = 0;
+        spec_in_flight = 0;
+        // several ranks, damping-parallel schedule (instrumentation off): see dp_round
+        dp_mode = (h->allreduce || h->comm) && (h->world >= 2 || h->dp_force) && h->dp_schedule &&
+                  h->profile_level == 0 && h->att[1].allocated;
+        const int64_t attempts_before = rep->attempts;
+        if ((rc = dp_rounds()) != SRK_OK) return rc;
+        while (undecided())
+            if ((rc = pair_round()) != SRK_OK) return rc;
         prev_attempts = rep->attempts - attempts_before;
         if (spec_in_flight) {
             // speculative attempts nobody needs are still running: later work on the main stream (the next derivatives
@@ -2918,10 +2969,10 @@ int srk_ba_optimize(srk_ba* h, const double* allowed_err_change, const double* m
             spec_in_flight = 0;
             spec_drain = true;
         }
-        if (decrease != 1) { // :857-873
-            rep->status = decrease == 2 ? SRK_STATUS_HESSIAN_OVERFLOW : SRK_STATUS_ERR_CONVERGED;
+        if (decrease != Decrease::Accepted) { // :857-873
+            rep->status = decrease == Decrease::Overflow ? SRK_STATUS_HESSIAN_OVERFLOW : SRK_STATUS_ERR_CONVERGED;
             result_true = false;
-            break;
+            return Done;
         }
         { // accept: the winning slot's trial scene becomes current, the old current set becomes that slot's trial set
             const int newcur = h->att[accepted_slot].trial;
@@ -2937,23 +2988,50 @@ int srk_ba_optimize(srk_ba* h, const double* allowed_err_change, const double* m
         if (allowed_err_change && std::fabs(change) < *allowed_err_change) { // :880-884
             rep->status = SRK_STATUS_SMALL_ERR_CHANGE;
             result_true = true;
-            break;
+            return Done;
         }
         err_value = err_new;
         hessian_factor /= 10; // :889
+        return Again;
     }
-    if (spec_drain) {
-        for (int k = 1; k < SRK_SLOTS; ++k) {
-            if (!h->att[k].allocated) continue;
-            HIPCHK(h, hipStreamSynchronize(h->att[k].stream)); // leave no speculative work behind
-            if (h->att[k].host_back[1] != 0.0 || h->att[k].host_back[2] != 0.0) h->poisoned = true; // a dropped attempt that failed
+
+    int finish()
+    {
+        if (spec_drain) {
+            for (int k = 1; k < SRK_SLOTS; ++k) {
+                if (!h->att[k].allocated) continue;
+                HIPCHK(h, hipStreamSynchronize(h->att[k].stream)); // leave no speculative work behind
+                if (h->att[k].host_back[1] != 0.0 || h->att[k].host_back[2] != 0.0) h->poisoned = true; // a dropped attempt that failed
+            }
         }
+        rep->hessian_factor = hessian_factor;
+        rep->optimized = result_true ? 1 : 0;
+        rep->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        return result_true ? 0 : 1;
     }
-    select_attempt(h, 0);
-    rep->hessian_factor = hessian_factor;
-    rep->optimized = result_true ? 1 : 0;
-    rep->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    return result_true ? 0 : 1;
+};
+
+} // namespace
+
+extern "C" {
+
+int srk_ba_optimize(srk_ba* h, const double* allowed_err_change, const double* max_hessian_factor,
+                    int64_t max_iterations, srk_ba_report* rep)
+{
+    srk_ba_report local;
+    if (!rep) rep = &local;
+    std::memset(rep, 0, sizeof *rep);
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    HIPCHK(h, hipSetDevice(h->device));
+    LmRun run{ h, rep, allowed_err_change, max_hessian_factor, max_iterations };
+    struct LeanGuard { // no per-attempt memsets while the loop runs (see phase_solve)
+        srk_ba* h;
+        explicit LeanGuard(srk_ba* hh) : h(hh) { h->lean_resets = true; }
+        ~LeanGuard() { h->lean_resets = false; }
+    } lean_guard(h);
+    int rc = run.begin();
+    while (rc == LmRun::Again) rc = run.iterate();
+    return rc < 0 ? rc : run.finish();
 }
 
 int srk_ba_compute_inplace(srk_ba* h, double f0, int64_t N, double* pts, int32_t M, double* cam_R, double* cam_T,
@@ -2989,7 +3067,7 @@ static int score_scene(srk_ba* h, double f0, int64_t N, const double* pts, int32
     int rc = validate_scene(h, f0, N, pts, M, cam_R, cam_T, K, row_ptr, obs_frame, obs_uv, min_frames);
     if (rc != SRK_OK) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     const int64_t O = row_ptr[N];
     std::vector<int32_t> obs_pt((size_t)O);
     for (int64_t i = 0; i < N; ++i)
@@ -3017,10 +3095,10 @@ static int score_scene(srk_ba* h, double f0, int64_t N, const double* pts, int32
     srk_launch_error_score(s, O, P<double>(h->sc_pts), P<double>(h->sc_cam), P<int32_t>(h->sc_frame), P<int32_t>(h->sc_pt),
                            P<double>(h->sc_uv), z_tol, P<double>(h->sc_partial), np, P<double>(h->sc_out));
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->A->host_back, h->sc_out.p, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(h->att[0].host_back, h->sc_out.p, 16, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    *err = h->A->host_back[0];
-    *count = (int64_t)h->A->host_back[1];
+    *err = h->att[0].host_back[0];
+    *count = (int64_t)h->att[0].host_back[1];
     return SRK_OK;
 }
 
@@ -3176,7 +3254,7 @@ extern "C" int srk_mvf_estimate_depths(srk_ba* h, int64_t n_tracks, const int64_
     }
     if (n_tracks == 0) return SRK_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     int rc;
     struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
         { &h->sc_pts, x_meter, (size_t)(24 * O) },       { &h->sc_R, cam_R, (size_t)(72 * (int64_t)n_frames) },
@@ -3207,7 +3285,7 @@ extern "C" int srk_mvf_relative_motion(srk_ba* h, int64_t n_points, const double
         return SRK_E_ARGS;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     int rc;
     const int64_t nblk = (n_points + 255) / 256;
     struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
@@ -3344,15 +3422,11 @@ int srk_ba_download(srk_ba* h, int which, double* dst, int64_t count)
     if (count != srk_ba_buffer_size(h, which)) { h->last_error = "download: wrong count"; return SRK_E_ARGS; }
     HIPCHK(h, hipSetDevice(h->device));
     const SrkDims& d = h->d;
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     HIPCHK(h, hipStreamSynchronize(s));
     for (int sl = 1; sl < SRK_SLOTS; ++sl) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
     // reduced camera system, rhs and corrections: those of the last attempt the LM loop judged (or of the staged calls)
-    struct SlotGuard {
-        srk_ba* h;
-        ~SlotGuard() { h->A = &h->att[0]; }
-    } guard{ h };
-    h->A = &h->att[h->last_slot];
+    const srk_ba::Attempt& att = h->att[h->last_slot];
     auto d2h = [&](void* dstp, const void* src, size_t bytes) -> int {
         if (bytes == 0) return SRK_OK;
         HIPCHK(h, hipMemcpy(dstp, src, bytes, hipMemcpyDeviceToHost));
@@ -3430,7 +3504,7 @@ int srk_ba_download(srk_ba* h, int which, double* dst, int64_t count)
         std::vector<double> row((size_t)d.ld);
         auto uvar = [&](int64_t v) { return h->frame_user.empty() ? v : fv * (int64_t)h->frame_user[(size_t)(v / fv)] + v % fv; };
         for (int64_t r = 0; r < n; ++r) {
-            if ((rc = d2h(row.data(), P<double>(h->A->S) + r * d.ld, (size_t)(8 * n))) != SRK_OK) return rc;
+            if ((rc = d2h(row.data(), P<double>(att.S) + r * d.ld, (size_t)(8 * n))) != SRK_OK) return rc;
             const int64_t ur = uvar(r);
             for (int64_t c = 0; c <= r; ++c) {
                 const int64_t uc = uvar(c);
@@ -3441,14 +3515,14 @@ int srk_ba_download(srk_ba* h, int which, double* dst, int64_t count)
         return SRK_OK;
     }
     case SRK_BUF_RCS_RHS:
-        if ((rc = d2h(dst, h->A->rhs.p, (size_t)(8 * d.fv * (int64_t)d.M))) != SRK_OK) return rc;
+        if ((rc = d2h(dst, att.rhs.p, (size_t)(8 * d.fv * (int64_t)d.M))) != SRK_OK) return rc;
         frames_to_user(h, dst, d.fv);
         return SRK_OK;
     case SRK_BUF_CORRECTIONS: {
         std::vector<double> tmp((size_t)(3 * d.N));
-        if ((rc = d2h(tmp.data(), h->A->dx.p, (size_t)(24 * d.N))) != SRK_OK) return rc;
+        if ((rc = d2h(tmp.data(), att.dx.p, (size_t)(24 * d.N))) != SRK_OK) return rc;
         for (int64_t i = 0; i < d.N; ++i) std::memcpy(dst + 3 * h->perm[(size_t)i], &tmp[(size_t)(3 * i)], 24);
-        if ((rc = d2h(dst + 3 * d.N, h->A->dc.p, (size_t)(8 * d.fv * (int64_t)d.M))) != SRK_OK) return rc;
+        if ((rc = d2h(dst + 3 * d.N, att.dc.p, (size_t)(8 * d.fv * (int64_t)d.M))) != SRK_OK) return rc;
         frames_to_user(h, dst + 3 * d.N, d.fv);
         return SRK_OK;
     }
@@ -3474,7 +3548,7 @@ int srk_ba_download_rcs_rows(srk_ba* h, const int64_t* rows, int64_t n_rows, dou
 {
     if (!h || !h->have_scene || !rows || !dst || n_rows < 0) return SRK_E_STATE;
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
     for (int sl = 1; sl < SRK_SLOTS; ++sl) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
     const SrkDims& d = h->d;
     if (h->shk_G > 0) {
@@ -3520,7 +3594,7 @@ int srk_ba_dense_spd_solve(srk_ba* h, int64_t n, const double* A, const double* 
 {
     if (!h || n <= 0 || !A || !b || !x) return SRK_E_ARGS;
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     int64_t ld = ((n + SRK_CHOL_NB - 1) / SRK_CHOL_NB) * SRK_CHOL_NB;
     DevBuf dA, dw, dy, dx, dinfo, ddinv;
     int rc;
@@ -3612,7 +3686,7 @@ int srk_ba_set_rcs_mode(srk_ba* h, int use_envelope)
     return SRK_OK;
 }
 
-int srk_ba_rcs_chunks(srk_ba* h) { return (h && h->have_scene) ? h->A->plan.P : 0; }
+int srk_ba_rcs_chunks(srk_ba* h) { return (h && h->have_scene) ? h->att[0].plan.P : 0; }
 
 // fraction of the lower triangle inside the skyline (1.0 = dense)
 double srk_ba_rcs_fill(srk_ba* h)
@@ -3628,11 +3702,12 @@ double srk_ba_solve_mfma_flops(srk_ba* h)
     if (!h || !h->have_scene) return -1.0;
     SrkSolveProf dry;
     dry.dry = true; // walks the launch sequence of the current mode without launching anything
-    return launch_solve(h, &dry) == SRK_OK ? dry.flops : -1.0;
+    return launch_solve(h, h->att[0], &dry) == SRK_OK ? dry.flops : -1.0;
 }
 
 // 1 (default) = an outer step of the blocked Cholesky is ONE launch whose workgroups hand tiles to each other (k_step256),
-// 0 = the k_panel / k_upd64 launch sequence.  Bit-identical results; takes effect at once.
+// 0 = the k_panel / k_upd64 launch sequence.  Each is bit-reproducible; they agree with each other to rounding
+// (include/srk_ba.h).  Takes effect at once.
 int srk_ba_set_solver_fusion(srk_ba* h, int on)
 {
     if (!h || (on != 0 && on != 1)) return SRK_E_ARGS;
@@ -3805,7 +3880,7 @@ int srk_ba_download_intrinsics(srk_ba* h, double* K, int32_t n_groups)
     if (!h->have_scene || h->shk_G == 0) { h->last_error = "download_intrinsics: the uploaded scene has no intrinsic groups"; return SRK_E_ARGS; }
     if (n_groups != h->shk_G) { h->last_error = "download_intrinsics: wrong number of groups"; return SRK_E_ARGS; }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
     for (int sl = 1; sl < SRK_SLOTS; ++sl) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
     for (int32_t g = 0; g < n_groups; ++g) {
         const int32_t fi = h->shk_first[(size_t)g]; // internal frame
@@ -3860,7 +3935,7 @@ int srk_ba_observation_weights(srk_ba* h, double* w, int64_t count)
         return SRK_OK;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->main_stream;
     HIPCHK(h, hipStreamSynchronize(s));
     DevBuf wd;
     int rc = dev_alloc(h, wd, (size_t)(8 * d.O));
