@@ -414,6 +414,35 @@ int srk_ba_robust_loss(srk_ba*, int* kind, double* delta_pixels);
  * the threshold: the outliers of a robust solve. */
 int srk_ba_observation_weights(srk_ba*, double* w, int64_t count);
 
+/* ---- per-observation information (EXTENSION) ----
+ * Observation o gets a scalar information q_o >= 0, a dimensionless multiplier of its squared residual (typically
+ * (sigma_ref / sigma_o)^2).  LM then minimises E = sum_o rho(q_o s_o): rho the identity without a loss (E = sum q_o s_o),
+ * Huber or Cauchy as above otherwise, the threshold delta keeping its meaning (pixels at unit information).  The weight
+ * of an observation in the Gauss-Newton blocks and the gradient is q rho'(q s); the gradient is the exact gradient of E.
+ * E is what the accept / reject test, the termination test, err_initial / err_final, srk_ba_iteration_log and
+ * srk_ba_phase_error report.  srk_ba_reproj_error and srk_ba_reproj_error_mvf stay unweighted, and
+ * srk_ba_observation_weights keeps returning the loss's factor rho'(q s) alone (all 1 without a loss).  q_o = 0 switches
+ * the observation off: exact zeros everywhere, stored factors (SRK_BUF_POINT_FRAME) included.  q = 1 everywhere is bit for
+ * bit the run without information.
+ *
+ * q is in the caller's observation order (the CSR order of the upload, the order of srk_ba_observation_weights); with
+ * several ranks it covers the rank's shard.  NULL clears the setting (the default).  The handle keeps a copy: it is
+ * applied by every later upload (srk_ba_compute_inplace and srk_ba_compute_inplace_f32 included) and is not touched by
+ * srk_ba_reset_scene.  With a scene resident it takes effect at the next optimise / phase call WITHOUT another upload:
+ * the scene, its internal orders, the skyline and the solver plan stay as they are.
+ * SRK_E_ARGS (text in srk_ba_last_error), the previous setting staying in force: a value that is negative or not finite;
+ * a count that is not the resident scene's number of observations (at an upload: a stored count that is not the new
+ * scene's); a landmark left with fewer than two observations of positive information (its 3 x 3 block would be
+ * singular).  A frame left without a positive observation is the caller's business: like any degenerate scene the solve
+ * reports failure. */
+int srk_ba_set_observation_information(srk_ba*, const double* q /* [count] or NULL */, int64_t count);
+/* the setting in the caller's order, or all 1 when none is set; count = the number of values set (of observations) */
+int srk_ba_observation_information(srk_ba*, double* q, int64_t count);
+/* the raw, unwhitened residuals f0 (ex, ey) of the resident scene in pixels (current scene: after srk_ba_optimize, the
+ * result), [count][2] in the caller's observation order; count = the number of observations (of this rank's shard).
+ * Works with or without information or a loss, and neither changes it. */
+int srk_ba_observation_residuals(srk_ba*, double* exy_pixels /* [count][2] */, int64_t count);
+
 /* device-time instrumentation of srk_ba_optimize / srk_ba_compute_inplace: 0 = none (default; report.ms_* stay 0
  * except ms_total), 1 = one HIP event pair per phase (fills report.ms_*), 2 = additionally event pairs around
  * every MFMA trailing-update launch (fills report.ms_solve_syrk / solve_mfma_flops).  Every event costs a few

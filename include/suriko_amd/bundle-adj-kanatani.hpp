@@ -164,6 +164,27 @@ public:
         if (rc < 0) Raise(rc);
     }
 
+    /// EXTENSION: per-observation information (srk_ba_set_observation_information): q[o] >= 0 multiplies observation o's
+    /// squared residual, E = sum rho(q s); one value per observation in the order ComputeInplace flattens them (corner tracks
+    /// with a salient point in repository order, inside a track by frame).  An empty vector clears it.  Applied from the next
+    /// ComputeInplace on.  Throws std::invalid_argument for a value that is negative or not finite, a count that is not the
+    /// resident scene's, or a landmark left with fewer than two observations of positive information.
+    void SetObservationInformation(const std::vector<Scalar>& q) {
+        int rc = srk_ba_set_observation_information(h_, q.empty() ? nullptr : q.data(), (int64_t)q.size());
+        if (rc < 0) Raise(rc);
+    }
+    /// EXTENSION: the raw residuals in pixels of the last ComputeInplace's result, (x, y) per observation in the same order
+    /// (srk_ba_observation_residuals); neither information nor a loss changes them
+    std::vector<Scalar> ObservationResiduals() {
+        const int64_t size = srk_ba_buffer_size(h_, SRK_BUF_POINT_FRAME); // 3 x frame variables per observation
+        if (size < 0) Raise((int)size);
+        const int64_t n = size / (3 * (srk_ba_intrinsic_groups(h_) > 0 ? 10 : srk_ba_frame_vars(h_)));
+        std::vector<Scalar> e((size_t)(2 * n));
+        int rc = srk_ba_observation_residuals(h_, e.data(), n);
+        if (rc < 0) Raise(rc);
+        return e;
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }

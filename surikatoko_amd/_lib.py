@@ -57,6 +57,7 @@ EXPORTS = [
     "srk_ba_set_stream", "srk_ba_set_allreduce", "srk_ba_rccl_get_unique_id", "srk_ba_rccl_init", "srk_ba_rccl_init_second", "srk_ba_rccl_set_comm", "srk_ba_compute_inplace", "srk_ba_compute_inplace_f32", "srk_ba_reproj_error", "srk_ba_reproj_error_mvf", "srk_mvf_estimate_depths", "srk_mvf_relative_motion",
     "srk_mvf_project_onto_so3", "srk_ba_set_schur_precision", "srk_ba_set_storage_precision", "srk_ba_set_speculation", "srk_ba_set_deterministic", "srk_ba_deterministic", "srk_ba_set_multi_schedule", "srk_ba_multi_schedule", "srk_ba_set_frame_reordering", "srk_ba_set_frame_order", "srk_ba_frame_order", "srk_frame_order", "srk_ba_set_solver_fusion", "srk_ba_solver_sync_timeouts", "srk_ba_iteration_log", "srk_ba_solver_fusion", "srk_ba_set_jacobian_mode", "srk_ba_jacobian_kernel", "srk_ba_set_fixed_intrinsics", "srk_ba_frame_vars", "srk_ba_schur_fallback_landmarks",
     "srk_ba_set_robust_loss", "srk_ba_robust_loss", "srk_ba_observation_weights",
+    "srk_ba_set_observation_information", "srk_ba_observation_information", "srk_ba_observation_residuals",
     "srk_ba_set_intrinsic_groups", "srk_ba_intrinsic_groups", "srk_ba_download_intrinsics",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
     "srk_ba_upload_scene", "srk_ba_optimize", "srk_ba_download_scene", "srk_ba_reset_scene", "srk_ba_phase_error",
@@ -108,6 +109,9 @@ def lib():
     L.srk_ba_set_robust_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
     L.srk_ba_robust_loss.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.srk_ba_observation_weights.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64]
+    L.srk_ba_set_observation_information.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64]
+    L.srk_ba_observation_information.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64]
+    L.srk_ba_observation_residuals.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64]
     L.srk_ba_set_intrinsic_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     L.srk_ba_intrinsic_groups.argtypes = [C.c_void_p]
     L.srk_ba_download_intrinsics.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]

@@ -439,6 +439,47 @@ class BundleAdjustmentKanatani:
                                                          C.c_int64(n)))
         return w
 
+    def _n_observations(self):
+        size = int(self._lib.srk_ba_buffer_size(C.c_void_p(self._h), C.c_int(BUF_POINT_FRAME)))
+        self._raise(size)
+        fv = 10 if self.intrinsic_groups() else self.frame_vars()
+        return size // (3 * fv)
+
+    def set_observation_information(self, q=None):
+        """Per-observation information: q[o] >= 0 multiplies observation o's squared residual,
+        E = sum rho(q s); q in the caller's observation order, None clears it (the default).  Kept across uploads and
+        reset_scene; with a scene resident it takes effect at the next optimise / phase call without another upload.
+        ValueError (the previous setting stays) for a negative or non-finite value, a wrong count, or a landmark left with
+        fewer than two observations of positive information."""
+        if q is None:
+            self._raise(self._lib.srk_ba_set_observation_information(C.c_void_p(self._h), None, C.c_int64(0)))
+            self._info_n = None
+            return
+        q = np.ascontiguousarray(q, dtype=np.float64).ravel()
+        self._raise(self._lib.srk_ba_set_observation_information(C.c_void_p(self._h), q.ctypes.data_as(C.POINTER(C.c_double)),
+                                                                 C.c_int64(q.size)))
+        self._info_n = int(q.size)
+
+    def observation_information(self):
+        """the information set on the handle in the caller's observation order; all 1 (one per observation of the resident
+        scene) when none is set"""
+        n = getattr(self, "_info_n", None)
+        if n is None:
+            n = self._n_observations()
+        q = np.empty(n, dtype=np.float64)
+        self._raise(self._lib.srk_ba_observation_information(C.c_void_p(self._h), q.ctypes.data_as(C.POINTER(C.c_double)),
+                                                             C.c_int64(n)))
+        return q
+
+    def observation_residuals(self):
+        """raw (unwhitened) residuals of the resident scene in pixels, [O, 2] in the caller's observation order: after an
+        optimise call those of the result.  Neither information nor a loss changes them."""
+        n = self._n_observations()
+        e = np.empty((n, 2), dtype=np.float64)
+        self._raise(self._lib.srk_ba_observation_residuals(C.c_void_p(self._h), e.ctypes.data_as(C.POINTER(C.c_double)),
+                                                           C.c_int64(n)))
+        return e
+
     def schur_fallback_landmarks(self):
         """landmarks of the uploaded scene that take the per-landmark Schur kernel (srk_ba_schur_fallback_landmarks)"""
         fn = self._lib.srk_ba_schur_fallback_landmarks

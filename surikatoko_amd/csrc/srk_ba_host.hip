@@ -183,6 +183,14 @@ struct srk_ba {
     std::vector<int64_t> shk_row_end, shk_col_begin; // skyline of the compact pose system (host, for the solve)
     int loss_kind = SRK_LOSS_NONE; // opt-in: robust loss (srk_ba_set_robust_loss); takes effect at the next optimise / phase call
     double loss_delta_pix = 0;     // its scale in pixels; the kernels get delta / f0 (robust_loss below)
+    // opt-in: per-observation information (srk_ba_set_observation_information).  info_user: the values in
+    // the caller's observation order, empty = none; kept across uploads and srk_ba_reset_scene.  info_on: the resident scene
+    // runs with them -- info_q holds them in the internal order, info_qf in the frame-major order of fobs_* (two-kernel
+    // derivative path only: fobs_of[internal observation] = its place there)
+    std::vector<double> info_user;
+    bool info_on = false;
+    DevBuf info_q, info_qf;
+    std::vector<int64_t> fobs_of;
     int profile_level = 0; // 0 = no events, 1 = phase events (report.ms_*), 2 = + event pairs around the MFMA updates
     bool chol_fused = true; // the solve's outer steps as one launch each (k_step256); srk_ba_set_solver_fusion
     // what the caller asked for.  A hand-off timeout switches chol_fused off for the rest of that call; the next upload /
@@ -366,7 +374,8 @@ void srk_ba_destroy(srk_ba* h)
                       &h->dj_ptr, &h->dj_ent, &h->dj_stage, &h->ds_pair_ptr, &h->ds_pair_fa, &h->ds_pair_fb, &h->ds_pair_ent, &h->ds_f_ptr, &h->ds_f_ent,
                       &h->jd_nf, &h->jd_frames, &h->jd_mask,
                       &h->jr_first, &h->jr_count, &h->jr_jmin, &h->jr_group, &h->lg_item, &h->lg_np, &h->lg_nf, &h->lg_pts, &h->lg_frames,
-                      &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk };
+                      &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk,
+                      &h->info_q, &h->info_qf };
     for (DevBuf* b : all) dev_free(*b);
     for (auto& a : h->att) {
         for (DevBuf* b : { &a.S, &a.rhs, &a.wy, &a.dc, &a.acc, &a.dx, &a.err_partial, &a.info, &a.dinv, &a.packed, &a.sync_flags, &a.irr, &a.det_stage, &a.det_rhs,
@@ -1074,6 +1083,33 @@ static bool frame_reorder(int mode, int64_t N, int32_t M, const int64_t* row_ptr
 }
 
 static void rearm_fusion(srk_ba* h);
+// per-observation information q (the caller's order) against a scene's CSR rows: every value finite and >= 0, one per
+// observation, and no landmark left with fewer than two observations of positive information (its 3 x 3 block would be singular)
+static int check_information(srk_ba* h, const char* who, const double* q, int64_t count, int64_t N, const int64_t* row_ptr)
+{
+    if (count != row_ptr[N]) {
+        h->last_error = std::string(who) + ": the observation information holds " + std::to_string(count) + " values, the scene " +
+                        std::to_string(row_ptr[N]) + " observations";
+        return SRK_E_ARGS;
+    }
+    for (int64_t o = 0; o < count; ++o)
+        if (!(std::isfinite(q[o]) && q[o] >= 0)) {
+            h->last_error = std::string(who) + ": observation information must be finite and not negative (observation " + std::to_string(o) + ")";
+            return SRK_E_ARGS;
+        }
+    for (int64_t i = 0; i < N; ++i) {
+        const int64_t cnt = row_ptr[i + 1] - row_ptr[i];
+        int64_t pos = 0;
+        for (int64_t o = row_ptr[i]; o < row_ptr[i + 1]; ++o) pos += q[o] > 0 ? 1 : 0;
+        if (pos < std::min<int64_t>(cnt, 2)) {
+            h->last_error = std::string(who) + ": observation information leaves landmark " + std::to_string(i) +
+                            " with fewer than two observations of positive information";
+            return SRK_E_ARGS;
+        }
+    }
+    return SRK_OK;
+}
+static int apply_information(srk_ba* h);
 static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_in, int32_t M,
                              const double* cam_R_in, const double* cam_T_in, const double* K_in, int shared_k,
                              const int64_t* row_ptr, const int32_t* obs_frame, const double* obs_uv,
@@ -1112,6 +1148,9 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     int rc = validate_scene(h, f0, N, pts_in, M, cam_R_in, cam_T_in, K_in, row_ptr, obs_frame, obs_uv);
     if (rc != SRK_OK) return rc;
     if (refuse_modes(h, h->fixed_k, h->deterministic, h->store_f32, h->schur_fp32, h->world, !h->igroup_user.empty())) return SRK_E_ARGS;
+    if (!h->info_user.empty() &&
+        check_information(h, "upload", h->info_user.data(), (int64_t)h->info_user.size(), N, row_ptr) != SRK_OK)
+        return SRK_E_ARGS;
     rearm_fusion(h);
     stage("validate");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1767,10 +1806,12 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     const bool need_frame_major = !h->jac_runs && !h->jac_fused;
     std::vector<int32_t> fobs_pt(need_frame_major ? (size_t)O : 0);
     std::vector<double> fobs_uv(need_frame_major ? (size_t)(2 * O) : 0);
+    h->fobs_of.assign(need_frame_major ? (size_t)O : 0, 0);
     if (need_frame_major) {
         std::vector<int64_t> fill(col_ptr.begin(), col_ptr.end() - 1);
         for (int64_t o = 0; o < O; ++o) {
             int64_t k = fill[(size_t)obs_frame[o]]++;
+            h->fobs_of[(size_t)o] = k;
             fobs_pt[(size_t)k] = obs_pt[(size_t)o];
             fobs_uv[(size_t)(2 * k)] = obs_uv[2 * o];
             fobs_uv[(size_t)(2 * k + 1)] = obs_uv[2 * o + 1];
@@ -1979,7 +2020,39 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
             for (DevBuf* b : { &a.Ssh, &a.rsh, &a.ysh, &a.dcsh, &a.dinvsh, &a.Tsh }) dev_free(*b);
     }
     stage("skyline, solver plans");
+    if ((rc = apply_information(h)) != SRK_OK) return rc;
     h->have_scene = true;
+    return SRK_OK;
+}
+
+// info_user (checked against the resident scene's rows) -> the device, in the internal order: landmark perm and observation
+// rank inside the landmark, the inverse of the mapping at the end of srk_ba_observation_weights; the frame-major copy beside it
+static int apply_information(srk_ba* h)
+{
+    const SrkDims& d = h->d;
+    h->info_on = false;
+    if (h->info_user.empty() || d.O == 0) return SRK_OK;
+    std::vector<double> qi((size_t)d.O), qf(h->fobs_of.size());
+    for (int64_t i = 0; i < d.N; ++i) {
+        const int64_t oi = h->row_ptr_int[(size_t)i], ou = h->row_ptr_user[(size_t)h->perm[(size_t)i]];
+        const int64_t cnt = h->row_ptr_int[(size_t)i + 1] - oi;
+        for (int64_t a = 0; a < cnt; ++a) {
+            const int64_t ai = h->obs_rank.empty() ? a : h->obs_rank[(size_t)(ou + a)];
+            qi[(size_t)(oi + ai)] = h->info_user[(size_t)(ou + a)];
+        }
+    }
+    for (size_t o = 0; o < qf.size(); ++o) qf[(size_t)h->fobs_of[o]] = qi[o];
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    int rc;
+    if ((rc = dev_alloc(h, h->info_q, (size_t)(8 * d.O))) != SRK_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->info_q.p, qi.data(), (size_t)(8 * d.O), hipMemcpyHostToDevice, s));
+    if (!qf.empty()) {
+        if ((rc = dev_alloc(h, h->info_qf, 8 * qf.size())) != SRK_OK) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->info_qf.p, qf.data(), 8 * qf.size(), hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope; every attempt stream starts behind this call
+    h->info_on = true;
     return SRK_OK;
 }
 
@@ -2186,13 +2259,16 @@ static int coll_group(srk_ba* h, int op, int G, double* const* ptrs, const int64
 
 // with_status: {solver info, point-update finite flag (lives behind acc)} are packed next to the error scalar and
 // summed over the ranks with it, so every rank takes the same accept / reject decision
-// the robust loss for the kernels: NULL when none is set, so the plain least-squares kernels run
+// the robust loss and the observation information for the kernels (DESIGN.md sections 10, 12): NULL when neither is set, so
+// the plain least-squares kernels run
 static const SrkLoss* robust_loss(const srk_ba* h, SrkLoss& L)
 {
-    if (h->loss_kind == SRK_LOSS_NONE) return nullptr;
+    if (h->loss_kind == SRK_LOSS_NONE && !h->info_on) return nullptr;
     L.kind = h->loss_kind;
     L.d = h->loss_delta_pix / h->f0;
     L.d2 = L.d * L.d;
+    L.q = h->info_on ? P<double>(h->info_q) : nullptr;
+    L.qf = h->info_on && !h->fobs_of.empty() ? P<double>(h->info_qf) : nullptr;
     return &L;
 }
 
@@ -3930,7 +4006,7 @@ int srk_ba_observation_weights(srk_ba* h, double* w, int64_t count)
     if (d.O == 0) return SRK_OK;
     SrkLoss Ls;
     const SrkLoss* L = robust_loss(h, Ls);
-    if (!L) {
+    if (!L || L->kind == SRK_LOSS_NONE) { // (information alone: the loss's factor is 1)
         std::fill(w, w + d.O, 1.0);
         return SRK_OK;
     }
@@ -3955,6 +4031,94 @@ int srk_ba_observation_weights(srk_ba* h, double* w, int64_t count)
         for (int64_t a = 0; a < cnt; ++a) {
             const int64_t ai = h->obs_rank.empty() ? a : h->obs_rank[(size_t)(ou + a)];
             w[ou + a] = wi[(size_t)(oi + ai)];
+        }
+    }
+    return SRK_OK;
+}
+
+// per-observation information: q[o] >= 0 multiplies observation o's squared residual, E = sum rho(q s).
+// q in the caller's observation order (the CSR order of the upload), NULL = none.  The handle keeps a copy: it is applied by
+// every later upload and survives srk_ba_reset_scene; with a scene resident it takes effect at the next optimise / phase
+// call, without another upload.  A refused call (SRK_E_ARGS) leaves the previous setting in force.
+int srk_ba_set_observation_information(srk_ba* h, const double* q, int64_t count)
+{
+    if (!h) return SRK_E_ARGS;
+    if (!q) {
+        h->info_user.clear();
+        h->info_on = false;
+        return SRK_OK;
+    }
+    try {
+        if (count < 0) { h->last_error = "set_observation_information: negative count"; return SRK_E_ARGS; }
+        if (h->have_scene) {
+            if (check_information(h, "set_observation_information", q, count, h->d.N, h->row_ptr_user.data()) != SRK_OK) return SRK_E_ARGS;
+        } else {
+            for (int64_t o = 0; o < count; ++o)
+                if (!(std::isfinite(q[o]) && q[o] >= 0)) {
+                    h->last_error = "set_observation_information: observation information must be finite and not negative (observation " + std::to_string(o) + ")";
+                    return SRK_E_ARGS;
+                }
+        }
+        std::vector<double> keep(q, q + count);
+        if (!h->have_scene) {
+            h->info_user.swap(keep);
+            return SRK_OK;
+        }
+        for (auto& a : h->att) // nothing of an earlier call may still read the values on the device
+            if (a.allocated && a.stream) HIPCHK(h, hipStreamSynchronize(a.stream));
+        h->info_user.swap(keep);
+        const bool was_on = h->info_on;
+        const int rc = apply_information(h);
+        if (rc != SRK_OK) { // (device failure: back to the previous values)
+            h->info_user.swap(keep);
+            h->info_on = false;
+            if (was_on) apply_information(h);
+        }
+        return rc;
+    } catch (const std::bad_alloc&) {
+        h->last_error = "set_observation_information: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+// the setting in the caller's order; all 1 when none is set
+int srk_ba_observation_information(srk_ba* h, double* q, int64_t count)
+{
+    if (!h || !q) return SRK_E_ARGS;
+    const int64_t want = !h->info_user.empty() ? (int64_t)h->info_user.size() : (h->have_scene ? h->d.O : count);
+    if (count != want) { h->last_error = "observation_information: count must be the number of observations"; return SRK_E_ARGS; }
+    if (h->info_user.empty()) std::fill(q, q + count, 1.0);
+    else std::copy(h->info_user.begin(), h->info_user.end(), q);
+    return SRK_OK;
+}
+// the raw residuals f0 (ex, ey) in pixels of the resident scene's observations, [count][2] in the caller's order; neither
+// information nor a loss touches them.  After srk_ba_optimize: the residuals of the result.
+int srk_ba_observation_residuals(srk_ba* h, double* exy_pixels, int64_t count)
+{
+    if (!h || !h->have_scene || !exy_pixels) return SRK_E_STATE;
+    const SrkDims& d = h->d;
+    if (count != d.O) { h->last_error = "observation_residuals: count must be the number of observations"; return SRK_E_ARGS; }
+    if (d.O == 0) return SRK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    HIPCHK(h, hipStreamSynchronize(s));
+    DevBuf ed;
+    int rc = dev_alloc(h, ed, (size_t)(16 * d.O));
+    if (rc != SRK_OK) return rc;
+    std::vector<double> ei((size_t)(2 * d.O));
+    srk_launch_obs_residuals(s, d, P<double>(h->pts[h->cur]), P<double>(h->cam[h->cur]), P<int32_t>(h->obs_frame),
+                             P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(ed));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ei.data(), ed.p, (size_t)(16 * d.O), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    dev_free(ed);
+    HIPCHK(h, e);
+    for (int64_t i = 0; i < d.N; ++i) { // internal order -> the caller's, as srk_ba_observation_weights
+        const int64_t oi = h->row_ptr_int[(size_t)i], ou = h->row_ptr_user[(size_t)h->perm[(size_t)i]];
+        const int64_t cnt = h->row_ptr_int[(size_t)i + 1] - oi;
+        for (int64_t a = 0; a < cnt; ++a) {
+            const int64_t ai = h->obs_rank.empty() ? a : h->obs_rank[(size_t)(ou + a)];
+            exy_pixels[2 * (ou + a)] = ei[(size_t)(2 * (oi + ai))];
+            exy_pixels[2 * (ou + a) + 1] = ei[(size_t)(2 * (oi + ai) + 1)];
         }
     }
     return SRK_OK;

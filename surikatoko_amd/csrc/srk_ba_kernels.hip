@@ -153,15 +153,16 @@ template <typename... Loss> struct SrkRobust {
     static constexpr bool on = sizeof...(Loss) == 1;
 };
 template <typename... Loss> __device__ __forceinline__ const SrkLoss& srk_loss(const Loss&... L) { return (L, ...); }
+// what the launchers send to the robust instantiations: a loss, or per-observation information (SrkLoss::q) without one
+static inline bool srk_robust_side(const SrkLoss* loss) { return loss && (loss->kind != SRK_LOSS_NONE || loss->q != nullptr); }
 
 // (w, rho) of one observation from its residual: s = ex^2 + ey^2, rho(s) its term of the objective, w = rho'(s) its IRLS
 // weight.  Every robust kernel that forms an observation's contribution calls this once, so V, U, W and the gradient all
 // see the same w.  Below the threshold (Huber s <= d^2) w is exactly 1 and rho is s itself: the kernels fold w (and
 // sqrt(w)) into scale factors they multiply anyway, and a multiply by 1.0 is exact, so a threshold above every residual
 // reproduces the plain kernels' values bit for bit.
-__device__ __forceinline__ void srk_robust_wr(double ex, double ey, const SrkLoss& L, double& w, double& rho)
+__device__ __forceinline__ void srk_rho_w(double s, const SrkLoss& L, double& w, double& rho)
 {
-    const double s = ex * ex + ey * ey;
     w = 1.0;
     rho = s;
     if (L.kind == SRK_LOSS_HUBER) {
@@ -175,6 +176,19 @@ __device__ __forceinline__ void srk_robust_wr(double ex, double ey, const SrkLos
         w = 1.0 / (1.0 + t);
         rho = L.d2 * log1p(t);
     }
+}
+
+// ---- per-observation information (srk_ba_set_observation_information): observation o carries q_o >= 0,
+// its whitened squared residual is q s, its term of the objective rho(q s) and its weight in the normal equations
+// w_eff = q rho'(q s).  The robust instantiations read q from SrkLoss::q (internal observation order; k_jac_frames from
+// SrkLoss::qf, the frame-major order); a null pointer is q = 1.  Kind SRK_LOSS_NONE with a pointer is a valid robust-side
+// instantiation: rho the identity, w_eff = q.  The kernels use w_eff exactly where they used w, so q = 1 changes no bit
+// (1.0 * s and 1.0 * w are exact) and q = 0 gives exact zeros: sqrt(0) on the stored factors, 0 on the sums.
+__device__ __forceinline__ double srk_info(const double* __restrict__ q, int64_t o) { return q ? q[o] : 1.0; }
+__device__ __forceinline__ void srk_robust_wr(double ex, double ey, const SrkLoss& L, double qi, double& w, double& rho)
+{
+    srk_rho_w(qi * (ex * ex + ey * ey), L, w, rho);
+    w *= qi;
 }
 
 // A_v = r p'_v - p r'_v , B_v = r q'_v - q r'_v for the three landmark variables (:1450-1455)
@@ -254,7 +268,7 @@ __global__ __launch_bounds__(256) void k_jac_points(SrkDims d, const double* __r
             double sc = 0.7071067811865476 * g.s1; // sqrt(2 / r^4): both sides of every product carry it once
             if constexpr (SrkRobust<Loss...>::on) {
                 double w, rho;
-                srk_robust_wr(g.ex, g.ey, srk_loss(L...), w, rho);
+                srk_robust_wr(g.ex, g.ey, srk_loss(L...), srk_info(srk_loss(L...).q, o), w, rho);
                 if (w != 1.0) { // (an inlier's w is exactly 1: nothing to scale, no square root)
                     sc *= sqrt(w);
                     g.s1 *= w;
@@ -371,7 +385,7 @@ __global__ __launch_bounds__(256) void k_jac_fused(SrkDims d, const double* __re
             double s1 = 2 * ir2, s2 = s1 * ir2; // 2 / r^2 , 2 / r^4 (robust: both times w; sc below then carries sqrt(w))
             if constexpr (SrkRobust<Loss...>::on) {
                 double w, rho;
-                srk_robust_wr(p * ir - uv.x * c[46], q * ir - uv.y * c[46], srk_loss(L...), w, rho);
+                srk_robust_wr(p * ir - uv.x * c[46], q * ir - uv.y * c[46], srk_loss(L...), srk_info(srk_loss(L...).q, o), w, rho);
                 s1 *= w;
                 s2 *= w;
             }
@@ -479,7 +493,7 @@ void srk_launch_jac_fused(hipStream_t s, const SrkDims& d, const double* pts, co
 {
     if (d.O == 0) return;
     int64_t blocks = (d.O + SRK_JF_OBS - 1) / SRK_JF_OBS;
-    if (loss && loss->kind != SRK_LOSS_NONE) {
+    if (srk_robust_side(loss)) {
         const dim3 grid((unsigned)blocks);
         if (d.fv == 6)
             hipLaunchKernelGGL((k_jac_fused<double, 6, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W, Vg,
@@ -648,7 +662,9 @@ __global__ __launch_bounds__(256, 2) void k_jac_runs(SrkDims d, const double* __
                 double exs = (p * ir - uv.x * c[46]) * 1.4142135623730951, eys = (q * ir - uv.y * c[46]) * 1.4142135623730951;
                 if constexpr (SrkRobust<Loss...>::on) { // sqrt(w) on both sides of every product
                     double w, rho;
-                    srk_robust_wr(p * ir - uv.x * c[46], q * ir - uv.y * c[46], srk_loss(L...), w, rho);
+                    // (the information is read here, inside the valid branch, not in the prefetch: one more pipelined
+                    // pair of registers does not fit beside the frame sums)
+                    srk_robust_wr(p * ir - uv.x * c[46], q * ir - uv.y * c[46], srk_loss(L...), srk_info(srk_loss(L...).q, o), w, rho);
                     if (w != 1.0) { // (an inlier's w is exactly 1: nothing to scale, no square root)
                         const double sw = sqrt(w);
                         sc *= sw;
@@ -800,7 +816,7 @@ void srk_launch_jac_runs(hipStream_t s, const SrkDims& d, const double* pts, con
             else hipLaunchKernelGGL((k_jac_runs<double, MASKED, false, 10, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);    \
         }                                                                                                                             \
     } while (0)
-    const bool robust = loss && loss->kind != SRK_LOSS_NONE;
+    const bool robust = srk_robust_side(loss);
     if (d.fv == 6) { // fixed intrinsics: fp64 storage, never deterministic
         if (robust) {
             if (task_group) hipLaunchKernelGGL((k_jac_runs<double, true, false, 6, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);
@@ -824,7 +840,7 @@ void srk_launch_jac_points(hipStream_t s, const SrkDims& d, const double* pts, c
 {
     if (d.O == 0) return;
     int64_t blocks = (d.O + 255) / 256;
-    if (loss && loss->kind != SRK_LOSS_NONE) {
+    if (srk_robust_side(loss)) {
         const dim3 grid((unsigned)blocks);
         if (d.fv == 6)
             hipLaunchKernelGGL((k_jac_points<double, 6, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W, Vg,
@@ -887,7 +903,7 @@ __global__ __launch_bounds__(256) void k_jac_frames(SrkDims d, const double* __r
         obs_pqr(c, X0, X1, X2, uv.x, uv.y, g);
         if constexpr (SrkRobust<Loss...>::on) {
             double w, rho;
-            srk_robust_wr(g.ex, g.ey, srk_loss(L...), w, rho);
+            srk_robust_wr(g.ex, g.ey, srk_loss(L...), srk_info(srk_loss(L...).qf, k), w, rho);
             g.s1 *= w;
             g.s2 *= w;
         }
@@ -923,7 +939,7 @@ void srk_launch_jac_frames(hipStream_t s, const SrkDims& d, int64_t max_frame_ob
 {
     if (d.O == 0 || max_frame_obs == 0) return;
     int64_t chunks = (max_frame_obs + SRK_FCHUNK - 1) / SRK_FCHUNK;
-    if (loss && loss->kind != SRK_LOSS_NONE) {
+    if (srk_robust_side(loss)) {
         const dim3 grid((unsigned)chunks, (unsigned)d.M);
         if (d.fv == 6)
             hipLaunchKernelGGL((k_jac_frames<6, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, col_ptr, fobs_pt, fobs_uv, Ug, *loss);
@@ -2925,7 +2941,7 @@ __global__ __launch_bounds__(256) void k_error_robust(SrkDims d, const double* _
         const double* c = cam + (int64_t)SRK_CAM_PACK * obs_frame[o];
         double ex, ey, w, rho;
         err_residual(c, c[47], pts + 3 * (int64_t)obs_pt[o], reinterpret_cast<const double2*>(obs_uv)[o], ex, ey);
-        srk_robust_wr(ex, ey, L, w, rho);
+        srk_robust_wr(ex, ey, L, srk_info(L.q, o), w, rho);
         sum += rho;
     }
     sum = wave_sum(sum);
@@ -2961,7 +2977,7 @@ __global__ __launch_bounds__(256) void k_error_staged_robust(SrkDims d, const do
         const double* c = sCam[obs_frame[o] - jmin];
         double ex, ey, w, rho;
         err_residual(c, c[21], pts + 3 * (int64_t)obs_pt[o], reinterpret_cast<const double2*>(obs_uv)[o], ex, ey);
-        srk_robust_wr(ex, ey, L, w, rho);
+        srk_robust_wr(ex, ey, L, srk_info(L.q, o), w, rho);
         sum += rho;
     }
     sum = wave_sum(sum);
@@ -2982,8 +2998,22 @@ __global__ __launch_bounds__(256) void k_obs_weights(SrkDims d, const double* __
     const double* c = cam + (int64_t)SRK_CAM_PACK * obs_frame[o];
     double ex, ey, w, rho;
     err_residual(c, c[47], pts + 3 * (int64_t)obs_pt[o], reinterpret_cast<const double2*>(obs_uv)[o], ex, ey);
-    srk_robust_wr(ex, ey, L, w, rho);
+    srk_rho_w(srk_info(L.q, o) * (ex * ex + ey * ey), L, w, rho); // the loss's factor rho'(q s) alone, without q
     w_out[o] = w;
+}
+
+// the raw residuals f0 (ex, ey) in pixels of every observation of the resident scene, internal order
+// (srk_ba_observation_residuals): the residual as the error pass forms it, untouched by information and loss
+__global__ __launch_bounds__(256) void k_obs_residuals(SrkDims d, const double* __restrict__ pts, const double* __restrict__ cam,
+                                                       const int32_t* __restrict__ obs_frame, const int32_t* __restrict__ obs_pt,
+                                                       const double* __restrict__ obs_uv, double* __restrict__ e_out)
+{
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= d.O) return;
+    const double* c = cam + (int64_t)SRK_CAM_PACK * obs_frame[o];
+    double ex, ey;
+    err_residual(c, c[47], pts + 3 * (int64_t)obs_pt[o], reinterpret_cast<const double2*>(obs_uv)[o], ex, ey);
+    reinterpret_cast<double2*>(e_out)[o] = make_double2(c[47] * ex, c[47] * ey);
 }
 
 void srk_launch_obs_weights(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int32_t* obs_frame,
@@ -2992,6 +3022,13 @@ void srk_launch_obs_weights(hipStream_t s, const SrkDims& d, const double* pts, 
     if (d.O == 0) return;
     hipLaunchKernelGGL(k_obs_weights, dim3((unsigned)((d.O + 255) / 256)), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
                        loss, w);
+}
+
+void srk_launch_obs_residuals(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int32_t* obs_frame,
+                              const int32_t* obs_pt, const double* obs_uv, double* e)
+{
+    if (d.O == 0) return;
+    hipLaunchKernelGGL(k_obs_residuals, dim3((unsigned)((d.O + 255) / 256)), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, e);
 }
 
 // scoring variant (MultiViewIterativeFactorizer::ReprojError, multi-view-factorization.cpp:415-475): observations whose
@@ -3071,7 +3108,7 @@ void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const 
                       const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* partial,
                       int32_t n_partial, double* err_out, const int32_t* wg_jmin, int* info, int* info2, const SrkLoss* loss)
 {
-    const bool robust = loss && loss->kind != SRK_LOSS_NONE;
+    const bool robust = srk_robust_side(loss);
     if (wg_jmin && d.O > 0) { // staged cameras: one partial sum per run of SRK_JF_OBS observations
         const int64_t nb = srk_error_partials_staged(d);
         if (robust)

@@ -75,13 +75,20 @@ struct SrkDetSchur {
 // ---- robust loss (srk_ba_set_robust_loss): observation o with squared residual s = ex^2 + ey^2 ((pix/f0)^2) enters the
 // objective as rho(s) and the normal equations with the IRLS weight w = rho'(s).  Kinds: SRK_LOSS_HUBER rho = s for s <= d^2,
 // 2 d sqrt(s) - d^2 above; SRK_LOSS_CAUCHY rho = d^2 log(1 + s / d^2).  d = delta_pixels / f0.  The launchers below take a
-// loss pointer: NULL (or kind 0) launches the plain least-squares kernels, anything else their robust instantiations.
+// loss pointer: NULL (or kind 0 without information) launches the plain least-squares kernels, anything else their robust
+// instantiations.
 #define SRK_LOSS_NONE 0
 #define SRK_LOSS_HUBER 1
 #define SRK_LOSS_CAUCHY 2
 struct SrkLoss {
     int32_t kind; // SRK_LOSS_*
     double d, d2; // threshold in normalised units (pix / f0) and its square
+    // per-observation information q_o >= 0 (srk_ba_set_observation_information), device pointers, NULL =
+    // none (q = 1): the observation enters the objective as rho(q s) and the normal equations with q rho'(q s).  q in the
+    // internal (point-major) observation order, qf the same values in the frame-major order of fobs_* (k_jac_frames alone
+    // reads it).  Kind SRK_LOSS_NONE with q given is valid: rho is the identity then.
+    const double* q;
+    const double* qf;
 };
 
 // ---- BA kernels (srk_ba_kernels.hip) ----
@@ -161,10 +168,13 @@ void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const 
                       int32_t n_partial, double* err_out,
                       const int32_t* wg_jmin /* fused-Jacobian frame windows, or NULL: gather the cameras */,
                       int* info = nullptr, int* info2 = nullptr /* given: packed into err_out[1..2] and cleared */,
-                      const SrkLoss* loss = nullptr /* given (kind != 0): the sum of rho(s) instead of s */);
+                      const SrkLoss* loss = nullptr /* given (kind != 0 or information): the sum of rho(q s) instead of s */);
 // the IRLS weights w = rho'(s) of the resident scene, one per observation in the internal order (srk_ba_observation_weights)
 void srk_launch_obs_weights(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int32_t* obs_frame,
                             const int32_t* obs_pt, const double* obs_uv, const SrkLoss& loss, double* w);
+// the raw residuals f0 (ex, ey) in pixels, [O][2] in the internal order (srk_ba_observation_residuals)
+void srk_launch_obs_residuals(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int32_t* obs_frame,
+                              const int32_t* obs_pt, const double* obs_uv, double* e);
 int32_t srk_error_partials(const SrkDims& d);
 int64_t srk_error_partials_staged(const SrkDims& d); // partial sums written when wg_jmin is given
 void srk_launch_error_score(hipStream_t s, int64_t O, const double* pts, const double* cam, const int32_t* obs_frame,
