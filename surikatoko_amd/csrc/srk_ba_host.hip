@@ -2362,22 +2362,21 @@ static int phase_schur(srk_ba* h, srk_ba::Attempt& a, double c, bool local_only)
     srk_launch_env_zero(s, d.ld, P<int64_t>(h->env_col), P<double>(a.S), P<double>(a.rhs), P<int32_t>(a.irr)); // S band, rhs, hand-back counter
     const SrkDetSchur dets{ P<double>(a.det_stage), P<double>(a.det_rhs), P<int32_t>(h->ds_pair_ptr), P<int32_t>(h->ds_pair_fa),
                             P<int32_t>(h->ds_pair_fb), P<int32_t>(h->ds_pair_ent), h->ds_n_pairs, P<int32_t>(h->ds_f_ptr), P<int32_t>(h->ds_f_ent) };
-    if (d.fv == 6) {
-        // fixed intrinsics: the runs of at most SRK_WS_NF_HOST frames through k_schur_mm on 6-wide blocks, every other landmark
-        // through the per-landmark kernel
-        srk_launch_schur_grouped(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_pt), P<uint8_t>(h->obs_slot),
-                                 P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(a.S),
-                                 P<double>(a.rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
-                                 P<int32_t>(h->grp_frames), h->n_groups, h->n_groups_wide, h->n_groups_mid, 0,
-                                 P<int32_t>(a.irr), h->n_mm_uniform, h->n_mm_ragged, nullptr);
+    // the runs of at most SRK_WS_NF_HOST frames through k_schur_mm (with fixed intrinsics on 6-wide blocks, which are built
+    // neither for fp32 run sums nor for the deterministic mode: srk_dispatch_det, srk_launch_schur_grouped), the wider ones
+    // through k_schur_grouped
+    const bool cal = d.fv == 6;
+    srk_launch_schur_grouped(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_pt), P<uint8_t>(h->obs_slot),
+                             P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(a.S),
+                             P<double>(a.rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
+                             P<int32_t>(h->grp_frames), h->n_groups, h->n_groups_wide, h->n_groups_mid,
+                             !cal && h->schur_fp32 ? 1 : 0, P<int32_t>(a.irr), h->n_mm_uniform, h->n_mm_ragged,
+                             !cal && h->det_active ? &dets : nullptr);
+    if (cal) {
+        // fixed intrinsics: every other landmark through the per-landmark kernel
         srk_launch_schur(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg),
                          P<double>(a.S), P<double>(a.rhs), P<int32_t>(h->cal_list), h->n_cal_list);
     } else {
-        srk_launch_schur_grouped(s, d, c, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_pt), P<uint8_t>(h->obs_slot),
-                                 P<uint32_t>(h->pt_mask), P<double>(h->W), P<double>(h->Vg), P<double>(a.S),
-                                 P<double>(a.rhs), P<int32_t>(h->grp_first), P<int32_t>(h->grp_count), P<int32_t>(h->grp_nf),
-                                 P<int32_t>(h->grp_frames), h->n_groups, h->n_groups_wide, h->n_groups_mid, h->schur_fp32 ? 1 : 0,
-                                 P<int32_t>(a.irr), h->n_mm_uniform, h->n_mm_ragged, h->det_active ? &dets : nullptr);
         srk_launch_schur_long(s, d, c, P<double>(h->W), P<double>(h->Vg), P<double>(a.S), P<double>(a.rhs),
                               P<int32_t>(h->lg_item), h->n_long_items, P<int32_t>(h->lg_np), P<int32_t>(h->lg_nf), P<int32_t>(h->lg_pts),
                               P<int32_t>(h->lg_frames), P<int64_t>(h->lg_obs_off), P<int32_t>(h->lg_obs), h->long_fb);

@@ -10,6 +10,7 @@
 // run of landmarks) these kernels are HBM-bound streaming passes over the observation arrays: every global access is lane-contiguous (SoA blocks), per-landmark sums are wavefront
 // segmented reductions, per-frame sums are register accumulators + wavefront reductions + one atomic per block.
 #include "srk_dev.hpp"
+#include <cassert>
 #include <type_traits>
 
 #define WAVE 64
@@ -155,6 +156,59 @@ template <typename... Loss> struct SrkRobust {
 template <typename... Loss> __device__ __forceinline__ const SrkLoss& srk_loss(const Loss&... L) { return (L, ...); }
 // what the launchers send to the robust instantiations: a loss, or per-observation information (SrkLoss::q) without one
 static inline bool srk_robust_side(const SrkLoss* loss) { return loss && (loss->kind != SRK_LOSS_NONE || loss->q != nullptr); }
+
+// ------------------------------------------------------------------ variant dispatch: run-time choices -> template arguments
+// Every launcher of a kernel with variants goes through these helpers: each turns one run-time choice into a compile-time tag
+// and calls a generic lambda with it, and each offers only the combinations the library builds -- a kernel is instantiated for
+// exactly the tags its launcher's lambda can receive.  A combination the library does not build is an assert -- live in the
+// product build too (no -DNDEBUG), so it aborts the process where the rest of the library returns an error: it marks a bug in
+// the host code, which refuses every one of these combinations at the setters (fixed_k_conflict), never a caller's input.
+//
+// The layout of the point-frame blocks: (storage type WT of W, frame variables FV) is one of (double, 10), (float, 10)
+// (srk_ba_set_storage_precision) and (double, 6) (srk_ba_set_fixed_intrinsics).  Fixed intrinsics mean fp64 storage: the 18-plane
+// layout is built for double alone and the host refuses the two modes together, so there is no (float, 6) and d.w_f32 is not
+// looked at when d.fv == 6.  f(layout tag, W as WT*).
+template <typename WT_, int FV_> struct SrkLayout {
+    using WT = WT_;
+    static constexpr int FV = FV_;
+};
+template <typename WP, typename F> static inline void srk_dispatch_layout(const SrkDims& d, WP* W, F&& f)
+{
+    static_assert(std::is_same_v<std::remove_const_t<WP>, double>, "the launchers take W as double*, whatever it stores");
+    using WF = std::conditional_t<std::is_const_v<WP>, const float, float>;
+    assert(!(d.fv == 6 && d.w_f32) && "fixed intrinsics keep fp64 storage");
+    if (d.fv == 6) f(SrkLayout<double, 6>{}, W);
+    else if (d.w_f32) f(SrkLayout<float, 10>{}, reinterpret_cast<WF*>(W));
+    else f(SrkLayout<double, 10>{}, W);
+}
+// FV alone, for the kernels that do not touch W: f(std::integral_constant<int, FV>)
+template <typename F> static inline void srk_dispatch_fv(int fv, F&& f)
+{
+    if (fv == 6) f(std::integral_constant<int, 6>{});
+    else f(std::integral_constant<int, 10>{});
+}
+// a flag: f(std::true_type) or f(std::false_type)
+template <typename F> static inline void srk_dispatch_bool(bool on, F&& f)
+{
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+// the deterministic mode (DET) is built for FV = 10 only -- the host refuses it with fixed intrinsics -- so a 6-variable layout
+// is offered std::false_type alone, and asking for `det` with it is a caller's error
+template <typename Layout, typename F> static inline void srk_dispatch_det(Layout, bool det, F&& f)
+{
+    assert((Layout::FV == 10 || !det) && "the deterministic mode is not built for fixed intrinsics");
+    if constexpr (Layout::FV == 10) {
+        if (det) return f(std::true_type{});
+    }
+    f(std::false_type{});
+}
+// the `Loss...` pack: f() for the plain kernel, f(*loss) for the robust side (the lambda's `auto... L` is the kernel's pack)
+template <typename F> static inline void srk_dispatch_loss(const SrkLoss* loss, F&& f)
+{
+    if (srk_robust_side(loss)) f(*loss);
+    else f();
+}
 
 // (w, rho) of one observation from its residual: s = ex^2 + ey^2, rho(s) its term of the objective, w = rho'(s) its IRLS
 // weight.  Every robust kernel that forms an observation's contribution calls this once, so V, U, W and the gradient all
@@ -492,29 +546,14 @@ void srk_launch_jac_fused(hipStream_t s, const SrkDims& d, const double* pts, co
                           double* Vg, double* Ug, const int32_t* wg_jmin, const SrkLoss* loss)
 {
     if (d.O == 0) return;
-    int64_t blocks = (d.O + SRK_JF_OBS - 1) / SRK_JF_OBS;
-    if (srk_robust_side(loss)) {
-        const dim3 grid((unsigned)blocks);
-        if (d.fv == 6)
-            hipLaunchKernelGGL((k_jac_fused<double, 6, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W, Vg,
-                               Ug, wg_jmin, *loss);
-        else if (d.w_f32)
-            hipLaunchKernelGGL((k_jac_fused<float, 10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                               reinterpret_cast<float*>(W), Vg, Ug, wg_jmin, *loss);
-        else
-            hipLaunchKernelGGL((k_jac_fused<double, 10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W,
-                               Vg, Ug, wg_jmin, *loss);
-        return;
-    }
-    if (d.fv == 6)
-        hipLaunchKernelGGL((k_jac_fused<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                           W, Vg, Ug, wg_jmin);
-    else if (d.w_f32)
-        hipLaunchKernelGGL(k_jac_fused<float>, dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                           reinterpret_cast<float*>(W), Vg, Ug, wg_jmin);
-    else
-        hipLaunchKernelGGL(k_jac_fused<double>, dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                           W, Vg, Ug, wg_jmin);
+    const dim3 grid((unsigned)((d.O + SRK_JF_OBS - 1) / SRK_JF_OBS));
+    srk_dispatch_layout(d, W, [&](auto lay, auto* Wp) {
+        srk_dispatch_loss(loss, [&](auto... L) {
+            using Lay = decltype(lay);
+            hipLaunchKernelGGL((k_jac_fused<typename Lay::WT, Lay::FV, decltype(L)...>), grid, dim3(256), 0, s, d, pts, cam, obs_frame,
+                               obs_pt, obs_uv, Wp, Vg, Ug, wg_jmin, L...);
+        });
+    });
 }
 
 // ------------------------------------------------------------------ K2 by runs: a lane keeps ONE frame for a whole task
@@ -794,43 +833,20 @@ void srk_launch_jac_runs(hipStream_t s, const SrkDims& d, const double* pts, con
 {
     if (n_tasks <= 0) return;
     const dim3 grid((unsigned)((n_tasks + 3) / 4));
-#define SRK_JR_ARGS(WP) d, pts, cam, row_ptr, obs_frame, obs_uv, WP, Vg, Ug, task_first, task_count, n_tasks, wg_jmin, task_group, grp_nf, grp_frames, pt_mask, det ? det->stage : nullptr, frames_stride
-#define SRK_JR_LAUNCH(MASKED)                                                                                                         \
-    do {                                                                                                                              \
-        if (det) {                                                                                                                    \
-            if (d.w_f32) hipLaunchKernelGGL((k_jac_runs<float, MASKED, true>), grid, dim3(256), 0, s, SRK_JR_ARGS(reinterpret_cast<float*>(W))); \
-            else hipLaunchKernelGGL((k_jac_runs<double, MASKED, true>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));                          \
-        } else {                                                                                                                      \
-            if (d.w_f32) hipLaunchKernelGGL((k_jac_runs<float, MASKED, false>), grid, dim3(256), 0, s, SRK_JR_ARGS(reinterpret_cast<float*>(W))); \
-            else hipLaunchKernelGGL((k_jac_runs<double, MASKED, false>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));                         \
-        }                                                                                                                             \
-    } while (0)
-    // the robust instantiations: the same choices, the loss behind the last argument
-#define SRK_JR_LAUNCH_ROBUST(MASKED)                                                                                                  \
-    do {                                                                                                                              \
-        if (det) {                                                                                                                    \
-            if (d.w_f32) hipLaunchKernelGGL((k_jac_runs<float, MASKED, true, 10, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(reinterpret_cast<float*>(W)), *loss); \
-            else hipLaunchKernelGGL((k_jac_runs<double, MASKED, true, 10, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);     \
-        } else {                                                                                                                      \
-            if (d.w_f32) hipLaunchKernelGGL((k_jac_runs<float, MASKED, false, 10, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(reinterpret_cast<float*>(W)), *loss); \
-            else hipLaunchKernelGGL((k_jac_runs<double, MASKED, false, 10, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);    \
-        }                                                                                                                             \
-    } while (0)
-    const bool robust = srk_robust_side(loss);
-    if (d.fv == 6) { // fixed intrinsics: fp64 storage, never deterministic
-        if (robust) {
-            if (task_group) hipLaunchKernelGGL((k_jac_runs<double, true, false, 6, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);
-            else hipLaunchKernelGGL((k_jac_runs<double, false, false, 6, SrkLoss>), grid, dim3(256), 0, s, SRK_JR_ARGS(W), *loss);
-        } else if (task_group) hipLaunchKernelGGL((k_jac_runs<double, true, false, 6>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));
-        else hipLaunchKernelGGL((k_jac_runs<double, false, false, 6>), grid, dim3(256), 0, s, SRK_JR_ARGS(W));
-    } else if (robust) {
-        if (task_group) SRK_JR_LAUNCH_ROBUST(true);
-        else SRK_JR_LAUNCH_ROBUST(false);
-    } else if (task_group) SRK_JR_LAUNCH(true); // tasks over unions of frame lists (ragged tracks)
-    else SRK_JR_LAUNCH(false);
-#undef SRK_JR_LAUNCH_ROBUST
-#undef SRK_JR_LAUNCH
-#undef SRK_JR_ARGS
+    // MASKED: tasks over unions of frame lists (ragged tracks); the robust instantiations take the loss behind the last argument
+    srk_dispatch_layout(d, W, [&](auto lay, auto* Wp) {
+        srk_dispatch_bool(task_group != nullptr, [&](auto masked) {
+            srk_dispatch_det(lay, det != nullptr, [&](auto dt) {
+                srk_dispatch_loss(loss, [&](auto... L) {
+                    using Lay = decltype(lay);
+                    hipLaunchKernelGGL((k_jac_runs<typename Lay::WT, decltype(masked)::value, decltype(dt)::value, Lay::FV, decltype(L)...>),
+                                       grid, dim3(256), 0, s, d, pts, cam, row_ptr, obs_frame, obs_uv, Wp, Vg, Ug, task_first, task_count,
+                                       n_tasks, wg_jmin, task_group, grp_nf, grp_frames, pt_mask, det ? det->stage : nullptr,
+                                       frames_stride, L...);
+                });
+            });
+        });
+    });
     if (det) hipLaunchKernelGGL(k_jac_det_gather, dim3((unsigned)d.M), dim3(128), 0, s, d.M, det->ptr, det->ent, det->stage, Ug);
 }
 
@@ -839,29 +855,14 @@ void srk_launch_jac_points(hipStream_t s, const SrkDims& d, const double* pts, c
                            double* Vg, const SrkLoss* loss)
 {
     if (d.O == 0) return;
-    int64_t blocks = (d.O + 255) / 256;
-    if (srk_robust_side(loss)) {
-        const dim3 grid((unsigned)blocks);
-        if (d.fv == 6)
-            hipLaunchKernelGGL((k_jac_points<double, 6, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W, Vg,
-                               *loss);
-        else if (d.w_f32)
-            hipLaunchKernelGGL((k_jac_points<float, 10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                               reinterpret_cast<float*>(W), Vg, *loss);
-        else
-            hipLaunchKernelGGL((k_jac_points<double, 10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, W,
-                               Vg, *loss);
-        return;
-    }
-    if (d.fv == 6)
-        hipLaunchKernelGGL((k_jac_points<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                           W, Vg);
-    else if (d.w_f32)
-        hipLaunchKernelGGL(k_jac_points<float>, dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                           reinterpret_cast<float*>(W), Vg);
-    else
-        hipLaunchKernelGGL(k_jac_points<double>, dim3((unsigned)blocks), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                           W, Vg);
+    const dim3 grid((unsigned)((d.O + 255) / 256));
+    srk_dispatch_layout(d, W, [&](auto lay, auto* Wp) {
+        srk_dispatch_loss(loss, [&](auto... L) {
+            using Lay = decltype(lay);
+            hipLaunchKernelGGL((k_jac_points<typename Lay::WT, Lay::FV, decltype(L)...>), grid, dim3(256), 0, s, d, pts, cam, obs_frame,
+                               obs_pt, obs_uv, Wp, Vg, L...);
+        });
+    });
 }
 
 // ------------------------------------------------------------------ K2b: frame-major Jacobian pass
@@ -938,21 +939,13 @@ void srk_launch_jac_frames(hipStream_t s, const SrkDims& d, int64_t max_frame_ob
                            double* Ug, const SrkLoss* loss)
 {
     if (d.O == 0 || max_frame_obs == 0) return;
-    int64_t chunks = (max_frame_obs + SRK_FCHUNK - 1) / SRK_FCHUNK;
-    if (srk_robust_side(loss)) {
-        const dim3 grid((unsigned)chunks, (unsigned)d.M);
-        if (d.fv == 6)
-            hipLaunchKernelGGL((k_jac_frames<6, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, col_ptr, fobs_pt, fobs_uv, Ug, *loss);
-        else
-            hipLaunchKernelGGL((k_jac_frames<10, SrkLoss>), grid, dim3(256), 0, s, d, pts, cam, col_ptr, fobs_pt, fobs_uv, Ug, *loss);
-        return;
-    }
-    if (d.fv == 6)
-        hipLaunchKernelGGL(k_jac_frames<6>, dim3((unsigned)chunks, (unsigned)d.M), dim3(256), 0, s, d, pts, cam, col_ptr,
-                           fobs_pt, fobs_uv, Ug);
-    else
-        hipLaunchKernelGGL(k_jac_frames<10>, dim3((unsigned)chunks, (unsigned)d.M), dim3(256), 0, s, d, pts, cam, col_ptr,
-                           fobs_pt, fobs_uv, Ug);
+    const dim3 grid((unsigned)((max_frame_obs + SRK_FCHUNK - 1) / SRK_FCHUNK), (unsigned)d.M);
+    srk_dispatch_fv(d.fv, [&](auto fv) {
+        srk_dispatch_loss(loss, [&](auto... L) {
+            hipLaunchKernelGGL((k_jac_frames<decltype(fv)::value, decltype(L)...>), grid, dim3(256), 0, s, d, pts, cam, col_ptr, fobs_pt,
+                               fobs_uv, Ug, L...);
+        });
+    });
 }
 
 // expand the packed per-frame accumulators to the oracle's [M][10][10] + [M][10] layout (tests / downloads)
@@ -1137,16 +1130,12 @@ void srk_launch_schur(hipStream_t s, const SrkDims& d, double c, const int64_t* 
                       int64_t n_list)
 {
     if (n_list <= 0) return;
-    int64_t blocks = n_list < 65536 ? n_list : 65536;
-    if (d.fv == 6) // fixed intrinsics (fp64 storage only: srk_ba_set_fixed_intrinsics)
-        hipLaunchKernelGGL((k_schur<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, c, row_ptr, obs_frame, W, Vg, S, rhs,
-                           pt_list, n_list);
-    else if (d.w_f32)
-        hipLaunchKernelGGL(k_schur<float>, dim3((unsigned)blocks), dim3(256), 0, s, d, c, row_ptr, obs_frame,
-                           reinterpret_cast<const float*>(W), Vg, S, rhs, pt_list, n_list);
-    else
-        hipLaunchKernelGGL(k_schur<double>, dim3((unsigned)blocks), dim3(256), 0, s, d, c, row_ptr, obs_frame, W, Vg, S, rhs,
-                           pt_list, n_list);
+    const dim3 grid((unsigned)(n_list < 65536 ? n_list : 65536));
+    srk_dispatch_layout(d, W, [&](auto lay, auto* Wp) {
+        using Lay = decltype(lay);
+        hipLaunchKernelGGL((k_schur<typename Lay::WT, Lay::FV>), grid, dim3(256), 0, s, d, c, row_ptr, obs_frame, Wp, Vg, S, rhs, pt_list,
+                           n_list);
+    });
 }
 
 // ------------------------------------------------------------------ K3g: Schur accumulation, grouped landmarks
@@ -1228,7 +1217,7 @@ __global__ __launch_bounds__(SRK_GRP_THREADS) void k_schur_grouped(
     const uint8_t* __restrict__ obs_slot, const uint32_t* __restrict__ pt_mask, const WT* __restrict__ W,
     const double* __restrict__ Vg, double* __restrict__ S, double* __restrict__ rhs,
     const int32_t* __restrict__ grp_first, const int32_t* __restrict__ grp_count, const int32_t* __restrict__ grp_nf,
-    const int32_t* __restrict__ grp_frames, int nf_skip /* runs with at most this many frames belong to k_schur_mm / k_schur_ws */)
+    const int32_t* __restrict__ grp_frames, int nf_skip /* runs with at most this many frames belong to k_schur_mm */)
 {
     // one LDS arena: W | Y staging during the accumulation, then the staging buffer of the coalesced flush
     using L = SchurLayout<T>;
@@ -1441,245 +1430,8 @@ __global__ __launch_bounds__(SRK_GRP_THREADS) void k_schur_grouped(
     }
 }
 
-// ------------------------------------------------------------------ K3w: the same, with a dedicated loader wave
-// k_schur_grouped spends about as long staging (global -> LDS, Y = E^-1 W, three barriers a round) as multiplying,
-// and with 214 accumulator-heavy VGPRs only one workgroup fits a CU, so nothing overlaps the two.  A run over at most
-// SRK_WS_NF frames has nf (nf + 1) <= 420 half blocks = the lanes of waves 0..6: wave 7 does nothing but stage.  Here
-// it stages round r + 1 into the second half of a double-buffered LDS arena (and already has round r + 2's global
-// loads in flight) while waves 0..6 multiply round r -- one barrier per round, the multiply never waits for memory.
-#define SRK_WS_NF 20
-template <typename T, typename WT>
-__global__ __launch_bounds__(SRK_GRP_THREADS) void k_schur_ws(
-    SrkDims d, double c, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ obs_pt,
-    const uint8_t* __restrict__ obs_slot, const uint32_t* __restrict__ pt_mask, const WT* __restrict__ W,
-    const double* __restrict__ Vg, double* __restrict__ S, double* __restrict__ rhs,
-    const int32_t* __restrict__ grp_first, const int32_t* __restrict__ grp_count, const int32_t* __restrict__ grp_nf,
-    const int32_t* __restrict__ grp_frames)
-{
-    using L = SchurLayout<T>;
-    constexpr int PB = SRK_GRP_PB;
-    constexpr int W_LM = SRK_WS_NF * L::WS, Y_LM = SRK_WS_NF * L::YS; // elements per staged landmark
-    constexpr int BUF = PB * (W_LM + Y_LM);                           // one staging buffer
-    constexpr int CAP = 2 * BUF;                                      // the flush uses both
-    __shared__ __attribute__((aligned(16))) T sBuf[CAP];
-    __shared__ __attribute__((aligned(16))) double sE[SRK_GRP_MAXPTS][12];
-    __shared__ double sRhs[SRK_WS_NF * 10];
-    __shared__ int32_t sF[SRK_WS_NF];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t p0 = grp_first[blockIdx.x];
-    const int np = grp_count[blockIdx.x];
-    const int nfu = grp_nf[blockIdx.x];
-    const bool ragged = nfu < 0;
-    const int nf = ragged ? -nfu : nfu;
-    if (nf > SRK_WS_NF) return; // k_schur_grouped takes the wider runs
-    if (tid < nf) sF[tid] = grp_frames[(int64_t)blockIdx.x * SRK_GRP_MAXNF + tid];
-    if (tid < nf * 10) sRhs[tid] = 0.0;
-    if (tid < np) { // 3x3 damped block inverses; a singular block contributes nothing (:1877-1881)
-        double Einv[9], g[3];
-        bool ok = point_block_inverse(Vg, d.Ns, p0 + tid, c, Einv, g);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) sE[tid][k] = ok ? Einv[k] : 0.0;
-#pragma unroll
-        for (int m = 0; m < 3; ++m)
-            sE[tid][9 + m] = ok ? Einv[3 * m] * g[0] + Einv[3 * m + 1] * g[1] + Einv[3 * m + 2] * g[2] : 0.0;
-    }
-    const int R = (np + PB - 1) / PB;
-    const int nf10 = nf * 10;
-    // one pass of the flush streams the staged block rows a0 .. a1 - 1 out of LDS: one wave per row of S, the lanes walk
-    // the row's 10 (a + 1) columns
-    auto flush_stream = [&](int a0, int a1) {
-        for (int rho = wv; rho < 10 * (a1 - a0); rho += SRK_GRP_THREADS / 64) {
-            const int a = a0 + rho / 10, r = rho - 10 * (a - a0);
-            const int w = 10 * (a + 1);
-            const int64_t row = 10 * (int64_t)sF[a] + r;
-            if (srk_is_fixed_var(row, d)) continue;
-            const T* src = sBuf + 50 * (a * (a + 1) - a0 * (a0 + 1)) + r * w;
-            double* dst = S + row * d.ld;
-            for (int cw = lane; cw < w; cw += 64) {
-                const int b = cw / 10, cc = cw - b * 10;
-                const int64_t col = 10 * (int64_t)sF[b] + cc;
-                if (srk_is_fixed_var(col, d)) continue;
-#ifdef SRK_SCH_NOFLUSH
-                if (d.N >= 0) continue;
-#endif
-                atomicAdd(&dst[col], -(double)src[cw]);
-            }
-        }
-    };
-    auto flush_span = [&](int a0, int& a1) { // block rows that fit the arena from a0 on
-        int used = 0;
-        a1 = a0;
-        while (a1 < nf && used + 100 * (a1 + 1) <= CAP) { used += 100 * (a1 + 1); ++a1; }
-    };
-    __syncthreads(); // sE, sF, sRhs are visible
-    // The two roles are two separate code paths with the same barrier sequence (R + 1 for the rounds, two per flush
-    // pass), so that the accumulators live only in the multiplier path and the prefetch registers only in the loader's.
-    if (wv == 7) {
-        // ---- loader.  A round's observations are contiguous, at most PB nf <= 80: the lane covers q = lane and
-        // q = lane + 64; for each it moves the 30 W values (k-major in memory: one coalesced load per k).
-        const unsigned magic_nf = (65536u + nf - 1) / nf; // q < 128
-        double pre[30][2];
-        int dq[2]; // LDS offset of (staged landmark, frame slot) for the two q of this lane
-        int nq_pre = 0;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) { // uniform runs: landmark q / nf, slot q % nf
-            const int q = lane + 64 * h;
-            const int pl = (int)((q * magic_nf) >> 16);
-            dq[h] = pl * W_LM + (q - pl * nf) * L::WS;
-        }
-        auto load_round = [&](int r) { // global loads of round r into `pre` (left in flight)
-            const int pb = r * PB;
-            const int nbn = np - pb < PB ? np - pb : PB;
-            const int64_t oa = row_ptr[p0 + pb];
-            nq_pre = (int)(row_ptr[p0 + pb + nbn] - oa);
-#pragma unroll
-            for (int k = 0; k < 30; ++k) {
-                pre[k][0] = lane < nq_pre ? w_entry<WT>(W, d.Os, oa + lane, k) : 0.0;
-                pre[k][1] = lane + 64 < nq_pre ? w_entry<WT>(W, d.Os, oa + lane + 64, k) : 0.0;
-            }
-            if (ragged) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int q = lane + 64 * h;
-                    if (q < nq_pre) dq[h] = (obs_pt[oa + q] - (int)(p0 + pb)) * W_LM + (int)obs_slot[oa + q] * L::WS;
-                }
-            }
-        };
-        auto stage_round = [&](T* bw) { // `pre` -> W in LDS (Y = E^-1 W is the multipliers' first step of the round)
-#pragma unroll
-            for (int k = 0; k < 30; ++k) {
-                const int m = k / 10, rr = k - 10 * m;
-                const int ko = L::WM * m + rr + (rr >= 5 ? L::WH - 5 : 0);
-                if (lane < nq_pre) bw[dq[0] + ko] = (T)pre[k][0];
-                if (lane + 64 < nq_pre) bw[dq[1] + ko] = (T)pre[k][1];
-            }
-        };
-        load_round(0);
-        stage_round(sBuf);
-        if (R > 1) load_round(1);
-        __syncthreads();
-        for (int r = 0; r < R; ++r) {
-            __syncthreads(); // the multipliers' Y of round r: pass at once, they must not wait for the staging below
-            if (r + 1 < R) {
-#ifndef SRK_WS_NOSTAGE
-                stage_round(sBuf + ((r + 1) & 1) * BUF);
-#endif
-#ifndef SRK_WS_NOLOAD
-                if (r + 2 < R) load_round(r + 2);
-#endif
-            }
-            __syncthreads(); // their products of round r
-        }
-        for (int a0 = 0; a0 < nf;) {
-            int a1;
-            flush_span(a0, a1);
-            __syncthreads();
-            __syncthreads();
-            flush_stream(a0, a1);
-            a0 = a1;
-        }
-    } else {
-        // ---- multipliers: half block u = tid -> (block pair (a, b), b <= a ; rows 5 hf .. 5 hf + 4)
-        const bool act = tid < nf * (nf + 1);
-        int sa, sb, sh;
-        {
-            int pi = act ? tid >> 1 : 0;
-            sh = act ? tid & 1 : 0;
-            sa = (int)((sqrtf(8.0f * (float)pi + 1.0f) - 1.0f) * 0.5f);
-            while ((sa + 1) * (sa + 2) / 2 <= pi) ++sa;
-            while (sa * (sa + 1) / 2 > pi) --sa;
-            sb = pi - sa * (sa + 1) / 2;
-        }
-        const int offW = sa * L::WS + L::WH * sh, offY = sb * L::YS;
-        T acc[5][10];
-#pragma unroll
-        for (int i = 0; i < 5; ++i)
-#pragma unroll
-            for (int cc = 0; cc < 10; ++cc) acc[i][cc] = 0;
-        // Y stage map: item t = tid + 448 i -> (staging slot pl, frame a, frame variable fv); the same thread keeps the
-        // rhs term W^T (E^-1 g) of its items (the PB slots of one (a, fv) meet in sRhs at the end)
-        constexpr int YI = (PB * SRK_WS_NF * 10 + 447) / 448;
-        int ypl[YI], ywo[YI], yyo[YI], ye[YI];
-        double racc[YI];
-#pragma unroll
-        for (int i = 0; i < YI; ++i) {
-            const int t = tid + 448 * i;
-            const int pl = t / nf10, e = t - pl * nf10;
-            const int a = e / 10, fv = e - a * 10;
-            ypl[i] = pl < PB ? pl : (1 << 30);
-            ywo[i] = pl * W_LM + a * L::WS + fv + (fv >= 5 ? L::WH - 5 : 0);
-            yyo[i] = pl * Y_LM + a * L::YS + fv;
-            ye[i] = e;
-            racc[i] = 0;
-        }
-        __syncthreads();
-        for (int r = 0; r < R; ++r) {
-            T* bw = sBuf + (r & 1) * BUF;
-            T* by = bw + PB * W_LM;
-            const int pb = r * PB;
-            const int nb = np - pb < PB ? np - pb : PB;
-#pragma unroll
-            for (int i = 0; i < YI; ++i) {
-                if (ypl[i] >= nb) continue;
-                T* wp = bw + ywo[i];
-                T* yp = by + yyo[i];
-                if (ragged && !((pt_mask[p0 + pb + ypl[i]] >> (ye[i] / 10)) & 1u)) { // landmark misses this frame: zeros
-                    wp[0] = wp[L::WM] = wp[2 * L::WM] = (T)0;
-                    yp[0] = yp[L::YM] = yp[2 * L::YM] = (T)0;
-                    continue;
-                }
-                const double2* E2 = reinterpret_cast<const double2*>(sE[pb + ypl[i]]); // rows are 96 B: 16-byte aligned
-                const double2 e01 = E2[0], e23 = E2[1], e45 = E2[2], e67 = E2[3], e89 = E2[4], eab = E2[5];
-                const double w0 = (double)wp[0], w1 = (double)wp[L::WM], w2 = (double)wp[2 * L::WM];
-                yp[0] = (T)(e01.x * w0 + e01.y * w1 + e23.x * w2);
-                yp[L::YM] = (T)(e23.y * w0 + e45.x * w1 + e45.y * w2);
-                yp[2 * L::YM] = (T)(e67.x * w0 + e67.y * w1 + e89.x * w2);
-                racc[i] += w0 * e89.y + w1 * eab.x + w2 * eab.y;
-            }
-            __syncthreads();
-            if (act) {
-                for (int pl = 0; pl < nb; ++pl) {
-#ifdef SRK_SCH_NOACC
-                    if (d.N >= 0) continue;
-#endif
-#pragma unroll
-                    for (int m = 0; m < 3; ++m)
-                        schur_tile_update(acc, bw + pl * W_LM + offW + L::WM * m, by + pl * Y_LM + offY + L::YM * m);
-                }
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int i = 0; i < YI; ++i)
-            if (ypl[i] < PB && ypl[i] < np) atomicAdd(&sRhs[ye[i]], racc[i]);
-        // flush: the tiles are transposed through LDS a few block rows at a time
-        for (int a0 = 0; a0 < nf;) {
-            int a1;
-            flush_span(a0, a1);
-            __syncthreads();
-            if (act && sa >= a0 && sa < a1) {
-                int off = 50 * (sa * (sa + 1) - a0 * (a0 + 1)); // sum_{a'=a0}^{a-1} 100 (a' + 1)
-                int w = 10 * (sa + 1);
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-#pragma unroll
-                    for (int cc = 0; cc < 10; ++cc) sBuf[off + (5 * sh + i) * w + 10 * sb + cc] = acc[i][cc];
-            }
-            __syncthreads();
-            flush_stream(a0, a1);
-            a0 = a1;
-        }
-    }
-    // rhs += sum F^T E^-1 g (the multipliers' sRhs adds precede the flush's barriers; nf >= 1 means at least one pass)
-    if (tid < nf10) {
-        const int a = tid / 10, r = tid - a * 10;
-        const int64_t row = 10 * (int64_t)sF[a] + r;
-        if (!srk_is_fixed_var(row, d)) atomicAdd(&rhs[row], sRhs[tid]);
-    }
-}
-
 // ------------------------------------------------------------------ K3m: the run's sum as an fp64 MFMA product
-// SQ counters of the register-tile kernels above (tools/schur_pmc.sh): LDS array 65 % busy, a quarter of that bank
+// SQ counters of the register-tile kernel above (tools/schur_pmc.sh): LDS array 65 % busy, a quarter of that bank
 // conflicts, vector ALU 50 % -- every FMA operand is an LDS read (0.3-0.4 doubles per FMA).  But the sum over a run's
 // landmarks IS a matrix product: with E_i = L_i L_i^T and the run's Z_i = L_i^-1 W_i stacked as rows k = (landmark, point
 // coordinate),
@@ -1702,6 +1454,8 @@ extern "C" void srk_dbg_mm_stamps(long long* out) { (void)hipMemcpyFromSymbol(ou
 // global loads they have just put in flight for a later round, and every flush pass wait for its atomics
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 #define SRK_MM_THREADS 1024
+#define SRK_WS_NF 20    // frames of a run at most (200 columns = 13 tiles); k_schur_grouped takes the wider runs (its nf_skip)
+static_assert(SRK_WS_NF == SRK_WS_NF_HOST, "host / kernel run limit differ");
 #define SRK_MM_CW 12    // multiplying waves
 #define SRK_MM_SLOTS 8  // tiles per multiplying wave
 #define SRK_MM_LDW 208  // row stride of the round buffers (doubles): 13 tiles of 16 columns
@@ -2491,19 +2245,17 @@ void srk_launch_schur_long(hipStream_t s, const SrkDims& d, double c, const doub
                            const int32_t* run_pts, const int32_t* run_frames, const int64_t* run_obs_off, const int32_t* run_obs, int fb)
 {
     if (n_items <= 0) return;
-#define SRK_LONG_LAUNCH(FBV)                                                                                                       \
-    do {                                                                                                                           \
-        if (d.w_f32)                                                                                                               \
-            hipLaunchKernelGGL((k_schur_long<float, FBV>), dim3((unsigned)n_items), dim3(LongCfg<FBV>::THREADS), 0, s, d, c,         \
-                               reinterpret_cast<const float*>(W), Vg, S, rhs, item, run_np, run_nf, run_pts, run_frames, run_obs_off, \
-                               run_obs);                                                                                           \
-        else                                                                                                                       \
-            hipLaunchKernelGGL((k_schur_long<double, FBV>), dim3((unsigned)n_items), dim3(LongCfg<FBV>::THREADS), 0, s, d, c, W, Vg, S, \
-                               rhs, item, run_np, run_nf, run_pts, run_frames, run_obs_off, run_obs);                               \
-    } while (0)
-    if (fb == 16) SRK_LONG_LAUNCH(16);
-    else SRK_LONG_LAUNCH(8);
-#undef SRK_LONG_LAUNCH
+    // 10-wide blocks only: with fixed intrinsics the host hands the long tracks to the per-landmark kernel (srk_launch_schur)
+    assert(d.fv != 6 && "k_schur_long is not built for fixed intrinsics");
+    srk_dispatch_layout(d, W, [&](auto lay, auto* Wp) {
+        using Lay = decltype(lay);
+        if constexpr (Lay::FV == 10)
+            srk_dispatch_bool(fb == 16, [&](auto wide) {
+                constexpr int FB = decltype(wide)::value ? 16 : 8;
+                hipLaunchKernelGGL((k_schur_long<typename Lay::WT, FB>), dim3((unsigned)n_items), dim3(LongCfg<FB>::THREADS), 0, s, d, c,
+                                   Wp, Vg, S, rhs, item, run_np, run_nf, run_pts, run_frames, run_obs_off, run_obs);
+            });
+    });
 }
 
 void srk_launch_schur_grouped(hipStream_t s, const SrkDims& d, double c, const int64_t* row_ptr, const int32_t* obs_pt,
@@ -2513,75 +2265,45 @@ void srk_launch_schur_grouped(hipStream_t s, const SrkDims& d, double c, const i
                               int fp32_accumulate, int32_t* irr, int64_t n_mm_uniform, int64_t n_mm_ragged, const SrkDetSchur* det)
 {
     if (n_groups <= 0) return;
-    if (d.fv == 6) {
-        // fixed intrinsics (fp64 storage and sums only, never deterministic): the runs over at most SRK_WS_NF frames on 6-wide
-        // blocks; the host hands every other landmark to the per-landmark kernel (srk_launch_schur)
-        if (n_mm_uniform + n_mm_ragged > 0) {
-            if (n_mm_ragged > 0)
-                hipLaunchKernelGGL((k_schur_mm<double, 1, false, 6>), dim3((unsigned)n_groups), dim3(SRK_MM_THREADS), 0, s, d, c, row_ptr,
-                                   obs_pt, obs_slot, pt_mask, W, Vg, S, rhs, grp_first, grp_count, grp_nf, grp_frames, irr, nullptr, nullptr);
-            else
-                hipLaunchKernelGGL((k_schur_mm<double, 0, false, 6>), dim3((unsigned)n_groups), dim3(SRK_MM_THREADS), 0, s, d, c, row_ptr,
-                                   obs_pt, obs_slot, pt_mask, W, Vg, S, rhs, grp_first, grp_count, grp_nf, grp_frames, irr, nullptr, nullptr);
-        }
-        return;
-    }
-    // runs over at most SRK_WS_NF frames go to the MFMA kernel, fp64 only (the opt-in fp32 accumulation keeps the packed
-    // FMA register-tile kernel).  SRK_SCHUR_NO_WS / SRK_SCHUR_VALU: development switches back to the register-tile kernels.
-#ifdef SRK_DEV
-    static const bool env_no_ws = getenv("SRK_SCHUR_NO_WS") != nullptr;
-    static const bool env_valu = getenv("SRK_SCHUR_VALU") != nullptr; // development: the register-tile kernel k_schur_ws
-#else
-    const bool env_no_ws = false, env_valu = false;
-#endif
-    const bool no_ws = env_no_ws || fp32_accumulate;
-    const int nf_skip = no_ws ? 0 : SRK_WS_NF;
-#define SRK_SCHUR_ARGS(WP) d, c, row_ptr, obs_pt, obs_slot, pt_mask, WP, Vg, S, rhs, grp_first, grp_count, grp_nf, grp_frames
-    const dim3 grid((unsigned)n_groups), block(SRK_GRP_THREADS);
-    const float* Wf = reinterpret_cast<const float*>(W);
-    // every kernel in two instantiations: W stored as double, or as float (srk_ba_set_storage_precision; loads widen)
-#define SRK_SCHUR_LAUNCH(KERNEL, BLOCK, ...)                                                                        \
-    do {                                                                                                            \
-        if (d.w_f32) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ float>), grid, BLOCK, 0, s, SRK_SCHUR_ARGS(Wf));        \
-        else hipLaunchKernelGGL((KERNEL<__VA_ARGS__ double>), grid, BLOCK, 0, s, SRK_SCHUR_ARGS(W));               \
-    } while (0)
-#define SRK_SCHUR_LAUNCH_SKIP(KERNEL, ...)                                                                          \
-    do {                                                                                                            \
-        if (d.w_f32) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ float>), grid, block, 0, s, SRK_SCHUR_ARGS(Wf), nf_skip); \
-        else hipLaunchKernelGGL((KERNEL<__VA_ARGS__ double>), grid, block, 0, s, SRK_SCHUR_ARGS(W), nf_skip);       \
-    } while (0)
-    if (!no_ws && n_wide + n_mid < n_groups) { // runs over at most SRK_WS_NF frames: the MFMA kernel
-        if (env_valu) SRK_SCHUR_LAUNCH(k_schur_ws, block, double, );
-        else {
-#define SRK_MM_LAUNCH(KIND)                                                                                                      \
-    do {                                                                                                                         \
-        if (det) {                                                                                                               \
-            if (d.w_f32) hipLaunchKernelGGL((k_schur_mm<float, KIND, true>), grid, dim3(SRK_MM_THREADS), 0, s, SRK_SCHUR_ARGS(Wf), irr, det->stage, det->stage_rhs); \
-            else hipLaunchKernelGGL((k_schur_mm<double, KIND, true>), grid, dim3(SRK_MM_THREADS), 0, s, SRK_SCHUR_ARGS(W), irr, det->stage, det->stage_rhs);         \
-        } else {                                                                                                                 \
-            if (d.w_f32) hipLaunchKernelGGL((k_schur_mm<float, KIND, false>), grid, dim3(SRK_MM_THREADS), 0, s, SRK_SCHUR_ARGS(Wf), irr, nullptr, nullptr);          \
-            else hipLaunchKernelGGL((k_schur_mm<double, KIND, false>), grid, dim3(SRK_MM_THREADS), 0, s, SRK_SCHUR_ARGS(W), irr, nullptr, nullptr);                  \
-        }                                                                                                                        \
-    } while (0)
-            if (n_mm_ragged > 0) SRK_MM_LAUNCH(1);
-            else if (n_mm_uniform > 0) SRK_MM_LAUNCH(0);
-#undef SRK_MM_LAUNCH
-            if (det && n_mm_ragged + n_mm_uniform > 0)
-                hipLaunchKernelGGL(k_schur_det_gather, dim3((unsigned)(det->n_pairs + d.M)), dim3(128), 0, s, d, det->stage, det->stage_rhs,
-                                   det->pair_ptr, det->pair_fa, det->pair_fb, det->pair_ent, det->n_pairs, det->f_ptr, det->f_ent, S, rhs);
-        }
-    }
-    if (no_ws ? n_wide < n_groups : n_mid > 0) { // (SRK_WS_NF <) frames <= SRK_GRP_NF1: one half block per thread
-        if (fp32_accumulate) SRK_SCHUR_LAUNCH_SKIP(k_schur_grouped, 1, float, );
-        else SRK_SCHUR_LAUNCH_SKIP(k_schur_grouped, 1, double, );
-    }
-    if (n_wide > 0) { // more than SRK_GRP_NF1 frames: two half blocks per thread
-        if (fp32_accumulate) SRK_SCHUR_LAUNCH_SKIP(k_schur_grouped, 2, float, );
-        else SRK_SCHUR_LAUNCH_SKIP(k_schur_grouped, 2, double, );
-    }
-#undef SRK_SCHUR_LAUNCH
-#undef SRK_SCHUR_LAUNCH_SKIP
-#undef SRK_SCHUR_ARGS
+    // runs over at most SRK_WS_NF frames go to the MFMA kernel, which sums in fp64 only: with the opt-in fp32 accumulation
+    // every run stays with the packed-FMA register-tile kernel k_schur_grouped (nf_skip = 0)
+    assert(!(d.fv == 6 && fp32_accumulate) && "fp32 run sums are not built for fixed intrinsics");
+    // (n_mm_uniform + n_mm_ragged = n_groups - n_wide - n_mid: the host counts all four from the same grp_nf values)
+    const bool mm = !fp32_accumulate && n_mm_uniform + n_mm_ragged > 0;
+    const int nf_skip = fp32_accumulate ? 0 : SRK_WS_NF;
+    const dim3 grid((unsigned)n_groups);
+    srk_dispatch_layout(d, W, [&](auto lay, auto* Wp) {
+        using Lay = decltype(lay);
+        using WT = typename Lay::WT;
+        if (mm) // KIND 1 as soon as one run is ragged (a uniform run is the full-mask case of it)
+            srk_dispatch_bool(n_mm_ragged > 0, [&](auto ragged) {
+                srk_dispatch_det(lay, det != nullptr, [&](auto dt) {
+                    constexpr int KIND = decltype(ragged)::value ? 1 : 0;
+                    constexpr bool DET = decltype(dt)::value;
+                    hipLaunchKernelGGL((k_schur_mm<WT, KIND, DET, Lay::FV>), grid, dim3(SRK_MM_THREADS), 0, s, d, c, row_ptr, obs_pt,
+                                       obs_slot, pt_mask, Wp, Vg, S, rhs, grp_first, grp_count, grp_nf, grp_frames, irr,
+                                       DET ? det->stage : nullptr, DET ? det->stage_rhs : nullptr);
+                    if constexpr (DET)
+                        hipLaunchKernelGGL(k_schur_det_gather, dim3((unsigned)(det->n_pairs + d.M)), dim3(128), 0, s, d, det->stage,
+                                           det->stage_rhs, det->pair_ptr, det->pair_fa, det->pair_fb, det->pair_ent, det->n_pairs,
+                                           det->f_ptr, det->f_ent, S, rhs);
+                });
+            });
+        // the wider runs, 10-wide blocks only: with fixed intrinsics (6-wide) the host hands every landmark outside k_schur_mm's
+        // runs to the per-landmark kernel (srk_launch_schur)
+        if constexpr (Lay::FV == 10)
+            srk_dispatch_bool(fp32_accumulate != 0, [&](auto f32) {
+                using T = std::conditional_t<decltype(f32)::value, float, double>; // type of the run sums
+                auto launch = [&](auto slots) {
+                    hipLaunchKernelGGL((k_schur_grouped<decltype(slots)::value, T, WT>), grid, dim3(SRK_GRP_THREADS), 0, s, d, c, row_ptr,
+                                       obs_pt, obs_slot, pt_mask, Wp, Vg, S, rhs, grp_first, grp_count, grp_nf, grp_frames, nf_skip);
+                };
+                // (SRK_WS_NF <) frames <= SRK_GRP_NF1: one half block per thread
+                if (fp32_accumulate ? n_wide < n_groups : n_mid > 0) launch(std::integral_constant<int, 1>{});
+                // more than SRK_GRP_NF1 frames: two half blocks per thread
+                if (n_wide > 0) launch(std::integral_constant<int, 2>{});
+            });
+    });
 }
 
 // G (block diagonal of the frame blocks, diagonal * (1+c), gauge rows/cols dropped) is added after the landmark
@@ -2645,12 +2367,11 @@ void srk_launch_assemble(hipStream_t s, const SrkDims& d, double c, const double
     const int fv = d.fv == 6 ? 6 : 10;
     int64_t n = (int64_t)d.M * (fv * fv + fv) + (d.ld - fv * (int64_t)d.M);
     const dim3 grid((unsigned)((n + 255) / 256 + SRK_ASM_TAIL));
-    if (fv == 6)
-        hipLaunchKernelGGL((k_assemble<double, 6>), grid, dim3(256), 0, s, d, c, Ug, S, rhs, ident, row_ptr, obs_frame, W, Vg, irr);
-    else if (d.w_f32)
-        hipLaunchKernelGGL(k_assemble<float>, grid, dim3(256), 0, s, d, c, Ug, S, rhs, ident, row_ptr, obs_frame,
-                           reinterpret_cast<const float*>(W), Vg, irr);
-    else hipLaunchKernelGGL(k_assemble<double>, grid, dim3(256), 0, s, d, c, Ug, S, rhs, ident, row_ptr, obs_frame, W, Vg, irr);
+    srk_dispatch_layout(d, W, [&](auto lay, auto* Wp) {
+        using Lay = decltype(lay);
+        hipLaunchKernelGGL((k_assemble<typename Lay::WT, Lay::FV>), grid, dim3(256), 0, s, d, c, Ug, S, rhs, ident, row_ptr, obs_frame,
+                           Wp, Vg, irr);
+    });
 }
 
 // mirror the lower triangle into the upper one (downloads / exchange of the full matrix)
@@ -2757,14 +2478,11 @@ void srk_launch_backsub(hipStream_t s, const SrkDims& d, double c, const int32_t
     // acc must be zero on entry (the caller's memset, or k_point_update of the slot's previous attempt); the info word is
     // the int right behind acc
     if (d.O > 0) {
-        int64_t blocks = (d.O + 255) / 256;
-        if (d.fv == 6)
-            hipLaunchKernelGGL((k_backsub_obs<double, 6>), dim3((unsigned)blocks), dim3(256), 0, s, d, obs_frame, obs_pt, W, dc, acc);
-        else if (d.w_f32)
-            hipLaunchKernelGGL(k_backsub_obs<float>, dim3((unsigned)blocks), dim3(256), 0, s, d, obs_frame, obs_pt,
-                               reinterpret_cast<const float*>(W), dc, acc);
-        else
-            hipLaunchKernelGGL(k_backsub_obs<double>, dim3((unsigned)blocks), dim3(256), 0, s, d, obs_frame, obs_pt, W, dc, acc);
+        const dim3 grid((unsigned)((d.O + 255) / 256));
+        srk_dispatch_layout(d, W, [&](auto lay, auto* Wp) {
+            using Lay = decltype(lay);
+            hipLaunchKernelGGL((k_backsub_obs<typename Lay::WT, Lay::FV>), grid, dim3(256), 0, s, d, obs_frame, obs_pt, Wp, dc, acc);
+        });
     }
     if (d.N > 0) {
         int* info = reinterpret_cast<int*>(acc + 3 * d.Ns);
@@ -2829,41 +2547,63 @@ __global__ void k_cam_apply(int32_t M, const double* __restrict__ R, const doubl
 void srk_launch_cam_apply(hipStream_t s, int32_t M, const double* R, const double* T, const double* dc, double* Rn,
                           double* Tn, const double* K, double f0, double* pack, int fv)
 {
-    if (fv == 6) hipLaunchKernelGGL(k_cam_apply<6>, dim3((M + 63) / 64), dim3(64), 0, s, M, R, T, dc, Rn, Tn, K, f0, pack);
-    else hipLaunchKernelGGL(k_cam_apply<10>, dim3((M + 63) / 64), dim3(64), 0, s, M, R, T, dc, Rn, Tn, K, f0, pack);
+    srk_dispatch_fv(fv, [&](auto fvc) {
+        hipLaunchKernelGGL(k_cam_apply<decltype(fvc)::value>, dim3((M + 63) / 64), dim3(64), 0, s, M, R, T, dc, Rn, Tn, K, f0, pack);
+    });
 }
 
 // ------------------------------------------------------------------ K1: reprojection error
 #define SRK_ERR_BLOCKS 1024
+
+// the homogeneous image point (p, q, r) = K (R X + T) of one observation
+__device__ __forceinline__ void err_pqr(const double* c /* R T K: 0..20 */, const double* X, double& p, double& q, double& r)
+{
+    double X0 = X[0], X1 = X[1], X2 = X[2];
+    double xc0 = c[0] * X0 + c[1] * X1 + c[2] * X2 + c[9];
+    double xc1 = c[3] * X0 + c[4] * X1 + c[5] * X2 + c[10];
+    double xc2 = c[6] * X0 + c[7] * X1 + c[8] * X2 + c[11];
+    p = c[12] * xc0 + c[13] * xc1 + c[14] * xc2;
+    q = c[15] * xc0 + c[16] * xc1 + c[17] * xc2;
+    r = c[18] * xc0 + c[19] * xc1 + c[20] * xc2;
+}
+// the residual of one observation as the error pass forms it (divisions, not the derivative kernels' reciprocal)
+__device__ __forceinline__ void err_residual(const double* c /* R T K: 0..20 */, double f0, const double* X, double2 uv, double& ex,
+                                             double& ey)
+{
+    double p, q, r;
+    err_pqr(c, X, p, q, r);
+    ex = p / r - uv.x / f0;
+    ey = q / r - uv.y / f0;
+}
+// the workgroup's sum in a fixed order: lanes, then the four waves as (0 + 1) + (2 + 3)
+__device__ __forceinline__ void err_block_sum(double sum, double* __restrict__ out)
+{
+    __shared__ double red[4];
+    sum = wave_sum(sum);
+    int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = sum;
+    lds_barrier();
+    if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
+}
 
 __global__ __launch_bounds__(256) void k_error(SrkDims d, const double* __restrict__ pts,
                                                const double* __restrict__ cam, const int32_t* __restrict__ obs_frame,
                                                const int32_t* __restrict__ obs_pt, const double* __restrict__ obs_uv,
                                                double* __restrict__ partial)
 {
-    __shared__ double red[4];
     double sum = 0;
     for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < d.O; o += (int64_t)gridDim.x * 256) {
         int32_t pt = obs_pt[o];
         const double* c = cam + (int64_t)SRK_CAM_PACK * obs_frame[o];
         double2 uv = reinterpret_cast<const double2*>(obs_uv)[o];
         const double* X = pts + 3 * (int64_t)pt;
-        double X0 = X[0], X1 = X[1], X2 = X[2];
-        double xc0 = c[0] * X0 + c[1] * X1 + c[2] * X2 + c[9];
-        double xc1 = c[3] * X0 + c[4] * X1 + c[5] * X2 + c[10];
-        double xc2 = c[6] * X0 + c[7] * X1 + c[8] * X2 + c[11];
-        double p = c[12] * xc0 + c[13] * xc1 + c[14] * xc2;
-        double q = c[15] * xc0 + c[16] * xc1 + c[17] * xc2;
-        double r = c[18] * xc0 + c[19] * xc1 + c[20] * xc2;
+        double p, q, r;
+        err_pqr(c, X, p, q, r);
         double f0 = c[47];
         double ex = p / r - uv.x / f0, ey = q / r - uv.y / f0;
         sum += ex * ex + ey * ey;
     }
-    sum = wave_sum(sum);
-    int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = sum;
-    lds_barrier();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    err_block_sum(sum, partial + blockIdx.x);
 }
 
 // Staged variant: when the host found that every run of SRK_JF_OBS consecutive observations touches at most
@@ -2876,7 +2616,6 @@ __global__ __launch_bounds__(256) void k_error_staged(SrkDims d, const double* _
                                                       const int32_t* __restrict__ wg_jmin, double* __restrict__ partial)
 {
     __shared__ double sCam[SRK_JF_SLOTS][23]; // R, T, K (0..20), f0; odd stride: conflict-free across frames
-    __shared__ double red[4];
     const int jmin = wg_jmin[blockIdx.x];
     {
         const int nfr = d.M - jmin < SRK_JF_SLOTS ? d.M - jmin : SRK_JF_SLOTS;
@@ -2895,47 +2634,26 @@ __global__ __launch_bounds__(256) void k_error_staged(SrkDims d, const double* _
         const double* c = sCam[obs_frame[o] - jmin];
         double2 uv = reinterpret_cast<const double2*>(obs_uv)[o];
         const double* X = pts + 3 * (int64_t)obs_pt[o];
-        double X0 = X[0], X1 = X[1], X2 = X[2];
-        double xc0 = c[0] * X0 + c[1] * X1 + c[2] * X2 + c[9];
-        double xc1 = c[3] * X0 + c[4] * X1 + c[5] * X2 + c[10];
-        double xc2 = c[6] * X0 + c[7] * X1 + c[8] * X2 + c[11];
-        double p = c[12] * xc0 + c[13] * xc1 + c[14] * xc2;
-        double q = c[15] * xc0 + c[16] * xc1 + c[17] * xc2;
-        double r = c[18] * xc0 + c[19] * xc1 + c[20] * xc2;
+        double p, q, r;
+        err_pqr(c, X, p, q, r);
         double f0 = c[21];
         double ex = p / r - uv.x / f0, ey = q / r - uv.y / f0;
         sum += ex * ex + ey * ey;
     }
-    sum = wave_sum(sum);
-    int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = sum;
-    lds_barrier();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    err_block_sum(sum, partial + blockIdx.x);
 }
 
 // ---- robust loss: the sum of rho(s) instead of s, same partial sums and fixed-order final sum.
 // (Kernels of their own rather than a pack on k_error / k_error_staged, whose names carry no template.)
-// the residual of one observation as k_error forms it (divisions, not the derivative kernels' reciprocal)
-__device__ __forceinline__ void err_residual(const double* c /* R T K: 0..20 */, double f0, const double* __restrict__ X,
-                                             double2 uv, double& ex, double& ey)
-{
-    double X0 = X[0], X1 = X[1], X2 = X[2];
-    double xc0 = c[0] * X0 + c[1] * X1 + c[2] * X2 + c[9];
-    double xc1 = c[3] * X0 + c[4] * X1 + c[5] * X2 + c[10];
-    double xc2 = c[6] * X0 + c[7] * X1 + c[8] * X2 + c[11];
-    double p = c[12] * xc0 + c[13] * xc1 + c[14] * xc2;
-    double q = c[15] * xc0 + c[16] * xc1 + c[17] * xc2;
-    double r = c[18] * xc0 + c[19] * xc1 + c[20] * xc2;
-    ex = p / r - uv.x / f0;
-    ey = q / r - uv.y / f0;
-}
-
+// They share the projection (err_pqr) and the tail (err_block_sum) with the plain kernels; the loops stay written out because
+// these read f0 and the indices in another order than the plain ones, and the instruction schedule follows that order:
+// one templated loop body kept k_error and k_error_staged as they were but changed the schedule of these two and of
+// k_error_score, and that change has not been measured against the kernels it replaces.
 __global__ __launch_bounds__(256) void k_error_robust(SrkDims d, const double* __restrict__ pts,
                                                       const double* __restrict__ cam, const int32_t* __restrict__ obs_frame,
                                                       const int32_t* __restrict__ obs_pt, const double* __restrict__ obs_uv,
                                                       double* __restrict__ partial, SrkLoss L)
 {
-    __shared__ double red[4];
     double sum = 0;
     for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < d.O; o += (int64_t)gridDim.x * 256) {
         const double* c = cam + (int64_t)SRK_CAM_PACK * obs_frame[o];
@@ -2944,11 +2662,7 @@ __global__ __launch_bounds__(256) void k_error_robust(SrkDims d, const double* _
         srk_robust_wr(ex, ey, L, srk_info(L.q, o), w, rho);
         sum += rho;
     }
-    sum = wave_sum(sum);
-    int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = sum;
-    lds_barrier();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    err_block_sum(sum, partial + blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_error_staged_robust(SrkDims d, const double* __restrict__ pts,
@@ -2958,7 +2672,6 @@ __global__ __launch_bounds__(256) void k_error_staged_robust(SrkDims d, const do
                                                              SrkLoss L)
 {
     __shared__ double sCam[SRK_JF_SLOTS][23]; // as k_error_staged
-    __shared__ double red[4];
     const int jmin = wg_jmin[blockIdx.x];
     {
         const int nfr = d.M - jmin < SRK_JF_SLOTS ? d.M - jmin : SRK_JF_SLOTS;
@@ -2980,11 +2693,7 @@ __global__ __launch_bounds__(256) void k_error_staged_robust(SrkDims d, const do
         srk_robust_wr(ex, ey, L, srk_info(L.q, o), w, rho);
         sum += rho;
     }
-    sum = wave_sum(sum);
-    int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = sum;
-    lds_barrier();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    err_block_sum(sum, partial + blockIdx.x);
 }
 
 // the IRLS weight of every observation of the resident scene, internal order (srk_ba_observation_weights maps it back to the

@@ -2,8 +2,10 @@
 kernel (instruction text; labels and symbol names normalised).  Kernels that gained a frame-variable template parameter are
 matched with FV = 10 (the default layout) against the revision's kernel of the same name.  Host only: needs hipcc and git.
 
-    python tools/isa_compare.py [REV]        (REV defaults to HEAD)
-Prints one line per kernel that differs and a summary; exit status 0 when every kernel of REV has an identical counterpart.
+    python tools/isa_compare.py [REV] [--allow-missing NAME ...]        (REV defaults to HEAD)
+Prints one line per kernel that differs and a summary; exit status 0 when every kernel of REV has an identical counterpart and
+the working tree instantiates nothing that REV did not.  A kernel of REV without a counterpart is an error unless its function
+name is given with --allow-missing (a kernel taken out on purpose): it is then printed as "retired" and counted apart.
 """
 import os
 import re
@@ -57,8 +59,20 @@ def key(name):
     return name
 
 
+def function_name(demangled):
+    m = re.match(r"^(?:void )?(\w+)", demangled)
+    return m.group(1) if m else demangled
+
+
 def main():
-    rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
+    args, allowed = sys.argv[1:], set()
+    while "--allow-missing" in args:
+        i = args.index("--allow-missing")
+        if i + 1 >= len(args):
+            sys.exit("--allow-missing needs a kernel's function name")
+        allowed.add(args[i + 1])
+        del args[i:i + 2]
+    rev = args[0] if args else "HEAD"
     with tempfile.TemporaryDirectory() as tmp:
         old_dir = os.path.join(tmp, "old")
         os.makedirs(old_dir)
@@ -70,10 +84,13 @@ def main():
         new = kernels(device_asm(os.path.join(ROOT, CSRC), os.path.join(tmp, "new.s")))
     dold, dnew = demangle(list(old)), demangle(list(new))
     new_by_key = {key(dnew[k]): k for k in new}
-    same, bad = 0, 0
+    same, bad, retired = 0, 0, 0
     for k in old:
         nk = new_by_key.get(key(dold[k]))
-        if nk is None:
+        if nk is None and function_name(dold[k]) in allowed:
+            print("retired :", dold[k][:150])
+            retired += 1
+        elif nk is None:
             print("missing :", dold[k][:150])
             bad += 1
         elif old[k] == new[nk]:
@@ -82,8 +99,13 @@ def main():
             n_diff = sum(1 for a, b in zip(old[k], new[nk]) if a != b) + abs(len(old[k]) - len(new[nk]))
             print(f"differs : {dold[k][:110]}  ({len(old[k])} -> {len(new[nk])} instructions, {n_diff} lines differ)")
             bad += 1
-    print(f"{same} of {len(old)} kernels of {rev} identical in the working tree; {len(new) - len(old)} new instantiations")
-    return 0 if bad == 0 else 1
+    old_keys = {key(dold[k]) for k in old}
+    added = sorted(k for k in new_by_key if k not in old_keys)
+    for k in added:
+        print("new     :", k[:150])
+    print(f"{same} of {len(old) - retired} kernels of {rev} identical in the working tree ({retired} retired); "
+          f"{len(added)} new instantiations")
+    return 0 if bad == 0 and not added else 1
 
 
 if __name__ == "__main__":
