@@ -443,6 +443,50 @@ int srk_ba_observation_information(srk_ba*, double* q, int64_t count);
  * Works with or without information or a loss, and neither changes it. */
 int srk_ba_observation_residuals(srk_ba*, double* exy_pixels /* [count][2] */, int64_t count);
 
+/* ---- constant parameter blocks (EXTENSION) ----
+ * Frames and landmarks that keep their values: old keyframes of a sliding window, a fixed map, ground-control points,
+ * motion-only (every landmark constant) and structure-only (every frame constant) refinement.  Flags are non-zero for
+ * constant, in the caller's frame and landmark numbering; either array may be NULL (none of that kind), both NULL clears
+ * the setting (the default).  The handle keeps a copy: it is applied by every later upload (srk_ba_compute_inplace and
+ * srk_ba_compute_inplace_f32 included; the gauge choice below is part of the uploaded scene) and is not touched by
+ * srk_ba_reset_scene.  An upload whose scene has other counts than the stored setting fails with SRK_E_ARGS.
+ *
+ * A constant frame: every one of its frame variables (10, or 6 with fixed intrinsics) has correction exactly 0; its rows and
+ * columns of the reduced camera system are identity and its rhs 0.  A constant landmark: its 3 x 3 block is the identity, its
+ * gradient 0 and the point-frame blocks of its observations exact zeros, so it adds nothing to the reduced system and its
+ * correction is exactly 0; its observations still enter the frame blocks, the frame gradients and the error.
+ * Nothing is compacted: a constant frame keeps its rows of the system and a constant landmark still passes through the
+ * Schur sum (as zeros).  Two small masking passes after the derivative pass and after the assembly impose the blocks; none
+ * is launched without constant blocks, and every other kernel runs unchanged.
+ *
+ * keep_gauge = 1: the reference's seven gauge variables (the pose of frame 0, one translation component of frame 1) stay
+ * constant in addition -- for a constant set that does not determine the similarity, or one that holds the caller's frames 0
+ * and 1 anyway.  keep_gauge = 0: only the listed blocks are constant; the caller asserts that they fix the seven gauge
+ * freedoms (two constant frames with distinct centres, a frame and a landmark off its centre, three non-collinear
+ * landmarks); if they do not, the system is singular and the solve reports failure like any degenerate scene.  The gauge
+ * NORMALISATION of the world still uses the caller's frames 0 and 1: it is only a change of coordinates.
+ * Every frame constant and every landmark constant are both valid; everything constant is SRK_E_ARGS.
+ * Refused with SRK_E_ARGS (and a srk_ba_last_error text) by whichever call comes second: intrinsic groups, more than one
+ * rank.  Fixed intrinsics, deterministic mode, f32 storage, fp32 Schur sums, every Jacobian and rcs mode, solver fusion,
+ * speculation, frame reordering, robust losses and information work unchanged.
+ *
+ * Results: in the resident (normalised) scene the constant blocks keep the uploaded bits through every attempt and accept
+ * (SRK_BUF_POINTS, SRK_BUF_CAM_R, SRK_BUF_CAM_T).  srk_ba_compute_inplace does not write constant blocks back: the caller's
+ * entries stay bit-identical.  srk_ba_download_scene writes their reverted values (the input up to the normalise / revert
+ * round trip).  Downloads: SRK_BUF_RCS, SRK_BUF_RCS_RHS and srk_ba_download_rcs_rows show the identity rows and zero rhs,
+ * SRK_BUF_POINT_BLOCKS the identity and SRK_BUF_POINT_FRAME zeros for constant landmarks, SRK_BUF_CORRECTIONS and
+ * SRK_BUF_GRAD zeros at constant entries; SRK_BUF_FRAME_BLOCKS stays the unmasked per-frame blocks. */
+int srk_ba_set_constant_blocks(srk_ba*, const uint8_t* frame_const /* [n_frames] or NULL */, int32_t n_frames,
+                               const uint8_t* point_const /* [n_points] or NULL */, int64_t n_points, int keep_gauge);
+/* the setting: flags (0 / 1) into the arrays given (an array is left untouched when that kind was set as NULL) and
+ * keep_gauge; any pointer may be NULL.  Returns 1 if a setting is stored, 0 if not. */
+int srk_ba_constant_blocks(srk_ba*, uint8_t* frame_const, uint8_t* point_const, int* keep_gauge);
+/* the lengths of the stored flag arrays (0 = that kind was set as NULL); returns 1 if a setting is stored, 0 if not */
+int srk_ba_constant_counts(srk_ba*, int32_t* n_frames, int64_t* n_points);
+/* device time in ms of the last launch of the two masking passes (the landmark pass of the last derivative pass, the frame
+ * pass of the last assembly), taken with srk_ba_set_profile >= 1; 0 for a pass that was not launched or not timed */
+int srk_ba_constant_pass_ms(srk_ba*, double* points_ms, double* frames_ms);
+
 /* device-time instrumentation of srk_ba_optimize / srk_ba_compute_inplace: 0 = none (default; report.ms_* stay 0
  * except ms_total), 1 = one HIP event pair per phase (fills report.ms_*), 2 = additionally event pairs around
  * every MFMA trailing-update launch (fills report.ms_solve_syrk / solve_mfma_flops).  Every event costs a few

@@ -42,6 +42,8 @@ public:
     size_t SalientPointsCount() const { return pts_.size(); }
     Point3& GetSalientPoint(size_t id) { return pts_.at(id - offset_ - 1); }
     const Point3& GetSalientPoint(size_t id) const { return pts_.at(id - offset_ - 1); }
+    /// the place of a salient point in the map (the order of AddSalientPoint): what per-point arrays are indexed by
+    size_t SalientPointIndex(size_t id) const { return id - offset_ - 1; }
 private:
     std::vector<Point3> pts_;
     size_t offset_;
@@ -97,6 +99,7 @@ public:
                         std::vector<Matrix3>* intrinsic_cam_mats, const BundleAdjustmentKanataniTermCriteria& term_crit,
                         int64_t max_iterations = 0) {
         Flat f = Flatten(f0, map, inverse_orient_cams, track_rep, shared_intrinsic_cam_mat, intrinsic_cam_mats);
+        ApplyConstantBlocks(map, f, inverse_orient_cams.size());
         Scalar a = term_crit.AllowedReprojErrRelativeChange().value_or(0), m = term_crit.MaxHessianFactor().value_or(0);
         int rc = srk_ba_compute_inplace(h_, f0, (int64_t)f.ids.size(), f.pts.data(), (int32_t)inverse_orient_cams.size(),
                                         f.R.data(), f.T.data(), f.K.data(), f.shared, f.row_ptr.data(), f.frames.data(),
@@ -185,6 +188,29 @@ public:
         return e;
     }
 
+    /// EXTENSION: constant parameter blocks from the next ComputeInplace on (srk_ba_set_constant_blocks).  frame_flags[j] != 0:
+    /// frame j keeps its pose (and intrinsics); point_flags[k] != 0: the k-th salient point of the map (the order of
+    /// AddSalientPoint) keeps its coordinates -- the adapter maps them to pnt_ind, the order of the tracks that carry a salient
+    /// point, the way it maps the points themselves.  Either vector may be empty (none of that kind), both empty clears the
+    /// setting.  keep_gauge: the reference's seven gauge variables stay constant as well; false = the constant set alone
+    /// fixes the similarity.  Constant entries of the map and of inverse_orient_cams stay bit-identical.  ComputeInplace
+    /// throws std::invalid_argument for flag vectors of another size than the map / the cameras, for everything constant,
+    /// and where the library refuses the combination (intrinsic groups, more than one rank).
+    void SetConstantBlocks(const std::vector<uint8_t>& frame_flags, const std::vector<uint8_t>& point_flags, bool keep_gauge = true) {
+        if (frame_flags.empty() && point_flags.empty()) { ClearConstantBlocks(); return; }
+        const_frames_ = frame_flags;
+        const_points_ = point_flags;
+        const_keep_gauge_ = keep_gauge;
+        const_set_ = true;
+    }
+    void ClearConstantBlocks() {
+        const_set_ = false;
+        const_frames_.clear();
+        const_points_.clear();
+        int rc = srk_ba_set_constant_blocks(h_, nullptr, 0, nullptr, 0, 1);
+        if (rc < 0) Raise(rc);
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
@@ -224,6 +250,20 @@ private:
         else for (const Matrix3& k : *Ks) f.K.insert(f.K.end(), k.begin(), k.end());
         return f;
     }
+    // the stored flags against this call's scene: points from salient-point order to pnt_ind (f.ids)
+    void ApplyConstantBlocks(const FragmentMap& map, const Flat& f, size_t n_frames) {
+        if (!const_set_) return;
+        if (!const_frames_.empty() && const_frames_.size() != n_frames) throw std::invalid_argument("constant blocks: one frame flag per camera");
+        if (!const_points_.empty() && const_points_.size() != map.SalientPointsCount()) throw std::invalid_argument("constant blocks: one point flag per salient point of the map");
+        std::vector<uint8_t> pc;
+        if (!const_points_.empty()) {
+            pc.resize(f.ids.size());
+            for (size_t i = 0; i < f.ids.size(); ++i) pc[i] = const_points_.at(map.SalientPointIndex(f.ids[i]));
+        }
+        int rc = srk_ba_set_constant_blocks(h_, const_frames_.empty() ? nullptr : const_frames_.data(), (int32_t)const_frames_.size(),
+                                            const_points_.empty() ? nullptr : pc.data(), (int64_t)pc.size(), const_keep_gauge_ ? 1 : 0);
+        if (rc < 0) Raise(rc);
+    }
     [[noreturn]] void Raise(int rc) const {
         std::string msg = srk_ba_last_error(h_);
         if (rc == SRK_E_ARGS) throw std::invalid_argument(msg);
@@ -234,6 +274,8 @@ private:
     std::string status_;
     Scalar f0_ = 0;
     size_t points_count_ = 0, frames_count_ = 0;
+    bool const_set_ = false, const_keep_gauge_ = true;
+    std::vector<uint8_t> const_frames_, const_points_;
 };
 
 } // namespace suriko_amd

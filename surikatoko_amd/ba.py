@@ -480,6 +480,64 @@ class BundleAdjustmentKanatani:
                                                            C.c_int64(n)))
         return e
 
+    def _const_flags(self, sel, n, what):
+        """index list or boolean mask -> uint8 flags of length n (None stays None)"""
+        if sel is None:
+            return None
+        a = np.asarray(sel)
+        if a.dtype == np.bool_:
+            if n is not None and a.size != n:
+                raise ValueError(f"set_constant_blocks: the {what} mask has {a.size} entries, expected {n}")
+            return np.ascontiguousarray(a.ravel(), dtype=np.uint8)
+        if n is None:
+            raise ValueError(f"set_constant_blocks: an index list of {what} needs the count (n_{what}=..., or an uploaded scene)")
+        idx = a.astype(np.int64).ravel()
+        if idx.size and (idx.min() < 0 or idx.max() >= n):
+            raise ValueError(f"set_constant_blocks: a {what} index is out of range")
+        flags = np.zeros(n, dtype=np.uint8)
+        flags[idx] = 1
+        return flags
+
+    def set_constant_blocks(self, frames=None, points=None, keep_gauge=True, n_frames=None, n_points=None):
+        """Constant parameter blocks (next upload): frames / points are index lists or boolean masks in
+        the caller's numbering, None = none of that kind; both None clears the setting (the default).  A constant frame or
+        landmark keeps its values bit for bit; its observations still count.  keep_gauge=True keeps the reference's seven
+        gauge variables constant as well; with False the constant set alone must fix the similarity.  Index lists take the
+        counts from n_frames / n_points or from the scene last passed to this object.  Not with intrinsic groups or more
+        than one rank, and not with everything constant (ValueError)."""
+        if frames is None and points is None:
+            self._raise(self._lib.srk_ba_set_constant_blocks(C.c_void_p(self._h), None, C.c_int32(0), None, C.c_int64(0), C.c_int(1)))
+            return
+        if n_frames is None and self._scene is not None:
+            n_frames = self._scene.M
+        if n_points is None and self._scene is not None:
+            n_points = self._scene.N
+        ff = self._const_flags(frames, n_frames, "frames")
+        pf = self._const_flags(points, n_points, "points")
+        self._raise(self._lib.srk_ba_set_constant_blocks(
+            C.c_void_p(self._h), _p(ff) if ff is not None else None, C.c_int32(ff.size if ff is not None else 0),
+            _p(pf) if pf is not None else None, C.c_int64(pf.size if pf is not None else 0), C.c_int(int(bool(keep_gauge)))))
+
+    def constant_blocks(self):
+        """None when no constant blocks are set, else (frame_mask, point_mask, keep_gauge): boolean masks in the caller's
+        numbering, None for a kind that was not given"""
+        nf, npt, kg = C.c_int32(0), C.c_int64(0), C.c_int(1)
+        rc = self._lib.srk_ba_constant_counts(C.c_void_p(self._h), C.byref(nf), C.byref(npt))
+        self._raise(rc)
+        if rc == 0:
+            return None
+        ff = np.zeros(nf.value, dtype=np.uint8)
+        pf = np.zeros(npt.value, dtype=np.uint8)
+        self._raise(self._lib.srk_ba_constant_blocks(C.c_void_p(self._h), _p(ff) if nf.value else None,
+                                                     _p(pf) if npt.value else None, C.byref(kg)))
+        return (ff.astype(bool) if nf.value else None, pf.astype(bool) if npt.value else None, bool(kg.value))
+
+    def constant_pass_ms(self):
+        """(landmark pass, frame pass): device ms of the last launch of the two masking passes, with set_profile >= 1"""
+        a, b = C.c_double(0), C.c_double(0)
+        self._raise(self._lib.srk_ba_constant_pass_ms(C.c_void_p(self._h), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def schur_fallback_landmarks(self):
         """landmarks of the uploaded scene that take the per-landmark Schur kernel (srk_ba_schur_fallback_landmarks)"""
         fn = self._lib.srk_ba_schur_fallback_landmarks

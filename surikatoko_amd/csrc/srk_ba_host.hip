@@ -191,6 +191,19 @@ struct srk_ba {
     bool info_on = false;
     DevBuf info_q, info_qf;
     std::vector<int64_t> fobs_of;
+    // opt-in: constant parameter blocks (srk_ba_set_constant_blocks).  cst_frame_user / cst_point_user: the
+    // flags in the caller's numbering (either may be empty = none of that kind), kept across uploads and srk_ba_reset_scene.
+    // The uploaded scene: the constant landmarks in the internal order and the constant internal frames (ascending) on the
+    // device, the frames' flags by internal index on the host (SRK_BUF_GRAD).  Both counts 0 = no masking pass is launched.
+    bool cst_set = false;
+    int cst_keep_gauge = 1;
+    std::vector<uint8_t> cst_frame_user, cst_point_user;
+    DevBuf cst_pts, cst_frames;
+    int64_t n_cst_pts = 0;
+    int32_t n_cst_frames = 0;
+    std::vector<uint8_t> cst_frame_int;
+    hipEvent_t ev_cst[4]{}; // profile level >= 1: around the last k_const_points / k_const_frames launch (created on first use)
+    bool cst_timed[2] = { false, false };
     int profile_level = 0; // 0 = no events, 1 = phase events (report.ms_*), 2 = + event pairs around the MFMA updates
     bool chol_fused = true; // the solve's outer steps as one launch each (k_step256); srk_ba_set_solver_fusion
     // what the caller asked for.  A hand-off timeout switches chol_fused off for the rest of that call; the next upload /
@@ -375,7 +388,7 @@ void srk_ba_destroy(srk_ba* h)
                       &h->jd_nf, &h->jd_frames, &h->jd_mask,
                       &h->jr_first, &h->jr_count, &h->jr_jmin, &h->jr_group, &h->lg_item, &h->lg_np, &h->lg_nf, &h->lg_pts, &h->lg_frames,
                       &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk,
-                      &h->info_q, &h->info_qf };
+                      &h->info_q, &h->info_qf, &h->cst_pts, &h->cst_frames };
     for (DevBuf* b : all) dev_free(*b);
     for (auto& a : h->att) {
         for (DevBuf* b : { &a.S, &a.rhs, &a.wy, &a.dc, &a.acc, &a.dx, &a.err_partial, &a.info, &a.dinv, &a.packed, &a.sync_flags, &a.irr, &a.det_stage, &a.det_rhs,
@@ -392,6 +405,8 @@ void srk_ba_destroy(srk_ba* h)
         if (e) hipEventDestroy(e);
     for (auto& e : h->chol_ev) hipEventDestroy(e);
     if (h->ev_jac) hipEventDestroy(h->ev_jac);
+    for (auto& e : h->ev_cst)
+        if (e) hipEventDestroy(e);
     if (h->ev_comm) hipEventDestroy(h->ev_comm);
     if (h->comm_stream) hipStreamDestroy(h->comm_stream);
     for (int sl = 1; sl < SRK_SLOTS; ++sl)
@@ -455,10 +470,20 @@ static const char* groups_conflict(bool groups, bool fixed_k, bool store_f32, bo
     if (world > 1) return "intrinsic groups: not available with more than one rank";
     return nullptr;
 }
+// constant parameter blocks (srk_ba_set_constant_blocks) mask the 10- or 6-variable system of one rank: the fold of shared
+// intrinsics would drop a constant frame's observations from its group's K, and the mask would have to follow the exchange
+static const char* constant_conflict(bool constant, bool groups, int world)
+{
+    if (!constant) return nullptr;
+    if (groups) return "constant blocks: not available with intrinsic groups";
+    if (world > 1) return "constant blocks: not available with more than one rank";
+    return nullptr;
+}
 static bool refuse_modes(srk_ba* h, bool fixed_k, bool deterministic, bool store_f32, bool schur_fp32, int world, bool groups)
 {
     const char* e = fixed_k_conflict(fixed_k, deterministic, store_f32, schur_fp32, world);
     if (!e) e = groups_conflict(groups, fixed_k, store_f32, schur_fp32, world);
+    if (!e) e = constant_conflict(h->cst_set, groups, world);
     if (e) h->last_error = e;
     return e != nullptr;
 }
@@ -1110,6 +1135,7 @@ static int check_information(srk_ba* h, const char* who, const double* q, int64_
     return SRK_OK;
 }
 static int apply_information(srk_ba* h);
+static int apply_constant_blocks(srk_ba* h);
 static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_in, int32_t M,
                              const double* cam_R_in, const double* cam_T_in, const double* K_in, int shared_k,
                              const int64_t* row_ptr, const int32_t* obs_frame, const double* obs_uv,
@@ -1151,6 +1177,16 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     if (!h->info_user.empty() &&
         check_information(h, "upload", h->info_user.data(), (int64_t)h->info_user.size(), N, row_ptr) != SRK_OK)
         return SRK_E_ARGS;
+    if (h->cst_set) {
+        if (!h->cst_frame_user.empty() && (int64_t)h->cst_frame_user.size() != (int64_t)M) {
+            h->last_error = "constant blocks: set for " + std::to_string(h->cst_frame_user.size()) + " frames, the scene has " + std::to_string(M);
+            return SRK_E_ARGS;
+        }
+        if (!h->cst_point_user.empty() && (int64_t)h->cst_point_user.size() != N) {
+            h->last_error = "constant blocks: set for " + std::to_string(h->cst_point_user.size()) + " landmarks, the scene has " + std::to_string(N);
+            return SRK_E_ARGS;
+        }
+    }
     rearm_fusion(h);
     stage("validate");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1544,6 +1580,9 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     d.comp = 1;
     d.g0 = g0;
     d.g1 = g1;
+    // constant blocks without the reference's gauge: no frame index matches, so srk_is_fixed_var is false for every variable
+    // and the masking passes are the only source of identity rows besides the padding
+    if (h->cst_set && !h->cst_keep_gauge) d.g0 = d.g1 = -1;
     d.w_f32 = h->store_f32 ? 1 : 0;
     h->d = d;
     h->f0 = f0;
@@ -2021,7 +2060,45 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     }
     stage("skyline, solver plans");
     if ((rc = apply_information(h)) != SRK_OK) return rc;
+    if ((rc = apply_constant_blocks(h)) != SRK_OK) return rc;
     h->have_scene = true;
+    return SRK_OK;
+}
+
+// cst_frame_user / cst_point_user (counts checked at the start of the upload) -> the device lists of the resident scene: the
+// constant landmarks in the internal order (perm), the constant frames through the renumbering (frame_int), ascending
+static int apply_constant_blocks(srk_ba* h)
+{
+    const SrkDims& d = h->d;
+    h->n_cst_pts = 0;
+    h->n_cst_frames = 0;
+    h->cst_frame_int.clear();
+    if (!h->cst_set) return SRK_OK;
+    std::vector<int32_t> pl, fl;
+    if (!h->cst_point_user.empty())
+        for (int64_t i = 0; i < d.N; ++i)
+            if (h->cst_point_user[(size_t)h->perm[(size_t)i]]) pl.push_back((int32_t)i);
+    if (!h->cst_frame_user.empty()) {
+        h->cst_frame_int.assign((size_t)d.M, 0);
+        for (int32_t j = 0; j < d.M; ++j)
+            if (h->cst_frame_user[(size_t)j]) h->cst_frame_int[(size_t)(h->frame_int.empty() ? j : h->frame_int[(size_t)j])] = 1;
+        for (int32_t j = 0; j < d.M; ++j)
+            if (h->cst_frame_int[(size_t)j]) fl.push_back(j);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    int rc;
+    if (!pl.empty()) {
+        if ((rc = dev_alloc(h, h->cst_pts, 4 * pl.size())) != SRK_OK) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->cst_pts.p, pl.data(), 4 * pl.size(), hipMemcpyHostToDevice, s));
+    }
+    if (!fl.empty()) {
+        if ((rc = dev_alloc(h, h->cst_frames, 4 * fl.size())) != SRK_OK) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->cst_frames.p, fl.data(), 4 * fl.size(), hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope
+    h->n_cst_pts = (int64_t)pl.size();
+    h->n_cst_frames = (int32_t)fl.size();
     return SRK_OK;
 }
 
@@ -2293,6 +2370,14 @@ static int phase_error(srk_ba* h, srk_ba::Attempt& a, int which, double* err_hos
     return SRK_OK;
 }
 
+// the event pairs around the masking passes of the constant blocks (srk_ba_constant_pass_ms), created on first use
+static bool cst_events(srk_ba* h)
+{
+    for (auto& e : h->ev_cst)
+        if (!e && hipEventCreate(&e) != hipSuccess) return false;
+    return true;
+}
+
 static int phase_derivatives(srk_ba* h)
 {
     const SrkDims& d = h->d;
@@ -2327,6 +2412,14 @@ static int phase_derivatives(srk_ba* h)
                               P<int64_t>(h->col_ptr), P<int32_t>(h->fobs_pt), P<double>(h->fobs_uv), P<double>(h->Ug), L);
     }
     HIPCHK(h, hipGetLastError());
+    if (h->n_cst_pts > 0) { // constant landmarks: identity block, zero gradient, zero point-frame blocks
+        const bool timed = h->profile_level >= 1 && cst_events(h);
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[0], s));
+        srk_launch_const_points(s, d, P<int32_t>(h->cst_pts), h->n_cst_pts, P<int64_t>(h->row_ptr), P<double>(h->W), P<double>(h->Vg));
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[1], s));
+        h->cst_timed[0] = timed;
+        HIPCHK(h, hipGetLastError());
+    }
     // landmark shards: Ug stays this rank's partial sum; it enters the reduced camera system before that is summed
     return SRK_OK;
 }
@@ -2389,6 +2482,14 @@ static int phase_schur(srk_ba* h, srk_ba::Attempt& a, double c, bool local_only)
     srk_launch_assemble(s, d, c, P<double>(h->Ug), P<double>(a.S), P<double>(a.rhs), h->rank == 0 ? 1.0 : 0.0,
                         P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg), P<int32_t>(a.irr));
     HIPCHK(h, hipGetLastError());
+    if (h->n_cst_frames > 0) { // constant frames: identity rows and columns, zero rhs
+        const bool timed = h->profile_level >= 1 && cst_events(h);
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[2], s));
+        srk_launch_const_frames(s, d, P<int32_t>(h->cst_frames), h->n_cst_frames, P<int64_t>(h->env_col), P<double>(a.S), P<double>(a.rhs));
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[3], s));
+        h->cst_timed[1] = timed;
+        HIPCHK(h, hipGetLastError());
+    }
     if (h->shk_G > 0) { // shared intrinsics: S_sh = P^T S10 P, rhs_sh = P^T rhs10 (one rank only)
         srk_launch_rcs_fold(s, shk_args(h, a), P<double>(a.S), P<double>(a.rhs), P<double>(a.Ssh), P<double>(a.rsh));
         HIPCHK(h, hipGetLastError());
@@ -2473,6 +2574,9 @@ static int phase_cam_apply(srk_ba* h, srk_ba::Attempt& a)
     int cur = h->cur, tr = a.trial;
     srk_launch_cam_apply(a.stream, h->d.M, P<double>(h->camR[cur]), P<double>(h->camT[cur]), P<double>(a.dc),
                          P<double>(h->camR[tr]), P<double>(h->camT[tr]), kbuf(h, tr), h->f0, P<double>(h->cam[tr]), h->d.fv);
+    // constant frames: a zero correction does not return T bit for bit (it goes through R^T), so their trial pose is copied
+    srk_launch_const_cam_keep(a.stream, P<int32_t>(h->cst_frames), h->n_cst_frames, P<double>(h->camR[cur]), P<double>(h->camT[cur]),
+                              P<double>(h->cam[cur]), P<double>(h->camR[tr]), P<double>(h->camT[tr]), P<double>(h->cam[tr]));
     HIPCHK(h, hipGetLastError());
     return SRK_OK;
 }
@@ -3126,8 +3230,22 @@ int srk_ba_compute_inplace(srk_ba* h, double f0, int64_t N, double* pts, int32_t
     if (rc != SRK_OK) return rc;
     int result = srk_ba_optimize(h, allowed_err_change, max_hessian_factor, max_iterations, rep);
     if (result < 0) return result;
-    rc = srk_ba_download_scene(h, pts, cam_R, cam_T, 1);
+    if (!h->cst_set) {
+        rc = srk_ba_download_scene(h, pts, cam_R, cam_T, 1);
+        if (rc != SRK_OK) return rc;
+        return result;
+    }
+    // constant blocks are not written back: the caller's entries stay what they were, bit for bit
+    std::vector<double> p2((size_t)(3 * N)), r2((size_t)(9 * (int64_t)M)), t2((size_t)(3 * (int64_t)M));
+    rc = srk_ba_download_scene(h, p2.data(), r2.data(), t2.data(), 1);
     if (rc != SRK_OK) return rc;
+    for (int64_t i = 0; i < N; ++i)
+        if (h->cst_point_user.empty() || !h->cst_point_user[(size_t)i]) std::memcpy(pts + 3 * i, &p2[(size_t)(3 * i)], 24);
+    for (int32_t j = 0; j < M; ++j)
+        if (h->cst_frame_user.empty() || !h->cst_frame_user[(size_t)j]) {
+            std::memcpy(cam_R + 9 * (int64_t)j, &r2[9 * (size_t)j], 72);
+            std::memcpy(cam_T + 3 * (int64_t)j, &t2[3 * (size_t)j], 24);
+        }
     return result;
 }
 
@@ -3527,7 +3645,8 @@ int srk_ba_download(srk_ba* h, int which, double* dst, int64_t count)
         std::vector<double> ug((size_t)(ugs * (int64_t)d.M));
         if ((rc = d2h(ug.data(), h->Ug.p, ug.size() * 8)) != SRK_OK) return rc;
         for (int32_t j = 0; j < d.M; ++j)
-            for (int e = 0; e < d.fv; ++e) dst[3 * d.N + d.fv * (int64_t)j + e] = ug[(size_t)(ugs * (int64_t)j + ut + e)];
+            for (int e = 0; e < d.fv; ++e) // (constant frames report 0: their sums in Ug stay unmasked)
+                dst[3 * d.N + d.fv * (int64_t)j + e] = (!h->cst_frame_int.empty() && h->cst_frame_int[(size_t)j]) ? 0.0 : ug[(size_t)(ugs * (int64_t)j + ut + e)];
         frames_to_user(h, dst + 3 * d.N, d.fv);
         return SRK_OK;
     }
@@ -3965,6 +4084,67 @@ int srk_ba_download_intrinsics(srk_ba* h, double* K, int32_t n_groups)
         const double s = k22 / h->f0; // back to the caller's convention
         for (int e = 0; e < 8; ++e) k[e] *= s;
         k[8] = k22;
+    }
+    return SRK_OK;
+}
+// constant parameter blocks: flags in the caller's numbering, non-zero = constant; both NULL = none
+// (default).  Next upload.
+int srk_ba_set_constant_blocks(srk_ba* h, const uint8_t* frame_const, int32_t n_frames, const uint8_t* point_const, int64_t n_points,
+                               int keep_gauge)
+{
+    if (!h) return SRK_E_ARGS;
+    if (!frame_const && !point_const) {
+        h->cst_set = false;
+        h->cst_keep_gauge = 1;
+        h->cst_frame_user.clear();
+        h->cst_point_user.clear();
+        return SRK_OK;
+    }
+    if (keep_gauge != 0 && keep_gauge != 1) { h->last_error = "constant blocks: keep_gauge must be 0 or 1"; return SRK_E_ARGS; }
+    if (frame_const && n_frames < 1) { h->last_error = "constant blocks: need at least one frame"; return SRK_E_ARGS; }
+    if (point_const && n_points < 0) { h->last_error = "constant blocks: negative number of landmarks"; return SRK_E_ARGS; }
+    if (const char* e = constant_conflict(true, !h->igroup_user.empty(), h->world)) { h->last_error = e; return SRK_E_ARGS; }
+    bool all_frames = frame_const != nullptr, all_points = point_const != nullptr;
+    for (int32_t j = 0; frame_const && j < n_frames; ++j) all_frames = all_frames && frame_const[j] != 0;
+    for (int64_t i = 0; point_const && i < n_points; ++i) all_points = all_points && point_const[i] != 0;
+    if (all_frames && all_points) { h->last_error = "constant blocks: every frame and every landmark is constant, nothing is left to solve"; return SRK_E_ARGS; }
+    h->cst_frame_user.clear();
+    h->cst_point_user.clear();
+    if (frame_const) h->cst_frame_user.assign(frame_const, frame_const + n_frames);
+    if (point_const) h->cst_point_user.assign(point_const, point_const + n_points);
+    for (auto& f : h->cst_frame_user) f = f ? 1 : 0;
+    for (auto& f : h->cst_point_user) f = f ? 1 : 0;
+    h->cst_keep_gauge = keep_gauge;
+    h->cst_set = true;
+    return SRK_OK;
+}
+int srk_ba_constant_blocks(srk_ba* h, uint8_t* frame_const, uint8_t* point_const, int* keep_gauge)
+{
+    if (!h) return SRK_E_ARGS;
+    if (keep_gauge) *keep_gauge = h->cst_keep_gauge;
+    if (frame_const && !h->cst_frame_user.empty()) std::memcpy(frame_const, h->cst_frame_user.data(), h->cst_frame_user.size());
+    if (point_const && !h->cst_point_user.empty()) std::memcpy(point_const, h->cst_point_user.data(), h->cst_point_user.size());
+    return h->cst_set ? 1 : 0;
+}
+int srk_ba_constant_counts(srk_ba* h, int32_t* n_frames, int64_t* n_points)
+{
+    if (!h) return SRK_E_ARGS;
+    if (n_frames) *n_frames = (int32_t)h->cst_frame_user.size();
+    if (n_points) *n_points = (int64_t)h->cst_point_user.size();
+    return h->cst_set ? 1 : 0;
+}
+int srk_ba_constant_pass_ms(srk_ba* h, double* points_ms, double* frames_ms)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
+    for (int sl = 1; sl < SRK_SLOTS; ++sl)
+        if (h->att[sl].stream) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
+    for (int k = 0; k < 2; ++k) {
+        float ms = 0;
+        if (h->cst_timed[k] && hipEventElapsedTime(&ms, h->ev_cst[2 * k], h->ev_cst[2 * k + 1]) != hipSuccess) ms = 0;
+        double* out = k == 0 ? points_ms : frames_ms;
+        if (out) *out = h->cst_timed[k] ? (double)ms : 0.0;
     }
     return SRK_OK;
 }

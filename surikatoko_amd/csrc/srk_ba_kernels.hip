@@ -3165,3 +3165,91 @@ void srk_launch_rcs_expand(hipStream_t s, const SrkShk& k, const double* dcsh, d
 {
     hipLaunchKernelGGL(k_rcs_expand, dim3((k.M + 63) / 64), dim3(64), 0, s, k, dcsh, dc10, Kcur, Ktr);
 }
+
+// ------------------------------------------------------------------ constant parameter blocks (srk_ba_set_constant_blocks)
+// DESIGN.md section 13.  Constant frames and landmarks are imposed by masking what the unchanged kernels above produce: a
+// constant block becomes what a gauge variable already is -- identity diagonal, zero couplings, zero right-hand side -- so
+// its correction is exactly 0 in every solver mode.  None of these passes is launched when no block is constant.
+
+// Constant landmarks, after the derivative pass: the 3 x 3 block becomes the identity, the gradient 0, and the point factors
+// Ap, Bp (planes 0..5) of each of its observations 0, so that every block W = Ap Af + Bp Bf of the landmark is an exact zero.
+// One wave per landmark; a landmark's observations are consecutive, so the stores of a plane are lane-contiguous.
+template <typename WT>
+__global__ __launch_bounds__(256) void k_const_points(SrkDims d, const int32_t* __restrict__ list, int64_t n_list,
+                                                      const int64_t* __restrict__ row_ptr, WT* __restrict__ W,
+                                                      double* __restrict__ Vg)
+{
+    const int64_t li = (int64_t)blockIdx.x * (256 / WAVE) + threadIdx.x / WAVE;
+    if (li >= n_list) return;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t pt = list[li];
+    if (pt < 0 || pt >= d.N) return;
+    if (lane < 9) Vg[(int64_t)lane * d.Ns + pt] = (lane == 0 || lane == 3 || lane == 5) ? 1.0 : 0.0; // V00 V01 V02 V11 V12 V22 g0 g1 g2
+    const int64_t o0 = row_ptr[pt], o1 = row_ptr[pt + 1];
+    for (int64_t o = o0 + lane; o < o1; o += WAVE) {
+#pragma unroll
+        for (int k = SRK_WF_AP; k < SRK_WF_BP + 3; ++k) W[(int64_t)k * d.Os + o] = (WT)0;
+    }
+}
+void srk_launch_const_points(hipStream_t s, const SrkDims& d, const int32_t* list, int64_t n_list, const int64_t* row_ptr,
+                             double* W, double* Vg)
+{
+    if (n_list <= 0) return;
+    const dim3 grid((unsigned)((n_list + 256 / WAVE - 1) / (256 / WAVE)));
+    if (d.w_f32)
+        hipLaunchKernelGGL(k_const_points<float>, grid, dim3(256), 0, s, d, list, n_list, row_ptr, reinterpret_cast<float*>(W), Vg);
+    else
+        hipLaunchKernelGGL(k_const_points<double>, grid, dim3(256), 0, s, d, list, n_list, row_ptr, W, Vg);
+}
+
+// Constant frames, after k_assemble: workgroup (constant frame, 128-row tile) of the padded system.  For the frame's variables
+// r0 .. r0 + fv - 1: (a) their rows from the tile's first skyline column to the diagonal become 0, the diagonal itself 1, (b) their columns in every row below, where the row's tile reaches them (tested per tile and per
+// column: env_col is a multiple of 256 and need not be monotone), become 0, (c) their rhs becomes 0.  The lower triangle is
+// authoritative, so nothing right of the diagonal is touched.  Dense mode: env_col holds zeros.
+__global__ __launch_bounds__(128) void k_const_frames(int64_t ld, int fv, const int32_t* __restrict__ frames,
+                                                      const int64_t* __restrict__ env_col, double* __restrict__ S,
+                                                      double* __restrict__ rhs)
+{
+    const int64_t r0 = (int64_t)fv * frames[blockIdx.x], r1 = r0 + fv; // the frame's variables [r0, r1)
+    const int64_t t = blockIdx.y, t0 = 128 * t;
+    if (t0 + 128 <= r0 || r1 > ld) return; // the tile lies above the frame: nothing of it in there
+    const int64_t c0 = env_col[t];
+    // (a) + (c): the frame's own rows inside this tile, lanes along the columns
+    for (int64_t row = r0 > t0 ? r0 : t0; row < r1 && row < t0 + 128; ++row) {
+        double* p = S + row * ld;
+        for (int64_t c = c0 + threadIdx.x; c <= row; c += 128) p[c] = c == row ? 1.0 : 0.0;
+        if (threadIdx.x == 0) rhs[row] = 0.0;
+    }
+    // (b): the rows below the frame inside this tile, one lane per row
+    const int64_t row = t0 + threadIdx.x;
+    if (row >= r1 && row < ld) {
+        double* p = S + row * ld;
+        for (int64_t c = r0 > c0 ? r0 : c0; c < r1; ++c) p[c] = 0.0;
+    }
+}
+void srk_launch_const_frames(hipStream_t s, const SrkDims& d, const int32_t* frames, int32_t n_frames, const int64_t* env_col,
+                             double* S, double* rhs)
+{
+    if (n_frames <= 0) return;
+    hipLaunchKernelGGL(k_const_frames, dim3((unsigned)n_frames, (unsigned)(d.ld / 128)), dim3(128), 0, s, d.ld, (int)d.fv, frames,
+                       env_col, S, rhs);
+}
+
+// Constant frames, after k_cam_apply: a zero correction still sends T through R (R^T T), which need not return the same
+// bits, so the trial pose and camera pack of a constant frame are copied from the current scene.  One wave per frame.
+__global__ __launch_bounds__(64) void k_const_cam_keep(const int32_t* __restrict__ frames, const double* __restrict__ R,
+                                                       const double* __restrict__ T, const double* __restrict__ pack,
+                                                       double* __restrict__ Rn, double* __restrict__ Tn, double* __restrict__ packn)
+{
+    const int64_t j = frames[blockIdx.x];
+    const int l = threadIdx.x;
+    if (l < 9) Rn[9 * j + l] = R[9 * j + l];
+    if (l < 3) Tn[3 * j + l] = T[3 * j + l];
+    if (l < SRK_CAM_PACK) packn[SRK_CAM_PACK * j + l] = pack[SRK_CAM_PACK * j + l];
+}
+void srk_launch_const_cam_keep(hipStream_t s, const int32_t* frames, int32_t n_frames, const double* R, const double* T,
+                               const double* pack, double* Rn, double* Tn, double* packn)
+{
+    if (n_frames <= 0) return;
+    hipLaunchKernelGGL(k_const_cam_keep, dim3((unsigned)n_frames), dim3(64), 0, s, frames, R, T, pack, Rn, Tn, packn);
+}

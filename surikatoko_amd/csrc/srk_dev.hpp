@@ -17,7 +17,8 @@
 //   S        [ld][ld]  padded reduced camera system, row-major, LOWER triangle authoritative;
 //            variable index = fv*frame + var (fv = 10, or 6 = [Tx Ty Tz Wx Wy Wz] with fixed intrinsics: SrkDims::fv);
 //            the 7 gauge-fixed variables and the padding rows
-//            carry an identity diagonal and zero rhs, so their correction is exactly 0
+//            carry an identity diagonal and zero rhs, so their correction is exactly 0; so do the variables of constant
+//            frames (srk_ba_set_constant_blocks), through k_const_frames behind k_assemble
 //   rhs,dc   [ld]
 #pragma once
 #include <hip/hip_runtime.h>
@@ -157,6 +158,17 @@ void srk_launch_assemble(hipStream_t s, const SrkDims& d, double c, const double
                          double ident /* diagonal of fixed / padding variables */, const int64_t* row_ptr,
                          const int32_t* obs_frame, const double* W, const double* Vg,
                          const int32_t* irr /* landmarks handed back by k_schur_mm: served by the tail workgroups */);
+// constant parameter blocks (srk_ba_set_constant_blocks): masking passes behind the unchanged kernels,
+// launched only when the list is not empty.
+// after the derivative pass: identity block, zero gradient and zero point factors (planes 0..5 of W) for the listed landmarks
+void srk_launch_const_points(hipStream_t s, const SrkDims& d, const int32_t* list /* landmarks, internal order */, int64_t n_list,
+                             const int64_t* row_ptr, double* W, double* Vg);
+// after srk_launch_assemble: identity rows / columns and zero rhs for the variables of the listed frames, inside the skyline
+void srk_launch_const_frames(hipStream_t s, const SrkDims& d, const int32_t* frames /* internal frames, ascending */, int32_t n_frames,
+                             const int64_t* env_col, double* S, double* rhs);
+// after srk_launch_cam_apply: the trial pose and camera pack of the listed frames are those of the current scene, bit for bit
+void srk_launch_const_cam_keep(hipStream_t s, const int32_t* frames, int32_t n_frames, const double* R, const double* T,
+                               const double* pack, double* Rn, double* Tn, double* packn);
 void srk_launch_backsub(hipStream_t s, const SrkDims& d, double c, const int32_t* obs_frame, const int32_t* obs_pt,
                         const double* W, const double* Vg, const double* dc, double* acc, const double* pts,
                         double* pts_trial, double* dx);
