@@ -25,8 +25,15 @@ def run(rank, world, port, out_dir, spec_kwargs, iters, schedule="dp"):
         spec_kwargs.pop("_iters", None)
         shuffle = spec_kwargs.pop("_shuffle", None)
         drop = spec_kwargs.pop("_drop", None)
+        hetero = spec_kwargs.pop("_hetero", None)
         spec = sa.SceneSpec(**spec_kwargs)
         full = sa.generate_scene(spec)
+        if hetero is not None:  # every frame its own intrinsics (tests/hetero_cases.py), drawn at this seed
+            here = os.path.dirname(os.path.abspath(__file__))
+            if here not in sys.path:
+                sys.path.insert(0, here)
+            import hetero_cases
+            full = hetero_cases.per_frame_intrinsics(full, spec.f0, hetero_cases.SPREAD, hetero)
         if drop is not None:  # ragged tracks: hardly two landmarks see the same frames
             full = sa.drop_observations(full, drop, seed=11)
         if shuffle is not None:  # an unordered image set: the frame numbers say nothing about covisibility
