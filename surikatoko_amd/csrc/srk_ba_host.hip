@@ -8,6 +8,7 @@
 #include "../../include/srk_ba.h"
 #include "srk_dev.hpp"
 #include "srk_geom.hpp"
+#include "srk_plan.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -37,8 +38,9 @@ struct DevBuf {
 
 #define SRK_FUSION_RETRIES 3
 #define SRK_SLOTS 3 // attempt slots: two on one GPU (speculative pairs), up to three with several ranks (one damping factor each)
-struct srk_ba {
+struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided, srk_plan.hpp)
     int device = 0;
+    int cus = 256; // compute units of the device
     bool own_stream = true;
     std::string last_error;
 
@@ -46,7 +48,6 @@ struct srk_ba {
     bool have_scene = false;
     SrkDims d{};
     double f0 = 0;
-    int64_t max_frame_obs = 0;
     srk_ba_normalizer nrm{};
     bool normalized_on_upload = false;
 
@@ -55,45 +56,22 @@ struct srk_ba {
     DevBuf pts0, camR0, camT0; // copy of the uploaded (normalised) scene for srk_ba_reset_scene
     DevBuf row_ptr, obs_frame, obs_pt, obs_uv, col_ptr, fobs_pt, fobs_uv;
     DevBuf W, Vg, Ug, scratch;
-    // landmarks are stored sorted by frame list (internal order); perm[internal] = caller's pnt_ind
-    std::vector<int64_t> perm, row_ptr_user, row_ptr_int;
-    // Frames may be stored in another order than the caller's (frame_reorder below: unordered image sets, loop
-    // closures).  Both empty = the caller's order.  frame_int[caller's frame] = internal index, frame_user = its inverse;
-    // obs_rank[caller's observation] = its place inside its landmark's internal (re-sorted) observation list.
-    std::vector<int32_t> frame_int, frame_user, obs_rank;
     int frame_order_mode = -1; // srk_ba_set_frame_reordering: -1 automatic, 0 never, 1 whenever the ordering differs from the caller's
     std::vector<int32_t> frame_order_given; // srk_ba_set_frame_order: the numbering to use (several ranks: the same on every rank)
-    bool frame_order_supplied = false;      // the uploaded scene uses frame_order_given
     DevBuf grp_first, grp_count, grp_nf, grp_frames, obs_slot, pt_mask, gen_list, wg_jmin;
     DevBuf cal_list;      // fixed intrinsics: the landmarks outside the runs k_schur_mm takes (per-landmark kernel)
-    int64_t n_cal_list = 0;
     // long tracks (more than SRK_GRP_MAXNF_HOST frames): runs over frame-block pairs, k_schur_long
     DevBuf lg_item, lg_np, lg_nf, lg_pts, lg_frames, lg_obs_off, lg_obs;
-    int64_t n_long_items = 0, n_long_runs = 0;
     DevBuf sc_pts, sc_R, sc_T, sc_K, sc_cam, sc_frame, sc_pt, sc_uv, sc_partial, sc_out; // standalone scoring path
-    int64_t n_groups = 0, n_groups_wide = 0, n_groups_mid = 0, n_generic = 0;
-    int64_t n_mm_uniform = 0, n_mm_ragged = 0; // runs the MFMA kernel takes (<= SRK_WS_NF_HOST frames), by kind
-    bool jac_fused = false; // every 1024-observation workgroup touches < SRK_JF_SLOTS_HOST consecutive frames
     // run-based Jacobian kernel (k_jac_runs): tasks = pieces of runs of landmarks with identical frame lists
     DevBuf jr_first, jr_count, jr_jmin, jr_group;
-    // the derivative kernel's OWN runs (round 4): when a scene holds tracks over more than SRK_GRP_MAXNF_HOST frames the Schur
-    // kernels' runs do not cover every landmark; runs over unions of <= 32 frames (one mask word) built for the derivative kernel
-    // alone do, as long as no track is longer than that
-    DevBuf jd_nf, jd_frames, jd_mask;
-    bool jr_own_runs = false;
+    DevBuf jd_nf, jd_frames, jd_mask; // the derivative kernel's OWN runs (SrkPlanKept::jr_own_runs)
     // deterministic mode (srk_ba_set_deterministic; srk_dev.hpp: SrkDetJac / SrkDetSchur): index tables of the ordered second
     // passes and the derivative kernel's staging buffer (the Schur kernel's are per attempt slot)
     bool deterministic = false;       // asked for (takes effect at the next upload)
-    bool det_active = false;          // the uploaded scene runs that way (every landmark through k_jac_runs / k_schur_mm)
     DevBuf dj_ptr, dj_ent, dj_stage, ds_pair_ptr, ds_pair_fa, ds_pair_fb, ds_pair_ent, ds_f_ptr, ds_f_ent;
-    int32_t ds_n_pairs = 0;
-    bool jac_runs_masked = false; // the tasks are pieces of the Schur kernel's runs over UNIONS of frame lists (ragged tracks)
-    int32_t jr_tasks = 0, jr_min_nf = 64;
-    int long_fb = SRK_LONG_FB_HOST; // frames per block of k_schur_long's pairs: 8, or 16 when the scene has enough of them
-    bool jac_runs = false;  // the tasks are long enough to pay and every workgroup's frame window fits
     int jac_mode = -1;      // -1 = automatic, 0 = never k_jac_runs, 1 = whenever possible (srk_ba_set_jacobian_mode)
     // skyline of the reduced camera system (see k_env_zero): host + device copies
-    std::vector<int32_t> min_cv;                       // [M] smallest frame sharing a landmark with frame j
     std::vector<int64_t> env_col_h, env_off_h, row_end_h, col_begin_h;
     DevBuf env_col, env_off, band_col, band_off;
     int64_t env_packed = 0, band_packed = 0; // doubles inside the factorisation skyline / the pre-factorisation band
@@ -190,7 +168,6 @@ struct srk_ba {
     std::vector<double> info_user;
     bool info_on = false;
     DevBuf info_q, info_qf;
-    std::vector<int64_t> fobs_of;
     // opt-in: constant parameter blocks (srk_ba_set_constant_blocks).  cst_frame_user / cst_point_user: the
     // flags in the caller's numbering (either may be empty = none of that kind), kept across uploads and srk_ba_reset_scene.
     // The uploaded scene: the constant landmarks in the internal order and the constant internal frames (ascending) on the
@@ -274,13 +251,6 @@ RcclApi& rccl()
         }                                                                                            \
     } while (0)
 
-// SRK_DEBUG=1: plan and per-attempt traces on stderr
-static bool srk_debug()
-{
-    static const bool on = getenv("SRK_DEBUG") != nullptr;
-    return on;
-}
-
 static int dev_alloc(srk_ba* h, DevBuf& b, size_t bytes)
 {
     if (bytes == 0) bytes = 8;
@@ -327,6 +297,8 @@ srk_ba* srk_ba_create(int device_id)
     if (hipSetDevice(device_id) != hipSuccess) return nullptr;
     srk_ba* h = new srk_ba();
     h->device = device_id;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
     if (hipStreamCreate(&h->main_stream) != hipSuccess) {
         delete h;
         return nullptr;
@@ -976,137 +948,6 @@ static SrkShk shk_args(const srk_ba* h, const srk_ba::Attempt& a)
 // the intrinsics of scene buffer set w: its own copy with shared intrinsics (the trial K of an attempt), else the uploaded K
 static double* kbuf(srk_ba* h, int w) { return h->shk_G > 0 ? P<double>(h->Ks[w]) : P<double>(h->K); }
 
-// Internal frame order.  The reference treats the reduced camera system as a dense matrix (bundle-adj-kanatani.cpp:1911), so
-// the order of the frames means nothing to it.  Here everything fast depends on covisible frames having NEARBY indices: the
-// skyline of the system, its nested dissection (separators one bandwidth wide), the frame windows of the derivative kernels.
-// An image sequence in time order has that property; the same frames in any other order (an unordered image set), or a
-// sequence that closes a loop (the last frames see the first frames' landmarks), do not -- the solve alone then takes 5x
-// longer on the 1000-frame scene (one skyline chain instead of chunks).  So, when the caller's order is far from banded,
-// the frames are renumbered by reverse Cuthill-McKee on the covisibility graph (two frames adjacent iff they share a
-// landmark), started from a pseudo-peripheral frame: a shuffled sequence gets its band back, a closed loop becomes a band
-// of two to three times the width (twice is the optimum for a ring).  Only the numbering changes -- arithmetic per block, gauge (the caller's frames 0 and 1, wherever they
-// land: SrkDims::g0, g1) and results are those of the caller's order; every download maps back.
-// Returns true and fills to_int[caller's frame] = internal index when renumbering pays.  mode: see srk_ba::frame_order_mode.
-static bool frame_reorder(int mode, int64_t N, int32_t M, const int64_t* row_ptr, const int32_t* obs_frame, std::vector<int32_t>& to_int)
-{
-    if (mode == 0 || M < 3 || M > 16384) return false;
-    int64_t bw_nat = 0, lmax = 0;
-    for (int64_t i = 0; i < N; ++i) {
-        const int64_t k = row_ptr[i + 1] - row_ptr[i];
-        if (k < 1) continue;
-        lmax = std::max(lmax, k);
-        bw_nat = std::max<int64_t>(bw_nat, obs_frame[row_ptr[i + 1] - 1] - obs_frame[row_ptr[i]]); // lists ascend
-    }
-    if (mode < 0 && bw_nat <= 2 * lmax) return false; // as banded as tracks of that length allow
-    // covisibility graph as a bit matrix (M <= 16384: 32 MB); every distinct frame list once
-    const size_t wpr = ((size_t)M + 63) / 64;
-    std::vector<uint64_t> adj((size_t)M * wpr, 0);
-    std::unordered_set<uint64_t> seen;
-    int64_t pair_work = 0;
-    const int64_t pair_budget = 400000000; // ~1 s of host time
-    for (int64_t i = 0; i < N; ++i) {
-        const int64_t k = row_ptr[i + 1] - row_ptr[i];
-        if (k < 2) continue;
-        const int32_t* f = obs_frame + row_ptr[i];
-        uint64_t hsh = 1469598103934665603ull ^ (uint64_t)k;
-        for (int64_t a = 0; a < k; ++a) hsh = (hsh ^ (uint64_t)(uint32_t)f[a]) * 1099511628211ull;
-        if (!seen.insert(hsh).second) continue; // (a collision only costs ordering quality: the skyline is built from the observations)
-        auto link = [&](int32_t u, int32_t v) {
-            adj[(size_t)u * wpr + (size_t)(v >> 6)] |= 1ull << (v & 63);
-            adj[(size_t)v * wpr + (size_t)(u >> 6)] |= 1ull << (u & 63);
-        };
-        // all pairs of a list while the work stays bounded (long ragged tracks in an unordered set: ~1e6 distinct lists of
-        // ~500 frames would be 1e11 insertions before the first kernel); beyond the budget a list's chain of consecutive
-        // frames plus its first-last pair, which keeps the graph connected along every track
-        if (pair_work + k * (k - 1) / 2 <= pair_budget) {
-            pair_work += k * (k - 1) / 2;
-            for (int64_t a = 0; a < k; ++a)
-                for (int64_t b = a + 1; b < k; ++b) link(f[a], f[b]);
-        } else {
-            for (int64_t a = 0; a + 1 < k; ++a) link(f[a], f[a + 1]);
-            link(f[0], f[k - 1]);
-        }
-    }
-    std::vector<int32_t> deg((size_t)M, 0);
-    for (int32_t j = 0; j < M; ++j)
-        for (size_t w = 0; w < wpr; ++w) deg[(size_t)j] += __builtin_popcountll(adj[(size_t)j * wpr + w]);
-    std::vector<int32_t> order, level((size_t)M), nb;
-    std::vector<char> done((size_t)M, 0);
-    // breadth-first levels of the component of `root` among the frames not yet numbered; returns the last level's
-    // frame of smallest degree and the depth
-    std::vector<int32_t> stamp((size_t)M, 0); // visited in THIS search: stamp == bfs_id (no copy of an M-byte array per search)
-    int32_t bfs_id = 0;
-    auto bfs = [&](int32_t root, std::vector<int32_t>& out, int32_t& depth) -> int32_t {
-        out.clear();
-        out.push_back(root);
-        ++bfs_id;
-        struct Vis {
-            const std::vector<char>& done;
-            std::vector<int32_t>& stamp;
-            int32_t id;
-            struct Ref {
-                Vis& v;
-                size_t i;
-                operator bool() const { return v.done[i] || v.stamp[i] == v.id; }
-                Ref& operator=(int) { v.stamp[i] = v.id; return *this; }
-            };
-            Ref operator[](size_t i) { return Ref{ *this, i }; }
-        } vis{ done, stamp, bfs_id };
-        vis[(size_t)root] = 1;
-        level[(size_t)root] = 0;
-        for (size_t q = 0; q < out.size(); ++q) {
-            const int32_t u = out[q];
-            nb.clear();
-            for (size_t w = 0; w < wpr; ++w)
-                for (uint64_t bits = adj[(size_t)u * wpr + w]; bits; bits &= bits - 1) {
-                    const int32_t v = (int32_t)(64 * w) + __builtin_ctzll(bits);
-                    if (!vis[(size_t)v]) { vis[(size_t)v] = 1; nb.push_back(v); }
-                }
-            std::sort(nb.begin(), nb.end(), [&](int32_t a, int32_t b) { return deg[(size_t)a] != deg[(size_t)b] ? deg[(size_t)a] < deg[(size_t)b] : a < b; });
-            for (int32_t v : nb) { level[(size_t)v] = level[(size_t)u] + 1; out.push_back(v); }
-        }
-        depth = level[(size_t)out.back()];
-        int32_t far = out.back();
-        for (size_t q = out.size(); q-- > 0 && level[(size_t)out[q]] == depth;)
-            if (deg[(size_t)out[q]] < deg[(size_t)far] || (deg[(size_t)out[q]] == deg[(size_t)far] && out[q] < far)) far = out[q];
-        return far;
-    };
-    std::vector<int32_t> comp;
-    for (int32_t start = 0; start < M; ++start) {
-        if (done[(size_t)start]) continue;
-        if (deg[(size_t)start] == 0) { // a frame nobody shares a landmark with: a component of its own
-            done[(size_t)start] = 1;
-            order.push_back(start);
-            continue;
-        }
-        int32_t root = start, depth = -1, d2 = 0;
-        for (int it = 0; it < 4; ++it) { // George-Liu: walk to a frame of (nearly) greatest eccentricity
-            const int32_t far = bfs(root, comp, d2);
-            if (d2 <= depth) break;
-            depth = d2;
-            root = far;
-        }
-        bfs(root, comp, d2);
-        for (int32_t v : comp) { done[(size_t)v] = 1; order.push_back(v); }
-    }
-    std::reverse(order.begin(), order.end());
-    to_int.assign((size_t)M, 0);
-    for (int32_t i = 0; i < M; ++i) to_int[(size_t)order[(size_t)i]] = i;
-    int64_t bw_new = 0;
-    bool differs = false;
-    for (int32_t j = 0; j < M; ++j) differs = differs || to_int[(size_t)j] != j;
-    for (int64_t i = 0; i < N; ++i) {
-        int32_t lo = M, hi = -1;
-        for (int64_t o = row_ptr[i]; o < row_ptr[i + 1]; ++o) {
-            lo = std::min(lo, to_int[(size_t)obs_frame[o]]);
-            hi = std::max(hi, to_int[(size_t)obs_frame[o]]);
-        }
-        if (hi >= 0) bw_new = std::max<int64_t>(bw_new, hi - lo);
-    }
-    if (srk_debug()) fprintf(stderr, "srk_ba frame order: bandwidth %lld frames in the caller's order, %lld after reverse Cuthill-McKee\n", (long long)bw_nat, (long long)bw_new);
-    return mode > 0 ? differs : 10 * bw_new <= 7 * bw_nat;
-}
-
 static void rearm_fusion(srk_ba* h);
 // per-observation information q (the caller's order) against a scene's CSR rows: every value finite and >= 0, one per
 // observation, and no landmark left with fewer than two observations of positive information (its 3 x 3 block would be singular)
@@ -1235,338 +1076,21 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         }
     }
 
-    // ---- internal frame order (frame_reorder above; one rank only: shards would each find another order)
-    std::vector<int32_t> of_fr;
-    std::vector<double> ouv_fr;
-    h->frame_int.clear();
-    h->frame_user.clear();
-    h->obs_rank.clear();
-    int32_t g0 = 0, g1 = 1;
-    {
-        std::vector<int32_t> to_int;
-        bool renumber = false;
-        h->frame_order_supplied = false;
-        if (!h->frame_order_given.empty()) {
-            if ((int64_t)h->frame_order_given.size() != (int64_t)M) { h->last_error = "the supplied frame order is for another number of frames"; return SRK_E_ARGS; }
-            to_int = h->frame_order_given;
-            for (int32_t j = 0; j < M; ++j) renumber = renumber || to_int[(size_t)j] != j;
-            h->frame_order_supplied = renumber;
-        } else if (!(h->allreduce || h->comm))
-            renumber = frame_reorder(h->frame_order_mode, N, M, row_ptr, obs_frame, to_int);
-        if (renumber) {
-            h->frame_int = to_int;
-            h->frame_user.assign((size_t)M, 0);
-            for (int32_t j = 0; j < M; ++j) h->frame_user[(size_t)to_int[(size_t)j]] = j;
-            g0 = to_int[0];
-            g1 = to_int[1];
-            // cameras in the internal order; every landmark's observations re-sorted by internal frame
-            std::vector<double> r2(camR.size()), t2(camT.size()), k2(Kexp.size());
-            for (int32_t j = 0; j < M; ++j) {
-                const int64_t u = h->frame_user[(size_t)j];
-                std::memcpy(&r2[9 * (size_t)j], &camR[9 * (size_t)u], 72);
-                std::memcpy(&t2[3 * (size_t)j], &camT[3 * (size_t)u], 24);
-                std::memcpy(&k2[9 * (size_t)j], &Kexp[9 * (size_t)u], 72);
-            }
-            camR.swap(r2);
-            camT.swap(t2);
-            Kexp.swap(k2);
-            of_fr.resize((size_t)O);
-            ouv_fr.resize((size_t)(2 * O));
-            h->obs_rank.resize((size_t)O);
-            std::vector<std::pair<int32_t, int64_t>> key;
-            for (int64_t i = 0; i < N; ++i) {
-                key.clear();
-                for (int64_t o = row_ptr[i]; o < row_ptr[i + 1]; ++o) key.emplace_back(to_int[(size_t)obs_frame[o]], o);
-                std::sort(key.begin(), key.end());
-                for (size_t a = 0; a < key.size(); ++a) {
-                    const int64_t dst = row_ptr[i] + (int64_t)a, src = key[a].second;
-                    of_fr[(size_t)dst] = key[a].first;
-                    ouv_fr[(size_t)(2 * dst)] = obs_uv[2 * src];
-                    ouv_fr[(size_t)(2 * dst + 1)] = obs_uv[2 * src + 1];
-                    h->obs_rank[(size_t)src] = (int32_t)a;
-                }
-            }
-            obs_frame = of_fr.data();
-            obs_uv = ouv_fr.data();
-        }
-    }
-
+    if (!h->frame_order_given.empty() && (int64_t)h->frame_order_given.size() != (int64_t)M) { h->last_error = "the supplied frame order is for another number of frames"; return SRK_E_ARGS; }
+    // ---- the plan (srk_plan.cpp, host only): the internal frame and landmark order, the runs, tasks and tables of every kernel
+    SrkPlanOptions opt{ h->fixed_k, h->deterministic, h->schur_fp32, h->jac_mode, h->frame_order_mode, &h->frame_order_given,
+                        h->allreduce || h->comm /* multi_rank */, h->cus };
+#ifdef SRK_DEV
+    if (const char* e = getenv("SRK_SCHUR_RUN_SPLIT")) opt.run_split = std::max(1, std::min(16, atoi(e))); // development: fixed cut
+    opt.no_long = getenv("SRK_SCHUR_NO_LONG") != nullptr; // development: everything through the per-landmark kernel
+#endif
+    SrkScenePlan plan;
+    srk_plan_scene({ N, M, row_ptr, obs_frame, obs_uv, pts.data(), camR.data(), camT.data(), Kexp.data() }, opt, plan, stage);
     if (!h->igroup_user.empty()) {
         h->shk_G = h->igroup_n;
         h->shk_grp_h.assign((size_t)M, 0);
-        for (int32_t j = 0; j < M; ++j) h->shk_grp_h[(size_t)j] = h->igroup_user[(size_t)(h->frame_user.empty() ? j : h->frame_user[(size_t)j])];
+        for (int32_t j = 0; j < M; ++j) h->shk_grp_h[(size_t)j] = h->igroup_user[(size_t)(plan.frame_user.empty() ? j : plan.frame_user[(size_t)j])];
     }
-
-    // ---- internal landmark order: sorted by frame list, so that landmarks seeing exactly the same frames are
-    // contiguous (the grouped Schur kernel accumulates a run of them in registers and flushes once)
-    std::vector<int64_t> order((size_t)N);
-    std::iota(order.begin(), order.end(), (int64_t)0);
-    auto list_less = [&](int64_t x, int64_t y) {
-        int64_t ox = row_ptr[x], oy = row_ptr[y];
-        int64_t nx = row_ptr[x + 1] - ox, ny = row_ptr[y + 1] - oy;
-        if (nx == 0 || ny == 0) return nx < ny;
-        if (obs_frame[ox] != obs_frame[oy]) return obs_frame[ox] < obs_frame[oy];
-        if (nx != ny) return nx < ny;
-        for (int64_t k = 1; k < nx; ++k)
-            if (obs_frame[ox + k] != obs_frame[oy + k]) return obs_frame[ox + k] < obs_frame[oy + k];
-        return false;
-    };
-    stage("normalise, frame order");
-    // (large scenes: chunks sorted by a few host threads, then merged pairwise -- both stable, so the order is the one a
-    // single stable_sort gives)
-    const int n_thr = N >= 32768 ? (int)std::min<unsigned>(8, std::max<unsigned>(1, std::thread::hardware_concurrency())) : 1;
-    if (n_thr > 1) {
-        std::vector<int64_t> cut((size_t)n_thr + 1);
-        for (int t = 0; t <= n_thr; ++t) cut[(size_t)t] = N * t / n_thr;
-        std::vector<std::thread> th;
-        for (int t = 0; t < n_thr; ++t)
-            th.emplace_back([&, t] { std::stable_sort(order.begin() + cut[(size_t)t], order.begin() + cut[(size_t)t + 1], list_less); });
-        for (auto& x : th) x.join();
-        for (int w = 1; w < n_thr; w *= 2) {
-            th.clear();
-            for (int t = 0; t + w < n_thr; t += 2 * w)
-                th.emplace_back([&, t, w] {
-                    std::inplace_merge(order.begin() + cut[(size_t)t], order.begin() + cut[(size_t)(t + w)],
-                                       order.begin() + cut[(size_t)std::min(t + 2 * w, n_thr)], list_less);
-                });
-            for (auto& x : th) x.join();
-        }
-    } else
-        std::stable_sort(order.begin(), order.end(), list_less);
-    stage("sort landmarks by frame list");
-    h->perm = order;
-    h->row_ptr_user.assign(row_ptr, row_ptr + N + 1);
-    std::vector<int64_t> rp((size_t)N + 1, 0);
-    std::vector<int32_t> of((size_t)O);
-    std::vector<double> ouv((size_t)(2 * O)), ppts((size_t)(3 * N));
-    for (int64_t i = 0; i < N; ++i) {
-        const int64_t u = order[(size_t)i];
-        rp[(size_t)i + 1] = rp[(size_t)i] + (row_ptr[u + 1] - row_ptr[u]);
-    }
-    auto permute_range = [&](int64_t i0, int64_t i1) {
-        for (int64_t i = i0; i < i1; ++i) {
-            const int64_t u = order[(size_t)i];
-            const int64_t cnt = row_ptr[u + 1] - row_ptr[u];
-            std::memcpy(&of[(size_t)rp[(size_t)i]], obs_frame + row_ptr[u], (size_t)(4 * cnt));
-            std::memcpy(&ouv[(size_t)(2 * rp[(size_t)i])], obs_uv + 2 * row_ptr[u], (size_t)(16 * cnt));
-            std::memcpy(&ppts[(size_t)(3 * i)], &pts[(size_t)(3 * u)], 24);
-        }
-    };
-    if (n_thr > 1) {
-        std::vector<std::thread> th;
-        for (int t = 0; t < n_thr; ++t) th.emplace_back(permute_range, N * t / n_thr, N * (t + 1) / n_thr);
-        for (auto& x : th) x.join();
-    } else
-        permute_range(0, N);
-    h->row_ptr_int = rp;
-    pts.swap(ppts);
-    row_ptr = rp.data();
-    obs_frame = of.data();
-    obs_uv = ouv.data();
-    stage("permute observations");
-    // Runs of consecutive landmarks (internal order) whose frame lists fit a common set of <= SRK_GRP_MAXNF_HOST
-    // frames -> grouped Schur kernel: the run's blocks are accumulated over that UNION of frames, a landmark that does
-    // not see one of them contributes zeros there.  Identical lists (the circle-grid scenes) are the special case
-    // union == list ("uniform" run: no slot table needed); ragged feature tracks, where hardly two landmarks see
-    // exactly the same frames, still share a window of frames.  Landmarks with more frames -> per-landmark kernel.
-    std::vector<int32_t> grp_first, grp_count, grp_nf, grp_frames, gen_list, long_cand;
-    std::vector<uint8_t> obs_slot((size_t)O, 0);
-    std::vector<uint32_t> pt_mask((size_t)N, 0);
-    int64_t n_wide = 0, n_mid = 0;
-    {
-        std::vector<int32_t> uni, merged;
-        for (int64_t i = 0; i < N;) {
-            const int64_t nfi = rp[(size_t)i + 1] - rp[(size_t)i];
-            if (nfi == 0) { ++i; continue; }
-            if (nfi > SRK_GRP_MAXNF_HOST) { long_cand.push_back((int32_t)i); ++i; continue; }
-            const int64_t cap = nfi > SRK_GRP_NF1_HOST ? SRK_GRP_MAXNF_HOST : SRK_GRP_NF1_HOST;
-            uni.assign(of.begin() + rp[(size_t)i], of.begin() + rp[(size_t)i + 1]);
-            int64_t j = i + 1;
-            while (j < N && j - i < SRK_GRP_MAXPTS_HOST) {
-                const int64_t nfj = rp[(size_t)j + 1] - rp[(size_t)j];
-                if (nfj == 0 || nfj > cap) break;
-                // (the common case first: the same frame list as the run so far -- nothing to merge)
-                if (nfj == (int64_t)uni.size() && std::equal(uni.begin(), uni.end(), of.begin() + rp[(size_t)j])) { ++j; continue; }
-                merged.clear();
-                std::set_union(uni.begin(), uni.end(), of.begin() + rp[(size_t)j], of.begin() + rp[(size_t)j + 1],
-                               std::back_inserter(merged));
-                if ((int64_t)merged.size() > cap) break;
-                // a wider frame set costs every landmark of the run more flops; it only pays while the run is still
-                // small against its one-off flush (~ the work of a dozen landmarks)
-                if (merged.size() > uni.size() && j - i >= 24) break;
-                uni.swap(merged);
-                ++j;
-            }
-            bool uniform = true;
-            for (int64_t p = i; p < j; ++p) {
-                uint32_t mask = 0;
-                if (rp[(size_t)p + 1] - rp[(size_t)p] == (int64_t)uni.size()) { // as many frames as the union: the union itself
-                    for (int64_t o = rp[(size_t)p], k = 0; o < rp[(size_t)p + 1]; ++o, ++k) obs_slot[(size_t)o] = (uint8_t)k;
-                    mask = (uint32_t)((1ull << uni.size()) - 1);
-                } else {
-                    for (int64_t o = rp[(size_t)p]; o < rp[(size_t)p + 1]; ++o) {
-                        int slot = (int)(std::lower_bound(uni.begin(), uni.end(), of[(size_t)o]) - uni.begin());
-                        obs_slot[(size_t)o] = (uint8_t)slot;
-                        mask |= 1u << slot;
-                    }
-                    uniform = false;
-                }
-                pt_mask[(size_t)p] = mask;
-            }
-            grp_first.push_back((int32_t)i);
-            grp_count.push_back((int32_t)(j - i));
-            grp_nf.push_back(uniform ? (int32_t)uni.size() : -(int32_t)uni.size()); // negative = ragged run
-            for (int k = 0; k < SRK_GRP_MAXNF_HOST; ++k) grp_frames.push_back(k < (int)uni.size() ? uni[(size_t)k] : -1);
-            if ((int64_t)uni.size() > SRK_GRP_NF1_HOST) ++n_wide;
-            else if ((int64_t)uni.size() > SRK_WS_NF_HOST) ++n_mid;
-            i = j;
-        }
-    }
-    // A small scene (the dino set: 36 frames, 4983 points; the point sets of the multi-view-factorisation calls) has a few
-    // dozen full-length runs: a few dozen workgroups on 256 CUs, each staging up to 128 landmarks four at a time -- the sum
-    // takes as long as one workgroup's 32 rounds (config 1: 114 us for 16 k observations).  Such runs are cut into `split`
-    // equal parts over the SAME frame set (slots and masks stay as they are; a cut that left a remainder to merge with the
-    // next frame list made ragged and wider runs: measured, worse).  What stops the cut: every part flushes the whole tile
-    // triangle of its frame set, and the parts of one round of workgroups flush together -- the fp64 atomics of a burst
-    // drain at ~0.5 TB/s (100 frames x 5000 points, 20-frame tracks: 74 / 72 / 78 / 96 / 155 us with 1 / 2 / 3 / 4 / 8
-    // parts; config 1, 4-frame tracks: 114 / 68 / 57 / 49 us with 1 / 2 / 3 / 4 parts, `tools/run_len_probe.py`) -- and a
-    // second round of workgroups.  The model below is that shape: a double round of eight landmarks ~5.5 us, 2 KB a tile.
-    {
-        int cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        auto cost = [&](int split, int64_t* n_parts) {
-            double worst = 0, tiles = 0;
-            int64_t parts = 0;
-            for (size_t r = 0; r < grp_first.size(); ++r) {
-                const int64_t nfu = std::abs(grp_nf[r]), nt = (10 * nfu + 15) / 16, len = (grp_count[r] + split - 1) / split;
-                const int64_t k = std::min<int64_t>(split, (grp_count[r] + len - 1) / len);
-                parts += k;
-                tiles += (double)(k * nt * (nt + 1) / 2);
-                worst = std::max(worst, 4.5 + 5.5 * (double)((len + 7) / 8));
-            }
-            if (n_parts) *n_parts = parts;
-            return worst * (double)((parts + cus - 1) / cus) + tiles * 2048.0 / 0.5e6; // us
-        };
-        int split = 1;
-        if (!grp_first.empty() && (int)grp_first.size() < cus) {
-            double best = cost(1, nullptr);
-            for (int sp = 2; sp <= 8; ++sp) {
-                const double c = cost(sp, nullptr);
-                if (c < 0.9 * best) best = c, split = sp;
-            }
-        }
-#ifdef SRK_DEV
-        if (const char* e = getenv("SRK_SCHUR_RUN_SPLIT")) split = std::max(1, std::min(16, atoi(e))); // development: fixed cut
-#endif
-        if (split > 1) {
-            std::vector<int32_t> f2, c2, n2, fr2;
-            for (size_t r = 0; r < grp_first.size(); ++r) {
-                const int64_t len = (grp_count[r] + split - 1) / split;
-                for (int64_t a = 0; a < grp_count[r]; a += len) {
-                    f2.push_back(grp_first[r] + (int32_t)a);
-                    c2.push_back((int32_t)std::min<int64_t>(len, grp_count[r] - a));
-                    n2.push_back(grp_nf[r]);
-                    fr2.insert(fr2.end(), grp_frames.begin() + (ptrdiff_t)(r * SRK_GRP_MAXNF_HOST), grp_frames.begin() + (ptrdiff_t)((r + 1) * SRK_GRP_MAXNF_HOST));
-                    if (a > 0) {
-                        if (std::abs(grp_nf[r]) > SRK_GRP_NF1_HOST) ++n_wide;
-                        else if (std::abs(grp_nf[r]) > SRK_WS_NF_HOST) ++n_mid;
-                    }
-                }
-            }
-            grp_first.swap(f2); grp_count.swap(c2); grp_nf.swap(n2); grp_frames.swap(fr2);
-        }
-    }
-    // Long tracks (> SRK_GRP_MAXNF_HOST frames; every track of the demos' all-visible scenes): runs of consecutive
-    // candidates over the union of their frame lists (<= SRK_LONG_MAXNF_HOST frames), cut into blocks of 8 frames; one
-    // work item per pair of blocks (k_schur_long).  A track over more frames than a run holds keeps the per-landmark kernel.
-    std::vector<int32_t> lg_item, lg_np, lg_nf, lg_pts, lg_frames, lg_obs;
-    std::vector<int64_t> lg_obs_off;
-#ifdef SRK_DEV
-    const bool no_long = getenv("SRK_SCHUR_NO_LONG") != nullptr; // development: everything through the per-landmark kernel
-#else
-    const bool no_long = false;
-#endif
-    if (no_long) {
-        gen_list.insert(gen_list.end(), long_cand.begin(), long_cand.end());
-        long_cand.clear();
-    }
-    {
-        std::vector<int32_t> uni, merged;
-        for (size_t ci = 0; ci < long_cand.size();) {
-            const int64_t i = long_cand[ci];
-            const int64_t nfi = rp[(size_t)i + 1] - rp[(size_t)i];
-            if (nfi > SRK_LONG_MAXNF_HOST) { gen_list.push_back((int32_t)i); ++ci; continue; }
-            uni.assign(of.begin() + rp[(size_t)i], of.begin() + rp[(size_t)i + 1]);
-            size_t cj = ci + 1;
-            while (cj < long_cand.size() && cj - ci < SRK_LONG_PTS_HOST) {
-                const int64_t j = long_cand[cj];
-                if (rp[(size_t)j + 1] - rp[(size_t)j] > SRK_LONG_MAXNF_HOST) break;
-                merged.clear();
-                std::set_union(uni.begin(), uni.end(), of.begin() + rp[(size_t)j], of.begin() + rp[(size_t)j + 1],
-                               std::back_inserter(merged));
-                if ((int64_t)merged.size() > SRK_LONG_MAXNF_HOST) break;
-                // every landmark of the run pays for the whole union: let it grow freely only while the run is small
-                if (merged.size() > uni.size() && cj - ci >= 16 && (int64_t)merged.size() > nfi + nfi / 4 + SRK_LONG_FB_HOST) break;
-                uni.swap(merged);
-                ++cj;
-            }
-            const int nfu = (int)uni.size();
-            lg_np.push_back((int32_t)(cj - ci));
-            lg_nf.push_back((int32_t)nfu);
-            for (int k = 0; k < SRK_LONG_PTS_HOST; ++k) lg_pts.push_back(ci + k < cj ? long_cand[ci + (size_t)k] : 0);
-            for (int k = 0; k < SRK_LONG_MAXNF_HOST; ++k) lg_frames.push_back(k < nfu ? uni[(size_t)k] : -1);
-            ci = cj;
-        }
-    }
-    // Frame blocks of 8 or of 16 frames (round 4).  A workgroup stages both blocks of its pair for every landmark of the run:
-    // with 8-frame blocks that is two staged blocks for 25 MFMA tiles and the kernel spent its time staging (SQ counters on
-    // 200 frames x 20 000 points, every point in every frame: 7 vector-ALU, 0.85 memory and 0.9 LDS instructions per MFMA,
-    // matrix pipes 33 % busy); a pair of 16-frame blocks is two staged blocks for 100 tiles.  The larger blocks need enough
-    // pairs to fill the chip: small scenes (the 36- and 60-frame demo scenes) keep the 8-frame blocks.
-    {
-        int64_t items16 = 0, nf_sum = 0;
-        for (size_t r = 0; r < lg_np.size(); ++r) {
-            const int64_t nb16 = (lg_nf[r] + 15) / 16;
-            items16 += nb16 * (nb16 + 1) / 2;
-            nf_sum += lg_nf[r];
-        }
-        // (and frame sets long enough that the padding to 16 and the coarser diagonal pairs do not eat the gain.  Counting a
-        // staged block-frame as ~3 MFMA tiles -- what the counters above say -- 40 frames cost the same either way, 64 frames
-        // 30 % less with the larger blocks)
-        h->long_fb = (items16 >= 1024 && nf_sum >= 56 * (int64_t)lg_np.size()) ? 16 : SRK_LONG_FB_HOST;
-        const int FBh = h->long_fb;
-        for (size_t r = 0; r < lg_np.size(); ++r) {
-            const int32_t run = (int32_t)r;
-            const int nfu = lg_nf[r], nb = (nfu + FBh - 1) / FBh, nfp = nb * FBh;
-            const int32_t* uni_b = lg_frames.data() + r * SRK_LONG_MAXNF_HOST;
-            lg_obs_off.push_back((int64_t)lg_obs.size());
-            for (int k = 0; k < lg_np[r]; ++k) {
-                const int64_t p = lg_pts[r * SRK_LONG_PTS_HOST + (size_t)k];
-                const size_t base = lg_obs.size();
-                lg_obs.resize(base + (size_t)nfp, -1);
-                for (int64_t o = rp[(size_t)p]; o < rp[(size_t)p + 1]; ++o) {
-                    const int slot = (int)(std::lower_bound(uni_b, uni_b + nfu, of[(size_t)o]) - uni_b);
-                    lg_obs[base + (size_t)slot] = (int32_t)o;
-                }
-            }
-            for (int a = 0; a < nb; ++a)
-                for (int b = 0; b <= a; ++b) {
-                    lg_item.push_back(run); lg_item.push_back(a); lg_item.push_back(b); lg_item.push_back(0);
-                }
-        }
-    }
-    h->n_long_runs = (int64_t)lg_np.size();
-    h->n_long_items = (int64_t)lg_item.size() / 4;
-    h->n_groups = (int64_t)grp_first.size();
-    h->n_groups_wide = n_wide;
-    h->n_groups_mid = n_mid;
-    h->n_mm_uniform = h->n_mm_ragged = 0;
-    for (int32_t v : grp_nf) {
-        if (v > 0 && v <= SRK_WS_NF_HOST) ++h->n_mm_uniform;
-        if (v < 0 && -v <= SRK_WS_NF_HOST) ++h->n_mm_ragged;
-    }
-    h->n_generic = (int64_t)gen_list.size();
     SrkDims d{};
     d.N = N;
     d.M = M;
@@ -1578,8 +1102,8 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     d.fv = h->fixed_k ? 6 : 10;
     d.ld = ((d.fv * (int64_t)M + SRK_CHOL_NB - 1) / SRK_CHOL_NB) * SRK_CHOL_NB;
     d.comp = 1;
-    d.g0 = g0;
-    d.g1 = g1;
+    d.g0 = plan.g0;
+    d.g1 = plan.g1;
     // constant blocks without the reference's gauge: no frame index matches, so srk_is_fixed_var is false for every variable
     // and the masking passes are the only source of identity rows besides the padding
     if (h->cst_set && !h->cst_keep_gauge) d.g0 = d.g1 = -1;
@@ -1587,448 +1111,84 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     h->d = d;
     h->f0 = f0;
 
-    stage("Schur runs");
-    // observation side tables: obs -> point, and the frame-major copy (ordered by frame, then landmark)
-    std::vector<int32_t> obs_pt((size_t)O);
-    std::vector<int64_t> col_ptr((size_t)M + 1, 0);
-    for (int64_t i = 0; i < N; ++i)
-        for (int64_t o = row_ptr[i]; o < row_ptr[i + 1]; ++o) {
-            obs_pt[(size_t)o] = (int32_t)i;
-            col_ptr[(size_t)obs_frame[o] + 1]++;
-        }
-    h->max_frame_obs = 0;
-    for (int32_t j = 0; j < M; ++j) {
-        if (col_ptr[(size_t)j + 1] > h->max_frame_obs) h->max_frame_obs = col_ptr[(size_t)j + 1];
-        col_ptr[(size_t)j + 1] += col_ptr[(size_t)j];
-    }
-
-    // frame range of every SRK_JF_OBS_HOST-observation workgroup of the fused Jacobian kernel
-    std::vector<int32_t> wg_jmin;
-    h->jac_fused = true;
-    for (int64_t o0 = 0; o0 < O; o0 += SRK_JF_OBS_HOST) {
-        int32_t lo = obs_frame[o0], hi = obs_frame[o0];
-        for (int64_t o = o0; o < std::min<int64_t>(O, o0 + SRK_JF_OBS_HOST); ++o) {
-            lo = std::min(lo, obs_frame[o]);
-            hi = std::max(hi, obs_frame[o]);
-        }
-        if (hi - lo >= SRK_JF_SLOTS_HOST) h->jac_fused = false;
-        int64_t olast = std::min<int64_t>(O, o0 + SRK_JF_OBS_HOST) - 1;
-        if (obs_pt[(size_t)olast] - obs_pt[(size_t)o0] + 1 > SRK_JF_PMAX_HOST) h->jac_fused = false;
-        wg_jmin.push_back(lo);
-    }
-
-    stage("side tables, frame windows");
-    // tasks of the run-based Jacobian kernel: maximal runs of consecutive landmarks (internal order) with identical
-    // frame lists, cut into pieces (a multiple of the landmarks per step).  The kernel holds two 4-wave workgroups per
-    // CU (a wave keeps 61 frame sums and a step of look-ahead in ~250 registers); with about one task per wave slot
-    // every task runs at the same time and the stores of all of them share HBM from start to end (with 1.4 rounds of
-    // shorter tasks the second round ran at 2 TB/s).
-    std::vector<int32_t> jr_first, jr_count, jr_jmin;
-    // (the kernel addresses W with 32-bit byte offsets inside a plane and inside each half of the 30 planes)
-    h->jac_runs = h->jac_mode != 0 && O < (int64_t)1 << 27;
-    h->jr_min_nf = 64;
-    int64_t jr_piece_target = SRK_JR_TASK_PTS_MIN_HOST;
-    {
-        int cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        int64_t with_obs = 0;
-        for (int64_t i = 0; i < N; ++i) with_obs += rp[(size_t)i + 1] > rp[(size_t)i];
-        const int64_t slots = 8 * (int64_t)cus; // waves resident at once
-        jr_piece_target = std::min<int64_t>(SRK_JR_TASK_PTS_MAX_HOST, std::max<int64_t>(SRK_JR_TASK_PTS_MIN_HOST, (with_obs + slots - 1) / slots));
-    }
-    for (int64_t i = 0; i < N && h->jac_runs;) {
-        const int64_t nf = rp[(size_t)i + 1] - rp[(size_t)i];
-        if (nf == 0) { ++i; continue; }
-        if (nf > 64) { h->jac_runs = false; break; }
-        h->jr_min_nf = std::min<int32_t>(h->jr_min_nf, (int32_t)nf);
-        int64_t j = i + 1;
-        while (j < N && rp[(size_t)j + 1] - rp[(size_t)j] == nf &&
-               std::equal(of.begin() + rp[(size_t)i], of.begin() + rp[(size_t)i + 1], of.begin() + rp[(size_t)j])) ++j;
-        const int64_t g = 64 / nf, len = j - i;
-        const int64_t most = SRK_JR_TASK_PTS_MAX_HOST / g * g; // the kernel stages a task's landmarks in LDS
-        const int64_t pieces = std::max<int64_t>((len + most - 1) / most, (len + jr_piece_target / 2) / jr_piece_target);
-        const int64_t piece = std::max<int64_t>(g, ((len + pieces - 1) / pieces + g - 1) / g * g);
-        for (int64_t a = i; a < j; a += piece) {
-            jr_first.push_back((int32_t)a);
-            jr_count.push_back((int32_t)std::min<int64_t>(piece, j - a));
-        }
-        i = j;
-    }
-    if (h->jac_runs) {
-        // long enough to pay: a task flushes 65 sums per lane, which an iteration of the per-observation kernel costs.
-        // (Round 3, tools/jac_modes.py: at 240 observations a task -- C2 -- the run kernel takes 45 us where the fused
-        // per-observation kernel takes 64; tasks of one or two ragged landmarks, ~20 observations, 118 against 69.)
-        if (jr_first.empty() || (h->jac_mode != 1 && O / (int64_t)jr_first.size() < 128)) h->jac_runs = false;
-        for (size_t t0 = 0; t0 < jr_first.size() && h->jac_runs; t0 += 4) {
-            int32_t lo = M, hi = -1;
-            for (size_t t = t0; t < std::min(jr_first.size(), t0 + 4); ++t) {
-                const int64_t a = rp[(size_t)jr_first[t]], b = rp[(size_t)jr_first[t] + 1];
-                lo = std::min(lo, of[(size_t)a]);
-                hi = std::max(hi, of[(size_t)b - 1]);
-            }
-            if (hi - lo >= SRK_JF_SLOTS_HOST) h->jac_runs = false;
-            jr_jmin.push_back(lo);
-        }
-    }
-    // Ragged tracks: hardly two landmarks see exactly the same frames, so the runs above are too short to pay -- but the
-    // Schur kernel's runs (consecutive landmarks over the UNION of their frame lists, <= 24 frames, masks) are not.  The same
-    // kernel with a lane per (landmark, frame slot) CELL: tasks = pieces of those runs.  Needs every landmark in a run.
-    std::vector<int32_t> jr_group;
-    h->jac_runs_masked = false;
-    // The runs the union tasks are pieces of: the Schur kernels' (every landmark is in one when no track is longer than
-    // SRK_GRP_MAXNF_HOST frames), else runs of the derivative kernel's own over unions of <= 32 frames (a lane's observation is
-    // found from a 32-bit mask), when no track is longer than that.
-    std::vector<int32_t> jd_first, jd_count, jd_nf, jd_frames;
-    std::vector<uint32_t> jd_mask;
-    h->jr_own_runs = false;
-    constexpr int JD_MAXNF = 32;
-    if ((!h->jac_runs || h->jac_mode == 2) && h->jac_mode != 0 && O < (int64_t)1 << 27 && !long_cand.empty() && gen_list.empty()) {
-        bool fits = true;
-        for (int32_t p : long_cand) fits = fits && rp[(size_t)p + 1] - rp[(size_t)p] <= JD_MAXNF;
-        if (fits) {
-            jd_mask.assign((size_t)N, 0);
-            std::vector<int32_t> uni, merged;
-            for (int64_t i = 0; i < N;) {
-                const int64_t nfi = rp[(size_t)i + 1] - rp[(size_t)i];
-                if (nfi == 0) { ++i; continue; }
-                uni.assign(of.begin() + rp[(size_t)i], of.begin() + rp[(size_t)i + 1]);
-                int64_t j = i + 1;
-                while (j < N && j - i < SRK_GRP_MAXPTS_HOST) {
-                    const int64_t nfj = rp[(size_t)j + 1] - rp[(size_t)j];
-                    if (nfj == 0) break;
-                    if (nfj == (int64_t)uni.size() && std::equal(uni.begin(), uni.end(), of.begin() + rp[(size_t)j])) { ++j; continue; }
-                    merged.clear();
-                    std::set_union(uni.begin(), uni.end(), of.begin() + rp[(size_t)j], of.begin() + rp[(size_t)j + 1], std::back_inserter(merged));
-                    if ((int64_t)merged.size() > JD_MAXNF) break;
-                    if (merged.size() > uni.size() && j - i >= 24) break; // (a wider set costs every landmark of the run lanes)
-                    uni.swap(merged);
-                    ++j;
-                }
-                bool uniform = true;
-                for (int64_t p = i; p < j; ++p) {
-                    uint32_t mask = 0;
-                    for (int64_t o = rp[(size_t)p]; o < rp[(size_t)p + 1]; ++o)
-                        mask |= 1u << (int)(std::lower_bound(uni.begin(), uni.end(), of[(size_t)o]) - uni.begin());
-                    uniform = uniform && rp[(size_t)p + 1] - rp[(size_t)p] == (int64_t)uni.size();
-                    jd_mask[(size_t)p] = mask;
-                }
-                jd_first.push_back((int32_t)i);
-                jd_count.push_back((int32_t)(j - i));
-                jd_nf.push_back(uniform ? (int32_t)uni.size() : -(int32_t)uni.size());
-                for (int k = 0; k < JD_MAXNF; ++k) jd_frames.push_back(k < (int)uni.size() ? uni[(size_t)k] : -1);
-                i = j;
-            }
-            h->jr_own_runs = true;
-        }
-    }
-    const std::vector<int32_t>& rn_first = h->jr_own_runs ? jd_first : grp_first;
-    const std::vector<int32_t>& rn_count = h->jr_own_runs ? jd_count : grp_count;
-    const std::vector<int32_t>& rn_nf = h->jr_own_runs ? jd_nf : grp_nf;
-    const std::vector<int32_t>& rn_frames = h->jr_own_runs ? jd_frames : grp_frames;
-    const size_t rn_stride = h->jr_own_runs ? (size_t)JD_MAXNF : (size_t)SRK_GRP_MAXNF_HOST;
-    if ((!h->jac_runs || h->jac_mode == 2) && h->jac_mode != 0 && O < (int64_t)1 << 27 && (h->jr_own_runs || long_cand.empty()) && gen_list.empty() && !rn_first.empty()) {
-        const bool uniform_ok = h->jac_runs; // (mode 2: the union tasks are preferred, the uniform ones stay as the fallback)
-        std::vector<int32_t> u_first, u_count, u_jmin;
-        u_first.swap(jr_first); u_count.swap(jr_count); u_jmin.swap(jr_jmin);
-        jr_first.clear();
-        jr_count.clear();
-        jr_jmin.clear();
-        for (size_t gi = 0; gi < rn_first.size(); ++gi) {
-            const int64_t nfu = std::abs(rn_nf[gi]), g = 64 / nfu, len = rn_count[gi];
-            const int64_t most = SRK_JR_TASK_PTS_MAX_HOST / g * g;
-            const int64_t pieces = std::max<int64_t>((len + most - 1) / most, (len + jr_piece_target / 2) / jr_piece_target);
-            const int64_t piece = std::max<int64_t>(g, ((len + pieces - 1) / pieces + g - 1) / g * g);
-            for (int64_t a = 0; a < len; a += piece) {
-                jr_first.push_back(rn_first[gi] + (int32_t)a);
-                jr_count.push_back((int32_t)std::min<int64_t>(piece, len - a));
-                jr_group.push_back((int32_t)gi);
-            }
-        }
-        bool ok = h->jac_mode >= 1 || O / (int64_t)jr_first.size() >= 32; // (the dino stand-in: 40 a task, 31 against 60 us)
-        for (size_t t0 = 0; t0 < jr_first.size() && ok; t0 += 4) {
-            int32_t lo = M, hi = -1;
-            for (size_t t = t0; t < std::min(jr_first.size(), t0 + 4); ++t) {
-                const size_t gi = (size_t)jr_group[t];
-                lo = std::min(lo, rn_frames[gi * rn_stride]);
-                hi = std::max(hi, rn_frames[gi * rn_stride + (size_t)std::abs(rn_nf[gi]) - 1]);
-            }
-            if (hi - lo >= SRK_JF_SLOTS_HOST) ok = false;
-            jr_jmin.push_back(lo);
-        }
-        h->jac_runs_masked = ok;
-        if (!ok) { // back to the uniform tasks (if they were usable)
-            jr_first.swap(u_first); jr_count.swap(u_count); jr_jmin.swap(u_jmin);
-            jr_group.clear();
-            h->jac_runs = uniform_ok;
-            h->jr_own_runs = false;
-        } else
-            h->jac_runs = true;
-    }
-    h->jr_tasks = h->jac_runs ? (int32_t)jr_first.size() : 0;
-
-    // ---- deterministic mode: tables of the ordered second passes.  Covered: scenes whose landmarks all take the run-based
-    // derivative kernel and the MFMA Schur kernel (tracks over at most SRK_WS_NF_HOST frames, fp64 run sums).
-    std::vector<int32_t> dj_ptr, dj_ent, ds_pair_ptr, ds_pair_fa, ds_pair_fb, ds_pair_ent, ds_f_ptr, ds_f_ent;
-    h->det_active = false;
-    if (h->deterministic && h->jac_runs && n_wide == 0 && n_mid == 0 && lg_item.empty() && gen_list.empty() && !h->schur_fp32 &&
-        !grp_first.empty() && grp_first.size() < ((size_t)1 << 20) && jr_first.size() < ((size_t)1 << 25)) {
-        bool all_mm = true;
-        for (int32_t v : grp_nf) all_mm = all_mm && std::abs(v) <= SRK_WS_NF_HOST;
-        if (all_mm) {
-            // derivative tasks by frame
-            dj_ptr.assign((size_t)M + 1, 0);
-            auto task_frames = [&](size_t t, const int32_t*& fr) -> int {
-                if (!jr_group.empty()) {
-                    const size_t gi = (size_t)jr_group[t];
-                    fr = grp_frames.data() + gi * SRK_GRP_MAXNF_HOST;
-                    return std::abs(grp_nf[gi]);
-                }
-                fr = of.data() + rp[(size_t)jr_first[t]];
-                return (int)(rp[(size_t)jr_first[t] + 1] - rp[(size_t)jr_first[t]]);
-            };
-            for (size_t t = 0; t < jr_first.size(); ++t) {
-                const int32_t* fr;
-                const int nf = task_frames(t, fr);
-                for (int f = 0; f < nf; ++f) ++dj_ptr[(size_t)fr[f] + 1];
-            }
-            for (int32_t j = 0; j < M; ++j) dj_ptr[(size_t)j + 1] += dj_ptr[(size_t)j];
-            dj_ent.resize((size_t)dj_ptr[(size_t)M]);
-            {
-                std::vector<int32_t> fill(dj_ptr.begin(), dj_ptr.end() - 1);
-                for (size_t t = 0; t < jr_first.size(); ++t) {
-                    const int32_t* fr;
-                    const int nf = task_frames(t, fr);
-                    for (int f = 0; f < nf; ++f) dj_ent[(size_t)fill[(size_t)fr[f]]++] = (int32_t)(t * 64 + (size_t)f);
-                }
-            }
-            // Schur runs by block (fa >= fb) and by frame
-            std::vector<std::pair<int64_t, int32_t>> ents;
-            ds_f_ptr.assign((size_t)M + 1, 0);
-            for (size_t gi = 0; gi < grp_first.size(); ++gi) {
-                const int nf = std::abs(grp_nf[gi]);
-                const int32_t* fr = grp_frames.data() + gi * SRK_GRP_MAXNF_HOST;
-                for (int sa = 0; sa < nf; ++sa) {
-                    ++ds_f_ptr[(size_t)fr[sa] + 1];
-                    for (int sb = 0; sb <= sa; ++sb)
-                        ents.emplace_back((int64_t)fr[sa] * M + fr[sb], (int32_t)((uint32_t)gi | (uint32_t)sa << 20 | (uint32_t)sb << 25));
-                }
-            }
-            std::stable_sort(ents.begin(), ents.end(), [](const std::pair<int64_t, int32_t>& x, const std::pair<int64_t, int32_t>& y) { return x.first < y.first; });
-            ds_pair_ent.reserve(ents.size());
-            for (size_t e = 0; e < ents.size(); ++e) {
-                if (e == 0 || ents[e].first != ents[e - 1].first) {
-                    ds_pair_ptr.push_back((int32_t)e);
-                    ds_pair_fa.push_back((int32_t)(ents[e].first / M));
-                    ds_pair_fb.push_back((int32_t)(ents[e].first % M));
-                }
-                ds_pair_ent.push_back(ents[e].second);
-            }
-            ds_pair_ptr.push_back((int32_t)ents.size());
-            for (int32_t j = 0; j < M; ++j) ds_f_ptr[(size_t)j + 1] += ds_f_ptr[(size_t)j];
-            ds_f_ent.resize((size_t)ds_f_ptr[(size_t)M]);
-            {
-                std::vector<int32_t> fill(ds_f_ptr.begin(), ds_f_ptr.end() - 1);
-                for (size_t gi = 0; gi < grp_first.size(); ++gi) {
-                    const int nf = std::abs(grp_nf[gi]);
-                    const int32_t* fr = grp_frames.data() + gi * SRK_GRP_MAXNF_HOST;
-                    for (int sa = 0; sa < nf; ++sa) ds_f_ent[(size_t)fill[(size_t)fr[sa]]++] = (int32_t)((uint32_t)gi | (uint32_t)sa << 20);
-                }
-            }
-            h->ds_n_pairs = (int32_t)ds_pair_fa.size();
-            h->det_active = true;
-        }
-    }
-    stage("deterministic-mode tables");
-
-    // the frame-major copy of the observations (ordered by frame, then landmark): only the two-kernel derivative path reads it
-    const bool need_frame_major = !h->jac_runs && !h->jac_fused;
-    std::vector<int32_t> fobs_pt(need_frame_major ? (size_t)O : 0);
-    std::vector<double> fobs_uv(need_frame_major ? (size_t)(2 * O) : 0);
-    h->fobs_of.assign(need_frame_major ? (size_t)O : 0, 0);
-    if (need_frame_major) {
-        std::vector<int64_t> fill(col_ptr.begin(), col_ptr.end() - 1);
-        for (int64_t o = 0; o < O; ++o) {
-            int64_t k = fill[(size_t)obs_frame[o]]++;
-            h->fobs_of[(size_t)o] = k;
-            fobs_pt[(size_t)k] = obs_pt[(size_t)o];
-            fobs_uv[(size_t)(2 * k)] = obs_uv[2 * o];
-            fobs_uv[(size_t)(2 * k + 1)] = obs_uv[2 * o + 1];
-        }
-    }
-    stage("derivative tasks");
-#define ALLOC(buf, bytes)                              \
-    do {                                               \
-        int _r = dev_alloc(h, (buf), (size_t)(bytes)); \
-        if (_r != SRK_OK) return _r;                   \
-    } while (0)
+    // ---- the device buffers of the scene, each named once: allocated in this order, then filled from its host source (if any)
+    struct Up { DevBuf& buf; const void* src; size_t bytes; }; // src NULL: nothing to copy
+    std::vector<Up> up;
+    auto add = [&](DevBuf& b, const void* src, int64_t bytes) { up.push_back({ b, src, (size_t)bytes }); };
+    auto tab = [&](DevBuf& b, const auto& v, size_t at_least = 0) { add(b, v.empty() ? nullptr : v.data(), (int64_t)(sizeof(v[0]) * std::max(v.size(), at_least))); };
     // several ranks, damping-parallel schedule: one slot per damping factor of a round (at most three)
-    const bool multi_upload = h->allreduce || h->comm;
     // (srk_ba_set_speculation(h, 0) = strictly one attempt at a time, with several ranks as well: one slot, hence the
     // all-reduce schedule without pairs)
-    const int n_slots = (multi_upload && h->dp_schedule && h->speculate && (h->world >= 2 || h->dp_force))
+    const int n_slots = (opt.multi_rank && h->dp_schedule && h->speculate && (h->world >= 2 || h->dp_force))
                             ? (h->dp_force ? SRK_SLOTS : std::min(SRK_SLOTS, h->world))
                             : (h->speculate ? 2 : 1);
-    for (int w = 0; w < SRK_SLOTS + 1; ++w) {
-        if (w > n_slots) continue;
-        ALLOC(h->pts[w], 24 * N);
-        ALLOC(h->camR[w], 72 * (int64_t)M);
-        ALLOC(h->camT[w], 24 * (int64_t)M);
-        ALLOC(h->cam[w], 8 * SRK_CAM_PACK * (int64_t)M);
-        if (h->shk_G > 0) ALLOC(h->Ks[w], 72 * (int64_t)M);
+    for (int w = 0; w <= n_slots; ++w) { // the current scene (from the plan) and one trial scene per attempt slot
+        add(h->pts[w], w ? nullptr : plan.pts.data(), 24 * N);
+        add(h->camR[w], w ? nullptr : plan.camR.data(), 72 * (int64_t)M);
+        add(h->camT[w], w ? nullptr : plan.camT.data(), 24 * (int64_t)M);
+        add(h->cam[w], nullptr, 8 * SRK_CAM_PACK * (int64_t)M);
+        if (h->shk_G > 0) add(h->Ks[w], w ? nullptr : plan.K.data(), 72 * (int64_t)M);
     }
-    ALLOC(h->pts0, 24 * N);
-    ALLOC(h->camR0, 72 * (int64_t)M);
-    ALLOC(h->camT0, 24 * (int64_t)M);
-    ALLOC(h->K, 72 * (int64_t)M);
-    ALLOC(h->row_ptr, 8 * (N + 1));
-    ALLOC(h->obs_frame, 4 * O);
-    ALLOC(h->obs_pt, 4 * O);
-    ALLOC(h->obs_uv, 16 * O);
-    ALLOC(h->col_ptr, 8 * ((int64_t)M + 1));
-    ALLOC(h->fobs_pt, 4 * fobs_pt.size());
-    ALLOC(h->fobs_uv, 8 * fobs_uv.size());
-    ALLOC(h->W, (d.w_f32 ? 4 : 8) * SRK_WF_PLANES * d.Os); // the 21 rank-2 factors of every point-frame block, fp64 or (opt-in) float
-    ALLOC(h->Vg, 8 * 9 * d.Ns);
-    ALLOC(h->Ug, 8 * SRK_UGS(d.fv) * (int64_t)M); // the frame sums: 65 a frame, 27 with fixed intrinsics
+    tab(h->pts0, plan.pts); tab(h->camR0, plan.camR); tab(h->camT0, plan.camT); tab(h->K, plan.K);
+    tab(h->row_ptr, plan.row_ptr_int); tab(h->obs_frame, plan.obs_frame); tab(h->obs_pt, plan.obs_pt); tab(h->obs_uv, plan.obs_uv);
+    tab(h->col_ptr, plan.col_ptr); tab(h->fobs_pt, plan.fobs_pt); tab(h->fobs_uv, plan.fobs_uv);
+    add(h->W, nullptr, (d.w_f32 ? 4 : 8) * SRK_WF_PLANES * d.Os); // the 21 rank-2 factors of every point-frame block, fp64 or (opt-in) float
+    add(h->Vg, nullptr, 8 * 9 * d.Ns);
+    add(h->Ug, nullptr, 8 * SRK_UGS(d.fv) * (int64_t)M); // the frame sums: 65 a frame, 27 with fixed intrinsics
+    bool new_flags[SRK_SLOTS] = {};
     for (int sl = 0; sl < SRK_SLOTS; ++sl) {
         srk_ba::Attempt& a = h->att[sl];
         a.allocated = sl < n_slots;
         if (!a.allocated) continue;
-        if (h->det_active) {
-            ALLOC(a.det_stage, 8 * (int64_t)SRK_DET_STRIDE * (int64_t)grp_first.size());
-            ALLOC(a.det_rhs, 8 * (int64_t)SRK_DET_LD * (int64_t)grp_first.size());
+        if (plan.det_active) {
+            add(a.det_stage, nullptr, 8 * (int64_t)SRK_DET_STRIDE * plan.n_groups);
+            add(a.det_rhs, nullptr, 8 * (int64_t)SRK_DET_LD * plan.n_groups);
         }
-        ALLOC(a.S, 8 * d.ld * d.ld);
-        ALLOC(a.rhs, 8 * d.ld);
-        ALLOC(a.wy, 8 * 2 * d.ld);
-        ALLOC(a.dc, 8 * d.ld);
-        ALLOC(a.acc, 8 * 3 * d.Ns + 64);
-        ALLOC(a.dx, 24 * N);
-        ALLOC(a.err_partial, 8 * std::max<int64_t>(1024, srk_error_partials_staged(d)));
-        ALLOC(a.info, 64);
-        ALLOC(a.dinv, 8 * 64 * d.ld);
-        ALLOC(a.irr, 4 * (N + 2));
-        HIPCHK(h, hipMemsetAsync(a.irr.p, 0, 4, h->main_stream));
-        if (!a.sync_flags.p) { // flag words of the fused outer-step kernel: zeroed ONCE (they hold launch epochs)
-            ALLOC(a.sync_flags, 4 * SRK_SYNC_WORDS);
-            HIPCHK(h, hipMemset(a.sync_flags.p, 0, 4 * SRK_SYNC_WORDS));
-        }
-        a.sync.flags = P<unsigned>(a.sync_flags);
-        a.sync.fused = h->chol_fused;
+        add(a.S, nullptr, 8 * d.ld * d.ld);
+        add(a.rhs, nullptr, 8 * d.ld);
+        add(a.wy, nullptr, 8 * 2 * d.ld);
+        add(a.dc, nullptr, 8 * d.ld);
+        add(a.acc, nullptr, 8 * 3 * d.Ns + 64);
+        add(a.dx, nullptr, 24 * N);
+        add(a.err_partial, nullptr, 8 * std::max<int64_t>(1024, srk_error_partials_staged(d)));
+        add(a.info, nullptr, 64);
+        add(a.dinv, nullptr, 8 * 64 * d.ld);
+        add(a.irr, nullptr, 4 * (N + 2));
+        new_flags[sl] = !a.sync_flags.p; // flag words of the fused outer-step kernel: zeroed ONCE (they hold launch epochs)
+        if (new_flags[sl]) add(a.sync_flags, nullptr, 4 * SRK_SYNC_WORDS);
     }
-    // fixed intrinsics: k_schur_mm sums the runs of at most SRK_WS_NF_HOST frames on 6-wide blocks; every other landmark (wider
-    // runs, long tracks, the generic list) takes the per-landmark kernel
-    std::vector<int32_t> cal_list;
-    if (d.fv == 6) {
-        std::vector<char> in_mm((size_t)N, 0);
-        for (size_t r = 0; r < grp_first.size(); ++r)
-            if (std::abs(grp_nf[r]) <= SRK_WS_NF_HOST)
-                for (int32_t k = 0; k < grp_count[r]; ++k) in_mm[(size_t)(grp_first[r] + k)] = 1;
-        for (int64_t i = 0; i < N; ++i)
-            if (!in_mm[(size_t)i] && rp[(size_t)i + 1] > rp[(size_t)i]) cal_list.push_back((int32_t)i);
+    tab(h->cal_list, plan.cal_list);
+    tab(h->grp_first, plan.grp_first); tab(h->grp_count, plan.grp_count); tab(h->grp_nf, plan.grp_nf); tab(h->grp_frames, plan.grp_frames);
+    tab(h->obs_slot, plan.obs_slot); tab(h->pt_mask, plan.pt_mask); tab(h->gen_list, plan.gen_list);
+    tab(h->lg_item, plan.lg_item); tab(h->lg_np, plan.lg_np); tab(h->lg_nf, plan.lg_nf); tab(h->lg_pts, plan.lg_pts);
+    tab(h->lg_frames, plan.lg_frames); tab(h->lg_obs_off, plan.lg_obs_off); tab(h->lg_obs, plan.lg_obs);
+    tab(h->wg_jmin, plan.wg_jmin);
+    if (plan.jac_runs) {
+        tab(h->jr_first, plan.jr_first); tab(h->jr_count, plan.jr_count); tab(h->jr_jmin, plan.jr_jmin);
+        if (plan.jac_runs_masked) tab(h->jr_group, plan.jr_group);
     }
-    h->n_cal_list = (int64_t)cal_list.size();
-    ALLOC(h->cal_list, 4 * cal_list.size());
-    ALLOC(h->grp_first, 4 * grp_first.size());
-    ALLOC(h->grp_count, 4 * grp_count.size());
-    ALLOC(h->grp_nf, 4 * grp_nf.size());
-    ALLOC(h->grp_frames, 4 * grp_frames.size());
-    ALLOC(h->obs_slot, obs_slot.size());
-    ALLOC(h->pt_mask, 4 * pt_mask.size());
-    ALLOC(h->gen_list, 4 * gen_list.size());
-    ALLOC(h->lg_item, 4 * lg_item.size());
-    ALLOC(h->lg_np, 4 * lg_np.size());
-    ALLOC(h->lg_nf, 4 * lg_nf.size());
-    ALLOC(h->lg_pts, 4 * lg_pts.size());
-    ALLOC(h->lg_frames, 4 * lg_frames.size());
-    ALLOC(h->lg_obs_off, 8 * lg_obs_off.size());
-    ALLOC(h->lg_obs, 4 * lg_obs.size());
-    ALLOC(h->wg_jmin, 4 * wg_jmin.size());
-    if (h->jac_runs) {
-        ALLOC(h->jr_first, 4 * jr_first.size());
-        ALLOC(h->jr_count, 4 * jr_count.size());
-        ALLOC(h->jr_jmin, 4 * jr_jmin.size());
-        if (h->jac_runs_masked) ALLOC(h->jr_group, 4 * jr_group.size());
+    if (plan.det_active) {
+        tab(h->dj_ptr, plan.dj_ptr); tab(h->dj_ent, plan.dj_ent, 1);
+        add(h->dj_stage, nullptr, 8 * (int64_t)SRK_UG * 64 * (int64_t)plan.jr_first.size());
+        tab(h->ds_pair_ptr, plan.ds_pair_ptr); tab(h->ds_pair_fa, plan.ds_pair_fa, 1); tab(h->ds_pair_fb, plan.ds_pair_fb, 1); tab(h->ds_pair_ent, plan.ds_pair_ent, 1);
+        tab(h->ds_f_ptr, plan.ds_f_ptr); tab(h->ds_f_ent, plan.ds_f_ent, 1);
     }
-    if (h->det_active) {
-        ALLOC(h->dj_ptr, 4 * dj_ptr.size());
-        ALLOC(h->dj_ent, 4 * std::max<size_t>(dj_ent.size(), 1));
-        ALLOC(h->dj_stage, 8 * (int64_t)SRK_UG * 64 * (int64_t)jr_first.size());
-        ALLOC(h->ds_pair_ptr, 4 * ds_pair_ptr.size());
-        ALLOC(h->ds_pair_fa, 4 * std::max<size_t>(ds_pair_fa.size(), 1));
-        ALLOC(h->ds_pair_fb, 4 * std::max<size_t>(ds_pair_fb.size(), 1));
-        ALLOC(h->ds_pair_ent, 4 * std::max<size_t>(ds_pair_ent.size(), 1));
-        ALLOC(h->ds_f_ptr, 4 * ds_f_ptr.size());
-        ALLOC(h->ds_f_ent, 4 * std::max<size_t>(ds_f_ent.size(), 1));
+    if (plan.jr_own_runs) {
+        tab(h->jd_nf, plan.jd_nf); tab(h->jd_frames, plan.jd_frames); tab(h->jd_mask, plan.jd_mask);
     }
-    if (h->jr_own_runs) {
-        ALLOC(h->jd_nf, 4 * jd_nf.size());
-        ALLOC(h->jd_frames, 4 * jd_frames.size());
-        ALLOC(h->jd_mask, 4 * jd_mask.size());
-    }
-#undef ALLOC
+    for (const Up& u : up)
+        if ((rc = dev_alloc(h, u.buf, u.bytes)) != SRK_OK) return rc;
     hipStream_t s = h->main_stream;
     stage("device allocations");
-#define H2D(buf, src, bytes)                                                                               \
-    do {                                                                                                   \
-        if ((bytes) > 0) HIPCHK(h, hipMemcpyAsync((buf).p, (src), (size_t)(bytes), hipMemcpyHostToDevice, s)); \
-    } while (0)
-    H2D(h->pts[0], pts.data(), 24 * N);
-    H2D(h->camR[0], camR.data(), 72 * (int64_t)M);
-    H2D(h->camT[0], camT.data(), 24 * (int64_t)M);
-    H2D(h->pts0, pts.data(), 24 * N);
-    H2D(h->camR0, camR.data(), 72 * (int64_t)M);
-    H2D(h->camT0, camT.data(), 24 * (int64_t)M);
-    H2D(h->K, Kexp.data(), 72 * (int64_t)M);
-    if (h->shk_G > 0) H2D(h->Ks[0], Kexp.data(), 72 * (int64_t)M);
-    H2D(h->row_ptr, row_ptr, 8 * (N + 1));
-    H2D(h->obs_frame, obs_frame, 4 * O);
-    H2D(h->obs_pt, obs_pt.data(), 4 * O);
-    H2D(h->obs_uv, obs_uv, 16 * O);
-    H2D(h->col_ptr, col_ptr.data(), 8 * ((int64_t)M + 1));
-    H2D(h->fobs_pt, fobs_pt.data(), 4 * fobs_pt.size());
-    H2D(h->fobs_uv, fobs_uv.data(), 8 * fobs_uv.size());
-    if (h->jr_own_runs) {
-        H2D(h->jd_nf, jd_nf.data(), 4 * jd_nf.size());
-        H2D(h->jd_frames, jd_frames.data(), 4 * jd_frames.size());
-        H2D(h->jd_mask, jd_mask.data(), 4 * jd_mask.size());
-    }
-    if (h->det_active) {
-        H2D(h->dj_ptr, dj_ptr.data(), 4 * dj_ptr.size());
-        H2D(h->dj_ent, dj_ent.data(), 4 * dj_ent.size());
-        H2D(h->ds_pair_ptr, ds_pair_ptr.data(), 4 * ds_pair_ptr.size());
-        H2D(h->ds_pair_fa, ds_pair_fa.data(), 4 * ds_pair_fa.size());
-        H2D(h->ds_pair_fb, ds_pair_fb.data(), 4 * ds_pair_fb.size());
-        H2D(h->ds_pair_ent, ds_pair_ent.data(), 4 * ds_pair_ent.size());
-        H2D(h->ds_f_ptr, ds_f_ptr.data(), 4 * ds_f_ptr.size());
-        H2D(h->ds_f_ent, ds_f_ent.data(), 4 * ds_f_ent.size());
-    }
-    H2D(h->grp_first, grp_first.data(), 4 * grp_first.size());
-    H2D(h->grp_count, grp_count.data(), 4 * grp_count.size());
-    H2D(h->grp_nf, grp_nf.data(), 4 * grp_nf.size());
-    H2D(h->grp_frames, grp_frames.data(), 4 * grp_frames.size());
-    H2D(h->obs_slot, obs_slot.data(), obs_slot.size());
-    H2D(h->pt_mask, pt_mask.data(), 4 * pt_mask.size());
-    H2D(h->gen_list, gen_list.data(), 4 * gen_list.size());
-    H2D(h->cal_list, cal_list.data(), 4 * cal_list.size());
-    H2D(h->lg_item, lg_item.data(), 4 * lg_item.size());
-    H2D(h->lg_np, lg_np.data(), 4 * lg_np.size());
-    H2D(h->lg_nf, lg_nf.data(), 4 * lg_nf.size());
-    H2D(h->lg_pts, lg_pts.data(), 4 * lg_pts.size());
-    H2D(h->lg_frames, lg_frames.data(), 4 * lg_frames.size());
-    H2D(h->lg_obs_off, lg_obs_off.data(), 8 * lg_obs_off.size());
-    H2D(h->lg_obs, lg_obs.data(), 4 * lg_obs.size());
-    H2D(h->wg_jmin, wg_jmin.data(), 4 * wg_jmin.size());
-    if (h->jac_runs) {
-        H2D(h->jr_first, jr_first.data(), 4 * jr_first.size());
-        H2D(h->jr_count, jr_count.data(), 4 * jr_count.size());
-        H2D(h->jr_jmin, jr_jmin.data(), 4 * jr_jmin.size());
-        if (h->jac_runs_masked) H2D(h->jr_group, jr_group.data(), 4 * jr_group.size());
-    }
-#undef H2D
-    for (auto& a : h->att) {
+    for (const Up& u : up)
+        if (u.src && u.bytes > 0) HIPCHK(h, hipMemcpyAsync(u.buf.p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    for (int sl = 0; sl < SRK_SLOTS; ++sl) {
+        srk_ba::Attempt& a = h->att[sl];
         if (!a.allocated) continue;
+        HIPCHK(h, hipMemsetAsync(a.irr.p, 0, 4, s));
+        if (new_flags[sl]) HIPCHK(h, hipMemset(a.sync_flags.p, 0, 4 * SRK_SYNC_WORDS));
+        a.sync.flags = P<unsigned>(a.sync_flags);
+        a.sync.fused = h->chol_fused;
         HIPCHK(h, hipMemsetAsync(a.dc.p, 0, 8 * d.ld, s));
         HIPCHK(h, hipMemsetAsync(a.dx.p, 0, 24 * N > 0 ? 24 * N : 8, s));
     }
@@ -2036,19 +1196,10 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     for (int sl = 0; sl < SRK_SLOTS; ++sl) h->att[sl].trial = sl + 1;
     rc = compute_cam_packs(h, 0);
     if (rc != SRK_OK) return rc;
-    HIPCHK(h, hipStreamSynchronize(s)); // host staging vectors go out of scope
-    // covisibility of THIS shard; with several ranks the caller must supply the global one
-    // (srk_ba_set_covisibility) -- until then the skyline is the full lower triangle
-    h->min_cv.assign((size_t)M, 0);
-    if (!h->allreduce && !h->comm) {
-        for (int32_t j = 0; j < M; ++j) h->min_cv[(size_t)j] = j;
-        for (int64_t i = 0; i < N; ++i) {
-            if (row_ptr[i + 1] == row_ptr[i]) continue;
-            int32_t first = obs_frame[row_ptr[i]];
-            for (int64_t o = row_ptr[i]; o < row_ptr[i + 1]; ++o)
-                h->min_cv[(size_t)obs_frame[o]] = std::min(h->min_cv[(size_t)obs_frame[o]], first);
-        }
-    }
+    HIPCHK(h, hipStreamSynchronize(s)); // the plan's tables go out of scope
+    // what later calls read of the plan stays with the handle (copied, not moved: the handle's vectors keep their storage from
+    // upload to upload, and the planner's allocations come and go as a block)
+    static_cast<SrkPlanKept&>(*h) = plan;
     stage("host-to-device copies");
     rc = build_envelope(h);
     if (rc != SRK_OK) return rc;
@@ -2397,7 +1548,7 @@ static int phase_derivatives(srk_ba* h)
                             h->jr_own_runs ? P<int32_t>(h->jd_nf) : P<int32_t>(h->grp_nf),
                             h->jr_own_runs ? P<int32_t>(h->jd_frames) : P<int32_t>(h->grp_frames),
                             h->jr_own_runs ? P<uint32_t>(h->jd_mask) : P<uint32_t>(h->pt_mask), h->det_active ? &detj : nullptr,
-                            h->jr_own_runs ? 32 : SRK_GRP_MAXNF_HOST, L);
+                            h->jr_own_runs ? SRK_JD_MAXNF_HOST : SRK_GRP_MAXNF_HOST, L);
         if (h->profile_level >= 1) HIPCHK(h, hipEventRecord(h->ev[13], s));
     } else if (h->jac_fused) {
         srk_launch_jac_fused(s, d, P<double>(h->pts[c]), P<double>(h->cam[c]), P<int32_t>(h->obs_frame),
@@ -3955,7 +3106,7 @@ int srk_ba_set_speculation(srk_ba* h, int on)
     return SRK_OK;
 }
 
-// internal frame order (frame_reorder): -1 = automatic (renumber when the caller's order is far from banded), 0 = never,
+// internal frame order (srk_frame_reorder, srk_plan.cpp): -1 = automatic (renumber when the caller's order is far from banded), 0 = never,
 // 1 = whenever reverse Cuthill-McKee gives another order than the caller's; takes effect at the next upload
 int srk_ba_set_frame_reordering(srk_ba* h, int mode)
 {
@@ -3989,7 +3140,7 @@ int srk_frame_order(int mode, int64_t N, int32_t M, const int64_t* row_ptr, cons
 {
     if (N < 0 || M < 1 || !row_ptr || (row_ptr[N] > 0 && !obs_frame) || !to_internal) return SRK_E_ARGS;
     std::vector<int32_t> to_int;
-    const bool on = frame_reorder(mode, N, M, row_ptr, obs_frame, to_int);
+    const bool on = srk_frame_reorder(mode, N, M, row_ptr, obs_frame, to_int);
     for (int32_t j = 0; j < M; ++j) to_internal[j] = on ? to_int[(size_t)j] : j;
     return on ? 1 : 0;
 }

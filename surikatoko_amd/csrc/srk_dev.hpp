@@ -22,6 +22,7 @@
 //   rhs,dc   [ld]
 #pragma once
 #include <hip/hip_runtime.h>
+#include "srk_limits.hpp" // the SRK_*_HOST limits (shared with the host-only planner, srk_plan.hpp)
 #include <stdint.h>
 #include <vector>
 
@@ -99,17 +100,12 @@ void srk_launch_jac_points(hipStream_t s, const SrkDims& d, const double* pts, c
                            const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* W,
                            double* Vg, const SrkLoss* loss = nullptr);
 // fused single pass (point blocks + frame blocks); usable when every workgroup's frame range fits SRK_JF_SLOTS_HOST
-#define SRK_JF_OBS_HOST 1024
-#define SRK_JF_SLOTS_HOST 48
-#define SRK_JF_PMAX_HOST 448
 void srk_launch_jac_fused(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                           const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* W,
                           double* Vg, double* Ug, const int32_t* wg_jmin, const SrkLoss* loss = nullptr);
 // run-based single pass: one wave per task = consecutive landmarks with identical frame lists (nf <= 64 frames), about
 // SRK_JR_TASK_PTS_MIN_HOST .. MAX_HOST of them; four consecutive tasks (one workgroup) must touch fewer than
 // SRK_JF_SLOTS_HOST consecutive frames
-#define SRK_JR_TASK_PTS_MIN_HOST 12
-#define SRK_JR_TASK_PTS_MAX_HOST 96 // = SRK_JR_XMAX of the kernel
 void srk_launch_jac_runs(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int64_t* row_ptr,
                          const int32_t* obs_frame, const double* obs_uv, double* W, double* Vg, double* Ug,
                          const int32_t* task_first, const int32_t* task_count, int32_t n_tasks, const int32_t* wg_jmin,
@@ -124,10 +120,6 @@ void srk_launch_jac_frames(hipStream_t s, const SrkDims& d, int64_t max_frame_ob
 void srk_launch_schur(hipStream_t s, const SrkDims& d, double c, const int64_t* row_ptr, const int32_t* obs_frame,
                       const double* W, const double* Vg, double* S, double* rhs, const int32_t* pt_list,
                       int64_t n_list);
-#define SRK_GRP_MAXNF_HOST 24   // must match SRK_GRP_MAXNF in srk_ba_kernels.hip
-#define SRK_GRP_MAXPTS_HOST 128 // landmarks per workgroup run
-#define SRK_GRP_NF1_HOST 21     // must match SRK_GRP_NF1
-#define SRK_WS_NF_HOST 20       // must match SRK_WS_NF (runs the MFMA kernel k_schur_mm takes)
 void srk_launch_schur_grouped(hipStream_t s, const SrkDims& d, double c, const int64_t* row_ptr, const int32_t* obs_pt,
                               const uint8_t* obs_slot /* [O] slot of the observation's frame in its run's frame set */,
                               const uint32_t* pt_mask /* [N] slots a landmark sees */, const double* W, const double* Vg,
@@ -142,11 +134,6 @@ void srk_launch_schur_grouped(hipStream_t s, const SrkDims& d, double c, const i
                               const SrkDetSchur* det = nullptr /* deterministic mode (every run must be one of those) */);
 // tracks longer than SRK_GRP_MAXNF_HOST frames: runs of <= SRK_LONG_PTS_HOST landmarks over a frame set of
 // <= SRK_LONG_MAXNF_HOST frames, one workgroup per pair of 8-frame blocks (k_schur_long); longer tracks stay with k_schur.
-// (Round 3: 4096 -- the limit is only the row length of the run_frames table; it was 256, and a track over more frames fell
-// back to the per-landmark global-atomics kernel, a 30x cliff on all-visible scenes of more than 256 frames.)
-#define SRK_LONG_PTS_HOST 128
-#define SRK_LONG_MAXNF_HOST 4096
-#define SRK_LONG_FB_HOST 8
 void srk_launch_schur_long(hipStream_t s, const SrkDims& d, double c, const double* W, const double* Vg, double* S, double* rhs,
                            const int32_t* item /* [n_items][4]: run, row block, column block (<= row block), 0 */,
                            int64_t n_items, const int32_t* run_np, const int32_t* run_nf,

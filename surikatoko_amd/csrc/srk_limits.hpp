@@ -1,0 +1,25 @@
+// srk_limits.hpp -- the kernels' limits as the host sees them: plain constants, no HIP.  Included by srk_dev.hpp (the HIP
+// translation units) and by srk_plan.hpp (the host-only scene planner); srk_ba_kernels.hip asserts them against its own.
+#pragma once
+
+// fused single-pass derivative kernel: usable when every workgroup's frame range fits SRK_JF_SLOTS_HOST
+#define SRK_JF_OBS_HOST 1024
+#define SRK_JF_SLOTS_HOST 48
+#define SRK_JF_PMAX_HOST 448
+// run-based derivative kernel: one wave per task = consecutive landmarks with identical frame lists (nf <= 64 frames), about
+// SRK_JR_TASK_PTS_MIN_HOST .. MAX_HOST of them; four consecutive tasks (one workgroup) must touch fewer than
+// SRK_JF_SLOTS_HOST consecutive frames
+#define SRK_JR_TASK_PTS_MIN_HOST 12
+#define SRK_JR_TASK_PTS_MAX_HOST 96 // = SRK_JR_XMAX of the kernel
+#define SRK_JD_MAXNF_HOST 32        // frames of a run of the derivative kernel's own: one mask word
+#define SRK_GRP_MAXNF_HOST 24   // must match SRK_GRP_MAXNF in srk_ba_kernels.hip
+#define SRK_GRP_MAXPTS_HOST 128 // landmarks per workgroup run
+#define SRK_GRP_NF1_HOST 21     // must match SRK_GRP_NF1
+#define SRK_WS_NF_HOST 20       // must match SRK_WS_NF (runs the MFMA kernel k_schur_mm takes)
+// tracks longer than SRK_GRP_MAXNF_HOST frames: runs of <= SRK_LONG_PTS_HOST landmarks over a frame set of
+// <= SRK_LONG_MAXNF_HOST frames, one workgroup per pair of 8-frame blocks (k_schur_long); longer tracks stay with k_schur.
+// (Round 3: 4096 -- the limit is only the row length of the run_frames table; it was 256, and a track over more frames fell
+// back to the per-landmark global-atomics kernel, a 30x cliff on all-visible scenes of more than 256 frames.)
+#define SRK_LONG_PTS_HOST 128
+#define SRK_LONG_MAXNF_HOST 4096
+#define SRK_LONG_FB_HOST 8
