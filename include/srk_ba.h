@@ -487,6 +487,70 @@ int srk_ba_constant_counts(srk_ba*, int32_t* n_frames, int64_t* n_points);
  * pass of the last assembly), taken with srk_ba_set_profile >= 1; 0 for a pass that was not launched or not timed */
 int srk_ba_constant_pass_ms(srk_ba*, double* points_ms, double* frames_ms);
 
+/* ---- Gaussian position priors on landmarks and camera centres (EXTENSION) ----
+ * "This landmark was surveyed to 2 cm", "this camera's GPS fix is good to 1 m": the finite variances that constant blocks (the
+ * limit of zero variance) cannot state, and a solve that lands in the caller's absolute coordinates.  With priors LM minimises
+ *
+ *     E = sum_o rho(q_o s_o) + sum_{i in P} (X_i - Xbar_i)^T L_i (X_i - Xbar_i) + sum_{j in F} (C_j - Cbar_j)^T L_j (C_j - Cbar_j)
+ *
+ * X_i landmark i, C_j = -R_j^T T_j the centre of frame j; Xbar, Cbar and the information matrices L in the caller's world
+ * coordinates (the coordinates of the arrays passed to the upload).  L: symmetric positive semi-definite 3 x 3, given as
+ * [xx xy xz yy yz zz], in units of E -- (pix / f0)^2 -- per squared world unit: a prior of covariance Sigma beside
+ * observations of pixel noise sigma_px is L = (sigma_px / f0)^2 Sigma^-1.  No robust loss acts on a prior.  This E is what the
+ * accept / reject test, both termination tests, report.err_initial / err_final, srk_ba_iteration_log and srk_ba_phase_error
+ * use; srk_ba_reproj_error* stay the reprojection sums.  A landmark prior adds 2 L to the landmark's 3 x 3 block and
+ * 2 L (X - Xbar) to its gradient; a frame prior adds 2 L to the [Tx Ty Tz] part of the frame block and 2 L (C - Cbar) to those
+ * gradient entries (the translation variables move the centre directly and the rotation variables leave it alone), before the
+ * damping.  Neither adds a coupling: the skyline, the Schur kernels and the solver plans are those of the scene without priors.
+ *
+ * Both counts 0 clears the setting (the default).  The handle keeps a copy: it is applied by every later upload
+ * (srk_ba_compute_inplace and srk_ba_compute_inplace_f32 included) and is not touched by srk_ba_reset_scene.  It takes effect
+ * at the next upload, which maps it to the normalised scene X_n = s (R0 X + T0): Xbar_n = s (R0 Xbar + T0),
+ * L_n = R0 L R0^T / s^2 (the prior energy is invariant; srk_ba_normalize_position_priors).  An index beyond the uploaded scene's
+ * counts fails that upload with SRK_E_ARGS.
+ *
+ * keep_gauge = 1: the reference's seven gauge variables stay constant and the priors pull within that gauge.  keep_gauge = 0:
+ * nothing is held; the caller asserts that the priors fix the similarity (three non-collinear positions with positive definite
+ * L do); otherwise the system is singular and the solve reports failure like any degenerate scene.  The gauge is released
+ * when either this setting or srk_ba_set_constant_blocks says keep_gauge = 0.  The gauge NORMALISATION still uses the caller's
+ * frames 0 and 1.  A prior on a constant block adds a constant to E and nothing else.
+ *
+ * SRK_E_ARGS (text in srk_ba_last_error), the previous setting staying in force: indices not strictly ascending or negative,
+ * a value that is not finite, an L that is not positive semi-definite (all zeros is a valid, switched-off prior), keep_gauge
+ * outside {0, 1}, a NULL array of a kind whose count is positive.  Refused with SRK_E_ARGS by whichever call comes second:
+ * intrinsic groups, more than one rank.  Fixed intrinsics, deterministic mode, f32 storage, fp32 Schur sums, every Jacobian
+ * and rcs mode, solver fusion, speculation, frame reordering, robust losses, information and constant blocks work unchanged.
+ * Two small passes impose the priors (one behind the derivative kernels, one beside the error kernel); neither is launched
+ * without priors. */
+int srk_ba_set_position_priors(srk_ba*, int64_t n_point_priors, const int64_t* point_index /* strictly ascending */,
+                               const double* point_pos /* [n][3] */, const double* point_info /* [n][6]: xx xy xz yy yz zz */,
+                               int32_t n_frame_priors, const int32_t* frame_index /* strictly ascending, caller's numbering */,
+                               const double* frame_centre /* [n][3] */, const double* frame_info /* [n][6] */, int keep_gauge);
+/* the counts of the stored setting; returns 1 if a setting is stored, 0 if not */
+int srk_ba_position_prior_counts(srk_ba*, int64_t* n_point_priors, int32_t* n_frame_priors);
+/* the stored setting in the caller's coordinates, into arrays of the sizes srk_ba_position_prior_counts gives; any pointer may
+ * be NULL.  Returns 1 if a setting is stored, 0 if not.  Both calls report what the setter stored, i.e. what the NEXT upload
+ * applies; the resident scene runs with the setting that was stored when it was uploaded. */
+int srk_ba_position_priors(srk_ba*, int64_t* point_index, double* point_pos, double* point_info, int32_t* frame_index,
+                           double* frame_centre, double* frame_info, int* keep_gauge);
+/* the two prior sums of the resident scene's current state (0 without priors); srk_ba_phase_error minus these is the
+ * observation part */
+int srk_ba_prior_error(srk_ba*, double* e_points, double* e_frames);
+/* X - Xbar [n_point_priors][3] and C - Cbar [n_frame_priors][3] of the resident scene's current state in the caller's world
+ * coordinates (normalisation reverted), in the order of the setting: for chi-square checks of control points.  The offsets are
+ * those of the setting the resident scene was uploaded with; if the stored setting has been changed since (indices or
+ * positions), the call fails with SRK_E_STATE until the scene is uploaded again, so that counts and values cannot be mixed.
+ * srk_ba_prior_error always sums the lists of the resident scene. */
+int srk_ba_prior_residuals(srk_ba*, double* d_points, double* d_frames);
+/* host only, no device needed: positions [n][3] and information matrices [n][6] through a normaliser, as the upload maps them
+ * (pos_n = s (R0 pos + T0), L_n = R0 L R0^T / s^2).  Either pair of arrays may be NULL.  Returns SRK_OK or SRK_E_ARGS. */
+int srk_ba_normalize_position_priors(const srk_ba_normalizer* nrm, int64_t n, const double* pos, const double* info,
+                                     double* pos_out, double* info_out);
+/* device time in ms of the last launch of the two prior passes (behind the derivative kernels, beside the error kernel), taken
+ * with srk_ba_set_profile >= 1; 0 for a pass that was not launched or not timed.  One event pair serves all attempt slots: with
+ * speculation on, the error-side figure is that of whichever attempt recorded last (tools/prior_rate.py switches it off). */
+int srk_ba_prior_pass_ms(srk_ba*, double* derivative_ms, double* error_ms);
+
 /* device-time instrumentation of srk_ba_optimize / srk_ba_compute_inplace: 0 = none (default; report.ms_* stay 0
  * except ms_total), 1 = one HIP event pair per phase (fills report.ms_*), 2 = additionally event pairs around
  * every MFMA trailing-update launch (fills report.ms_solve_syrk / solve_mfma_flops).  Every event costs a few

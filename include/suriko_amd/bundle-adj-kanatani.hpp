@@ -10,6 +10,7 @@
 // bundle-adj-kanatani.cpp:2027-2034), pnt_ind = order of tracks that have a SalientPointId (:1161-1169) while
 // coordinates are fetched by salient-point id (:1171).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -100,6 +101,7 @@ public:
                         int64_t max_iterations = 0) {
         Flat f = Flatten(f0, map, inverse_orient_cams, track_rep, shared_intrinsic_cam_mat, intrinsic_cam_mats);
         ApplyConstantBlocks(map, f, inverse_orient_cams.size());
+        ApplyPositionPriors(map, f);
         Scalar a = term_crit.AllowedReprojErrRelativeChange().value_or(0), m = term_crit.MaxHessianFactor().value_or(0);
         int rc = srk_ba_compute_inplace(h_, f0, (int64_t)f.ids.size(), f.pts.data(), (int32_t)inverse_orient_cams.size(),
                                         f.R.data(), f.T.data(), f.K.data(), f.shared, f.row_ptr.data(), f.frames.data(),
@@ -211,6 +213,35 @@ public:
         if (rc < 0) Raise(rc);
     }
 
+    /// EXTENSION: Gaussian position priors from the next ComputeInplace on (srk_ba_set_position_priors).
+    /// A landmark prior names the k-th salient point of the map (the order of AddSalientPoint) -- the adapter maps it to
+    /// pnt_ind, the order of the tracks that carry a salient point, and drops priors on salient points no track carries; a
+    /// frame prior names a camera and holds its centre -R^T T.  Positions in the coordinates of the map and the cameras;
+    /// info = [xx xy xz yy yz zz], the information matrix in units of the error, (pix / f0)^2, per squared world unit (a prior
+    /// of covariance Sigma beside observations of pixel noise sigma_px: (sigma_px / f0)^2 Sigma^-1).  Both vectors empty clears
+    /// the setting.  keep_gauge: the reference's seven gauge variables stay constant as well; false = the priors alone fix the
+    /// similarity.  ComputeInplace throws std::invalid_argument for an index beyond the map / the cameras, a repeated index,
+    /// values the library refuses, and where it refuses the combination (intrinsic groups, more than one rank).
+    struct PositionPrior {
+        size_t index = 0;
+        Point3 position;
+        std::array<Scalar, 6> info{};
+    };
+    void SetPositionPriors(const std::vector<PositionPrior>& point_priors, const std::vector<PositionPrior>& frame_priors, bool keep_gauge = true) {
+        if (point_priors.empty() && frame_priors.empty()) { ClearPositionPriors(); return; }
+        prior_points_ = point_priors;
+        prior_frames_ = frame_priors;
+        prior_keep_gauge_ = keep_gauge;
+        prior_set_ = true;
+    }
+    void ClearPositionPriors() {
+        prior_set_ = false;
+        prior_points_.clear();
+        prior_frames_.clear();
+        int rc = srk_ba_set_position_priors(h_, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1);
+        if (rc < 0) Raise(rc);
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
@@ -264,6 +295,39 @@ private:
                                             const_points_.empty() ? nullptr : pc.data(), (int64_t)pc.size(), const_keep_gauge_ ? 1 : 0);
         if (rc < 0) Raise(rc);
     }
+    // the stored priors against this call's scene: landmarks from salient-point order to pnt_ind (f.ids), both kinds ascending
+    void ApplyPositionPriors(const FragmentMap& map, const Flat& f) {
+        if (!prior_set_) return;
+        std::vector<int64_t> at(map.SalientPointsCount(), -1); // salient point -> its prior
+        for (size_t k = 0; k < prior_points_.size(); ++k) {
+            if (prior_points_[k].index >= at.size()) throw std::invalid_argument("position priors: a landmark index is beyond the map");
+            if (at[prior_points_[k].index] >= 0) throw std::invalid_argument("position priors: a landmark is named twice");
+            at[prior_points_[k].index] = (int64_t)k;
+        }
+        std::vector<int64_t> pi;
+        std::vector<int32_t> fi;
+        std::vector<Scalar> pp, pl, fp, fl;
+        auto put = [](const PositionPrior& p, std::vector<Scalar>& pos, std::vector<Scalar>& info) {
+            pos.insert(pos.end(), { p.position.x, p.position.y, p.position.z });
+            info.insert(info.end(), p.info.begin(), p.info.end());
+        };
+        for (size_t i = 0; i < f.ids.size(); ++i) {
+            const int64_t k = at.at(map.SalientPointIndex(f.ids[i]));
+            if (k < 0) continue;
+            pi.push_back((int64_t)i);
+            put(prior_points_[(size_t)k], pp, pl);
+        }
+        std::vector<size_t> order(prior_frames_.size());
+        for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return prior_frames_[a].index < prior_frames_[b].index; });
+        for (size_t k : order) {
+            fi.push_back((int32_t)prior_frames_[k].index);
+            put(prior_frames_[k], fp, fl);
+        }
+        int rc = srk_ba_set_position_priors(h_, (int64_t)pi.size(), pi.data(), pp.data(), pl.data(), (int32_t)fi.size(), fi.data(),
+                                            fp.data(), fl.data(), prior_keep_gauge_ ? 1 : 0);
+        if (rc < 0) Raise(rc);
+    }
     [[noreturn]] void Raise(int rc) const {
         std::string msg = srk_ba_last_error(h_);
         if (rc == SRK_E_ARGS) throw std::invalid_argument(msg);
@@ -276,6 +340,8 @@ private:
     size_t points_count_ = 0, frames_count_ = 0;
     bool const_set_ = false, const_keep_gauge_ = true;
     std::vector<uint8_t> const_frames_, const_points_;
+    bool prior_set_ = false, prior_keep_gauge_ = true;
+    std::vector<PositionPrior> prior_points_, prior_frames_;
 };
 
 } // namespace suriko_amd

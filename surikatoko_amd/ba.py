@@ -141,6 +141,68 @@ def revert_normalization(scene, nrm):
                                       _p(scene.cam_T), C.byref(nrm))
 
 
+def prior_information(spec=None, n=None, info=None, sigma_pixels=None, f0=None):
+    """[n][6] information matrices (xx xy xz yy yz zz) of n position priors.  info= gives them directly: [n][6] or [n][3][3]
+    (or one [6] / [1][3][3] for all).  Otherwise spec is read by its number of dimensions alone: a scalar is one sigma for all,
+    1-D [3] per-axis sigmas for all, 2-D [n][3] per-axis sigmas, 3-D [n][3][3] (or [1][3][3] for all) covariances -- a single
+    covariance goes in as [1][3][3], so that per-axis sigmas of three priors are never taken for one.  World units; they become
+    L = (sigma_pixels / f0)^2 Sigma^-1, the prior beside observations of pixel noise sigma_pixels, in the units of the error,
+    (pix / f0)^2.  A covariance must be symmetric positive definite."""
+    def rows(a, what):
+        if n is not None and a.shape[0] == 1 and n != 1:
+            a = np.repeat(a, n, axis=0)
+        if n is not None and a.shape[0] != n:
+            raise ValueError(f"position priors: {a.shape[0]} {what} for {n} priors")
+        return a
+
+    def six(L):
+        return np.ascontiguousarray(np.stack([L[:, 0, 0], L[:, 0, 1], L[:, 0, 2], L[:, 1, 1], L[:, 1, 2], L[:, 2, 2]], axis=1))
+
+    if info is not None:
+        a = np.asarray(info, dtype=np.float64)
+        if a.ndim == 3 and a.shape[1:] == (3, 3):
+            return six(rows(a, "information matrices"))
+        if (a.ndim == 1 and a.size == 6) or (a.ndim == 2 and a.shape[1] == 6):
+            return np.ascontiguousarray(rows(a.reshape(-1, 6), "information matrices"))
+        raise ValueError("position priors: info= is [n][6] (xx xy xz yy yz zz) or [n][3][3]")
+    if spec is None:
+        raise ValueError("position priors: give a sigma, per-axis sigmas, covariances or info=")
+    if sigma_pixels is None or not f0:
+        raise ValueError("position priors: sigmas and covariances need sigma_pixels and the scene's f0 (or pass info=)")
+    a = np.asarray(spec, dtype=np.float64)
+    if a.ndim == 0:
+        cov = np.eye(3)[None] * float(a) ** 2
+    elif (a.ndim == 1 and a.size == 3) or (a.ndim == 2 and a.shape[1] == 3):
+        sg = a.reshape(-1, 3)
+        cov = np.zeros((sg.shape[0], 3, 3))
+        cov[:, np.arange(3), np.arange(3)] = sg ** 2
+    elif a.ndim == 3 and a.shape[1:] == (3, 3):
+        cov = a
+        if np.abs(cov - cov.transpose(0, 2, 1)).max() > 1e-12 * np.abs(cov).max():
+            raise ValueError("position priors: a covariance is not symmetric")
+    else:
+        raise ValueError("position priors: spec is a sigma, per-axis sigmas [n][3] or covariances [n][3][3]")
+    cov = rows(cov, "sigmas / covariances")
+    if not np.all(np.isfinite(cov)) or np.any(np.linalg.eigvalsh(0.5 * (cov + cov.transpose(0, 2, 1))) <= 0):
+        raise ValueError("position priors: sigmas must be positive and covariances positive definite")
+    L = np.linalg.inv(cov) * (float(sigma_pixels) / float(f0)) ** 2
+    return six(0.5 * (L + L.transpose(0, 2, 1)))
+
+
+def normalize_position_priors(nrm, pos, info):
+    """positions [n][3] and information matrices [n][6] through a Normalizer, as the upload maps them
+    (srk_ba_normalize_position_priors; host only).  Returns (pos_n, info_n)."""
+    pos = np.ascontiguousarray(np.asarray(pos, dtype=np.float64).reshape(-1, 3))
+    info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(-1, 6))
+    if pos.shape[0] != info.shape[0]:
+        raise ValueError("normalize_position_priors: one information matrix per position")
+    po, io = np.zeros_like(pos), np.zeros_like(info)
+    rc = lib().srk_ba_normalize_position_priors(C.byref(nrm), C.c_int64(pos.shape[0]), _p(pos), _p(info), _p(po), _p(io))
+    if rc != 0:
+        raise ValueError("srk_ba_normalize_position_priors: bad argument")
+    return po, io
+
+
 def check_world_is_normalized(scene, t1y=1.0, unity_comp_ind=1):
     """CheckWorldIsNormalized (.cpp:288-333)."""
     return bool(lib().srk_ba_check_world_is_normalized(C.c_int32(scene.M), _p(scene.cam_R), _p(scene.cam_T),
@@ -536,6 +598,79 @@ class BundleAdjustmentKanatani:
         """(landmark pass, frame pass): device ms of the last launch of the two masking passes, with set_profile >= 1"""
         a, b = C.c_double(0), C.c_double(0)
         self._raise(self._lib.srk_ba_constant_pass_ms(C.c_void_p(self._h), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _prior_arrays(self, arg, what, sigma_pixels, itype):
+        """(index, position, spec) or (index, position) with the information in a dict {'info': ...} -> sorted arrays"""
+        if arg is None:
+            return np.zeros(0, itype), np.zeros((0, 3)), np.zeros((0, 6))
+        if len(arg) != 3:
+            raise ValueError(f"set_position_priors: {what} = (index, position, spec)")
+        idx, pos, spec = arg
+        idx = np.asarray(idx).astype(itype).ravel()
+        pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+        if pos.shape[0] != idx.size:
+            raise ValueError(f"set_position_priors: {what}: one position per index")
+        if isinstance(spec, dict):
+            info = prior_information(n=idx.size, info=spec["info"])
+        else:
+            info = prior_information(spec, n=idx.size, sigma_pixels=sigma_pixels, f0=self._f0)
+        if info.shape[0] != idx.size:
+            raise ValueError(f"set_position_priors: {what}: one sigma / covariance / information matrix per index")
+        order = np.argsort(idx, kind="stable")
+        return np.ascontiguousarray(idx[order]), np.ascontiguousarray(pos[order]), np.ascontiguousarray(info[order])
+
+    def set_position_priors(self, points=None, frames=None, keep_gauge=True, sigma_pixels=None):
+        """Gaussian position priors (next upload): points / frames are (index, position, spec) in the
+        caller's numbering and world coordinates -- landmark positions, camera centres C = -R^T T.  spec is a scalar sigma,
+        per-axis sigmas [n][3], covariances [n][3][3] (world units; they need sigma_pixels, the pixel noise of the
+        observations, and the f0 of the scene last passed to this object -- before the first scene, convert with
+        prior_information(..., f0=...)), or {'info': L} with the information matrices [n][6] (xx xy xz yy yz zz) or [n][3][3]
+        in units of the error per squared world unit.  The shapes are read as prior_information reads them.  Both None
+        clears the setting (the default).  keep_gauge=True keeps the reference's seven gauge variables constant; with False
+        the priors alone must fix the similarity.  Not with intrinsic groups or more than one rank (ValueError)."""
+        pi, pp, pl = self._prior_arrays(points, "points", sigma_pixels, np.int64)
+        fi, fp, fl = self._prior_arrays(frames, "frames", sigma_pixels, np.int32)
+        self._raise(self._lib.srk_ba_set_position_priors(
+            C.c_void_p(self._h), C.c_int64(pi.size), _p(pi) if pi.size else None, _p(pp) if pi.size else None,
+            _p(pl) if pi.size else None, C.c_int32(fi.size), _p(fi) if fi.size else None, _p(fp) if fi.size else None,
+            _p(fl) if fi.size else None, C.c_int(int(bool(keep_gauge)))))
+
+    def position_priors(self):
+        """None when no priors are set, else a dict: point_index, point_pos, point_info, frame_index, frame_centre, frame_info
+        (information matrices as [n][6]: xx xy xz yy yz zz), keep_gauge -- the stored setting in the caller's coordinates"""
+        n, m, kg = C.c_int64(0), C.c_int32(0), C.c_int(1)
+        rc = self._lib.srk_ba_position_prior_counts(C.c_void_p(self._h), C.byref(n), C.byref(m))
+        self._raise(rc)
+        if rc == 0:
+            return None
+        pi, pp, pl = np.zeros(n.value, np.int64), np.zeros((n.value, 3)), np.zeros((n.value, 6))
+        fi, fp, fl = np.zeros(m.value, np.int32), np.zeros((m.value, 3)), np.zeros((m.value, 6))
+        q = lambda a: _p(a) if a.size else None
+        self._raise(self._lib.srk_ba_position_priors(C.c_void_p(self._h), q(pi), q(pp), q(pl), q(fi), q(fp), q(fl), C.byref(kg)))
+        return dict(point_index=pi, point_pos=pp, point_info=pl, frame_index=fi, frame_centre=fp, frame_info=fl,
+                    keep_gauge=bool(kg.value))
+
+    def prior_error(self):
+        """(landmark prior sum, frame prior sum) of the resident scene's current state; phase_error() minus both is the
+        observation part"""
+        a, b = C.c_double(0), C.c_double(0)
+        self._raise(self._lib.srk_ba_prior_error(C.c_void_p(self._h), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def prior_residuals(self):
+        """(X - Xbar [n][3], C - Cbar [n][3]) of the resident scene's current state in the caller's world coordinates, in the
+        order of position_priors()"""
+        n, m = C.c_int64(0), C.c_int32(0)
+        self._raise(self._lib.srk_ba_position_prior_counts(C.c_void_p(self._h), C.byref(n), C.byref(m)))
+        dp, df = np.zeros((n.value, 3)), np.zeros((m.value, 3))
+        self._raise(self._lib.srk_ba_prior_residuals(C.c_void_p(self._h), _p(dp) if n.value else None, _p(df) if m.value else None))
+        return dp, df
+
+    def prior_pass_ms(self):
+        """(derivative-side pass, error-side pass): device ms of the last launch of the two prior passes, with set_profile >= 1"""
+        a, b = C.c_double(0), C.c_double(0)
+        self._raise(self._lib.srk_ba_prior_pass_ms(C.c_void_p(self._h), C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def schur_fallback_landmarks(self):

@@ -181,6 +181,24 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     std::vector<uint8_t> cst_frame_int;
     hipEvent_t ev_cst[4]{}; // profile level >= 1: around the last k_const_points / k_const_frames launch (created on first use)
     bool cst_timed[2] = { false, false };
+    // opt-in: Gaussian position priors (srk_ba_set_position_priors).  pri_*_idx / _pos / _info: the setting
+    // in the caller's numbering and world coordinates, kept across uploads and srk_ba_reset_scene.  The uploaded scene: the
+    // lists in the internal order with the values mapped to the normalised world (SrkPrior), on the device.  Both counts 0 =
+    // neither prior pass is launched.
+    bool pri_set = false;
+    int pri_keep_gauge = 1;
+    std::vector<int64_t> pri_pt_idx;
+    std::vector<int32_t> pri_fr_idx;
+    std::vector<double> pri_pt_pos, pri_pt_info, pri_fr_pos, pri_fr_info;
+    DevBuf pri_pt_list, pri_pt_val, pri_fr_list, pri_fr_val;
+    // what the resident scene was uploaded with (indices and positions): srk_ba_prior_residuals answers for that setting only
+    std::vector<int64_t> app_pt_idx;
+    std::vector<int32_t> app_fr_idx;
+    std::vector<double> app_pt_pos, app_fr_pos;
+    int64_t n_pri_pts = 0;
+    int32_t n_pri_frames = 0;
+    hipEvent_t ev_pri[4]{}; // profile level >= 1: around the last k_prior_add / k_prior_error launch (created on first use)
+    bool pri_timed[2] = { false, false };
     int profile_level = 0; // 0 = no events, 1 = phase events (report.ms_*), 2 = + event pairs around the MFMA updates
     bool chol_fused = true; // the solve's outer steps as one launch each (k_step256); srk_ba_set_solver_fusion
     // what the caller asked for.  A hand-off timeout switches chol_fused off for the rest of that call; the next upload /
@@ -360,7 +378,7 @@ void srk_ba_destroy(srk_ba* h)
                       &h->jd_nf, &h->jd_frames, &h->jd_mask,
                       &h->jr_first, &h->jr_count, &h->jr_jmin, &h->jr_group, &h->lg_item, &h->lg_np, &h->lg_nf, &h->lg_pts, &h->lg_frames,
                       &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk,
-                      &h->info_q, &h->info_qf, &h->cst_pts, &h->cst_frames };
+                      &h->info_q, &h->info_qf, &h->cst_pts, &h->cst_frames, &h->pri_pt_list, &h->pri_pt_val, &h->pri_fr_list, &h->pri_fr_val };
     for (DevBuf* b : all) dev_free(*b);
     for (auto& a : h->att) {
         for (DevBuf* b : { &a.S, &a.rhs, &a.wy, &a.dc, &a.acc, &a.dx, &a.err_partial, &a.info, &a.dinv, &a.packed, &a.sync_flags, &a.irr, &a.det_stage, &a.det_rhs,
@@ -378,6 +396,8 @@ void srk_ba_destroy(srk_ba* h)
     for (auto& e : h->chol_ev) hipEventDestroy(e);
     if (h->ev_jac) hipEventDestroy(h->ev_jac);
     for (auto& e : h->ev_cst)
+        if (e) hipEventDestroy(e);
+    for (auto& e : h->ev_pri)
         if (e) hipEventDestroy(e);
     if (h->ev_comm) hipEventDestroy(h->ev_comm);
     if (h->comm_stream) hipStreamDestroy(h->comm_stream);
@@ -451,11 +471,21 @@ static const char* constant_conflict(bool constant, bool groups, int world)
     if (world > 1) return "constant blocks: not available with more than one rank";
     return nullptr;
 }
+// position priors (srk_ba_set_position_priors) add to the 10- or 6-variable blocks of one rank: the fold of shared intrinsics and
+// the exchange of the ranks' partial frame sums (a frame prior would have to come from rank 0 alone) can follow later
+static const char* prior_conflict(bool priors, bool groups, int world)
+{
+    if (!priors) return nullptr;
+    if (groups) return "position priors: not available with intrinsic groups";
+    if (world > 1) return "position priors: not available with more than one rank";
+    return nullptr;
+}
 static bool refuse_modes(srk_ba* h, bool fixed_k, bool deterministic, bool store_f32, bool schur_fp32, int world, bool groups)
 {
     const char* e = fixed_k_conflict(fixed_k, deterministic, store_f32, schur_fp32, world);
     if (!e) e = groups_conflict(groups, fixed_k, store_f32, schur_fp32, world);
     if (!e) e = constant_conflict(h->cst_set, groups, world);
+    if (!e) e = prior_conflict(h->pri_set, groups, world);
     if (e) h->last_error = e;
     return e != nullptr;
 }
@@ -618,6 +648,33 @@ void srk_ba_revert_normalization(int64_t N, double* pts, int32_t M, double* cam_
         for (int i = 0; i < 3; ++i) T[i] = T[i] / s + u[i];
         std::memcpy(R, RR, sizeof RR);
     }
+}
+
+// position priors through a normaliser (host only): pos_n = s (R0 pos + T0), L_n = R0 L R0^T / s^2, so that
+// (x_n - pos_n)^T L_n (x_n - pos_n) = (x - pos)^T L (x - pos) for x_n = s (R0 x + T0)
+int srk_ba_normalize_position_priors(const srk_ba_normalizer* nrm, int64_t n, const double* pos, const double* info,
+                                     double* pos_out, double* info_out)
+{
+    if (!nrm || n < 0 || (pos != nullptr) != (pos_out != nullptr) || (info != nullptr) != (info_out != nullptr)) return SRK_E_ARGS;
+    const double s = nrm->world_scale, is2 = 1.0 / (s * s);
+    const double* R = nrm->R0;
+    for (int64_t i = 0; pos && i < n; ++i) {
+        double y[3];
+        srk::se3_apply(nrm->R0, nrm->T0, pos + 3 * i, y);
+        for (int e = 0; e < 3; ++e) pos_out[3 * i + e] = y[e] * s;
+    }
+    for (int64_t i = 0; info && i < n; ++i) {
+        const double* l = info + 6 * i;
+        const double L[9] = { l[0], l[1], l[2], l[1], l[3], l[4], l[2], l[4], l[5] };
+        double RL[9], o[9];
+        srk::mat3_mul(R, L, RL);
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) o[3 * a + b] = (RL[3 * a] * R[3 * b] + RL[3 * a + 1] * R[3 * b + 1] + RL[3 * a + 2] * R[3 * b + 2]) * is2;
+        double* q = info_out + 6 * i; // the symmetric part: both triangles carry the same sum up to rounding
+        q[0] = o[0]; q[1] = 0.5 * (o[1] + o[3]); q[2] = 0.5 * (o[2] + o[6]);
+        q[3] = o[4]; q[4] = 0.5 * (o[5] + o[7]); q[5] = o[8];
+    }
+    return SRK_OK;
 }
 
 } // extern "C"
@@ -977,6 +1034,7 @@ static int check_information(srk_ba* h, const char* who, const double* q, int64_
 }
 static int apply_information(srk_ba* h);
 static int apply_constant_blocks(srk_ba* h);
+static int apply_position_priors(srk_ba* h);
 static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_in, int32_t M,
                              const double* cam_R_in, const double* cam_T_in, const double* K_in, int shared_k,
                              const int64_t* row_ptr, const int32_t* obs_frame, const double* obs_uv,
@@ -1025,6 +1083,16 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         }
         if (!h->cst_point_user.empty() && (int64_t)h->cst_point_user.size() != N) {
             h->last_error = "constant blocks: set for " + std::to_string(h->cst_point_user.size()) + " landmarks, the scene has " + std::to_string(N);
+            return SRK_E_ARGS;
+        }
+    }
+    if (h->pri_set) {
+        if (!h->pri_pt_idx.empty() && h->pri_pt_idx.back() >= N) {
+            h->last_error = "position priors: landmark index " + std::to_string(h->pri_pt_idx.back()) + ", the scene has " + std::to_string(N) + " landmarks";
+            return SRK_E_ARGS;
+        }
+        if (!h->pri_fr_idx.empty() && h->pri_fr_idx.back() >= M) {
+            h->last_error = "position priors: frame index " + std::to_string(h->pri_fr_idx.back()) + ", the scene has " + std::to_string(M) + " frames";
             return SRK_E_ARGS;
         }
     }
@@ -1107,6 +1175,8 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     // constant blocks without the reference's gauge: no frame index matches, so srk_is_fixed_var is false for every variable
     // and the masking passes are the only source of identity rows besides the padding
     if (h->cst_set && !h->cst_keep_gauge) d.g0 = d.g1 = -1;
+    // position priors without the reference's gauge: the priors fix the similarity
+    if (h->pri_set && !h->pri_keep_gauge) d.g0 = d.g1 = -1;
     d.w_f32 = h->store_f32 ? 1 : 0;
     h->d = d;
     h->f0 = f0;
@@ -1150,7 +1220,9 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         add(a.dc, nullptr, 8 * d.ld);
         add(a.acc, nullptr, 8 * 3 * d.Ns + 64);
         add(a.dx, nullptr, 24 * N);
-        add(a.err_partial, nullptr, 8 * std::max<int64_t>(1024, srk_error_partials_staged(d)));
+        // (position priors: their partial sums sit behind the observation partials of either error kernel)
+        add(a.err_partial, nullptr, 8 * (std::max<int64_t>(1024, srk_error_partials_staged(d)) +
+                                         (h->pri_set ? srk_prior_partials((int64_t)h->pri_pt_idx.size(), (int64_t)h->pri_fr_idx.size()) : 0)));
         add(a.info, nullptr, 64);
         add(a.dinv, nullptr, 8 * 64 * d.ld);
         add(a.irr, nullptr, 4 * (N + 2));
@@ -1212,8 +1284,103 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     stage("skyline, solver plans");
     if ((rc = apply_information(h)) != SRK_OK) return rc;
     if ((rc = apply_constant_blocks(h)) != SRK_OK) return rc;
+    if ((rc = apply_position_priors(h)) != SRK_OK) return rc;
     h->have_scene = true;
     return SRK_OK;
+}
+
+// the stored priors (indices checked at the start of the upload) -> the device lists of the resident scene: values through the
+// normaliser of this upload (the identity for a scene uploaded as already normalised), landmarks through the internal order
+// (perm), frames through the renumbering (frame_int), both ascending in the internal numbering
+static int apply_position_priors(srk_ba* h)
+{
+    const SrkDims& d = h->d;
+    h->n_pri_pts = 0;
+    h->n_pri_frames = 0;
+    h->app_pt_idx.clear(); h->app_pt_pos.clear(); h->app_fr_idx.clear(); h->app_fr_pos.clear();
+    if (!h->pri_set) return SRK_OK;
+    h->app_pt_idx = h->pri_pt_idx; h->app_pt_pos = h->pri_pt_pos;
+    h->app_fr_idx = h->pri_fr_idx; h->app_fr_pos = h->pri_fr_pos;
+    const size_t np = h->pri_pt_idx.size(), nf = h->pri_fr_idx.size();
+    std::vector<double> pn(3 * np), ln(6 * np), cn(3 * nf), fn(6 * nf);
+    srk_ba_normalize_position_priors(&h->nrm, (int64_t)np, np ? h->pri_pt_pos.data() : nullptr, np ? h->pri_pt_info.data() : nullptr,
+                                     np ? pn.data() : nullptr, np ? ln.data() : nullptr);
+    srk_ba_normalize_position_priors(&h->nrm, (int64_t)nf, nf ? h->pri_fr_pos.data() : nullptr, nf ? h->pri_fr_info.data() : nullptr,
+                                     nf ? cn.data() : nullptr, nf ? fn.data() : nullptr);
+    // an all-zero information matrix is a switched-off prior: it is left out of the lists, so that the sums (and their bits) are
+    // those of the setting without it
+    auto off = [](const double* info) {
+        for (int e = 0; e < 6; ++e)
+            if (info[e] != 0.0) return false;
+        return true;
+    };
+    std::vector<int32_t> pl, fl; // the lists, and each entry's place in the setting
+    std::vector<size_t> pk, fk;
+    if (np) {
+        std::vector<int64_t> slot((size_t)d.N, -1); // caller's landmark -> its place in the setting
+        for (size_t k = 0; k < np; ++k) slot[(size_t)h->pri_pt_idx[k]] = (int64_t)k;
+        for (int64_t i = 0; i < d.N; ++i) {
+            const int64_t k = slot[(size_t)h->perm[(size_t)i]];
+            if (k < 0 || off(&h->pri_pt_info[6 * (size_t)k])) continue;
+            pl.push_back((int32_t)i);
+            pk.push_back((size_t)k);
+        }
+    }
+    if (nf) {
+        std::vector<int32_t> slot((size_t)d.M, -1); // internal frame -> its place in the setting
+        for (size_t k = 0; k < nf; ++k) {
+            const int32_t j = h->pri_fr_idx[k];
+            slot[(size_t)(h->frame_int.empty() ? j : h->frame_int[(size_t)j])] = (int32_t)k;
+        }
+        for (int32_t j = 0; j < d.M; ++j) {
+            const int32_t k = slot[(size_t)j];
+            if (k < 0 || off(&h->pri_fr_info[6 * (size_t)k])) continue;
+            fl.push_back(j);
+            fk.push_back((size_t)k);
+        }
+    }
+    // the values as SoA planes over the list (SrkPrior)
+    auto planes = [](const std::vector<size_t>& at, const std::vector<double>& pos, const std::vector<double>& info) {
+        const size_t n = at.size();
+        std::vector<double> val(9 * n);
+        for (size_t i = 0; i < n; ++i) {
+            for (int e = 0; e < 3; ++e) val[(size_t)e * n + i] = pos[3 * at[i] + (size_t)e];
+            for (int e = 0; e < 6; ++e) val[(size_t)(3 + e) * n + i] = info[6 * at[i] + (size_t)e];
+        }
+        return val;
+    };
+    const std::vector<double> pv = planes(pk, pn, ln), fvv = planes(fk, cn, fn);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &h->pri_pt_list, pl.data(), 4 * pl.size() }, { &h->pri_pt_val, pv.data(), 8 * pv.size() },
+        { &h->pri_fr_list, fl.data(), 4 * fl.size() }, { &h->pri_fr_val, fvv.data(), 8 * fvv.size() },
+    };
+    for (auto& u : up) {
+        if (!u.bytes) continue;
+        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+        HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope
+    h->n_pri_pts = (int64_t)pl.size();
+    h->n_pri_frames = (int32_t)fl.size();
+    return SRK_OK;
+}
+// the prior lists of the resident scene for the kernels: NULL without priors, so that neither pass is launched
+static const SrkPrior* position_priors(const srk_ba* h, SrkPrior& p)
+{
+    if (h->n_pri_pts == 0 && h->n_pri_frames == 0) return nullptr;
+    p = SrkPrior{ P<int32_t>(h->pri_pt_list), P<double>(h->pri_pt_val), h->n_pri_pts,
+                  P<int32_t>(h->pri_fr_list), P<double>(h->pri_fr_val), h->n_pri_frames };
+    return &p;
+}
+// the event pairs around the two prior passes (srk_ba_prior_pass_ms), created on first use
+static bool pri_events(srk_ba* h)
+{
+    for (auto& e : h->ev_pri)
+        if (!e && hipEventCreate(&e) != hipSuccess) return false;
+    return true;
 }
 
 // cst_frame_user / cst_point_user (counts checked at the start of the upload) -> the device lists of the resident scene: the
@@ -1506,11 +1673,16 @@ static int phase_error(srk_ba* h, srk_ba::Attempt& a, int which, double* err_hos
     hipStream_t s = a.stream;
     int32_t np = srk_error_partials(d);
     SrkLoss L;
+    SrkPrior pr;
+    const SrkPrior* prior = position_priors(h, pr); // the prior sums of the scene being scored
+    // (one event pair for all attempt slots: with speculation on, srk_ba_prior_pass_ms reports the attempt that recorded last)
+    const bool timed = prior && h->profile_level >= 1 && pri_events(h);
+    if (prior) h->pri_timed[1] = timed;
     srk_launch_error(s, d, P<double>(h->pts[which]), P<double>(h->cam[which]), P<int32_t>(h->obs_frame),
                      P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(a.err_partial), np, a.err_dst,
                      h->jac_fused ? P<int32_t>(h->wg_jmin) : nullptr, with_status ? P<int>(a.info) : nullptr,
                      with_status ? reinterpret_cast<int*>(reinterpret_cast<char*>(a.acc.p) + 8 * 3 * d.Ns) : nullptr,
-                     robust_loss(h, L));
+                     robust_loss(h, L), prior, timed ? &h->ev_pri[2] : nullptr);
     HIPCHK(h, hipGetLastError());
     int rc = no_exchange ? SRK_OK : exchange(h, a, a.err_dst, with_status ? 3 : 1);
     if (rc != SRK_OK) return rc;
@@ -1563,6 +1735,15 @@ static int phase_derivatives(srk_ba* h)
                               P<int64_t>(h->col_ptr), P<int32_t>(h->fobs_pt), P<double>(h->fobs_uv), P<double>(h->Ug), L);
     }
     HIPCHK(h, hipGetLastError());
+    SrkPrior pr;
+    if (const SrkPrior* prior = position_priors(h, pr)) { // 2 L into the blocks, 2 L (x - xbar) into the gradients
+        const bool timed = h->profile_level >= 1 && pri_events(h);
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_pri[0], s));
+        srk_launch_prior_add(s, d, P<double>(h->pts[c]), P<double>(h->cam[c]), *prior, P<double>(h->Vg), P<double>(h->Ug));
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_pri[1], s));
+        h->pri_timed[0] = timed;
+        HIPCHK(h, hipGetLastError());
+    }
     if (h->n_cst_pts > 0) { // constant landmarks: identity block, zero gradient, zero point-frame blocks
         const bool timed = h->profile_level >= 1 && cst_events(h);
         if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[0], s));
@@ -3296,6 +3477,152 @@ int srk_ba_constant_pass_ms(srk_ba* h, double* points_ms, double* frames_ms)
         if (h->cst_timed[k] && hipEventElapsedTime(&ms, h->ev_cst[2 * k], h->ev_cst[2 * k + 1]) != hipSuccess) ms = 0;
         double* out = k == 0 ? points_ms : frames_ms;
         if (out) *out = h->cst_timed[k] ? (double)ms : 0.0;
+    }
+    return SRK_OK;
+}
+// position priors.  Next upload.
+static const char* check_prior_values(int64_t n, const double* pos, const double* info)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        for (int e = 0; e < 3; ++e)
+            if (!std::isfinite(pos[3 * i + e])) return "position priors: a position is not finite";
+        const double* l = info + 6 * i;
+        double m = 0;
+        for (int e = 0; e < 6; ++e) {
+            if (!std::isfinite(l[e])) return "position priors: an information matrix is not finite";
+            m = std::max(m, std::fabs(l[e]));
+        }
+        // positive semi-definite: every principal minor >= 0 (up to the rounding of a rank-deficient matrix)
+        const double xx = l[0], xy = l[1], xz = l[2], yy = l[3], yz = l[4], zz = l[5];
+        const double t2 = 1e-12 * m * m, t3 = 1e-12 * m * m * m;
+        const double det = xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz);
+        if (xx < 0 || yy < 0 || zz < 0 || xx * yy - xy * xy < -t2 || xx * zz - xz * xz < -t2 || yy * zz - yz * yz < -t2 || det < -t3)
+            return "position priors: an information matrix is not positive semi-definite";
+    }
+    return nullptr;
+}
+int srk_ba_set_position_priors(srk_ba* h, int64_t n_point_priors, const int64_t* point_index, const double* point_pos,
+                               const double* point_info, int32_t n_frame_priors, const int32_t* frame_index,
+                               const double* frame_centre, const double* frame_info, int keep_gauge)
+{
+    if (!h) return SRK_E_ARGS;
+    if (n_point_priors == 0 && n_frame_priors == 0) {
+        h->pri_set = false;
+        h->pri_keep_gauge = 1;
+        h->pri_pt_idx.clear(); h->pri_pt_pos.clear(); h->pri_pt_info.clear();
+        h->pri_fr_idx.clear(); h->pri_fr_pos.clear(); h->pri_fr_info.clear();
+        return SRK_OK;
+    }
+    if (keep_gauge != 0 && keep_gauge != 1) { h->last_error = "position priors: keep_gauge must be 0 or 1"; return SRK_E_ARGS; }
+    if (n_point_priors < 0 || n_frame_priors < 0) { h->last_error = "position priors: negative count"; return SRK_E_ARGS; }
+    if ((n_point_priors > 0 && (!point_index || !point_pos || !point_info)) || (n_frame_priors > 0 && (!frame_index || !frame_centre || !frame_info))) {
+        h->last_error = "position priors: null array";
+        return SRK_E_ARGS;
+    }
+    if (const char* e = prior_conflict(true, !h->igroup_user.empty(), h->world)) { h->last_error = e; return SRK_E_ARGS; }
+    for (int64_t i = 0; i < n_point_priors; ++i)
+        if (point_index[i] < 0 || point_index[i] > 2147483000LL || (i > 0 && point_index[i - 1] >= point_index[i])) {
+            h->last_error = "position priors: landmark indices must be non-negative and strictly ascending";
+            return SRK_E_ARGS;
+        }
+    for (int32_t i = 0; i < n_frame_priors; ++i)
+        if (frame_index[i] < 0 || (i > 0 && frame_index[i - 1] >= frame_index[i])) {
+            h->last_error = "position priors: frame indices must be non-negative and strictly ascending";
+            return SRK_E_ARGS;
+        }
+    const char* e = check_prior_values(n_point_priors, point_pos, point_info);
+    if (!e) e = check_prior_values(n_frame_priors, frame_centre, frame_info);
+    if (e) { h->last_error = e; return SRK_E_ARGS; }
+    h->pri_pt_idx.assign(point_index, point_index + n_point_priors);
+    h->pri_pt_pos.assign(point_pos, point_pos + 3 * n_point_priors);
+    h->pri_pt_info.assign(point_info, point_info + 6 * n_point_priors);
+    h->pri_fr_idx.assign(frame_index, frame_index + n_frame_priors);
+    h->pri_fr_pos.assign(frame_centre, frame_centre + 3 * (int64_t)n_frame_priors);
+    h->pri_fr_info.assign(frame_info, frame_info + 6 * (int64_t)n_frame_priors);
+    h->pri_keep_gauge = keep_gauge;
+    h->pri_set = true;
+    return SRK_OK;
+}
+int srk_ba_position_prior_counts(srk_ba* h, int64_t* n_point_priors, int32_t* n_frame_priors)
+{
+    if (!h) return SRK_E_ARGS;
+    if (n_point_priors) *n_point_priors = (int64_t)h->pri_pt_idx.size();
+    if (n_frame_priors) *n_frame_priors = (int32_t)h->pri_fr_idx.size();
+    return h->pri_set ? 1 : 0;
+}
+int srk_ba_position_priors(srk_ba* h, int64_t* point_index, double* point_pos, double* point_info, int32_t* frame_index,
+                           double* frame_centre, double* frame_info, int* keep_gauge)
+{
+    if (!h) return SRK_E_ARGS;
+    auto out = [](auto* dst, const auto& v) {
+        if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
+    };
+    out(point_index, h->pri_pt_idx); out(point_pos, h->pri_pt_pos); out(point_info, h->pri_pt_info);
+    out(frame_index, h->pri_fr_idx); out(frame_centre, h->pri_fr_pos); out(frame_info, h->pri_fr_info);
+    if (keep_gauge) *keep_gauge = h->pri_keep_gauge;
+    return h->pri_set ? 1 : 0;
+}
+int srk_ba_prior_error(srk_ba* h, double* e_points, double* e_frames)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    if (e_points) *e_points = 0;
+    if (e_frames) *e_frames = 0;
+    SrkPrior pr;
+    const SrkPrior* prior = position_priors(h, pr);
+    if (!prior) return SRK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    HIPCHK(h, hipStreamSynchronize(s));
+    const int32_t nb = srk_prior_partials(pr.n_pts, pr.n_frames);
+    DevBuf part;
+    int rc = dev_alloc(h, part, 8 * ((size_t)nb + 2));
+    if (rc != SRK_OK) return rc;
+    double out2[2] = { 0, 0 };
+    srk_launch_prior_error(s, P<double>(h->pts[h->cur]), P<double>(h->cam[h->cur]), pr, P<double>(part), P<double>(part) + nb);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out2, P<double>(part) + nb, 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    dev_free(part);
+    HIPCHK(h, e);
+    if (e_points) *e_points = out2[0];
+    if (e_frames) *e_frames = out2[1];
+    return SRK_OK;
+}
+int srk_ba_prior_residuals(srk_ba* h, double* d_points, double* d_frames)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    // the offsets belong to the setting the resident scene was uploaded with: a setter call since then has not reached the
+    // scene (srk_ba_prior_error still sums the uploaded lists), so the two must not be mixed
+    if (h->app_pt_idx != h->pri_pt_idx || h->app_fr_idx != h->pri_fr_idx || h->app_pt_pos != h->pri_pt_pos || h->app_fr_pos != h->pri_fr_pos) {
+        h->last_error = "prior_residuals: the position priors were changed after the upload; upload the scene again";
+        return SRK_E_STATE;
+    }
+    if (h->app_pt_idx.empty() && h->app_fr_idx.empty()) return SRK_OK;
+    const SrkDims& d = h->d;
+    std::vector<double> p((size_t)(3 * d.N)), R((size_t)(9 * (int64_t)d.M)), T((size_t)(3 * (int64_t)d.M));
+    int rc = srk_ba_download_scene(h, p.data(), R.data(), T.data(), 1); // the caller's world coordinates
+    if (rc != SRK_OK) return rc;
+    for (size_t k = 0; d_points && k < h->app_pt_idx.size(); ++k)
+        for (int e = 0; e < 3; ++e) d_points[3 * k + e] = p[(size_t)(3 * h->app_pt_idx[k] + e)] - h->app_pt_pos[3 * k + e];
+    for (size_t k = 0; d_frames && k < h->app_fr_idx.size(); ++k) {
+        const double* r = &R[9 * (size_t)h->app_fr_idx[k]];
+        const double* t = &T[3 * (size_t)h->app_fr_idx[k]];
+        for (int e = 0; e < 3; ++e) d_frames[3 * k + e] = -(r[e] * t[0] + r[3 + e] * t[1] + r[6 + e] * t[2]) - h->app_fr_pos[3 * k + e];
+    }
+    return SRK_OK;
+}
+int srk_ba_prior_pass_ms(srk_ba* h, double* derivative_ms, double* error_ms)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
+    for (int sl = 1; sl < SRK_SLOTS; ++sl)
+        if (h->att[sl].stream) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
+    for (int k = 0; k < 2; ++k) {
+        float ms = 0;
+        if (h->pri_timed[k] && hipEventElapsedTime(&ms, h->ev_pri[2 * k], h->ev_pri[2 * k + 1]) != hipSuccess) ms = 0;
+        double* out = k == 0 ? derivative_ms : error_ms;
+        if (out) *out = h->pri_timed[k] ? (double)ms : 0.0;
     }
     return SRK_OK;
 }

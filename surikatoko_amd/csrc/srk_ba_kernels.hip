@@ -2813,29 +2813,93 @@ int32_t srk_error_partials(const SrkDims& d)
 }
 int64_t srk_error_partials_staged(const SrkDims& d) { return d.O > 0 ? (d.O + SRK_JF_OBS - 1) / SRK_JF_OBS : 1; }
 
+// ------------------------------------------------------------------ position priors: the energy pass
+// (srk_ba_set_position_priors)
+// the centre C = -R^T T of a frame from its camera pack (0-8 R, 9-11 T)
+__device__ __forceinline__ void prior_centre(const double* __restrict__ c, double C[3])
+{
+    for (int e = 0; e < 3; ++e) C[e] = -(c[e] * c[9] + c[3 + e] * c[10] + c[6 + e] * c[11]);
+}
+// prior i of a list of n: the offset dx = x - xbar, and the information matrix
+__device__ __forceinline__ void prior_load(const double* __restrict__ val, int64_t n, int64_t i, const double x[3], double dx[3], double L[6])
+{
+    for (int e = 0; e < 3; ++e) dx[e] = x[e] - val[e * n + i];
+    for (int e = 0; e < 6; ++e) L[e] = val[(3 + e) * n + i];
+}
+// L dx for L = [xx xy xz yy yz zz]
+__device__ __forceinline__ void prior_mul(const double L[6], const double dx[3], double y[3])
+{
+    y[0] = L[0] * dx[0] + L[1] * dx[1] + L[2] * dx[2];
+    y[1] = L[1] * dx[0] + L[3] * dx[1] + L[4] * dx[2];
+    y[2] = L[2] * dx[0] + L[4] * dx[1] + L[5] * dx[2];
+}
+// Block b < nbp sums the landmark priors 256 b .. 256 b + 255, block nbp + b the frame priors 256 b ..: one lane per prior, the
+// block's sum in the fixed order of err_block_sum, one partial per block -- no atomics, the same bits from run to run.
+__global__ __launch_bounds__(256) void k_prior_error(const double* __restrict__ pts, const double* __restrict__ cam, SrkPrior p,
+                                                     int32_t nbp, double* __restrict__ partial)
+{
+    double sum = 0, x[3], dx[3], L[6], y[3];
+    bool have = false;
+    if ((int32_t)blockIdx.x < nbp) {
+        const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+        if (i < p.n_pts) {
+            const double* X = pts + 3 * (int64_t)p.pt_list[i];
+            x[0] = X[0]; x[1] = X[1]; x[2] = X[2];
+            prior_load(p.pt_val, p.n_pts, i, x, dx, L);
+            have = true;
+        }
+    } else {
+        const int64_t i = (int64_t)((int32_t)blockIdx.x - nbp) * 256 + threadIdx.x;
+        if (i < p.n_frames) {
+            prior_centre(cam + (int64_t)SRK_CAM_PACK * p.fr_list[i], x);
+            prior_load(p.fr_val, p.n_frames, i, x, dx, L);
+            have = true;
+        }
+    }
+    if (have) {
+        prior_mul(L, dx, y);
+        sum = dx[0] * y[0] + dx[1] * y[1] + dx[2] * y[2];
+    }
+    err_block_sum(sum, partial + blockIdx.x);
+}
+static int32_t launch_prior_partials(hipStream_t s, const double* pts, const double* cam, const SrkPrior& p, double* partial,
+                                     const hipEvent_t* ev)
+{
+    const int32_t nbp = (int32_t)((p.n_pts + 255) / 256), nb = srk_prior_partials(p.n_pts, p.n_frames);
+    if (ev) (void)hipEventRecord(ev[0], s);
+    hipLaunchKernelGGL(k_prior_error, dim3((unsigned)nb), dim3(256), 0, s, pts, cam, p, nbp, partial);
+    if (ev) (void)hipEventRecord(ev[1], s);
+    return nb;
+}
+void srk_launch_prior_error(hipStream_t s, const double* pts, const double* cam, const SrkPrior& p, double* partial, double* out2)
+{
+    const int32_t nbp = (int32_t)((p.n_pts + 255) / 256), nb = launch_prior_partials(s, pts, cam, p, partial, nullptr);
+    hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, nbp, partial, out2, (int*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, nb - nbp, partial + nbp, out2 + 1, (int*)nullptr, (int*)nullptr);
+}
+
 void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                       const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* partial,
-                      int32_t n_partial, double* err_out, const int32_t* wg_jmin, int* info, int* info2, const SrkLoss* loss)
+                      int32_t n_partial, double* err_out, const int32_t* wg_jmin, int* info, int* info2, const SrkLoss* loss,
+                      const SrkPrior* prior, const hipEvent_t* prior_ev)
 {
     const bool robust = srk_robust_side(loss);
-    if (wg_jmin && d.O > 0) { // staged cameras: one partial sum per run of SRK_JF_OBS observations
-        const int64_t nb = srk_error_partials_staged(d);
-        if (robust)
-            hipLaunchKernelGGL(k_error_staged_robust, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                               wg_jmin, partial, *loss);
-        else
-            hipLaunchKernelGGL(k_error_staged, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, wg_jmin,
-                               partial);
-        hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, (int32_t)nb, partial, err_out, info, info2);
-        return;
-    }
-    if (robust)
-        hipLaunchKernelGGL(k_error_robust, dim3((unsigned)n_partial), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
-                           partial, *loss);
-    else
-        hipLaunchKernelGGL(k_error, dim3((unsigned)n_partial), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+    const bool staged = wg_jmin && d.O > 0; // staged cameras: one partial sum per run of SRK_JF_OBS observations
+    int32_t nb = staged ? (int32_t)srk_error_partials_staged(d) : n_partial;
+    if (staged && robust)
+        hipLaunchKernelGGL(k_error_staged_robust, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv,
+                           wg_jmin, partial, *loss);
+    else if (staged)
+        hipLaunchKernelGGL(k_error_staged, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, wg_jmin,
                            partial);
-    hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, n_partial, partial, err_out, info, info2);
+    else if (robust)
+        hipLaunchKernelGGL(k_error_robust, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, partial,
+                           *loss);
+    else
+        hipLaunchKernelGGL(k_error, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, partial);
+    // position priors: their partials behind the observation partials, one final sum over both
+    if (prior) nb += launch_prior_partials(s, pts, cam, *prior, partial + nb, prior_ev);
+    hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, nb, partial, err_out, info, info2);
 }
 
 void srk_launch_error_score(hipStream_t s, int64_t O, const double* pts, const double* cam, const int32_t* obs_frame,
@@ -3252,4 +3316,49 @@ void srk_launch_const_cam_keep(hipStream_t s, const int32_t* frames, int32_t n_f
 {
     if (n_frames <= 0) return;
     hipLaunchKernelGGL(k_const_cam_keep, dim3((unsigned)n_frames), dim3(64), 0, s, frames, R, T, pack, Rn, Tn, packn);
+}
+
+// ------------------------------------------------------------------ position priors: the derivative-side pass
+// (srk_ba_set_position_priors).  Behind the derivative kernels (in deterministic mode behind their ordered
+// gather) and before k_const_points.  Lane t < n_pts: landmark prior t adds 2 L to the six block planes of Vg and
+// 2 L (X - Xbar) to its three gradient planes.  Lane n_pts + t: frame prior t forms the centre C from the current pose and adds
+// 2 L to the upper-triangle entries of the [Tx Ty Tz] part of the frame's block in Ug (variables 4..6 of ten, 0..2 of six) and
+// 2 L (C - Cbar) to those gradient entries.  Indices are unique, so every entry has one owner: no atomics.
+__global__ __launch_bounds__(256) void k_prior_add(SrkDims d, const double* __restrict__ pts, const double* __restrict__ cam,
+                                                   SrkPrior p, double* __restrict__ Vg, double* __restrict__ Ug)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double x[3], dx[3], L[6], y[3];
+    if (t < p.n_pts) {
+        const int64_t pt = p.pt_list[t];
+        if (pt < 0 || pt >= d.N) return;
+        for (int e = 0; e < 3; ++e) x[e] = pts[3 * pt + e];
+        prior_load(p.pt_val, p.n_pts, t, x, dx, L);
+        prior_mul(L, dx, y);
+        for (int e = 0; e < 6; ++e) Vg[(int64_t)e * d.Ns + pt] += 2.0 * L[e];
+        for (int e = 0; e < 3; ++e) Vg[(int64_t)(6 + e) * d.Ns + pt] += 2.0 * y[e];
+        return;
+    }
+    const int64_t f = t - p.n_pts;
+    if (f >= p.n_frames) return;
+    const int64_t j = p.fr_list[f];
+    if (j < 0 || j >= d.M) return;
+    prior_centre(cam + (int64_t)SRK_CAM_PACK * j, x);
+    prior_load(p.fr_val, p.n_frames, f, x, dx, L);
+    prior_mul(L, dx, y);
+    const int fv = d.fv, ut = fv * (fv + 1) / 2, t0 = 4 - SRK_FV_OFF(fv); // first translation variable of the frame
+    double* u = Ug + (int64_t)SRK_UGS(fv) * j;
+    int k = 0;
+    for (int a = 0; a < 3; ++a) {
+        const int va = t0 + a, row = va * fv - va * (va - 1) / 2; // row va of the upper triangle starts at its diagonal entry
+        for (int b = a; b < 3; ++b, ++k) u[row + (b - a)] += 2.0 * L[k];
+        u[ut + va] += 2.0 * y[a];
+    }
+}
+void srk_launch_prior_add(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const SrkPrior& p, double* Vg,
+                          double* Ug)
+{
+    const int64_t n = p.n_pts + p.n_frames;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_prior_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, pts, cam, p, Vg, Ug);
 }

@@ -156,6 +156,25 @@ void srk_launch_const_frames(hipStream_t s, const SrkDims& d, const int32_t* fra
 // after srk_launch_cam_apply: the trial pose and camera pack of the listed frames are those of the current scene, bit for bit
 void srk_launch_const_cam_keep(hipStream_t s, const int32_t* frames, int32_t n_frames, const double* R, const double* T,
                                const double* pack, double* Rn, double* Tn, double* packn);
+// position priors (srk_ba_set_position_priors): the lists of the resident scene.  Values as SoA planes
+// val[k n + i], k = 0..2 the prior position (normalised world), 3..8 the information matrix xx xy xz yy yz zz.  Every index
+// appears once, so each entry the passes touch has one owner.
+struct SrkPrior {
+    const int32_t* pt_list;  // landmarks with a prior, internal order, ascending
+    const double* pt_val;    // [9][n_pts]
+    int64_t n_pts;
+    const int32_t* fr_list;  // internal frames with a prior, ascending
+    const double* fr_val;    // [9][n_frames]
+    int32_t n_frames;
+};
+// partial sums the prior energy pass writes: one per 256 landmark priors, then one per 256 frame priors
+inline int32_t srk_prior_partials(int64_t n_pts, int64_t n_frames) { return (int32_t)((n_pts + 255) / 256 + (n_frames + 255) / 256); }
+// behind the derivative kernels, before srk_launch_const_points: 2 L into the landmark blocks and the [Tx Ty Tz] part of the
+// frame blocks, 2 L (X - Xbar) / 2 L (C - Cbar) into the gradients.  Launched only with priors.
+void srk_launch_prior_add(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const SrkPrior& p, double* Vg,
+                          double* Ug);
+// the two prior sums of a scene on their own (srk_ba_prior_error): partial [srk_prior_partials], out2 = {landmarks, frames}
+void srk_launch_prior_error(hipStream_t s, const double* pts, const double* cam, const SrkPrior& p, double* partial, double* out2);
 void srk_launch_backsub(hipStream_t s, const SrkDims& d, double c, const int32_t* obs_frame, const int32_t* obs_pt,
                         const double* W, const double* Vg, const double* dc, double* acc, const double* pts,
                         double* pts_trial, double* dx);
@@ -167,7 +186,10 @@ void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const 
                       int32_t n_partial, double* err_out,
                       const int32_t* wg_jmin /* fused-Jacobian frame windows, or NULL: gather the cameras */,
                       int* info = nullptr, int* info2 = nullptr /* given: packed into err_out[1..2] and cleared */,
-                      const SrkLoss* loss = nullptr /* given (kind != 0 or information): the sum of rho(q s) instead of s */);
+                      const SrkLoss* loss = nullptr /* given (kind != 0 or information): the sum of rho(q s) instead of s */,
+                      const SrkPrior* prior = nullptr /* given: the prior sums of this scene as srk_prior_partials more partials
+                                                         behind the observation partials, summed with them */,
+                      const hipEvent_t* prior_ev = nullptr /* given: two events recorded around the prior pass */);
 // the IRLS weights w = rho'(s) of the resident scene, one per observation in the internal order (srk_ba_observation_weights)
 void srk_launch_obs_weights(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int32_t* obs_frame,
                             const int32_t* obs_pt, const double* obs_uv, const SrkLoss& loss, double* w);
