@@ -5,11 +5,11 @@ the intrinsic rows and columns are zeroed and their diagonal set to 1, the intri
 of gradE are zeroed.  The two-phase step multiplies the diagonal by (1 + c) (bundle-adj-kanatani.cpp:1819,1831), so the
 intrinsic corrections come out exactly 0 and the rest is the calibrated step; the compact reduced system is the oracle's
 with the intrinsic rows and columns removed (V is point-only, so that is the Schur complement of the 6-variable Hessian).
-The LM loop restates bundle-adj-kanatani.cpp:720-893 with the decisions of orc_compute_inplace.
+The LM loop is lm_ref.loop.
 """
 import numpy as np
 
-import lm_trajectory as lt
+import lm_ref
 
 FV = 6
 INTR = slice(0, 4)  # [fx fy u0 v0] of the 10-variable layout
@@ -59,114 +59,64 @@ def expand_corrections(corr6, N, M):
     return np.concatenate([corr6[:3 * N], f.reshape(-1)])
 
 
+def solve_blocks(orc, so, blocks, c, out, fv=10, want_system=False, skyline=False, sel_rows=None):
+    """the tail of every step(): the oracle's two-phase solve of the blocks (gradE, V, U, W; with fv = 6 restricted) at damping
+    c, by its skyline Cholesky (sel_rows: rows of the inverse, in the fv layout) or its Householder QR.  Adds to out: ok,
+    corr10, corr (fv layout), with sel_rows rows, with want_system S / rhs in the oracle's 10M - 7 numbering (fv = 10) or
+    the compact 6M one with zero gauge rows and columns (fv = 6)."""
+    N, M = so.N, so.M
+    if skyline:
+        sel = sel_rows
+        if fv == 6 and sel_rows is not None:
+            sel = compact_to_reduced(M)[np.asarray(sel_rows)]
+        res = orc.two_phase_skyline(so, *blocks, c, sel_rows=sel)
+        ok, corr = res[0], res[1]
+        if sel is not None:
+            out["rows"] = res[2]
+    elif want_system:
+        ok, corr, S, rhs = orc.two_phase(so, *blocks, c, want_system=True)
+        if fv == 6:
+            idx = compact_to_reduced(M)
+            keep = idx >= 0
+            n = FV * M
+            Sc = np.zeros((n, n))
+            Sc[np.ix_(keep, keep)] = S[np.ix_(idx[keep], idx[keep])]
+            rc = np.zeros(n)
+            rc[keep] = rhs[idx[keep]]
+            S, rhs = Sc, rc
+        out.update(S=S, rhs=rhs)
+    else:
+        ok, corr = orc.two_phase(so, *blocks, c)
+    out.update(ok=ok, corr10=corr, corr=compact_corrections(corr, N, M) if fv == 6 else corr)
+    return out
+
+
 def step(orc, f0, so, c, want_system=False, skyline=False, sel_rows=None):
     """one calibrated attempt at damping c on the (normalised) oracle scene so.  Returns a dict with ok, corr (compact),
     corr10 (10-variable layout, intrinsics 0), the compact blocks, and with want_system the compact system S / rhs
     (gauge rows and columns zero)."""
     N, M = so.N, so.M
     gradE, V, U, W = orc.derivatives(f0, so)
-    g, V, Ur, Wr = restrict(gradE, V, U, W, N)
     out = dict(gradE10=gradE, U10=U, W10=W, V=V,
                grad=np.concatenate([gradE[:3 * N], gradE[3 * N:].reshape(M, 10)[:, 4:].reshape(-1)]),
                U=U[:, 4:, 4:].copy(), W=W[:, :, 4:].copy())
-    idx = compact_to_reduced(M)
-    if skyline:
-        sel = None if sel_rows is None else idx[np.asarray(sel_rows)]
-        res = orc.two_phase_skyline(so, g, V, Ur, Wr, c, sel_rows=sel)
-        ok, corr = res[0], res[1]
-        if sel is not None:
-            out["rows"] = res[2]
-    elif want_system:
-        ok, corr, S, rhs = orc.two_phase(so, g, V, Ur, Wr, c, want_system=True)
-        keep = idx >= 0
-        n = FV * M
-        Sc = np.zeros((n, n))
-        Sc[np.ix_(keep, keep)] = S[np.ix_(idx[keep], idx[keep])]
-        rc = np.zeros(n)
-        rc[keep] = rhs[idx[keep]]
-        out.update(S=Sc, rhs=rc)
-    else:
-        ok, corr = orc.two_phase(so, g, V, Ur, Wr, c)
-    out.update(ok=ok, corr10=corr, corr=compact_corrections(corr, N, M))
-    return out
-
-
-class Report:
-    pass
+    return solve_blocks(orc, so, restrict(gradE, V, U, W, N), c, out, FV, want_system, skyline, sel_rows)
 
 
 def compute_inplace(orc, f0, so, allowed_err_change=None, max_hessian_factor=None, max_iterations=0, skyline=False):
-    """the LM loop of bundle-adj-kanatani.cpp:720-893 (as orc_compute_inplace) around the calibrated step; so is changed in
-    place (normalised, optimised, normalisation reverted).  skyline: the oracle's skyline Cholesky instead of its
-    Householder QR (large scenes).  Returns (rc, report): rc 0 = true, 1 = false."""
-    rep = Report()
-    rep.status, rep.iterations, rep.attempts = 0, 0, 0
-    rep.attempts_per_iteration = []
-    rep.log = lt.AttemptLog().arrays()
-    log = lt.AttemptLog()
+    """lm_ref.loop around the calibrated step; so is changed in place (normalised, optimised, normalisation reverted).
+    skyline: the oracle's skyline Cholesky instead of its Householder QR (large scenes).  Returns (rc, report): rc 0 = true,
+    1 = false."""
+    rep = lm_ref.Report()
     ok, nrm = orc.normalize(so)
     if not ok:
         return 1, rep
-    N, M = so.N, so.M
-    hessian_factor = float(np.float32(0.0001))  # :723 float literal
-    err_value, _ = orc.reproj_error(f0, so)
-    rep.err_initial = rep.err_final = err_value
-    result_true = False
-    done = False
-    if allowed_err_change is not None and err_value < allowed_err_change:
-        rep.status, result_true, done = 1, True, True
-    while not done:
-        if max_iterations > 0 and rep.iterations >= max_iterations:
-            rep.status, result_true = 5, False
-            break
-        gradE, V, U, W = orc.derivatives(f0, so)
-        g, V, Ur, Wr = restrict(gradE, V, U, W, N)
-        bak = (so.points.copy(), so.cam_R.copy(), so.cam_T.copy())
-        have_prev, err_new_prev, decrease, n_att = False, 0.0, 0, 0
-        while not decrease:
-            rep.attempts += 1
-            n_att += 1
-            if skyline:
-                suc, corr = orc.two_phase_skyline(so, g, V, Ur, Wr, hessian_factor)
-            else:
-                suc, corr = orc.two_phase(so, g, V, Ur, Wr, hessian_factor)
-            if not suc:
-                log.add(rep.iterations, hessian_factor, np.nan, err_value, lt.SOLVE_FAILED)
-                decrease = 2
-                break
-            orc.apply_corrections(so, corr)
-            err_new, _ = orc.reproj_error(f0, so)
-            if err_new - err_value < 0:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.ACCEPTED)
-                decrease = 1
-                break
-            so.points[:], so.cam_R[:], so.cam_T[:] = bak
-            if have_prev and allowed_err_change is not None and abs(err_new - err_new_prev) < allowed_err_change:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.CONVERGED)
-                decrease = 3
-                break
-            used = hessian_factor
-            hessian_factor *= 10
-            if max_hessian_factor is not None and hessian_factor > max_hessian_factor:
-                log.add(rep.iterations, used, err_new, err_value, lt.CAP_OVERFLOW)
-                decrease = 2
-                break
-            log.add(rep.iterations, used, err_new, err_value, lt.REJECTED)
-            err_new_prev, have_prev = err_new, True
-        rep.attempts_per_iteration.append(n_att)
-        if decrease != 1:
-            rep.status = 3 if decrease == 2 else 4
-            result_true = False
-            break
-        rep.iterations += 1
-        change = err_new - err_value
-        rep.err_final = err_new
-        if allowed_err_change is not None and abs(change) < allowed_err_change:
-            rep.status, result_true = 2, True
-            break
-        err_value = err_new
-        hessian_factor /= 10
-    rep.hessian_factor = hessian_factor
-    rep.log = log.arrays()
+    two_phase = orc.two_phase_skyline if skyline else orc.two_phase
+    rc = lm_ref.loop(rep, so, energy=lambda: orc.reproj_error(f0, so)[0],
+                     prepare=lambda: restrict(*orc.derivatives(f0, so), so.N),
+                     solve=lambda blocks, c: two_phase(so, *blocks, c),
+                     apply=lambda corr: orc.apply_corrections(so, corr),
+                     allowed_err_change=allowed_err_change, max_hessian_factor=max_hessian_factor,
+                     max_iterations=max_iterations)
     orc.revert(so, nrm)
-    return (0 if result_true else 1), rep
+    return rc, rep

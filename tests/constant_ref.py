@@ -12,12 +12,12 @@ S = G (1 + c on the diagonal) - sum_i W_i^T (V_i (1 + c on the diagonal))^-1 W_i
 rhs = sum_i W_i^T (V_i (1 + c))^-1 g_i - g_f over all 10 M frame variables in numpy, and solve() solves it densely.
 (With the gauge rows dropped this is orc.two_phase's system: tests/test_constant_cpu.py.)
 
-The LM loop restates bundle-adj-kanatani.cpp:720-893 with the decisions of orc_compute_inplace, as calibrated_ref does.
+The LM loop is lm_ref.loop.
 """
 import numpy as np
 
 import calibrated_ref as cref
-import lm_trajectory as lt
+import lm_ref
 
 
 def flags(sel, n):
@@ -225,86 +225,31 @@ def system_check(S, fixed, bound=1e10):
     return cond
 
 
-class Report:
-    pass
-
-
 def compute_inplace(orc, f0, so, fconst, pconst, keep_gauge, fv=10, allowed_err_change=None, max_hessian_factor=None,
                     max_iterations=0, skyline=False):
-    """the LM loop of bundle-adj-kanatani.cpp:720-893 (as orc_compute_inplace) around the constant-block step; so is changed
-    in place (normalised, optimised, normalisation reverted; the constant blocks' values restored bit for bit from before the
-    normalisation, as srk_ba_compute_inplace leaves them).  skyline (keep_gauge = 1 only): the oracle's skyline Cholesky instead
-    of its Householder QR.  Returns (rc, report): rc 0 = true, 1 = false."""
-    rep = Report()
-    rep.status, rep.iterations, rep.attempts = 0, 0, 0
-    rep.attempts_per_iteration = []
-    rep.log = lt.AttemptLog().arrays()
-    log = lt.AttemptLog()
-    before = (so.points.copy(), so.cam_R.copy(), so.cam_T.copy())
+    """lm_ref.loop around the constant-block step; so is changed in place (normalised, optimised, normalisation reverted; the
+    constant blocks' values restored bit for bit from before the normalisation, as srk_ba_compute_inplace leaves them).
+    skyline (keep_gauge = 1 only): the oracle's skyline Cholesky instead of its Householder QR.  Returns (rc, report):
+    rc 0 = true, 1 = false."""
+    rep = lm_ref.Report()
+    before = (so.points[pconst].copy(), so.cam_R[fconst].copy(), so.cam_T[fconst].copy())
     ok, nrm = orc.normalize(so)
     if not ok:
         return 1, rep
-    hessian_factor = float(np.float32(0.0001))  # :723 float literal
-    err_value, _ = orc.reproj_error(f0, so)
-    rep.err_initial = rep.err_final = err_value
-    result_true = False
-    done = False
-    if allowed_err_change is not None and err_value < allowed_err_change:
-        rep.status, result_true, done = 1, True, True
-    while not done:
-        if max_iterations > 0 and rep.iterations >= max_iterations:
-            rep.status, result_true = 5, False
-            break
-        restricted = restrict_all(so, orc.derivatives(f0, so), fconst, pconst, fv)
-        bak = (so.points.copy(), so.cam_R.copy(), so.cam_T.copy())
-        have_prev, err_new_prev, decrease, n_att = False, 0.0, 0, 0
-        while not decrease:
-            rep.attempts += 1
-            n_att += 1
-            res = step_restricted(orc, so, restricted, hessian_factor, fconst, keep_gauge, fv, skyline=skyline)
-            if not res["ok"]:
-                log.add(rep.iterations, hessian_factor, np.nan, err_value, lt.SOLVE_FAILED)
-                decrease = 2
-                break
-            orc.apply_corrections(so, res["corr"])
-            so.points[pconst] = bak[0][pconst]  # a zero correction leaves a block as it is
-            so.cam_R[fconst] = bak[1][fconst]
-            so.cam_T[fconst] = bak[2][fconst]
-            err_new, _ = orc.reproj_error(f0, so)
-            if err_new - err_value < 0:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.ACCEPTED)
-                decrease = 1
-                break
-            so.points[:], so.cam_R[:], so.cam_T[:] = bak
-            if have_prev and allowed_err_change is not None and abs(err_new - err_new_prev) < allowed_err_change:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.CONVERGED)
-                decrease = 3
-                break
-            used = hessian_factor
-            hessian_factor *= 10
-            if max_hessian_factor is not None and hessian_factor > max_hessian_factor:
-                log.add(rep.iterations, used, err_new, err_value, lt.CAP_OVERFLOW)
-                decrease = 2
-                break
-            log.add(rep.iterations, used, err_new, err_value, lt.REJECTED)
-            err_new_prev, have_prev = err_new, True
-        rep.attempts_per_iteration.append(n_att)
-        if decrease != 1:
-            rep.status = 3 if decrease == 2 else 4
-            result_true = False
-            break
-        rep.iterations += 1
-        change = err_new - err_value
-        rep.err_final = err_new
-        if allowed_err_change is not None and abs(change) < allowed_err_change:
-            rep.status, result_true = 2, True
-            break
-        err_value = err_new
-        hessian_factor /= 10
-    rep.hessian_factor = hessian_factor
-    rep.log = log.arrays()
+    held = (so.points[pconst].copy(), so.cam_R[fconst].copy(), so.cam_T[fconst].copy())
+
+    def solve(restricted, c):
+        res = step_restricted(orc, so, restricted, c, fconst, keep_gauge, fv, skyline=skyline)
+        return res["ok"], res["corr"]
+
+    def apply(corr):
+        orc.apply_corrections(so, corr)
+        so.points[pconst], so.cam_R[fconst], so.cam_T[fconst] = held  # a zero correction leaves a block as it is
+
+    rc = lm_ref.loop(rep, so, energy=lambda: orc.reproj_error(f0, so)[0],
+                     prepare=lambda: restrict_all(so, orc.derivatives(f0, so), fconst, pconst, fv), solve=solve, apply=apply,
+                     allowed_err_change=allowed_err_change, max_hessian_factor=max_hessian_factor,
+                     max_iterations=max_iterations)
     orc.revert(so, nrm)
-    so.points[pconst] = before[0][pconst]
-    so.cam_R[fconst] = before[1][fconst]
-    so.cam_T[fconst] = before[2][fconst]
-    return (0 if result_true else 1), rep
+    so.points[pconst], so.cam_R[fconst], so.cam_T[fconst] = before
+    return rc, rep

@@ -1,7 +1,8 @@
 """Attempt-by-attempt comparison of a Levenberg-Marquardt run with a reference loop.
 
-The reference loops (oracle.compute_inplace(..., want_log=True) and the yardstick loops calibrated_ref, robust_ref and
-shared_k_ref) record every attempt in one format, a dict of equal-length numpy arrays:
+The reference loops (oracle.compute_inplace(..., want_log=True) and lm_ref.loop, the one Python loop behind the
+compute_inplace of calibrated_ref, robust_ref, weighted_ref, shared_k_ref, constant_ref and prior_ref) record every attempt in
+one format, a dict of equal-length numpy arrays:
 
   iteration  int64    accepted iterations before this attempt (the iteration the attempt belongs to)
   factor     float64  the damping factor (hessian_factor) the attempt used

@@ -9,13 +9,12 @@ to the direct translation -R^T T, the centre, and the rotation update leaves it 
 entries.  Everything here is numpy on priors that are already in the coordinates of the scene they are used with.
 
 The step is then the one of tests/constant_ref.py: orc.two_phase with the gauge kept, its dense numpy Schur complement over
-all 10 M frame variables without it.  The LM loop restates bundle-adj-kanatani.cpp:720-893 with the decisions of
-orc_compute_inplace, as calibrated_ref.compute_inplace and constant_ref.compute_inplace do.
+all 10 M frame variables without it.  The LM loop is lm_ref.loop.
 """
 import numpy as np
 
 import constant_ref as kref
-import lm_trajectory as lt
+import lm_ref
 
 
 def full(info6):
@@ -114,86 +113,31 @@ def step(orc, f0, so, c, pri, keep_gauge, fv=10, fconst=None, pconst=None, want_
     return out
 
 
-class Report:
-    pass
-
-
 def compute_inplace(orc, f0, so, pri_world, keep_gauge, fv=10, allowed_err_change=None, max_hessian_factor=None,
                     max_iterations=0, obs_energy=None, derivatives=None):
-    """the LM loop of bundle-adj-kanatani.cpp:720-893 (as orc_compute_inplace) around the step with priors.  pri_world: the
-    priors in the coordinates of so as given; so is changed in place (normalised, optimised, normalisation reverted).
-    Returns (rc, report): rc 0 = true, 1 = false."""
-    rep = Report()
-    rep.status, rep.iterations, rep.attempts = 0, 0, 0
-    rep.attempts_per_iteration = []
-    rep.log = lt.AttemptLog().arrays()
-    log = lt.AttemptLog()
+    """lm_ref.loop around the step with priors.  pri_world: the priors in the coordinates of so as given; so is changed in
+    place (normalised, optimised, normalisation reverted).  Returns (rc, report): rc 0 = true, 1 = false."""
+    rep = lm_ref.Report()
     ok, nrm = orc.normalize(so)
     if not ok:
         return 1, rep
     pri = normalised(pri_world, nrm)
     fconst, pconst = np.zeros(so.M, dtype=bool), np.zeros(so.N, dtype=bool)
 
-    def total(s):
-        e = obs_energy(s) if obs_energy else orc.reproj_error(f0, s)[0]
-        return e + sum(energy(pri, s))
+    def total():
+        e = obs_energy(so) if obs_energy else orc.reproj_error(f0, so)[0]
+        return e + sum(energy(pri, so))
 
-    hessian_factor = float(np.float32(0.0001))  # :723 float literal
-    err_value = total(so)
-    rep.err_initial = rep.err_final = err_value
-    result_true = False
-    done = False
-    if allowed_err_change is not None and err_value < allowed_err_change:
-        rep.status, result_true, done = 1, True, True
-    while not done:
-        if max_iterations > 0 and rep.iterations >= max_iterations:
-            rep.status, result_true = 5, False
-            break
+    def prepare():
         base = orc.derivatives(f0, so) if derivatives is None else derivatives(so)
-        restricted = kref.restrict_all(so, add_terms(base[:4], so, pri), fconst, pconst, fv)
-        bak = (so.points.copy(), so.cam_R.copy(), so.cam_T.copy())
-        have_prev, err_new_prev, decrease, n_att = False, 0.0, 0, 0
-        while not decrease:
-            rep.attempts += 1
-            n_att += 1
-            res = kref.step_restricted(orc, so, restricted, hessian_factor, fconst, keep_gauge, fv)
-            if not res["ok"]:
-                log.add(rep.iterations, hessian_factor, np.nan, err_value, lt.SOLVE_FAILED)
-                decrease = 2
-                break
-            orc.apply_corrections(so, res["corr"])
-            err_new = total(so)
-            if err_new - err_value < 0:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.ACCEPTED)
-                decrease = 1
-                break
-            so.points[:], so.cam_R[:], so.cam_T[:] = bak
-            if have_prev and allowed_err_change is not None and abs(err_new - err_new_prev) < allowed_err_change:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.CONVERGED)
-                decrease = 3
-                break
-            used = hessian_factor
-            hessian_factor *= 10
-            if max_hessian_factor is not None and hessian_factor > max_hessian_factor:
-                log.add(rep.iterations, used, err_new, err_value, lt.CAP_OVERFLOW)
-                decrease = 2
-                break
-            log.add(rep.iterations, used, err_new, err_value, lt.REJECTED)
-            err_new_prev, have_prev = err_new, True
-        rep.attempts_per_iteration.append(n_att)
-        if decrease != 1:
-            rep.status = 3 if decrease == 2 else 4
-            result_true = False
-            break
-        rep.iterations += 1
-        change = err_new - err_value
-        rep.err_final = err_new
-        if allowed_err_change is not None and abs(change) < allowed_err_change:
-            rep.status, result_true = 2, True
-            break
-        err_value = err_new
-        hessian_factor /= 10
-    rep.hessian_factor = hessian_factor
-    rep.log = log.arrays()
+        return kref.restrict_all(so, add_terms(base[:4], so, pri), fconst, pconst, fv)
+
+    def solve(restricted, c):
+        res = kref.step_restricted(orc, so, restricted, c, fconst, keep_gauge, fv)
+        return res["ok"], res["corr"]
+
+    rc = lm_ref.loop(rep, so, energy=total, prepare=prepare, solve=solve, apply=lambda corr: orc.apply_corrections(so, corr),
+                     allowed_err_change=allowed_err_change, max_hessian_factor=max_hessian_factor,
+                     max_iterations=max_iterations)
     orc.revert(so, nrm)
-    return (0 if result_true else 1), rep
+    return rc, rep

@@ -5,14 +5,16 @@ observation's landmark and frame (the library's variable order) are formed in nu
 A_v / r^2, and likewise B_v / r^2 for q/r (bundle-adj-kanatani.cpp:1450-1525).  With s = ex^2 + ey^2, rho the loss and
 w = rho'(s), the weighted Gauss-Newton blocks are  V, U, W = sum_o w_o 2 J_o^T J_o  and the gradient sum_o w_o 2 J_o^T e_o,
 the exact gradient of E = sum_o rho(s_o).  At w = 1 these are the oracle's orc_derivatives.  The step is the oracle's own
-two_phase / two_phase_skyline on those blocks; the LM loop restates bundle-adj-kanatani.cpp:720-893 on E.  Fixed intrinsics
+two_phase / two_phase_skyline on those blocks (calibrated_ref.solve_blocks); the LM loop is lm_ref.loop on E.  Fixed intrinsics
 (FV = 6): the blocks restricted with calibrated_ref.restrict.
+
+Every function takes an optional per-observation information q (tests/weighted_ref.py): s becomes q s and the weight of the
+blocks q rho'(q s).  q = None is unit information; 1.0 * x is exact, so the values are those without q bit for bit.
 """
 import numpy as np
 
-import lm_trajectory as lt
-
 import calibrated_ref as cref
+import lm_ref
 
 NONE, HUBER, CAUCHY = 0, 1, 2
 KINDS = {None: NONE, "huber": HUBER, "cauchy": CAUCHY}
@@ -60,20 +62,26 @@ def residuals(f0, so, sl=slice(None)):
     return pqr[:, 0] / pqr[:, 2] - uv[:, 0] / f0, pqr[:, 1] / pqr[:, 2] - uv[:, 1] / f0
 
 
-def energy(f0, so, kind=NONE, delta=None):
-    """E = sum_o rho(s_o) (delta in pixels)"""
+def _information(so, q):
+    return np.ones(so.O) if q is None else np.asarray(q, dtype=np.float64)
+
+
+def energy(f0, so, kind=NONE, delta=None, q=None):
+    """E = sum_o rho(q_o s_o) (delta in pixels; q = None: unit information, 1.0 * s is exact)"""
     d = (delta / f0) if kind != NONE else 0.0
+    q = _information(so, q)
     e = 0.0
     for a in range(0, so.O, CHUNK):
-        ex, ey = residuals(f0, so, slice(a, min(a + CHUNK, so.O)))
-        e += float(rho_w(ex * ex + ey * ey, kind, d)[0].sum())
+        sl = slice(a, min(a + CHUNK, so.O))
+        ex, ey = residuals(f0, so, sl)
+        e += float(rho_w(q[sl] * (ex * ex + ey * ey), kind, d)[0].sum())
     return e
 
 
-def weights(f0, so, kind=NONE, delta=None):
-    """w_o of every observation (caller's order)"""
+def weights(f0, so, kind=NONE, delta=None, q=None):
+    """the loss's factor w_o = rho'(q_o s_o) of every observation (caller's order)"""
     ex, ey = residuals(f0, so)
-    return rho_w(ex * ex + ey * ey, kind, (delta / f0) if kind != NONE else 0.0)[1]
+    return rho_w(_information(so, q) * (ex * ex + ey * ey), kind, (delta / f0) if kind != NONE else 0.0)[1]
 
 
 def jacobian(f0, so, sl=slice(None)):
@@ -116,10 +124,12 @@ def jacobian(f0, so, sl=slice(None)):
     return ex, ey, A, B, r
 
 
-def derivatives(f0, so, kind=NONE, delta=None):
-    """weighted (gradE [3N + 10M], V [N,3,3], U [M,10,10], W [O,3,10]) in the oracle's layout, and the weights"""
+def derivatives(f0, so, kind=NONE, delta=None, q=None):
+    """weighted (gradE [3N + 10M], V [N,3,3], U [M,10,10], W [O,3,10]) in the oracle's layout, and the loss's factors
+    rho'(q s); the blocks carry w_eff = q rho'(q s)"""
     N, M, O = so.N, so.M, so.O
     d = (delta / f0) if kind != NONE else 0.0
+    q = _information(so, q)
     gradE = np.zeros(3 * N + 10 * M)
     V = np.zeros((N, 3, 3))
     U = np.zeros((M, 10, 10))
@@ -129,8 +139,9 @@ def derivatives(f0, so, kind=NONE, delta=None):
     for a in range(0, O, CHUNK):
         sl = slice(a, min(a + CHUNK, O))
         ex, ey, A, B, r = jacobian(f0, so, sl)
-        _, w = rho_w(ex * ex + ey * ey, kind, d)
-        wts[sl] = w
+        _, wl = rho_w(q[sl] * (ex * ex + ey * ey), kind, d)
+        wts[sl] = wl
+        w = q[sl] * wl
         ir2 = 1.0 / (r * r)
         Jx, Jy = A * ir2[:, None], B * ir2[:, None]  # d ex / dv, d ey / dv
         g = 2.0 * w[:, None] * (ex[:, None] * Jx + ey[:, None] * Jy)
@@ -145,127 +156,41 @@ def derivatives(f0, so, kind=NONE, delta=None):
     return gradE, V, U, W, wts
 
 
-def step(orc, f0, so, c, kind=NONE, delta=None, fv=10, want_system=False, skyline=False, sel_rows=None):
+def step(orc, f0, so, c, kind=NONE, delta=None, fv=10, want_system=False, skyline=False, sel_rows=None, q=None):
     """one robust attempt at damping c on the (normalised) oracle scene so, the blocks at the current scene.  Returns a dict:
     ok, corr (fv layout), corr10, the weighted blocks (gradE, V, U, W in the 10-variable layout), weights; with want_system
     the system S / rhs of the oracle's 10M - 7 numbering (fv = 10) or the compact 6M one (fv = 6)."""
-    N, M = so.N, so.M
-    gradE, V, U, W, wts = derivatives(f0, so, kind, delta)
+    gradE, V, U, W, wts = derivatives(f0, so, kind, delta, q)
     out = dict(gradE=gradE, V=V, U=U, W=W, weights=wts)
-    g, Ur, Wr = gradE, U, W
-    if fv == 6:
-        g, V, Ur, Wr = cref.restrict(gradE, V, U, W, N)
-    if skyline:
-        sel = sel_rows
-        if fv == 6 and sel_rows is not None:
-            sel = cref.compact_to_reduced(M)[np.asarray(sel_rows)]
-        res = orc.two_phase_skyline(so, g, V, Ur, Wr, c, sel_rows=sel)
-        ok, corr = res[0], res[1]
-        if sel is not None:
-            out["rows"] = res[2]
-    elif want_system:
-        ok, corr, S, rhs = orc.two_phase(so, g, V, Ur, Wr, c, want_system=True)
-        if fv == 6:
-            idx = cref.compact_to_reduced(M)
-            keep = idx >= 0
-            n = 6 * M
-            Sc = np.zeros((n, n))
-            Sc[np.ix_(keep, keep)] = S[np.ix_(idx[keep], idx[keep])]
-            rc = np.zeros(n)
-            rc[keep] = rhs[idx[keep]]
-            S, rhs = Sc, rc
-        out.update(S=S, rhs=rhs)
-    else:
-        ok, corr = orc.two_phase(so, g, V, Ur, Wr, c)
-    out.update(ok=ok, corr10=corr, corr=cref.compact_corrections(corr, N, M) if fv == 6 else corr)
-    return out
-
-
-class Report:
-    pass
+    blocks = cref.restrict(gradE, V, U, W, so.N) if fv == 6 else (gradE, V, U, W)
+    return cref.solve_blocks(orc, so, blocks, c, out, fv, want_system, skyline, sel_rows)
 
 
 def compute_inplace(orc, f0, so, kind=NONE, delta=None, allowed_err_change=None, max_hessian_factor=None, max_iterations=0,
-                    fv=10, skyline=False, normalize=True):
-    """the LM loop of bundle-adj-kanatani.cpp:720-893 (as orc_compute_inplace) on E = sum rho(s) with the IRLS step; so is
-    changed in place (normalised, optimised, normalisation reverted unless normalize=False).  Returns (rc, report) with
-    report.errors = E after every accepted iteration and report.attempts_per_iteration."""
-    rep = Report()
-    rep.status, rep.iterations, rep.attempts = 0, 0, 0
-    rep.attempts_per_iteration, rep.errors = [], []
-    rep.log = lt.AttemptLog().arrays()
-    log = lt.AttemptLog()
+                    fv=10, skyline=False, normalize=True, q=None):
+    """lm_ref.loop on E = sum rho(q s) with the IRLS step; so is changed in place (normalised, optimised, normalisation
+    reverted unless normalize=False).  Returns (rc, report) with report.errors = E after every accepted iteration and
+    report.attempts_per_iteration."""
+    rep = lm_ref.Report()
     nrm = None
     if normalize:
         ok, nrm = orc.normalize(so)
         if not ok:
             return 1, rep
-    N = so.N
-    hessian_factor = float(np.float32(0.0001))  # :723 float literal
-    err_value = energy(f0, so, kind, delta)
-    rep.err_initial = rep.err_final = err_value
-    result_true = False
-    done = False
-    if allowed_err_change is not None and err_value < allowed_err_change:
-        rep.status, result_true, done = 1, True, True
-    while not done:
-        if max_iterations > 0 and rep.iterations >= max_iterations:
-            rep.status, result_true = 5, False
-            break
-        gradE, V, U, W, _ = derivatives(f0, so, kind, delta)
-        if fv == 6:
-            gradE, V, U, W = cref.restrict(gradE, V, U, W, N)
-        bak = (so.points.copy(), so.cam_R.copy(), so.cam_T.copy())
-        have_prev, err_new_prev, decrease, n_att = False, 0.0, 0, 0
-        while not decrease:
-            rep.attempts += 1
-            n_att += 1
-            if skyline:
-                suc, corr = orc.two_phase_skyline(so, gradE, V, U, W, hessian_factor)
-            else:
-                suc, corr = orc.two_phase(so, gradE, V, U, W, hessian_factor)
-            if not suc:
-                log.add(rep.iterations, hessian_factor, np.nan, err_value, lt.SOLVE_FAILED)
-                decrease = 2
-                break
-            orc.apply_corrections(so, corr)
-            err_new = energy(f0, so, kind, delta)
-            if err_new - err_value < 0:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.ACCEPTED)
-                decrease = 1
-                break
-            so.points[:], so.cam_R[:], so.cam_T[:] = bak
-            if have_prev and allowed_err_change is not None and abs(err_new - err_new_prev) < allowed_err_change:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.CONVERGED)
-                decrease = 3
-                break
-            used = hessian_factor
-            hessian_factor *= 10
-            if max_hessian_factor is not None and hessian_factor > max_hessian_factor:
-                log.add(rep.iterations, used, err_new, err_value, lt.CAP_OVERFLOW)
-                decrease = 2
-                break
-            log.add(rep.iterations, used, err_new, err_value, lt.REJECTED)
-            err_new_prev, have_prev = err_new, True
-        rep.attempts_per_iteration.append(n_att)
-        if decrease != 1:
-            rep.status = 3 if decrease == 2 else 4
-            result_true = False
-            break
-        rep.iterations += 1
-        change = err_new - err_value
-        rep.err_final = err_new
-        rep.errors.append(err_new)
-        if allowed_err_change is not None and abs(change) < allowed_err_change:
-            rep.status, result_true = 2, True
-            break
-        err_value = err_new
-        hessian_factor /= 10
-    rep.hessian_factor = hessian_factor
-    rep.log = log.arrays()
+    two_phase = orc.two_phase_skyline if skyline else orc.two_phase
+
+    def prepare():
+        blocks = derivatives(f0, so, kind, delta, q)[:4]
+        return cref.restrict(*blocks, so.N) if fv == 6 else blocks
+
+    rc = lm_ref.loop(rep, so, energy=lambda: energy(f0, so, kind, delta, q), prepare=prepare,
+                     solve=lambda blocks, c: two_phase(so, *blocks, c),
+                     apply=lambda corr: orc.apply_corrections(so, corr),
+                     allowed_err_change=allowed_err_change, max_hessian_factor=max_hessian_factor,
+                     max_iterations=max_iterations)
     if nrm is not None:
         orc.revert(so, nrm)
-    return (0 if result_true else 1), rep
+    return rc, rep
 
 
 def inject_outliers(sc, frac, lo_pix, hi_pix, seed):

@@ -5,15 +5,14 @@ Every frame f belongs to a group g(f); each group has one [fx fy u0 v0].  P (10M
 camera variables, so the landmark Schur complement commutes with it: S_sh(c) = P^T S10(c) P and rhs_sh = P^T rhs10, with
 S10(c), rhs10 the oracle's damped reduced system (gauge rows removed).  The step solves S_sh, expands dc10 = P dc_sh and
 back-substitutes the points with the oracle's blocks; each group's K takes the additions of bundle-adj-kanatani.cpp:2025-2033.
-The LM loop restates bundle-adj-kanatani.cpp:720-893 as calibrated_ref does, with the trial K kept on accept.
+The LM loop is lm_ref.loop, with K among the saved arrays: the trial K is kept on accept.
 The closed-form frame derivatives are the derivatives of the error only with K(2,2) = f0 (test_oracle_fd_checkers.py), so the
 library and this yardstick work on every frame's K scaled by f0 / K(2,2) (the same projections): per_frame_scene, to_caller.
 """
 import numpy as np
 
-import lm_trajectory as lt
-
 import calibrated_ref as cref
+import lm_ref
 import robust_ref as rref
 
 
@@ -126,79 +125,26 @@ def to_caller(K, k22):
     return K * (k22 / K[:, 8:9])
 
 
-class Report:
-    pass
-
-
 def compute_inplace(orc, f0, so, groups, allowed_err_change=None, max_hessian_factor=None, max_iterations=0):
-    """the LM loop of bundle-adj-kanatani.cpp:720-893 (as orc_compute_inplace) around the shared-intrinsics step; so (per
-    frame K) is changed in place: normalised, optimised, K of every group updated, normalisation reverted.  Returns
-    (rc, report): rc 0 = true, 1 = false."""
-    rep = Report()
-    rep.status, rep.iterations, rep.attempts = 0, 0, 0
-    rep.attempts_per_iteration = []
-    rep.log = lt.AttemptLog().arrays()
-    log = lt.AttemptLog()
+    """lm_ref.loop around the shared-intrinsics step, which forms its derivatives at every attempt; so (per frame K) is
+    changed in place: normalised, optimised, K of every group updated, normalisation reverted.  Returns (rc, report):
+    rc 0 = true, 1 = false."""
+    rep = lm_ref.Report()
     ok, nrm = orc.normalize(so)
     if not ok:
         return 1, rep
-    M = so.M
     groups = np.asarray(groups)
-    hessian_factor = float(np.float32(0.0001))  # :723 float literal
-    err_value, _ = orc.reproj_error(f0, so)
-    rep.err_initial = rep.err_final = err_value
-    result_true = False
-    done = False
-    if allowed_err_change is not None and err_value < allowed_err_change:
-        rep.status, result_true, done = 1, True, True
-    while not done:
-        if max_iterations > 0 and rep.iterations >= max_iterations:
-            rep.status, result_true = 5, False
-            break
-        bak = (so.points.copy(), so.cam_R.copy(), so.cam_T.copy(), so.K.copy())
-        have_prev, err_new_prev, decrease, n_att = False, 0.0, 0, 0
-        while not decrease:
-            rep.attempts += 1
-            n_att += 1
-            out = step(orc, f0, so, groups, hessian_factor)
-            if not out["ok"] or not np.all(np.isfinite(out["corr"])):
-                log.add(rep.iterations, hessian_factor, np.nan, err_value, lt.SOLVE_FAILED)
-                decrease = 2
-                break
-            orc.apply_corrections(so, out["corr10"])
-            so.K[:] = apply_k(so.K, out["dc"], M, groups)
-            err_new, _ = orc.reproj_error(f0, so)
-            if err_new - err_value < 0:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.ACCEPTED)
-                decrease = 1
-                break
-            so.points[:], so.cam_R[:], so.cam_T[:], so.K[:] = bak
-            if have_prev and allowed_err_change is not None and abs(err_new - err_new_prev) < allowed_err_change:
-                log.add(rep.iterations, hessian_factor, err_new, err_value, lt.CONVERGED)
-                decrease = 3
-                break
-            used = hessian_factor
-            hessian_factor *= 10
-            if max_hessian_factor is not None and hessian_factor > max_hessian_factor:
-                log.add(rep.iterations, used, err_new, err_value, lt.CAP_OVERFLOW)
-                decrease = 2
-                break
-            log.add(rep.iterations, used, err_new, err_value, lt.REJECTED)
-            err_new_prev, have_prev = err_new, True
-        rep.attempts_per_iteration.append(n_att)
-        if decrease != 1:
-            rep.status = 3 if decrease == 2 else 4
-            result_true = False
-            break
-        rep.iterations += 1
-        change = err_new - err_value
-        rep.err_final = err_new
-        if allowed_err_change is not None and abs(change) < allowed_err_change:
-            rep.status, result_true = 2, True
-            break
-        err_value = err_new
-        hessian_factor /= 10
-    rep.hessian_factor = hessian_factor
-    rep.log = log.arrays()
+
+    def solve(_, c):
+        out = step(orc, f0, so, groups, c)
+        return out["ok"] and bool(np.all(np.isfinite(out["corr"]))), out
+
+    def apply(out):
+        orc.apply_corrections(so, out["corr10"])
+        so.K[:] = apply_k(so.K, out["dc"], so.M, groups)
+
+    rc = lm_ref.loop(rep, so, energy=lambda: orc.reproj_error(f0, so)[0], prepare=lambda: None, solve=solve, apply=apply,
+                     allowed_err_change=allowed_err_change, max_hessian_factor=max_hessian_factor,
+                     max_iterations=max_iterations, saved=("points", "cam_R", "cam_T", "K"))
     orc.revert(so, nrm)
-    return (0 if result_true else 1), rep
+    return rc, rep

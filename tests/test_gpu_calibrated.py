@@ -14,6 +14,7 @@ from surikatoko_amd import _lib
 from conftest import load_golden, rel_err, sym_scaled_err, class_rel_err
 import calibrated_ref as cref
 import lm_trajectory as lt
+from gpu_common import orc_scene as _orc_scene, run_lm as _run, compare_runs as _compare_runs
 
 pytestmark = pytest.mark.gpu
 
@@ -24,10 +25,6 @@ def cal():
     h.set_fixed_intrinsics(True)
     yield h
     h.close()
-
-
-def _orc_scene(orc, sc):
-    return orc.Scene(sc.points, sc.cam_R, sc.cam_T, sc.K, sc.shared_k, sc.row_ptr, sc.obs_frame, sc.obs_uv)
 
 
 def _gauge_zero(corr_frames, M):
@@ -166,15 +163,6 @@ def test_calibrated_c3_sampled_rows_and_corrections_vs_skyline_yardstick(orc, ca
 
 # ------------------------------------------------------------------ end to end
 
-def _run(gpu, sc, f0, allowed=None, max_factor=None, max_iterations=0):
-    crit = sa.BundleAdjustmentKanataniTermCriteria()
-    crit.AllowedReprojErrRelativeChange(allowed)
-    crit.MaxHessianFactor(max_factor)
-    sg = sc.copy()
-    ok = gpu.ComputeInplace(f0, sg, crit, max_iterations)
-    return ok, gpu.report, sg, gpu.iteration_log()
-
-
 def _same_as_yardstick(orc, gpu, sc, f0, skyline=False, **kw):
     so = _orc_scene(orc, sc)
     rc_o, rep_o = cref.compute_inplace(orc, f0, so, kw.get("allowed"), kw.get("max_factor"), kw.get("max_iterations", 0),
@@ -208,17 +196,6 @@ def test_calibrated_c2_ten_iterations_vs_python_lm_loop(orc, cal):
     finally:
         orc.set_threads(threads)
     assert rep.iterations == 10
-
-
-def _compare_runs(a, b, tol=1e-7):
-    (ok_a, rep_a, sg_a, log_a), (ok_b, rep_b, sg_b, log_b) = a, b
-    assert ok_a == ok_b and rep_a.status == rep_b.status
-    assert (rep_a.iterations, rep_a.attempts) == (rep_b.iterations, rep_b.attempts)
-    assert list(log_a["attempts"]) == list(log_b["attempts"])
-    assert rep_a.err_final == pytest.approx(rep_b.err_final, rel=tol)
-    assert np.abs(sg_a.points - sg_b.points).max() < tol
-    assert np.abs(sg_a.cam_R - sg_b.cam_R).max() < tol
-    assert np.abs(sg_a.cam_T - sg_b.cam_T).max() < tol
 
 
 BAND = sa.SceneSpec(n_frames=120, grid_nx=30, grid_ny=20, vis_window=8)

@@ -23,24 +23,12 @@ import constant_cases as cc
 import constant_ref as kref
 import lm_trajectory as lt
 import weighted_ref as wr
+from gpu_common import orc_scene as _orc_scene, handle as _handle, run_lm as _run, compare_runs as _compare_runs
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-def _orc_scene(orc, sc):
-    return orc.Scene(sc.points, sc.cam_R, sc.cam_T, sc.K, sc.shared_k, sc.row_ptr, sc.obs_frame, sc.obs_uv)
-
-
-def _handle(fv=10, **modes):
-    h = sa.BundleAdjustmentKanatani(0)
-    if fv == 6:
-        h.set_fixed_intrinsics(True)
-    for k, v in modes.items():
-        getattr(h, "set_" + k)(v)
-    return h
 
 
 def _set(h, fconst, pconst, keep_gauge):
@@ -240,26 +228,6 @@ def test_constant_phases_huber_loss_and_information(orc):
 
 
 # ------------------------------------------------------------------ reordered frames
-
-def _run(gpu, sc, f0, allowed=None, max_factor=None, max_iterations=0):
-    crit = sa.BundleAdjustmentKanataniTermCriteria()
-    crit.AllowedReprojErrRelativeChange(allowed)
-    crit.MaxHessianFactor(max_factor)
-    sg = sc.copy()
-    ok = gpu.ComputeInplace(f0, sg, crit, max_iterations)
-    return ok, gpu.report, sg, gpu.iteration_log()
-
-
-def _compare_runs(a, b, tol=1e-7):
-    (ok_a, rep_a, sg_a, log_a), (ok_b, rep_b, sg_b, log_b) = a, b
-    assert ok_a == ok_b and rep_a.status == rep_b.status
-    assert (rep_a.iterations, rep_a.attempts) == (rep_b.iterations, rep_b.attempts)
-    assert list(log_a["attempts"]) == list(log_b["attempts"])
-    assert rep_a.err_final == pytest.approx(rep_b.err_final, rel=tol)
-    assert np.abs(sg_a.points - sg_b.points).max() < tol
-    assert np.abs(sg_a.cam_R - sg_b.cam_R).max() < tol
-    assert np.abs(sg_a.cam_T - sg_b.cam_T).max() < tol
-
 
 @pytest.mark.parametrize("name", cc.REORDER_CASES)
 def test_constant_shuffled_frames_take_the_reordering_and_agree(orc, name):

@@ -25,6 +25,7 @@ import lm_trajectory as lt
 import robust_ref as rr
 import shared_k_ref as kref
 import weighted_ref as wr
+from gpu_common import orc_scene as _orc_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -40,10 +41,6 @@ def handles():
     yield h
     for x in h.values():
         x.close()
-
-
-def _orc_scene(orc, sc):
-    return orc.Scene(sc.points, sc.cam_R, sc.cam_T, sc.K, sc.shared_k, sc.row_ptr, sc.obs_frame, sc.obs_uv)
 
 
 def _with_outliers(sc, frac=0.05, seed=7):

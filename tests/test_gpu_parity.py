@@ -14,6 +14,7 @@ import surikatoko_amd as sa
 from surikatoko_amd import ba as B
 from conftest import load_golden, rel_err, sym_scaled_err, class_rel_err
 import lm_trajectory as lt
+from gpu_common import orc_scene as _orc_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -23,10 +24,6 @@ def gpu():
     h = sa.BundleAdjustmentKanatani(0)
     yield h
     h.close()
-
-
-def _orc_scene(orc, sc):
-    return orc.Scene(sc.points, sc.cam_R, sc.cam_T, sc.K, sc.shared_k, sc.row_ptr, sc.obs_frame, sc.obs_uv)
 
 
 def _golden_scene(name):

@@ -21,6 +21,7 @@ from conftest import load_golden, rel_err, sym_scaled_err, class_rel_err
 import calibrated_ref as cref
 import lm_trajectory as lt
 import robust_ref as rr
+from gpu_common import orc_scene as _orc_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -36,10 +37,6 @@ def handles():
     yield h
     for x in h.values():
         x.close()
-
-
-def _orc_scene(orc, sc):
-    return orc.Scene(sc.points, sc.cam_R, sc.cam_T, sc.K, sc.shared_k, sc.row_ptr, sc.obs_frame, sc.obs_uv)
 
 
 def _with_outliers(sc, frac=0.05, seed=7):

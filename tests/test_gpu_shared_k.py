@@ -16,6 +16,7 @@ import shared_k_ref as kref
 import lm_trajectory as lt
 import robust_ref as rref
 import dataclasses
+from gpu_common import run_lm as _run
 
 pytestmark = pytest.mark.gpu
 
@@ -144,15 +145,6 @@ def test_shared_k_phases_c2_full_size(orc, shk):
 
 
 # ------------------------------------------------------------------ staged steps, modes
-
-def _run(gpu, sc, f0, allowed=None, max_factor=None, max_iterations=0):
-    crit = sa.BundleAdjustmentKanataniTermCriteria()
-    crit.AllowedReprojErrRelativeChange(allowed)
-    crit.MaxHessianFactor(max_factor)
-    sg = sc.copy()
-    ok = gpu.ComputeInplace(f0, sg, crit, max_iterations)
-    return ok, gpu.report, sg, gpu.iteration_log()
-
 
 def _staged(h, sc, f0, groups, c, steps=3):
     """`steps` accepted shared-intrinsics steps through the staged calls; returns the scene and K after them"""

@@ -52,10 +52,7 @@ import hetero_cases as hc
 import lm_trajectory as lt
 import robust_ref as rr
 import weighted_ref as wr
-
-
-def _oscene(orc, sc):
-    return orc.Scene(sc.points, sc.cam_R, sc.cam_T, sc.K, sc.shared_k, sc.row_ptr, sc.obs_frame, sc.obs_uv)
+from gpu_common import orc_scene as _oscene
 
 
 def _qr_gate(orc, sc, f0, c):

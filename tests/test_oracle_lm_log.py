@@ -9,10 +9,7 @@ import calibrated_ref as cref
 import lm_exit_cases as cases
 import lm_trajectory as lt
 import shared_k_ref as skr
-
-
-def _oscene(orc, sc):
-    return orc.Scene(sc.points, sc.cam_R, sc.cam_T, sc.K, sc.shared_k, sc.row_ptr, sc.obs_frame, sc.obs_uv)
+from gpu_common import orc_scene as _oscene
 
 
 RUNS = {

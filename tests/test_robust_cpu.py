@@ -13,12 +13,9 @@ import surikatoko_amd as sa
 from surikatoko_amd import _lib
 import robust_ref as rr
 from conftest import class_rel_err
+from gpu_common import orc_scene as _oscene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _oscene(orc, sc):
-    return orc.Scene(sc.points, sc.cam_R, sc.cam_T, sc.K, sc.shared_k, sc.row_ptr, sc.obs_frame, sc.obs_uv)
 
 
 def _scene(orc, ragged=False, outliers=False, **kw):
