@@ -551,6 +551,69 @@ int srk_ba_normalize_position_priors(const srk_ba_normalizer* nrm, int64_t n, co
  * speculation on, the error-side figure is that of whichever attempt recorded last (tools/prior_rate.py switches it off). */
 int srk_ba_prior_pass_ms(srk_ba*, double* derivative_ms, double* error_ms);
 
+/* ---- relative-pose factors between frames (EXTENSION) ----
+ * A calibrated stereo rig, odometry between consecutive keyframes, a loop closure between frames that share no landmark: terms
+ * that tie two frames together.  With R_j, T_j the world -> camera pose of frame j and C_j = -R_j^T T_j its centre, factor k
+ * between frames a != b carries a measured relative rotation Z_k of R_a R_b^T (3 x 3, row-major), a measured relative
+ * translation z_k of R_a (C_b - C_a) (the centre of b in a's frame, world units) and a symmetric positive semi-definite 6 x 6
+ * information matrix L_k, given as the 21 entries of its upper triangle row by row in the order [t; r]:
+ *
+ *     e_t = R_a (C_b - C_a) - z_k,   e_r = Log(Z_k^T R_a R_b^T) (rotation vector, angle < pi),
+ *     E = (everything E is without factors) + sum_k [e_t; e_r]^T L_k [e_t; e_r]
+ *
+ * L is in units of E, (pix / f0)^2, per squared world unit (tt), per world unit and radian (tr), per squared radian (rr): a
+ * factor of covariance Sigma beside observations of pixel noise sigma_px is L = (sigma_px / f0)^2 Sigma^-1.  No robust loss
+ * and no observation information acts on a factor.  This E is what the accept / reject test, both termination tests,
+ * report.err_initial / err_final, srk_ba_iteration_log and srk_ba_phase_error use; srk_ba_reproj_error* stay the reprojection
+ * sums.  A factor adds 2 J_a^T L J_a and 2 J_b^T L J_b to the pose part of the two frame blocks (before the damping),
+ * 2 J_a^T L e and 2 J_b^T L e to the two frame gradients, and 2 J_a^T L J_b as the pose x pose block (a, b) of the reduced camera
+ * system, undamped.  The Jacobians are exact (the inverse right Jacobian of SO(3) at e_r included), so the gradient is the
+ * gradient of E.  The pairs enter the covisibility: the frame renumbering, the skyline and the solver plans know them.
+ *
+ * n = 0 clears the setting (the default).  The handle keeps a copy: it is applied by every later upload
+ * (srk_ba_compute_inplace and srk_ba_compute_inplace_f32 included) and is not touched by srk_ba_reset_scene.  It takes effect
+ * at the next upload, which maps it to the normalised scene X_n = s (R0 X + T0): Z and L_rr stay, z_n = s z, L_tt / s^2,
+ * L_tr / s (srk_ba_normalize_relative_pose_factors).  An index beyond the uploaded scene's frames fails that upload with
+ * SRK_E_ARGS.  A factor whose L is all zeros is switched off: the upload leaves it out, plan included.
+ *
+ * There is no keep_gauge argument: relative poses leave the rigid motion of the world free and fix its scale only through
+ * their translation parts.  The gauge is what srk_ba_set_constant_blocks and srk_ba_set_position_priors say, by default the
+ * reference's seven variables -- the scale is then held at the initial scene's and metric factors pull within it.  For metric
+ * scale: srk_ba_set_constant_blocks with frame 0 constant and keep_gauge = 0.  A factor to a constant frame acts as an
+ * absolute pull on the other frame.
+ *
+ * SRK_E_ARGS (text in srk_ba_last_error), the previous setting staying in force: a == b, a negative index, an unordered pair
+ * given twice (in either direction), pairs not sorted by (min, max), a value that is not finite, a Z that is not a rotation to
+ * 1e-9 (orthogonality and determinant), an L that is not positive semi-definite, a NULL array.  Refused with SRK_E_ARGS by
+ * whichever call comes second: intrinsic groups, more than one rank.  Everything else works unchanged.  Three small passes
+ * impose the factors (behind the derivative kernels, behind the assembly of the reduced camera system, beside the error
+ * kernel); none is launched without factors. */
+int srk_ba_set_relative_pose_factors(srk_ba*, int32_t n, const int32_t* frame_a, const int32_t* frame_b /* caller's numbering */,
+                                     const double* rel_R /* [n][9] */, const double* rel_t /* [n][3] */,
+                                     const double* info /* [n][21] */);
+/* host only, no device and no handle needed: the checks of the setter on their own.  SRK_OK, or SRK_E_ARGS with *why (may be
+ * NULL) pointing at a static text. */
+int srk_ba_check_relative_pose_factors(int32_t n, const int32_t* frame_a, const int32_t* frame_b, const double* rel_R,
+                                       const double* rel_t, const double* info, const char** why);
+/* the count of the stored setting; returns 1 if a setting is stored, 0 if not */
+int srk_ba_relative_pose_factor_count(srk_ba*, int32_t* n);
+/* the stored setting (what the NEXT upload applies) into arrays of the sizes the count gives; any pointer may be NULL.
+ * Returns 1 if a setting is stored, 0 if not. */
+int srk_ba_relative_pose_factors(srk_ba*, int32_t* frame_a, int32_t* frame_b, double* rel_R, double* rel_t, double* info);
+/* the factor sum of the resident scene's current state (0 without factors) */
+int srk_ba_relative_pose_error(srk_ba*, double* e);
+/* [e_t; e_r] [n][6] of the resident scene's current state in the caller's world units and radians, in the order of the
+ * setting.  They belong to the setting the resident scene was uploaded with; if the stored setting has been changed since,
+ * the call fails with SRK_E_STATE until the scene is uploaded again. */
+int srk_ba_relative_pose_residuals(srk_ba*, double* r);
+/* host only, no device needed: measured translations [n][3] and information matrices [n][21] through a normaliser, as the
+ * upload maps them.  Either pair of arrays may be NULL.  Returns SRK_OK or SRK_E_ARGS. */
+int srk_ba_normalize_relative_pose_factors(const srk_ba_normalizer* nrm, int32_t n, const double* rel_t, const double* info,
+                                           double* rel_t_out, double* info_out);
+/* device time in ms of the last launch of the three passes, taken with srk_ba_set_profile >= 1; 0 for a pass that was not
+ * launched or not timed.  One event pair a pass serves all attempt slots (tools/relpose_rate.py switches speculation off). */
+int srk_ba_relative_pose_pass_ms(srk_ba*, double* derivative_ms, double* couple_ms, double* error_ms);
+
 /* device-time instrumentation of srk_ba_optimize / srk_ba_compute_inplace: 0 = none (default; report.ms_* stay 0
  * except ms_total), 1 = one HIP event pair per phase (fills report.ms_*), 2 = additionally event pairs around
  * every MFMA trailing-update launch (fills report.ms_solve_syrk / solve_mfma_flops).  Every event costs a few

@@ -102,6 +102,7 @@ public:
         Flat f = Flatten(f0, map, inverse_orient_cams, track_rep, shared_intrinsic_cam_mat, intrinsic_cam_mats);
         ApplyConstantBlocks(map, f, inverse_orient_cams.size());
         ApplyPositionPriors(map, f);
+        ApplyRelativePoseFactors();
         Scalar a = term_crit.AllowedReprojErrRelativeChange().value_or(0), m = term_crit.MaxHessianFactor().value_or(0);
         int rc = srk_ba_compute_inplace(h_, f0, (int64_t)f.ids.size(), f.pts.data(), (int32_t)inverse_orient_cams.size(),
                                         f.R.data(), f.T.data(), f.K.data(), f.shared, f.row_ptr.data(), f.frames.data(),
@@ -242,6 +243,34 @@ public:
         if (rc < 0) Raise(rc);
     }
 
+    /// EXTENSION: relative-pose factors between cameras from the next ComputeInplace on (srk_ba_set_relative_pose_factors;
+    /// DESIGN.md section 15).  Factor between cameras a != b: rel_R measures R_a R_b^T (row-major, the orientation of camera b
+    /// in camera a's frame), rel_t measures R_a (C_b - C_a) (the centre of b in a's frame, world units), info the 21 entries of
+    /// the upper triangle of the 6 x 6 information matrix, row by row in the order [t; r], in units of the error, (pix / f0)^2.
+    /// Any order: the adapter sorts the factors by (min, max) of their cameras.  An empty vector clears the setting.
+    /// ComputeInplace throws std::invalid_argument for a camera beyond the cameras, a pair named twice, values the library
+    /// refuses, and where it refuses the combination (intrinsic groups, more than one rank).
+    struct RelativePoseFactor {
+        size_t frame_a = 0, frame_b = 0;
+        std::array<Scalar, 9> rel_R{};
+        Point3 rel_t;
+        std::array<Scalar, 21> info{};
+    };
+    void SetRelativePoseFactors(const std::vector<RelativePoseFactor>& factors) {
+        if (factors.empty()) { ClearRelativePoseFactors(); return; }
+        relpose_ = factors;
+        std::stable_sort(relpose_.begin(), relpose_.end(), [](const RelativePoseFactor& x, const RelativePoseFactor& y) {
+            const size_t x0 = std::min(x.frame_a, x.frame_b), x1 = std::max(x.frame_a, x.frame_b);
+            const size_t y0 = std::min(y.frame_a, y.frame_b), y1 = std::max(y.frame_a, y.frame_b);
+            return x0 != y0 ? x0 < y0 : x1 < y1;
+        });
+    }
+    void ClearRelativePoseFactors() {
+        relpose_.clear();
+        int rc = srk_ba_set_relative_pose_factors(h_, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (rc < 0) Raise(rc);
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
@@ -328,6 +357,21 @@ private:
                                             fp.data(), fl.data(), prior_keep_gauge_ ? 1 : 0);
         if (rc < 0) Raise(rc);
     }
+    // the stored factors, sorted by SetRelativePoseFactors, as the flat arrays of the C ABI
+    void ApplyRelativePoseFactors() {
+        if (relpose_.empty()) return;
+        std::vector<int32_t> fa, fb;
+        std::vector<Scalar> R, t, L;
+        for (const RelativePoseFactor& f : relpose_) {
+            fa.push_back((int32_t)f.frame_a);
+            fb.push_back((int32_t)f.frame_b);
+            R.insert(R.end(), f.rel_R.begin(), f.rel_R.end());
+            t.insert(t.end(), { f.rel_t.x, f.rel_t.y, f.rel_t.z });
+            L.insert(L.end(), f.info.begin(), f.info.end());
+        }
+        int rc = srk_ba_set_relative_pose_factors(h_, (int32_t)fa.size(), fa.data(), fb.data(), R.data(), t.data(), L.data());
+        if (rc < 0) Raise(rc);
+    }
     [[noreturn]] void Raise(int rc) const {
         std::string msg = srk_ba_last_error(h_);
         if (rc == SRK_E_ARGS) throw std::invalid_argument(msg);
@@ -342,6 +386,7 @@ private:
     std::vector<uint8_t> const_frames_, const_points_;
     bool prior_set_ = false, prior_keep_gauge_ = true;
     std::vector<PositionPrior> prior_points_, prior_frames_;
+    std::vector<RelativePoseFactor> relpose_;
 };
 
 } // namespace suriko_amd

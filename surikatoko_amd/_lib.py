@@ -62,6 +62,9 @@ EXPORTS = [
     "srk_ba_set_constant_blocks", "srk_ba_constant_blocks", "srk_ba_constant_counts", "srk_ba_constant_pass_ms",
     "srk_ba_set_position_priors", "srk_ba_position_prior_counts", "srk_ba_position_priors", "srk_ba_prior_error",
     "srk_ba_prior_residuals", "srk_ba_normalize_position_priors", "srk_ba_prior_pass_ms",
+    "srk_ba_set_relative_pose_factors", "srk_ba_check_relative_pose_factors", "srk_ba_relative_pose_factor_count", "srk_ba_relative_pose_factors",
+    "srk_ba_relative_pose_error", "srk_ba_relative_pose_residuals", "srk_ba_normalize_relative_pose_factors",
+    "srk_ba_relative_pose_pass_ms",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
     "srk_ba_upload_scene", "srk_ba_optimize", "srk_ba_download_scene", "srk_ba_reset_scene", "srk_ba_phase_error",
     "srk_ba_phase_derivatives", "srk_ba_phase_schur", "srk_ba_phase_solve", "srk_ba_phase_backsub",
@@ -131,6 +134,14 @@ def lib():
     L.srk_ba_prior_residuals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.srk_ba_normalize_position_priors.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.srk_ba_prior_pass_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.srk_ba_set_relative_pose_factors.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.srk_ba_check_relative_pose_factors.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p)]
+    L.srk_ba_relative_pose_factor_count.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.srk_ba_relative_pose_factors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.srk_ba_relative_pose_error.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.srk_ba_relative_pose_residuals.argtypes = [C.c_void_p, C.c_void_p]
+    L.srk_ba_normalize_relative_pose_factors.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.srk_ba_relative_pose_pass_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.srk_ba_revert_normalization.restype = None
     L.srk_circle_camera_shots.restype = None
     _lib = L

@@ -203,6 +203,77 @@ def normalize_position_priors(nrm, pos, info):
     return po, io
 
 
+_RP_TRI = [(r, c) for r in range(6) for c in range(r, 6)]  # the 21 entries of the upper triangle of a 6 x 6, row by row
+
+
+def relative_pose_information(n, info=None, sigma_t=None, sigma_r=None, covariance=None, sigma_pixels=1.0, f0=None):
+    """[n][21] information matrices of n relative-pose factors: the upper triangle row by row, order [t; r].  info= gives them
+    directly: [n][21] or [n][6][6] (or one for all).  Otherwise sigma_t (world units) and sigma_r (radians), scalars or [n], or
+    covariance= [n][6][6] (or one [6][6] for all), become L = (sigma_pixels / f0)^2 Sigma^-1: the factor beside observations of
+    pixel noise sigma_pixels, in the units of the error, (pix / f0)^2."""
+    def rows(a):
+        if a.shape[0] == 1 and n != 1:
+            a = np.repeat(a, n, axis=0)
+        if a.shape[0] != n:
+            raise ValueError(f"relative-pose factors: {a.shape[0]} information matrices / sigmas / covariances for {n} factors")
+        return a
+
+    def tri(L):
+        return np.ascontiguousarray(np.stack([L[:, r, c] for r, c in _RP_TRI], axis=1))
+
+    if info is not None:
+        a = np.asarray(info, dtype=np.float64)
+        if a.shape[-2:] == (6, 6) and a.ndim in (2, 3):
+            return tri(rows(a.reshape(-1, 6, 6)))
+        if a.shape[-1] == 21 and a.ndim in (1, 2):
+            return np.ascontiguousarray(rows(a.reshape(-1, 21)))
+        raise ValueError("relative-pose factors: info= is [n][21] (upper triangle, row by row) or [n][6][6]")
+    if not f0:
+        raise ValueError("relative-pose factors: sigmas and covariances need the scene's f0 (or pass info=)")
+    if covariance is not None:
+        cov = np.asarray(covariance, dtype=np.float64)
+        if cov.shape[-2:] != (6, 6) or cov.ndim not in (2, 3):
+            raise ValueError("relative-pose factors: covariance= is [n][6][6] or [6][6]")
+        cov = rows(cov.reshape(-1, 6, 6))
+        if np.abs(cov - cov.transpose(0, 2, 1)).max() > 1e-12 * np.abs(cov).max():
+            raise ValueError("relative-pose factors: a covariance is not symmetric")
+    else:
+        if sigma_t is None or sigma_r is None:
+            raise ValueError("relative-pose factors: give info=, sigma_t= and sigma_r=, or covariance=")
+        st = rows(np.asarray(sigma_t, dtype=np.float64).reshape(-1))
+        sr = rows(np.asarray(sigma_r, dtype=np.float64).reshape(-1))
+        cov = np.zeros((n, 6, 6))
+        for e in range(3):
+            cov[:, e, e] = st ** 2
+            cov[:, 3 + e, 3 + e] = sr ** 2
+    if not np.all(np.isfinite(cov)) or np.any(np.linalg.eigvalsh(0.5 * (cov + cov.transpose(0, 2, 1))) <= 0):
+        raise ValueError("relative-pose factors: sigmas must be positive and covariances positive definite")
+    L = np.linalg.inv(cov) * (float(sigma_pixels) / float(f0)) ** 2
+    return tri(0.5 * (L + L.transpose(0, 2, 1)))
+
+
+def relative_pose(scene, a, b):
+    """(Z, z) of the pair (a, b) as the scene's poses have it: Z = R_a R_b^T, the orientation of camera b in camera a's frame,
+    and z = R_a (C_b - C_a), the centre of b in a's frame -- the measurement a factor with zero residual carries"""
+    R = np.asarray(scene.cam_R, dtype=np.float64).reshape(-1, 3, 3)
+    T = np.asarray(scene.cam_T, dtype=np.float64).reshape(-1, 3)
+    return R[a] @ R[b].T, R[a] @ (R[a].T @ T[a] - R[b].T @ T[b])
+
+
+def normalize_relative_pose_factors(nrm, rel_t, info):
+    """measured translations [n][3] and information matrices [n][21] through a Normalizer, as the upload maps them
+    (srk_ba_normalize_relative_pose_factors; host only).  Returns (rel_t_n, info_n)."""
+    rel_t = np.ascontiguousarray(np.asarray(rel_t, dtype=np.float64).reshape(-1, 3))
+    info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(-1, 21))
+    if rel_t.shape[0] != info.shape[0]:
+        raise ValueError("normalize_relative_pose_factors: one information matrix per translation")
+    to, io = np.zeros_like(rel_t), np.zeros_like(info)
+    rc = lib().srk_ba_normalize_relative_pose_factors(C.byref(nrm), C.c_int32(rel_t.shape[0]), _p(rel_t), _p(info), _p(to), _p(io))
+    if rc != 0:
+        raise ValueError("srk_ba_normalize_relative_pose_factors: bad argument")
+    return to, io
+
+
 def check_world_is_normalized(scene, t1y=1.0, unity_comp_ind=1):
     """CheckWorldIsNormalized (.cpp:288-333)."""
     return bool(lib().srk_ba_check_world_is_normalized(C.c_int32(scene.M), _p(scene.cam_R), _p(scene.cam_T),
@@ -672,6 +743,64 @@ class BundleAdjustmentKanatani:
         a, b = C.c_double(0), C.c_double(0)
         self._raise(self._lib.srk_ba_prior_pass_ms(C.c_void_p(self._h), C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def set_relative_pose_factors(self, pairs=None, rel_R=None, rel_t=None, info=None, sigma_t=None, sigma_r=None, covariance=None,
+                                  sigma_pixels=1.0):
+        """Relative-pose factors between frames (next upload).  pairs [n][2] = (a, b) in the caller's
+        numbering, sorted by (min, max); rel_R [n][3][3] measures R_a R_b^T, rel_t [n][3] measures R_a (C_b - C_a) in world
+        units (relative_pose(scene, a, b) gives both for a scene's poses).  The information comes as info= ([n][21] upper
+        triangle row by row in the order [t; r], or [n][6][6], in units of the error), as sigma_t= / sigma_r= (world units,
+        radians) or as covariance= ([n][6][6]); the last two become L = (sigma_pixels / f0)^2 Sigma^-1 with the f0 of the
+        scene last passed to this object.  pairs None or empty clears the setting.  There is no keep_gauge: the gauge is what
+        set_constant_blocks / set_position_priors say.  Not with intrinsic groups or more than one rank (ValueError)."""
+        if pairs is None or len(pairs) == 0:
+            self._raise(self._lib.srk_ba_set_relative_pose_factors(C.c_void_p(self._h), C.c_int32(0), None, None, None, None, None))
+            return
+        pr = np.asarray(pairs).astype(np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        fa, fb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        Z = np.ascontiguousarray(np.asarray(rel_R, dtype=np.float64).reshape(-1, 9))
+        z = np.ascontiguousarray(np.asarray(rel_t, dtype=np.float64).reshape(-1, 3))
+        if Z.shape[0] != n or z.shape[0] != n:
+            raise ValueError("set_relative_pose_factors: one rotation and one translation per pair")
+        L = relative_pose_information(n, info=info, sigma_t=sigma_t, sigma_r=sigma_r, covariance=covariance,
+                                      sigma_pixels=sigma_pixels, f0=self._f0)
+        self._raise(self._lib.srk_ba_set_relative_pose_factors(C.c_void_p(self._h), C.c_int32(n), _p(fa), _p(fb), _p(Z), _p(z), _p(L)))
+
+    def relative_pose_factors(self):
+        """None when no factors are set, else a dict: pairs [n][2], rel_R [n][3][3], rel_t [n][3], info [n][21] -- the stored
+        setting in the caller's numbering and coordinates"""
+        n = C.c_int32(0)
+        rc = self._lib.srk_ba_relative_pose_factor_count(C.c_void_p(self._h), C.byref(n))
+        self._raise(rc)
+        if rc == 0:
+            return None
+        fa, fb = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        Z, z, L = np.zeros((n.value, 9)), np.zeros((n.value, 3)), np.zeros((n.value, 21))
+        self._raise(self._lib.srk_ba_relative_pose_factors(C.c_void_p(self._h), _p(fa), _p(fb), _p(Z), _p(z), _p(L)))
+        return dict(pairs=np.stack([fa, fb], axis=1), rel_R=Z.reshape(-1, 3, 3), rel_t=z, info=L)
+
+    def relative_pose_error(self):
+        """the factor sum of the resident scene's current state; phase_error() minus this (and the prior sums) is the
+        observation part"""
+        e = C.c_double(0)
+        self._raise(self._lib.srk_ba_relative_pose_error(C.c_void_p(self._h), C.byref(e)))
+        return e.value
+
+    def relative_pose_residuals(self):
+        """[e_t; e_r] [n][6] of the resident scene's current state in the caller's world units and radians, in the order of
+        relative_pose_factors()"""
+        n = C.c_int32(0)
+        self._raise(self._lib.srk_ba_relative_pose_factor_count(C.c_void_p(self._h), C.byref(n)))
+        r = np.zeros((n.value, 6))
+        self._raise(self._lib.srk_ba_relative_pose_residuals(C.c_void_p(self._h), _p(r) if n.value else None))
+        return r
+
+    def relative_pose_pass_ms(self):
+        """(derivative-side pass, coupling pass, error-side pass): device ms of the last launch, with set_profile >= 1"""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._raise(self._lib.srk_ba_relative_pose_pass_ms(C.c_void_p(self._h), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def schur_fallback_landmarks(self):
         """landmarks of the uploaded scene that take the per-landmark Schur kernel (srk_ba_schur_fallback_landmarks)"""

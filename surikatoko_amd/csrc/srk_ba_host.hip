@@ -199,6 +199,21 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     int32_t n_pri_frames = 0;
     hipEvent_t ev_pri[4]{}; // profile level >= 1: around the last k_prior_add / k_prior_error launch (created on first use)
     bool pri_timed[2] = { false, false };
+    // opt-in: relative-pose factors between frames (srk_ba_set_relative_pose_factors).  rp_a / rp_b / rp_R /
+    // rp_t / rp_info: the setting in the caller's numbering and world coordinates, kept across uploads and srk_ba_reset_scene.
+    // The uploaded scene: rp_act = the factors of the setting that are switched on (the planner has their pairs), and the
+    // device lists in the internal numbering with the values mapped to the normalised world (SrkRelPose).
+    bool rp_set = false;
+    std::vector<int32_t> rp_a, rp_b;
+    std::vector<double> rp_R, rp_t, rp_info;
+    std::vector<int32_t> rp_act, rp_int_a, rp_int_b; // active factors: place in the setting, internal frames
+    std::vector<int32_t> app_rp_a, app_rp_b;         // what the resident scene was uploaded with (srk_ba_relative_pose_residuals)
+    std::vector<double> app_rp_R, app_rp_t;
+    bool app_rp = false;
+    DevBuf rp_fa, rp_fb, rp_val, rp_fr_list, rp_fr_ptr, rp_fr_ent, rp_tgt, rp_cpl;
+    int32_t n_rp = 0, n_rp_frames = 0;
+    hipEvent_t ev_rp[6]{}; // profile level >= 1: around the last k_relpose_add / k_relpose_couple / k_relpose_error launch
+    bool rp_timed[3] = { false, false, false };
     int profile_level = 0; // 0 = no events, 1 = phase events (report.ms_*), 2 = + event pairs around the MFMA updates
     bool chol_fused = true; // the solve's outer steps as one launch each (k_step256); srk_ba_set_solver_fusion
     // what the caller asked for.  A hand-off timeout switches chol_fused off for the rest of that call; the next upload /
@@ -378,7 +393,8 @@ void srk_ba_destroy(srk_ba* h)
                       &h->jd_nf, &h->jd_frames, &h->jd_mask,
                       &h->jr_first, &h->jr_count, &h->jr_jmin, &h->jr_group, &h->lg_item, &h->lg_np, &h->lg_nf, &h->lg_pts, &h->lg_frames,
                       &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk,
-                      &h->info_q, &h->info_qf, &h->cst_pts, &h->cst_frames, &h->pri_pt_list, &h->pri_pt_val, &h->pri_fr_list, &h->pri_fr_val };
+                      &h->info_q, &h->info_qf, &h->cst_pts, &h->cst_frames, &h->pri_pt_list, &h->pri_pt_val, &h->pri_fr_list, &h->pri_fr_val,
+                      &h->rp_fa, &h->rp_fb, &h->rp_val, &h->rp_fr_list, &h->rp_fr_ptr, &h->rp_fr_ent, &h->rp_tgt, &h->rp_cpl };
     for (DevBuf* b : all) dev_free(*b);
     for (auto& a : h->att) {
         for (DevBuf* b : { &a.S, &a.rhs, &a.wy, &a.dc, &a.acc, &a.dx, &a.err_partial, &a.info, &a.dinv, &a.packed, &a.sync_flags, &a.irr, &a.det_stage, &a.det_rhs,
@@ -398,6 +414,8 @@ void srk_ba_destroy(srk_ba* h)
     for (auto& e : h->ev_cst)
         if (e) hipEventDestroy(e);
     for (auto& e : h->ev_pri)
+        if (e) hipEventDestroy(e);
+    for (auto& e : h->ev_rp)
         if (e) hipEventDestroy(e);
     if (h->ev_comm) hipEventDestroy(h->ev_comm);
     if (h->comm_stream) hipStreamDestroy(h->comm_stream);
@@ -480,12 +498,22 @@ static const char* prior_conflict(bool priors, bool groups, int world)
     if (world > 1) return "position priors: not available with more than one rank";
     return nullptr;
 }
+// relative-pose factors (srk_ba_set_relative_pose_factors) add to the pose part of the 10- or 6-variable blocks and couple two
+// frames of one rank's system: the fold of shared intrinsics and the exchange of the ranks' partial sums can follow later
+static const char* relpose_conflict(bool factors, bool groups, int world)
+{
+    if (!factors) return nullptr;
+    if (groups) return "relative-pose factors: not available with intrinsic groups";
+    if (world > 1) return "relative-pose factors: not available with more than one rank";
+    return nullptr;
+}
 static bool refuse_modes(srk_ba* h, bool fixed_k, bool deterministic, bool store_f32, bool schur_fp32, int world, bool groups)
 {
     const char* e = fixed_k_conflict(fixed_k, deterministic, store_f32, schur_fp32, world);
     if (!e) e = groups_conflict(groups, fixed_k, store_f32, schur_fp32, world);
     if (!e) e = constant_conflict(h->cst_set, groups, world);
     if (!e) e = prior_conflict(h->pri_set, groups, world);
+    if (!e) e = relpose_conflict(h->rp_set, groups, world);
     if (e) h->last_error = e;
     return e != nullptr;
 }
@@ -673,6 +701,22 @@ int srk_ba_normalize_position_priors(const srk_ba_normalizer* nrm, int64_t n, co
         double* q = info_out + 6 * i; // the symmetric part: both triangles carry the same sum up to rounding
         q[0] = o[0]; q[1] = 0.5 * (o[1] + o[3]); q[2] = 0.5 * (o[2] + o[6]);
         q[3] = o[4]; q[4] = 0.5 * (o[5] + o[7]); q[5] = o[8];
+    }
+    return SRK_OK;
+}
+
+// relative-pose factors through a normaliser (host only).  A relative pose is invariant under R0 and T0 and scales with s:
+// z_n = s z, L_tt / s^2, L_tr / s, L_rr as it is, so that [e_t; e_r]^T L [e_t; e_r] is the same number in both worlds
+int srk_ba_normalize_relative_pose_factors(const srk_ba_normalizer* nrm, int32_t n, const double* rel_t, const double* info,
+                                           double* rel_t_out, double* info_out)
+{
+    if (!nrm || n < 0 || (rel_t != nullptr) != (rel_t_out != nullptr) || (info != nullptr) != (info_out != nullptr)) return SRK_E_ARGS;
+    const double s = nrm->world_scale, is = 1.0 / s;
+    for (int64_t i = 0; rel_t && i < 3 * (int64_t)n; ++i) rel_t_out[i] = s * rel_t[i];
+    for (int64_t i = 0; info && i < n; ++i) {
+        int k = 0;
+        for (int r = 0; r < 6; ++r)
+            for (int c = r; c < 6; ++c, ++k) info_out[21 * i + k] = info[21 * i + k] * (r < 3 ? is : 1.0) * (c < 3 ? is : 1.0);
     }
     return SRK_OK;
 }
@@ -1035,6 +1079,7 @@ static int check_information(srk_ba* h, const char* who, const double* q, int64_
 static int apply_information(srk_ba* h);
 static int apply_constant_blocks(srk_ba* h);
 static int apply_position_priors(srk_ba* h);
+static int apply_relative_pose_factors(srk_ba* h);
 static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_in, int32_t M,
                              const double* cam_R_in, const double* cam_T_in, const double* K_in, int shared_k,
                              const int64_t* row_ptr, const int32_t* obs_frame, const double* obs_uv,
@@ -1096,6 +1141,22 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
             return SRK_E_ARGS;
         }
     }
+    // relative-pose factors: the switched-on ones (an all-zero information matrix is left out, plan included, so that the
+    // run has the bits of the run without it); their pairs go to the planner in the caller's numbering
+    h->rp_act.clear();
+    std::vector<int32_t> rel_a, rel_b;
+    for (size_t k = 0; h->rp_set && k < h->rp_a.size(); ++k) {
+        if (h->rp_a[k] >= M || h->rp_b[k] >= M) {
+            h->last_error = "relative-pose factors: frame index " + std::to_string(std::max(h->rp_a[k], h->rp_b[k])) + ", the scene has " + std::to_string(M) + " frames";
+            return SRK_E_ARGS;
+        }
+        bool off = true;
+        for (int e = 0; e < 21; ++e) off = off && h->rp_info[21 * k + (size_t)e] == 0.0;
+        if (off) continue;
+        h->rp_act.push_back((int32_t)k);
+        rel_a.push_back(h->rp_a[k]);
+        rel_b.push_back(h->rp_b[k]);
+    }
     rearm_fusion(h);
     stage("validate");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1152,6 +1213,9 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     if (const char* e = getenv("SRK_SCHUR_RUN_SPLIT")) opt.run_split = std::max(1, std::min(16, atoi(e))); // development: fixed cut
     opt.no_long = getenv("SRK_SCHUR_NO_LONG") != nullptr; // development: everything through the per-landmark kernel
 #endif
+    opt.rel_a = rel_a.data();
+    opt.rel_b = rel_b.data();
+    opt.n_rel = (int64_t)rel_a.size();
     SrkScenePlan plan;
     srk_plan_scene({ N, M, row_ptr, obs_frame, obs_uv, pts.data(), camR.data(), camT.data(), Kexp.data() }, opt, plan, stage);
     if (!h->igroup_user.empty()) {
@@ -1222,7 +1286,8 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         add(a.dx, nullptr, 24 * N);
         // (position priors: their partial sums sit behind the observation partials of either error kernel)
         add(a.err_partial, nullptr, 8 * (std::max<int64_t>(1024, srk_error_partials_staged(d)) +
-                                         (h->pri_set ? srk_prior_partials((int64_t)h->pri_pt_idx.size(), (int64_t)h->pri_fr_idx.size()) : 0)));
+                                         (h->pri_set ? srk_prior_partials((int64_t)h->pri_pt_idx.size(), (int64_t)h->pri_fr_idx.size()) : 0) +
+                                         srk_relpose_partials((int64_t)h->rp_act.size())));
         add(a.info, nullptr, 64);
         add(a.dinv, nullptr, 8 * 64 * d.ld);
         add(a.irr, nullptr, 4 * (N + 2));
@@ -1285,8 +1350,89 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     if ((rc = apply_information(h)) != SRK_OK) return rc;
     if ((rc = apply_constant_blocks(h)) != SRK_OK) return rc;
     if ((rc = apply_position_priors(h)) != SRK_OK) return rc;
+    if ((rc = apply_relative_pose_factors(h)) != SRK_OK) return rc;
     h->have_scene = true;
     return SRK_OK;
+}
+
+// the switched-on factors (rp_act, checked at the start of the upload; the planner has seen their pairs) -> the device lists of
+// the resident scene: frames through the renumbering (frame_int), values through the normaliser of this upload, the per-frame
+// lists of incident factors in factor order, and each factor's place in S
+static int apply_relative_pose_factors(srk_ba* h)
+{
+    const SrkDims& d = h->d;
+    h->n_rp = 0;
+    h->n_rp_frames = 0;
+    h->rp_int_a.clear(); h->rp_int_b.clear();
+    h->app_rp = h->rp_set;
+    h->app_rp_a = h->rp_a; h->app_rp_b = h->rp_b; h->app_rp_R = h->rp_R; h->app_rp_t = h->rp_t;
+    const size_t n = h->rp_act.size();
+    if (n == 0) return SRK_OK;
+    std::vector<double> tn(h->rp_t.size()), ln(h->rp_info.size());
+    srk_ba_normalize_relative_pose_factors(&h->nrm, (int32_t)h->rp_a.size(), h->rp_t.data(), h->rp_info.data(), tn.data(), ln.data());
+    std::vector<int32_t> fa(n), fb(n);
+    std::vector<double> val((size_t)SRK_RP_PLANES * n);
+    std::vector<int64_t> tgt(n);
+    const int64_t t0 = 4 - (10 - d.fv); // first pose variable of a frame
+    for (size_t i = 0; i < n; ++i) {
+        const size_t k = (size_t)h->rp_act[i];
+        fa[i] = h->frame_int.empty() ? h->rp_a[k] : h->frame_int[(size_t)h->rp_a[k]];
+        fb[i] = h->frame_int.empty() ? h->rp_b[k] : h->frame_int[(size_t)h->rp_b[k]];
+        for (int e = 0; e < 9; ++e) val[(size_t)e * n + i] = h->rp_R[9 * k + (size_t)e];
+        for (int e = 0; e < 3; ++e) val[(size_t)(9 + e) * n + i] = tn[3 * k + (size_t)e];
+        for (int e = 0; e < 21; ++e) val[(size_t)(12 + e) * n + i] = ln[21 * k + (size_t)e];
+        const int64_t hi = std::max(fa[i], fb[i]), lo = std::min(fa[i], fb[i]);
+        tgt[i] = (d.fv * hi + t0) * d.ld + d.fv * lo + t0;
+    }
+    std::vector<int32_t> cnt((size_t)d.M, 0), list, ptr(1, 0), ent;
+    for (size_t i = 0; i < n; ++i) { ++cnt[(size_t)fa[i]]; ++cnt[(size_t)fb[i]]; }
+    std::vector<int32_t> at((size_t)d.M, -1);
+    for (int32_t j = 0; j < d.M; ++j)
+        if (cnt[(size_t)j]) {
+            at[(size_t)j] = (int32_t)list.size();
+            list.push_back(j);
+            ptr.push_back(ptr.back() + cnt[(size_t)j]);
+        }
+    ent.resize((size_t)ptr.back());
+    std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+    for (size_t i = 0; i < n; ++i) { // factor order inside every frame's list
+        ent[(size_t)fill[(size_t)at[(size_t)fa[i]]]++] = (int32_t)(2 * i);
+        ent[(size_t)fill[(size_t)at[(size_t)fb[i]]]++] = (int32_t)(2 * i + 1);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &h->rp_fa, fa.data(), 4 * n }, { &h->rp_fb, fb.data(), 4 * n }, { &h->rp_val, val.data(), 8 * val.size() },
+        { &h->rp_fr_list, list.data(), 4 * list.size() }, { &h->rp_fr_ptr, ptr.data(), 4 * ptr.size() },
+        { &h->rp_fr_ent, ent.data(), 4 * ent.size() }, { &h->rp_tgt, tgt.data(), 8 * n },
+    };
+    for (auto& u : up) {
+        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+        HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((rc = dev_alloc(h, h->rp_cpl, 8 * 36 * n)) != SRK_OK) return rc;
+    HIPCHK(h, hipMemsetAsync(h->rp_cpl.p, 0, 8 * 36 * n, s));
+    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope
+    h->rp_int_a = fa;
+    h->rp_int_b = fb;
+    h->n_rp = (int32_t)n;
+    h->n_rp_frames = (int32_t)list.size();
+    return SRK_OK;
+}
+// the factor lists of the resident scene for the kernels: NULL without factors, so that none of the three passes is launched
+static const SrkRelPose* relpose_factors(const srk_ba* h, SrkRelPose& p)
+{
+    if (h->n_rp == 0) return nullptr;
+    p = SrkRelPose{ P<int32_t>(h->rp_fa), P<int32_t>(h->rp_fb), P<double>(h->rp_val), h->n_rp, P<int32_t>(h->rp_fr_list),
+                    P<int32_t>(h->rp_fr_ptr), P<int32_t>(h->rp_fr_ent), h->n_rp_frames, P<int64_t>(h->rp_tgt), P<double>(h->rp_cpl) };
+    return &p;
+}
+static bool rp_events(srk_ba* h)
+{
+    for (auto& e : h->ev_rp)
+        if (!e && hipEventCreate(&e) != hipSuccess) return false;
+    return true;
 }
 
 // the stored priors (indices checked at the start of the upload) -> the device lists of the resident scene: values through the
@@ -1678,11 +1824,15 @@ static int phase_error(srk_ba* h, srk_ba::Attempt& a, int which, double* err_hos
     // (one event pair for all attempt slots: with speculation on, srk_ba_prior_pass_ms reports the attempt that recorded last)
     const bool timed = prior && h->profile_level >= 1 && pri_events(h);
     if (prior) h->pri_timed[1] = timed;
+    SrkRelPose rpl;
+    const SrkRelPose* relpose = relpose_factors(h, rpl); // the factor sum of the scene being scored
+    const bool rp_timed = relpose && h->profile_level >= 1 && rp_events(h);
+    if (relpose) h->rp_timed[2] = rp_timed;
     srk_launch_error(s, d, P<double>(h->pts[which]), P<double>(h->cam[which]), P<int32_t>(h->obs_frame),
                      P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(a.err_partial), np, a.err_dst,
                      h->jac_fused ? P<int32_t>(h->wg_jmin) : nullptr, with_status ? P<int>(a.info) : nullptr,
                      with_status ? reinterpret_cast<int*>(reinterpret_cast<char*>(a.acc.p) + 8 * 3 * d.Ns) : nullptr,
-                     robust_loss(h, L), prior, timed ? &h->ev_pri[2] : nullptr);
+                     robust_loss(h, L), prior, timed ? &h->ev_pri[2] : nullptr, relpose, rp_timed ? &h->ev_rp[4] : nullptr);
     HIPCHK(h, hipGetLastError());
     int rc = no_exchange ? SRK_OK : exchange(h, a, a.err_dst, with_status ? 3 : 1);
     if (rc != SRK_OK) return rc;
@@ -1742,6 +1892,15 @@ static int phase_derivatives(srk_ba* h)
         srk_launch_prior_add(s, d, P<double>(h->pts[c]), P<double>(h->cam[c]), *prior, P<double>(h->Vg), P<double>(h->Ug));
         if (timed) HIPCHK(h, hipEventRecord(h->ev_pri[1], s));
         h->pri_timed[0] = timed;
+        HIPCHK(h, hipGetLastError());
+    }
+    SrkRelPose rpl;
+    if (const SrkRelPose* relpose = relpose_factors(h, rpl)) { // the factors' terms into Ug, the coupling blocks aside
+        const bool timed = h->profile_level >= 1 && rp_events(h);
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[0], s));
+        srk_launch_relpose_add(s, d, P<double>(h->cam[c]), *relpose, P<double>(h->Ug));
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[1], s));
+        h->rp_timed[0] = timed;
         HIPCHK(h, hipGetLastError());
     }
     if (h->n_cst_pts > 0) { // constant landmarks: identity block, zero gradient, zero point-frame blocks
@@ -1814,6 +1973,15 @@ static int phase_schur(srk_ba* h, srk_ba::Attempt& a, double c, bool local_only)
     srk_launch_assemble(s, d, c, P<double>(h->Ug), P<double>(a.S), P<double>(a.rhs), h->rank == 0 ? 1.0 : 0.0,
                         P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg), P<int32_t>(a.irr));
     HIPCHK(h, hipGetLastError());
+    SrkRelPose rpl;
+    if (const SrkRelPose* relpose = relpose_factors(h, rpl)) { // the coupling blocks, before the constant frames are masked
+        const bool timed = h->profile_level >= 1 && rp_events(h);
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[2], s));
+        srk_launch_relpose_couple(s, d, *relpose, P<double>(a.S));
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[3], s));
+        h->rp_timed[1] = timed;
+        HIPCHK(h, hipGetLastError());
+    }
     if (h->n_cst_frames > 0) { // constant frames: identity rows and columns, zero rhs
         const bool timed = h->profile_level >= 1 && cst_events(h);
         if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[2], s));
@@ -3196,6 +3364,10 @@ int srk_ba_set_covisibility(srk_ba* h, const int32_t* min_cv)
             if (min_cv[j] < 0 || min_cv[j] > j) { h->last_error = "min_cv[j] must be in [0, j]"; return SRK_E_ARGS; }
             h->min_cv[(size_t)j] = min_cv[j];
         }
+        for (size_t i = 0; i < h->rp_int_a.size(); ++i) { // the pairs of the relative-pose factors are part of the skyline
+            const int32_t hi = std::max(h->rp_int_a[i], h->rp_int_b[i]), lo = std::min(h->rp_int_a[i], h->rp_int_b[i]);
+            h->min_cv[(size_t)hi] = std::min(h->min_cv[(size_t)hi], lo);
+        }
     } else {
         std::fill(h->min_cv.begin(), h->min_cv.end(), 0);
     }
@@ -3623,6 +3795,191 @@ int srk_ba_prior_pass_ms(srk_ba* h, double* derivative_ms, double* error_ms)
         if (h->pri_timed[k] && hipEventElapsedTime(&ms, h->ev_pri[2 * k], h->ev_pri[2 * k + 1]) != hipSuccess) ms = 0;
         double* out = k == 0 ? derivative_ms : error_ms;
         if (out) *out = h->pri_timed[k] ? (double)ms : 0.0;
+    }
+    return SRK_OK;
+}
+// relative-pose factors.  Next upload.
+// positive semi-definite 6 x 6 (full symmetric A, destroyed): elimination with diagonal pivoting; every pivot must be >= 0 up to
+// the rounding of a rank-deficient matrix, and once the largest remaining diagonal entry is ~0 so must be everything left
+static bool relpose_info_psd(double* A)
+{
+    double m = 0;
+    for (int e = 0; e < 36; ++e) m = std::max(m, std::fabs(A[e]));
+    if (m == 0) return true;
+    for (int k = 0; k < 6; ++k) {
+        int p = k;
+        for (int i = k + 1; i < 6; ++i)
+            if (A[7 * i] > A[7 * p]) p = i;
+        if (A[7 * p] <= 1e-12 * m) {
+            for (int i = k; i < 6; ++i)
+                for (int j = k; j < 6; ++j)
+                    if (i == j ? A[7 * i] < -1e-12 * m : std::fabs(A[6 * i + j]) > 1e-11 * m) return false;
+            return true;
+        }
+        for (int j = 0; j < 6; ++j) std::swap(A[6 * k + j], A[6 * p + j]);
+        for (int i = 0; i < 6; ++i) std::swap(A[6 * i + k], A[6 * i + p]);
+        for (int i = k + 1; i < 6; ++i) {
+            const double f = A[6 * i + k] / A[7 * k];
+            for (int j = k + 1; j < 6; ++j) A[6 * i + j] -= f * A[6 * k + j];
+        }
+    }
+    return true;
+}
+static const char* check_relpose(int32_t n, const int32_t* fa, const int32_t* fb, const double* R, const double* t, const double* info)
+{
+    for (int32_t i = 0; i < n; ++i) {
+        if (fa[i] < 0 || fb[i] < 0) return "relative-pose factors: negative frame index";
+        if (fa[i] == fb[i]) return "relative-pose factors: a factor needs two different frames";
+        if (i > 0) {
+            const int32_t lo0 = std::min(fa[i - 1], fb[i - 1]), hi0 = std::max(fa[i - 1], fb[i - 1]);
+            const int32_t lo1 = std::min(fa[i], fb[i]), hi1 = std::max(fa[i], fb[i]);
+            if (lo0 == lo1 && hi0 == hi1) return "relative-pose factors: a pair of frames is given twice";
+            if (lo1 < lo0 || (lo1 == lo0 && hi1 < hi0)) return "relative-pose factors: pairs must be sorted by (min, max) of their frames";
+        }
+        const double* z = R + 9 * (int64_t)i;
+        for (int e = 0; e < 9; ++e)
+            if (!std::isfinite(z[e])) return "relative-pose factors: a rotation is not finite";
+        for (int e = 0; e < 3; ++e)
+            if (!std::isfinite(t[3 * (int64_t)i + e])) return "relative-pose factors: a translation is not finite";
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) {
+                const double g = z[a] * z[b] + z[3 + a] * z[3 + b] + z[6 + a] * z[6 + b] - (a == b ? 1.0 : 0.0);
+                if (std::fabs(g) > 1e-9) return "relative-pose factors: a measured rotation is not orthogonal to 1e-9";
+            }
+        const double det = z[0] * (z[4] * z[8] - z[5] * z[7]) - z[1] * (z[3] * z[8] - z[5] * z[6]) + z[2] * (z[3] * z[7] - z[4] * z[6]);
+        if (std::fabs(det - 1.0) > 1e-9) return "relative-pose factors: a measured rotation has determinant != 1";
+        double A[36];
+        int k = 0;
+        for (int r = 0; r < 6; ++r)
+            for (int c = r; c < 6; ++c, ++k) {
+                const double v = info[21 * (int64_t)i + k];
+                if (!std::isfinite(v)) return "relative-pose factors: an information matrix is not finite";
+                A[6 * r + c] = A[6 * c + r] = v;
+            }
+        if (!relpose_info_psd(A)) return "relative-pose factors: an information matrix is not positive semi-definite";
+    }
+    return nullptr;
+}
+int srk_ba_check_relative_pose_factors(int32_t n, const int32_t* frame_a, const int32_t* frame_b, const double* rel_R,
+                                       const double* rel_t, const double* info, const char** why)
+{
+    const char* e = nullptr;
+    if (n < 0) e = "relative-pose factors: negative count";
+    else if (n > 0 && (!frame_a || !frame_b || !rel_R || !rel_t || !info)) e = "relative-pose factors: null array";
+    else e = check_relpose(n, frame_a, frame_b, rel_R, rel_t, info);
+    if (why) *why = e;
+    return e ? SRK_E_ARGS : SRK_OK;
+}
+int srk_ba_set_relative_pose_factors(srk_ba* h, int32_t n, const int32_t* frame_a, const int32_t* frame_b, const double* rel_R,
+                                     const double* rel_t, const double* info)
+{
+    if (!h) return SRK_E_ARGS;
+    if (n == 0) {
+        h->rp_set = false;
+        h->rp_a.clear(); h->rp_b.clear(); h->rp_R.clear(); h->rp_t.clear(); h->rp_info.clear();
+        return SRK_OK;
+    }
+    const char* e = nullptr;
+    if (srk_ba_check_relative_pose_factors(n, frame_a, frame_b, rel_R, rel_t, info, &e) != SRK_OK) { h->last_error = e; return SRK_E_ARGS; }
+    if ((e = relpose_conflict(true, !h->igroup_user.empty(), h->world))) { h->last_error = e; return SRK_E_ARGS; }
+    h->rp_a.assign(frame_a, frame_a + n);
+    h->rp_b.assign(frame_b, frame_b + n);
+    h->rp_R.assign(rel_R, rel_R + 9 * (int64_t)n);
+    h->rp_t.assign(rel_t, rel_t + 3 * (int64_t)n);
+    h->rp_info.assign(info, info + 21 * (int64_t)n);
+    h->rp_set = true;
+    return SRK_OK;
+}
+int srk_ba_relative_pose_factor_count(srk_ba* h, int32_t* n)
+{
+    if (!h) return SRK_E_ARGS;
+    if (n) *n = (int32_t)h->rp_a.size();
+    return h->rp_set ? 1 : 0;
+}
+int srk_ba_relative_pose_factors(srk_ba* h, int32_t* frame_a, int32_t* frame_b, double* rel_R, double* rel_t, double* info)
+{
+    if (!h) return SRK_E_ARGS;
+    auto out = [](auto* dst, const auto& v) {
+        if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
+    };
+    out(frame_a, h->rp_a); out(frame_b, h->rp_b); out(rel_R, h->rp_R); out(rel_t, h->rp_t); out(info, h->rp_info);
+    return h->rp_set ? 1 : 0;
+}
+int srk_ba_relative_pose_error(srk_ba* h, double* e_out)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    if (e_out) *e_out = 0;
+    SrkRelPose rp;
+    if (!relpose_factors(h, rp)) return SRK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    HIPCHK(h, hipStreamSynchronize(s));
+    const int32_t nb = srk_relpose_partials(rp.n);
+    DevBuf part;
+    int rc = dev_alloc(h, part, 8 * ((size_t)nb + 1));
+    if (rc != SRK_OK) return rc;
+    double out = 0;
+    srk_launch_relpose_error(s, P<double>(h->cam[h->cur]), rp, P<double>(part), P<double>(part) + nb);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&out, P<double>(part) + nb, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    dev_free(part);
+    HIPCHK(h, e);
+    if (e_out) *e_out = out;
+    return SRK_OK;
+}
+int srk_ba_relative_pose_residuals(srk_ba* h, double* r_out)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    // the residuals belong to the setting the resident scene was uploaded with: a setter call since then has not reached it
+    if (h->app_rp != h->rp_set || h->app_rp_a != h->rp_a || h->app_rp_b != h->rp_b || h->app_rp_R != h->rp_R || h->app_rp_t != h->rp_t) {
+        h->last_error = "relative_pose_residuals: the factors were changed after the upload; upload the scene again";
+        return SRK_E_STATE;
+    }
+    if (h->app_rp_a.empty() || !r_out) return SRK_OK;
+    const SrkDims& d = h->d;
+    std::vector<double> p((size_t)(3 * d.N)), R((size_t)(9 * (int64_t)d.M)), T((size_t)(3 * (int64_t)d.M));
+    int rc = srk_ba_download_scene(h, p.data(), R.data(), T.data(), 1); // the caller's world coordinates
+    if (rc != SRK_OK) return rc;
+    auto centre = [&](int32_t j, double* C) {
+        const double* r = &R[9 * (size_t)j];
+        const double* t = &T[3 * (size_t)j];
+        for (int e = 0; e < 3; ++e) C[e] = -(r[e] * t[0] + r[3 + e] * t[1] + r[6 + e] * t[2]);
+    };
+    for (size_t k = 0; k < h->app_rp_a.size(); ++k) {
+        const double* ra = &R[9 * (size_t)h->app_rp_a[k]];
+        const double* rb = &R[9 * (size_t)h->app_rp_b[k]];
+        const double* Z = &h->app_rp_R[9 * k];
+        double Ca[3], Cb[3], Pm[9], M[9];
+        centre(h->app_rp_a[k], Ca);
+        centre(h->app_rp_b[k], Cb);
+        double* e = r_out + 6 * k;
+        for (int r = 0; r < 3; ++r)
+            e[r] = ra[3 * r] * (Cb[0] - Ca[0]) + ra[3 * r + 1] * (Cb[1] - Ca[1]) + ra[3 * r + 2] * (Cb[2] - Ca[2]) - h->app_rp_t[3 * k + (size_t)r];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) Pm[3 * r + c] = ra[3 * r] * rb[3 * c] + ra[3 * r + 1] * rb[3 * c + 1] + ra[3 * r + 2] * rb[3 * c + 2];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) M[3 * r + c] = Z[r] * Pm[c] + Z[3 + r] * Pm[3 + c] + Z[6 + r] * Pm[6 + c];
+        // Log as the kernels take it (k_relpose_error)
+        const double v[3] = { 0.5 * (M[7] - M[5]), 0.5 * (M[2] - M[6]), 0.5 * (M[3] - M[1]) };
+        const double s2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], sn = std::sqrt(s2), cs = 0.5 * (M[0] + M[4] + M[8] - 1.0);
+        const double f = (sn < 1e-4 && cs > 0) ? 1.0 + s2 / 6.0 + 3.0 * s2 * s2 / 40.0 : std::atan2(sn, cs) / sn;
+        for (int c = 0; c < 3; ++c) e[3 + c] = f * v[c];
+    }
+    return SRK_OK;
+}
+int srk_ba_relative_pose_pass_ms(srk_ba* h, double* derivative_ms, double* couple_ms, double* error_ms)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
+    for (int sl = 1; sl < SRK_SLOTS; ++sl)
+        if (h->att[sl].stream) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
+    double* outs[3] = { derivative_ms, couple_ms, error_ms };
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0;
+        if (h->rp_timed[k] && hipEventElapsedTime(&ms, h->ev_rp[2 * k], h->ev_rp[2 * k + 1]) != hipSuccess) ms = 0;
+        if (outs[k]) *outs[k] = h->rp_timed[k] ? (double)ms : 0.0;
     }
     return SRK_OK;
 }

@@ -2878,10 +2878,108 @@ void srk_launch_prior_error(hipStream_t s, const double* pts, const double* cam,
     hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, nb - nbp, partial + nbp, out2 + 1, (int*)nullptr, (int*)nullptr);
 }
 
+// ------------------------------------------------------------------ relative-pose factors: residual, Jacobians, energy pass
+// (srk_ba_set_relative_pose_factors)
+// rotation vector of the rotation M (angle < pi): the antisymmetric part is sin(angle) axis; the series of asin(x) / x where
+// the angle is small
+__device__ __forceinline__ void rp_log(const double M[9], double phi[3])
+{
+    const double v[3] = { 0.5 * (M[7] - M[5]), 0.5 * (M[2] - M[6]), 0.5 * (M[3] - M[1]) };
+    const double s2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], sn = sqrt(s2), cs = 0.5 * (M[0] + M[4] + M[8] - 1.0);
+    const double k = (sn < 1e-4 && cs > 0) ? 1.0 + s2 / 6.0 + 3.0 * s2 * s2 / 40.0 : atan2(sn, cs) / sn;
+    for (int e = 0; e < 3; ++e) phi[e] = k * v[e];
+}
+// inverse right Jacobian of SO(3) at phi: I + [phi]x / 2 + k [phi]x^2, k = 1 / t^2 - (1 + cos t) / (2 t sin t) -> 1 / 12 + t^2 / 720
+__device__ __forceinline__ void rp_jrinv(const double p[3], double J[9])
+{
+    const double t2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+    double k;
+    if (t2 < 1e-6) k = 1.0 / 12.0 + t2 / 720.0;
+    else {
+        const double t = sqrt(t2);
+        k = 1.0 / t2 - (1.0 + cos(t)) / (2.0 * t * sin(t));
+    }
+    // [p]x^2 = p p^T - t2 I
+    J[0] = 1.0 + k * (p[0] * p[0] - t2); J[1] = -0.5 * p[2] + k * p[0] * p[1]; J[2] = 0.5 * p[1] + k * p[0] * p[2];
+    J[3] = 0.5 * p[2] + k * p[0] * p[1]; J[4] = 1.0 + k * (p[1] * p[1] - t2); J[5] = -0.5 * p[0] + k * p[1] * p[2];
+    J[6] = -0.5 * p[1] + k * p[0] * p[2]; J[7] = 0.5 * p[0] + k * p[1] * p[2]; J[8] = 1.0 + k * (p[2] * p[2] - t2);
+}
+// factor i of n between the camera packs ca, cb: e = [e_t; e_r] and d = C_b - C_a
+__device__ __forceinline__ void rp_residual(const double* __restrict__ ca, const double* __restrict__ cb,
+                                            const double* __restrict__ val, int64_t n, int64_t i, double e[6], double d[3])
+{
+    double Ca[3], Cb[3], P[9], M[9];
+    prior_centre(ca, Ca);
+    prior_centre(cb, Cb);
+    for (int k = 0; k < 3; ++k) d[k] = Cb[k] - Ca[k];
+    for (int r = 0; r < 3; ++r) e[r] = ca[3 * r] * d[0] + ca[3 * r + 1] * d[1] + ca[3 * r + 2] * d[2] - val[(9 + r) * n + i];
+    for (int r = 0; r < 3; ++r) // P = R_a R_b^T
+        for (int c = 0; c < 3; ++c) P[3 * r + c] = ca[3 * r] * cb[3 * c] + ca[3 * r + 1] * cb[3 * c + 1] + ca[3 * r + 2] * cb[3 * c + 2];
+    for (int r = 0; r < 3; ++r) // M = Z^T P
+        for (int c = 0; c < 3; ++c) M[3 * r + c] = val[r * n + i] * P[c] + val[(3 + r) * n + i] * P[3 + c] + val[(6 + r) * n + i] * P[6 + c];
+    rp_log(M, e + 3);
+}
+// the information matrix of factor i as a full symmetric 6 x 6
+__device__ __forceinline__ void rp_info(const double* __restrict__ val, int64_t n, int64_t i, double L[36])
+{
+    int k = 12;
+    for (int r = 0; r < 6; ++r)
+        for (int c = r; c < 6; ++c, ++k) L[6 * r + c] = L[6 * c + r] = val[k * n + i];
+}
+// the 6 x 6 Jacobian of e over the pose variables [Tx Ty Tz Wx Wy Wz] of frame a (side 0) or frame b (side 1): the translation
+// correction is added to the centre, the rotation correction multiplies the direct rotation R^T from the left (k_cam_apply)
+//   side 0: [-R_a, R_a [d]x; 0, -Jr^-1(e_r) R_b]      side 1: [R_a, 0; 0, Jr^-1(e_r) R_b]
+__device__ __forceinline__ void rp_jac(const double* __restrict__ ca, const double* __restrict__ cb, const double e[6],
+                                       const double d[3], int side, double J[36])
+{
+    double Ji[9];
+    rp_jrinv(e + 3, Ji);
+    const double sg = side ? 1.0 : -1.0;
+    const double dx[9] = { 0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0 };
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            J[6 * r + c] = sg * ca[3 * r + c];
+            J[6 * r + 3 + c] = side ? 0.0 : ca[3 * r] * dx[c] + ca[3 * r + 1] * dx[3 + c] + ca[3 * r + 2] * dx[6 + c];
+            J[6 * (3 + r) + c] = 0.0;
+            J[6 * (3 + r) + 3 + c] = sg * (Ji[3 * r] * cb[c] + Ji[3 * r + 1] * cb[3 + c] + Ji[3 * r + 2] * cb[6 + c]);
+        }
+}
+// One lane per factor, the block's sum in the fixed order of err_block_sum, one partial per block: no atomics, the same bits
+// from run to run.
+__global__ __launch_bounds__(256) void k_relpose_error(const double* __restrict__ cam, SrkRelPose p, double* __restrict__ partial)
+{
+    double sum = 0;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < p.n) {
+        double e[6], d[3], L[36];
+        rp_residual(cam + (int64_t)SRK_CAM_PACK * p.fa[i], cam + (int64_t)SRK_CAM_PACK * p.fb[i], p.val, p.n, i, e, d);
+        rp_info(p.val, p.n, i, L);
+        for (int r = 0; r < 6; ++r) {
+            double y = 0;
+            for (int c = 0; c < 6; ++c) y += L[6 * r + c] * e[c];
+            sum += e[r] * y;
+        }
+    }
+    err_block_sum(sum, partial + blockIdx.x);
+}
+static int32_t launch_relpose_partials(hipStream_t s, const double* cam, const SrkRelPose& p, double* partial, const hipEvent_t* ev)
+{
+    const int32_t nb = srk_relpose_partials(p.n);
+    if (ev) (void)hipEventRecord(ev[0], s);
+    hipLaunchKernelGGL(k_relpose_error, dim3((unsigned)nb), dim3(256), 0, s, cam, p, partial);
+    if (ev) (void)hipEventRecord(ev[1], s);
+    return nb;
+}
+void srk_launch_relpose_error(hipStream_t s, const double* cam, const SrkRelPose& p, double* partial, double* out)
+{
+    const int32_t nb = launch_relpose_partials(s, cam, p, partial, nullptr);
+    hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, nb, partial, out, (int*)nullptr, (int*)nullptr);
+}
+
 void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                       const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* partial,
                       int32_t n_partial, double* err_out, const int32_t* wg_jmin, int* info, int* info2, const SrkLoss* loss,
-                      const SrkPrior* prior, const hipEvent_t* prior_ev)
+                      const SrkPrior* prior, const hipEvent_t* prior_ev, const SrkRelPose* relpose, const hipEvent_t* relpose_ev)
 {
     const bool robust = srk_robust_side(loss);
     const bool staged = wg_jmin && d.O > 0; // staged cameras: one partial sum per run of SRK_JF_OBS observations
@@ -2899,6 +2997,8 @@ void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const 
         hipLaunchKernelGGL(k_error, dim3((unsigned)nb), dim3(256), 0, s, d, pts, cam, obs_frame, obs_pt, obs_uv, partial);
     // position priors: their partials behind the observation partials, one final sum over both
     if (prior) nb += launch_prior_partials(s, pts, cam, *prior, partial + nb, prior_ev);
+    // relative-pose factors: their partials behind the priors' 
+    if (relpose) nb += launch_relpose_partials(s, cam, *relpose, partial + nb, relpose_ev);
     hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, nb, partial, err_out, info, info2);
 }
 
@@ -3361,4 +3461,104 @@ void srk_launch_prior_add(hipStream_t s, const SrkDims& d, const double* pts, co
     const int64_t n = p.n_pts + p.n_frames;
     if (n <= 0) return;
     hipLaunchKernelGGL(k_prior_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, pts, cam, p, Vg, Ug);
+}
+
+// ------------------------------------------------------------------ relative-pose factors: the derivative-side pass and the coupling pass
+// (srk_ba_set_relative_pose_factors).  k_relpose_add: behind k_prior_add and before k_const_points.
+// Lane t < n_frames: the t-th frame with incident factors walks its list in factor order; for each it forms e and its own
+// Jacobian J from the current camera packs and adds 2 J^T L J to the upper triangle of the pose part of the frame's block in Ug
+// (variables 4..9 of ten, 0..5 of six) and 2 J^T L e to those gradient entries.  Lane n_frames + k: factor k writes its coupling
+// block 2 J_a^T L J_b into cpl[k], rows belonging to the frame with the larger internal index (transposed when that is b).
+// Every entry has one owner and a fixed order of additions: no atomics.
+__global__ __launch_bounds__(64) void k_relpose_add(SrkDims d, const double* __restrict__ cam, SrkRelPose p, double* __restrict__ Ug)
+{
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    double e[6], dd[3], L[36], J[36], LJ[36];
+    if (t < p.n_frames) {
+        const int64_t j = p.fr_list[t];
+        if (j < 0 || j >= d.M) return;
+        const int fv = d.fv, ut = fv * (fv + 1) / 2, t0 = 4 - SRK_FV_OFF(fv); // first pose variable of the frame
+        double* u = Ug + (int64_t)SRK_UGS(fv) * j;
+        for (int32_t q = p.fr_ptr[t]; q < p.fr_ptr[t + 1]; ++q) {
+            const int32_t k = p.fr_ent[q] >> 1, side = p.fr_ent[q] & 1;
+            const double* ca = cam + (int64_t)SRK_CAM_PACK * p.fa[k];
+            const double* cb = cam + (int64_t)SRK_CAM_PACK * p.fb[k];
+            rp_residual(ca, cb, p.val, p.n, k, e, dd);
+            rp_info(p.val, p.n, k, L);
+            rp_jac(ca, cb, e, dd, side, J);
+            for (int r = 0; r < 6; ++r)
+                for (int c = 0; c < 6; ++c) {
+                    double y = 0;
+                    for (int x = 0; x < 6; ++x) y += L[6 * r + x] * J[6 * x + c];
+                    LJ[6 * r + c] = y;
+                }
+            for (int a = 0; a < 6; ++a) {
+                const int va = t0 + a, row = va * fv - va * (va - 1) / 2; // row va of the upper triangle starts at its diagonal entry
+                for (int b = a; b < 6; ++b) {
+                    double y = 0;
+                    for (int x = 0; x < 6; ++x) y += J[6 * x + a] * LJ[6 * x + b];
+                    u[row + (b - a)] += 2.0 * y;
+                }
+                double g = 0;
+                for (int x = 0; x < 6; ++x) {
+                    double le = 0;
+                    for (int c = 0; c < 6; ++c) le += L[6 * x + c] * e[c];
+                    g += J[6 * x + a] * le;
+                }
+                u[ut + va] += 2.0 * g;
+            }
+        }
+        return;
+    }
+    const int64_t k = t - p.n_frames;
+    if (k >= p.n) return;
+    const int32_t fa = p.fa[k], fb = p.fb[k];
+    const double* ca = cam + (int64_t)SRK_CAM_PACK * fa;
+    const double* cb = cam + (int64_t)SRK_CAM_PACK * fb;
+    rp_residual(ca, cb, p.val, p.n, k, e, dd);
+    rp_info(p.val, p.n, k, L);
+    rp_jac(ca, cb, e, dd, 1, J); // J_b
+    for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) {
+            double y = 0;
+            for (int x = 0; x < 6; ++x) y += L[6 * r + x] * J[6 * x + c];
+            LJ[6 * r + c] = y;
+        }
+    rp_jac(ca, cb, e, dd, 0, J); // J_a
+    double* out = p.cpl + 36 * k;
+    for (int a = 0; a < 6; ++a)
+        for (int b = 0; b < 6; ++b) {
+            double y = 0;
+            for (int x = 0; x < 6; ++x) y += J[6 * x + a] * LJ[6 * x + b];
+            out[fa > fb ? 6 * a + b : 6 * b + a] = 2.0 * y;
+        }
+}
+void srk_launch_relpose_add(hipStream_t s, const SrkDims& d, const double* cam, const SrkRelPose& rp, double* Ug)
+{
+    const int64_t n = (int64_t)rp.n_frames + rp.n;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_relpose_add, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d, cam, rp, Ug);
+}
+
+// k_relpose_couple: behind k_assemble (the Schur sums and the frame blocks are in S) and before k_const_frames.  One wave per
+// factor; lane e < 36 adds entry (e / 6, e % 6) of the factor's block to S at the factor's target, inside the lower triangle and
+// the skyline (the planner put the pair into min_cv).  A gauge-fixed variable keeps its identity row and column.  The damping
+// does not enter.  One owner per entry.
+__global__ __launch_bounds__(64) void k_relpose_couple(SrkDims d, SrkRelPose p, double* __restrict__ S)
+{
+    const int64_t k = blockIdx.x;
+    const int e = threadIdx.x;
+    if (k >= p.n || e >= 36) return;
+    const int r = e / 6, c = e - 6 * r;
+    const int64_t at = p.tgt[k], row = at / d.ld + r, col = at % d.ld + c;
+    if (row >= d.ld || col >= row) return;
+    const bool fixed = d.fv == 6 ? (srk_is_fixed_var_fv<6>(row, d) || srk_is_fixed_var_fv<6>(col, d))
+                                 : (srk_is_fixed_var_fv<10>(row, d) || srk_is_fixed_var_fv<10>(col, d));
+    if (fixed) return;
+    S[row * d.ld + col] += p.cpl[36 * k + e];
+}
+void srk_launch_relpose_couple(hipStream_t s, const SrkDims& d, const SrkRelPose& rp, double* S)
+{
+    if (rp.n <= 0) return;
+    hipLaunchKernelGGL(k_relpose_couple, dim3((unsigned)rp.n), dim3(64), 0, s, d, rp, S);
 }

@@ -175,6 +175,33 @@ void srk_launch_prior_add(hipStream_t s, const SrkDims& d, const double* pts, co
                           double* Ug);
 // the two prior sums of a scene on their own (srk_ba_prior_error): partial [srk_prior_partials], out2 = {landmarks, frames}
 void srk_launch_prior_error(hipStream_t s, const double* pts, const double* cam, const SrkPrior& p, double* partial, double* out2);
+// relative-pose factors (srk_ba_set_relative_pose_factors): the lists of the resident scene.  Values as
+// SoA planes val[k n + i]: k = 0..8 the measured rotation Z (row-major), 9..11 the measured translation z (normalised world),
+// 12..32 the upper triangle of the information matrix row by row.  Every unordered pair appears once, so each entry the
+// passes touch has one owner.
+#define SRK_RP_PLANES 33
+struct SrkRelPose {
+    const int32_t* fa;       // [n] internal frame a of each factor
+    const int32_t* fb;       // [n] internal frame b
+    const double* val;       // [SRK_RP_PLANES][n]
+    int32_t n;
+    const int32_t* fr_list;  // [n_frames] internal frames with incident factors, ascending
+    const int32_t* fr_ptr;   // [n_frames + 1] CSR into fr_ent
+    const int32_t* fr_ent;   // 2 * factor + side (0: the frame is a, 1: it is b), in factor order
+    int32_t n_frames;
+    const int64_t* tgt;      // [n] offset in S of entry (0, 0) of the factor's block: row = first pose variable of the frame
+                             // with the larger internal index, column = that of the other
+    double* cpl;             // [n][36] the blocks 2 J^T L J in that orientation, written by the derivative-side pass
+};
+// partial sums the factor energy pass writes: one per 256 factors
+inline int32_t srk_relpose_partials(int64_t n) { return (int32_t)((n + 255) / 256); }
+// behind srk_launch_prior_add, before srk_launch_const_points: the factors' terms into the frame blocks and gradients of Ug,
+// and the coupling blocks into rp.cpl.  Launched only with factors.
+void srk_launch_relpose_add(hipStream_t s, const SrkDims& d, const double* cam, const SrkRelPose& rp, double* Ug);
+// behind srk_launch_assemble, before srk_launch_const_frames: rp.cpl into the lower triangle of S, fixed variables skipped
+void srk_launch_relpose_couple(hipStream_t s, const SrkDims& d, const SrkRelPose& rp, double* S);
+// the factor sum of a scene on its own (srk_ba_relative_pose_error): partial [srk_relpose_partials], out = the sum
+void srk_launch_relpose_error(hipStream_t s, const double* cam, const SrkRelPose& rp, double* partial, double* out);
 void srk_launch_backsub(hipStream_t s, const SrkDims& d, double c, const int32_t* obs_frame, const int32_t* obs_pt,
                         const double* W, const double* Vg, const double* dc, double* acc, const double* pts,
                         double* pts_trial, double* dx);
@@ -189,7 +216,10 @@ void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const 
                       const SrkLoss* loss = nullptr /* given (kind != 0 or information): the sum of rho(q s) instead of s */,
                       const SrkPrior* prior = nullptr /* given: the prior sums of this scene as srk_prior_partials more partials
                                                          behind the observation partials, summed with them */,
-                      const hipEvent_t* prior_ev = nullptr /* given: two events recorded around the prior pass */);
+                      const hipEvent_t* prior_ev = nullptr /* given: two events recorded around the prior pass */,
+                      const SrkRelPose* relpose = nullptr /* given: the factor sum as srk_relpose_partials more partials behind
+                                                             the priors' */,
+                      const hipEvent_t* relpose_ev = nullptr /* given: two events recorded around that pass */);
 // the IRLS weights w = rho'(s) of the resident scene, one per observation in the internal order (srk_ba_observation_weights)
 void srk_launch_obs_weights(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int32_t* obs_frame,
                             const int32_t* obs_pt, const double* obs_uv, const SrkLoss& loss, double* w);

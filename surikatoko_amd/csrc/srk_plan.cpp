@@ -29,7 +29,9 @@ bool srk_debug()
 // of two to three times the width (twice is the optimum for a ring).  Only the numbering changes -- arithmetic per block, gauge (the caller's frames 0 and 1, wherever they
 // land: SrkDims::g0, g1) and results are those of the caller's order; every download maps back.
 // Returns true and fills to_int[caller's frame] = internal index when renumbering pays.  mode: SrkPlanOptions::frame_order_mode.
-bool srk_frame_reorder(int mode, int64_t N, int32_t M, const int64_t* row_ptr, const int32_t* obs_frame, std::vector<int32_t>& to_int)
+// rel_a / rel_b: pairs of frames tied by a relative-pose factor -- edges of the graph like a shared landmark.
+bool srk_frame_reorder(int mode, int64_t N, int32_t M, const int64_t* row_ptr, const int32_t* obs_frame, std::vector<int32_t>& to_int,
+                       const int32_t* rel_a, const int32_t* rel_b, int64_t n_rel)
 {
     if (mode == 0 || M < 3 || M > 16384) return false;
     int64_t bw_nat = 0, lmax = 0;
@@ -39,6 +41,7 @@ bool srk_frame_reorder(int mode, int64_t N, int32_t M, const int64_t* row_ptr, c
         lmax = std::max(lmax, k);
         bw_nat = std::max<int64_t>(bw_nat, obs_frame[row_ptr[i + 1] - 1] - obs_frame[row_ptr[i]]); // lists ascend
     }
+    for (int64_t k = 0; k < n_rel; ++k) bw_nat = std::max<int64_t>(bw_nat, std::abs(rel_a[k] - rel_b[k]));
     if (mode < 0 && bw_nat <= 2 * lmax) return false; // as banded as tracks of that length allow
     // covisibility graph as a bit matrix (M <= 16384: 32 MB); every distinct frame list once
     const size_t wpr = ((size_t)M + 63) / 64;
@@ -68,6 +71,11 @@ bool srk_frame_reorder(int mode, int64_t N, int32_t M, const int64_t* row_ptr, c
             for (int64_t a = 0; a + 1 < k; ++a) link(f[a], f[a + 1]);
             link(f[0], f[k - 1]);
         }
+    }
+    for (int64_t k = 0; k < n_rel; ++k) {
+        const int32_t u = rel_a[k], v = rel_b[k];
+        adj[(size_t)u * wpr + (size_t)(v >> 6)] |= 1ull << (v & 63);
+        adj[(size_t)v * wpr + (size_t)(u >> 6)] |= 1ull << (u & 63);
     }
     std::vector<int32_t> deg((size_t)M, 0);
     for (int32_t j = 0; j < M; ++j)
@@ -145,6 +153,7 @@ bool srk_frame_reorder(int mode, int64_t N, int32_t M, const int64_t* row_ptr, c
         }
         if (hi >= 0) bw_new = std::max<int64_t>(bw_new, hi - lo);
     }
+    for (int64_t k = 0; k < n_rel; ++k) bw_new = std::max<int64_t>(bw_new, std::abs(to_int[(size_t)rel_a[k]] - to_int[(size_t)rel_b[k]]));
     if (srk_debug()) fprintf(stderr, "srk_ba frame order: bandwidth %lld frames in the caller's order, %lld after reverse Cuthill-McKee\n", (long long)bw_nat, (long long)bw_new);
     return mode > 0 ? differs : 10 * bw_new <= 7 * bw_nat;
 }
@@ -180,7 +189,7 @@ void plan_frame_order(const SrkSceneIn& in, const SrkPlanOptions& opt, Plan& p, 
         for (int32_t j = 0; j < M; ++j) renumber = renumber || to_int[(size_t)j] != j;
         p.frame_order_supplied = renumber;
     } else if (!opt.multi_rank)
-        renumber = srk_frame_reorder(opt.frame_order_mode, N, M, in.row_ptr, in.obs_frame, to_int);
+        renumber = srk_frame_reorder(opt.frame_order_mode, N, M, in.row_ptr, in.obs_frame, to_int, opt.rel_a, opt.rel_b, opt.n_rel);
     if (renumber) {
         p.frame_int = to_int;
         p.frame_user.assign((size_t)M, 0);
@@ -733,7 +742,8 @@ void plan_cal_list(Plan& p)
 
 // covisibility of THIS shard; with several ranks the caller must supply the global one (srk_ba_set_covisibility) -- until
 // then the skyline is the full lower triangle
-void plan_min_cv(Plan& p, int32_t M, bool multi_rank)
+// A relative-pose factor between frames a and b puts a block at (max, min) of the system like a shared landmark does.
+void plan_min_cv(Plan& p, int32_t M, bool multi_rank, const SrkPlanOptions& opt)
 {
     const std::vector<int64_t>& rp = p.row_ptr_int;
     p.min_cv.assign((size_t)M, 0);
@@ -745,6 +755,11 @@ void plan_min_cv(Plan& p, int32_t M, bool multi_rank)
         if (rp[i + 1] == rp[i]) continue;
         const int32_t first = of[rp[i]];
         for (int64_t o = rp[i]; o < rp[i + 1]; ++o) cv[of[o]] = std::min(cv[of[o]], first);
+    }
+    for (int64_t k = 0; k < opt.n_rel; ++k) {
+        const int32_t a = p.frame_int.empty() ? opt.rel_a[k] : p.frame_int[(size_t)opt.rel_a[k]];
+        const int32_t b = p.frame_int.empty() ? opt.rel_b[k] : p.frame_int[(size_t)opt.rel_b[k]];
+        cv[std::max(a, b)] = std::min(cv[std::max(a, b)], std::min(a, b));
     }
 }
 
@@ -788,6 +803,6 @@ void srk_plan_scene(const SrkSceneIn& in, const SrkPlanOptions& opt, SrkScenePla
     plan_frame_major(p);
     if (opt.fixed_k) plan_cal_list(p);
     p.n_cal_list = (int64_t)p.cal_list.size();
-    plan_min_cv(p, M, opt.multi_rank);
+    plan_min_cv(p, M, opt.multi_rank, opt);
     if (stage) stage("derivative tasks");
 }

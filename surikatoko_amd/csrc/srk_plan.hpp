@@ -28,6 +28,11 @@ struct SrkPlanOptions {
     int cus = 256;             // compute units of the device
     int run_split = 0;         // development build: SRK_SCHUR_RUN_SPLIT (0 = the model decides)
     bool no_long = false;      // development build: SRK_SCHUR_NO_LONG
+    // relative-pose factors (srk_ba_set_relative_pose_factors): the pairs of frames they tie, caller's numbering, switched-off
+    // factors left out.  Edges of the graph the renumbering looks at, and entries of min_cv like a shared landmark.
+    const int32_t* rel_a = nullptr;
+    const int32_t* rel_b = nullptr;
+    int64_t n_rel = 0;
 };
 
 // What later calls read of a plan.  The handle (srk_ba) derives from this and keeps it when the tables are on the device.
@@ -40,7 +45,7 @@ struct SrkPlanKept {
     std::vector<int32_t> frame_int, frame_user, obs_rank;
     bool frame_order_supplied = false; // the scene uses the supplied frame order
     std::vector<int64_t> fobs_of;      // two-kernel derivative path only: [internal observation] = its place in the frame-major copy
-    std::vector<int32_t> min_cv;       // [M] smallest frame sharing a landmark with frame j
+    std::vector<int32_t> min_cv;       // [M] smallest frame sharing a landmark (or a relative-pose factor) with frame j
     int64_t max_frame_obs = 0;
     int64_t n_cal_list = 0;
     int64_t n_long_items = 0, n_long_runs = 0;
@@ -79,6 +84,8 @@ void srk_plan_scene(const SrkSceneIn& in, const SrkPlanOptions& opt, SrkScenePla
                     const std::function<void(const char*)>& stage);
 
 // Returns true and fills to_int[caller's frame] = internal index when renumbering the frames pays.  mode: SrkPlanOptions::frame_order_mode.
-bool srk_frame_reorder(int mode, int64_t N, int32_t M, const int64_t* row_ptr, const int32_t* obs_frame, std::vector<int32_t>& to_int);
+// rel_a / rel_b: n_rel more pairs of frames (relative-pose factors) that count as covisible.
+bool srk_frame_reorder(int mode, int64_t N, int32_t M, const int64_t* row_ptr, const int32_t* obs_frame, std::vector<int32_t>& to_int,
+                       const int32_t* rel_a = nullptr, const int32_t* rel_b = nullptr, int64_t n_rel = 0);
 
 bool srk_debug(); // SRK_DEBUG=1: plan and per-attempt traces on stderr
