@@ -614,6 +614,59 @@ int srk_ba_normalize_relative_pose_factors(const srk_ba_normalizer* nrm, int32_t
  * launched or not timed.  One event pair a pass serves all attempt slots (tools/relpose_rate.py switches speculation off). */
 int srk_ba_relative_pose_pass_ms(srk_ba*, double* derivative_ms, double* couple_ms, double* error_ms);
 
+/* ---- marginal covariances of frames and landmarks (EXTENSION) ----
+ * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
+ * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior
+ * residual.  E is the objective LM minimises, every loss, information weight, prior and factor included; the library's blocks are
+ * the Gauss-Newton Hessian H of E in the factor-2 convention (a prior adds 2 L), so with pixel noise sigma_px the covariance of
+ * the estimate is 2 (sigma_px / f0)^2 H^-1.  With H = [[V, W], [W^T, U]] in point-major order and S = L L^T its Schur complement
+ * onto the frame variables, the block of frame j is Y^T Y with Y = L^-1 E_j (E_j the unit columns of the frame's variables) and
+ * the block of landmark i is V_i^-1 + Z^T Z with Z = L^-1 B_i, B_i holding W_o^T V_i^-1 in the rows of the frame of each of its
+ * observations o: one forward substitution with many right-hand sides on the factor of S and a small Gram product per block.
+ * Variables that do not move -- the seven gauge variables, constant frames, constant landmarks -- have covariance exactly 0:
+ * their rows and columns of a frame block are exact zeros and a constant landmark returns a zero block.  Every block is exactly
+ * symmetric.  Cross-covariances between two frames or two landmarks are not computed.
+ *
+ * srk_ba_phase_covariance: the staged entry point, after srk_ba_phase_derivatives and srk_ba_phase_schur(c).  Returns the raw
+ * blocks of the inverse of the system in slot 0, in the resident (normalised) scene's variables: frame_blocks [n][FV][FV]
+ * (FV = srk_ba_frame_vars, per-frame variable order as everywhere), point_blocks [n][3][3].  c = 0 is H^-1; with c > 0, V and the
+ * diagonal of S carry (1 + c) and the result is the inverse of that damped matrix (well conditioned; what the tests pin the
+ * arithmetic with).  Frame and landmark indices are in the caller's numbering, in any order, repeats allowed.  Whatever the rcs
+ * mode or chunk plan, the call factorises slot 0's system in place with the single-chain solver's unfused launch sequence (no
+ * hand-offs, so nothing can time out) and LEAVES THE SYSTEM CONSUMED, as srk_ba_phase_solve does in mode 1: SRK_BUF_RCS holds
+ * the factor afterwards, SRK_BUF_RCS_RHS and SRK_BUF_CORRECTIONS zeros; call srk_ba_phase_schur again before another solve.
+ * Returns 0 ok, 1 = the system is not positive definite, a landmark block is not invertible or a result is not finite (the
+ * output arrays are untouched), negative on error.
+ *
+ * srk_ba_covariances: the convenience call on the resident scene's current state (after srk_ba_optimize: the result): the
+ * derivative pass, the undamped system, the blocks above, scaled by 2 (sigma_pixels / f0)^2.  caller_coordinates = 1 maps them
+ * to the coordinates of the uploaded arrays (srk_ba_revert_covariances), 0 leaves them in the normalised scene's.  The scene is
+ * not changed.  In the default ten-variable mode the result is the covariance of the ten-variable problem; where per-frame
+ * intrinsics are close to unobservable (planar scenes) the undamped system is numerically singular and the call returns 1: use
+ * srk_ba_set_fixed_intrinsics for covariances of a calibrated rig.
+ *
+ * SRK_E_STATE without a scene.  SRK_E_ARGS (text in srk_ba_last_error): an index out of range, a negative count, a NULL array
+ * with a positive count, sigma_pixels not finite and positive; intrinsic groups or more than one rank (as priors refuse them).
+ * Fixed intrinsics, robust losses, information, constant blocks, priors, factors, frame reordering, deterministic mode and both
+ * storage precisions work unchanged.  The three kernels use no atomics and a fixed summation order: the same system gives the
+ * same bits.  Nothing is launched or allocated unless one of these calls is made. */
+int srk_ba_phase_covariance(srk_ba*, int32_t n_frames_sel, const int32_t* frames /* caller's numbering */,
+                            double* frame_blocks /* [n][FV][FV] */, int64_t n_points_sel, const int64_t* points,
+                            double* point_blocks /* [n][3][3] */);
+int srk_ba_covariances(srk_ba*, double sigma_pixels, int32_t n_frames_sel, const int32_t* frames, double* frame_cov /* [n][FV][FV] */,
+                       int64_t n_points_sel, const int64_t* points, double* point_cov /* [n][3][3] */, int caller_coordinates);
+/* host only, no device and no handle needed: blocks in the normalised scene's variables to the caller's coordinates, in place.
+ * X_n = s (R0 X + T0), so a landmark maps as R0^T Sigma R0 / s^2.  The pose variables of a frame are [centre; rotation vector
+ * applied to the direct rotation from the left] and map as D Sigma D^T with D = diag(R0^T / s, R0^T); with
+ * frame_vars = 10 the four intrinsic variables in front are not transformed (D has the identity there).  frame_vars: 6 or 10.
+ * Either count may be 0.  Returns SRK_OK or SRK_E_ARGS. */
+int srk_ba_revert_covariances(const srk_ba_normalizer* nrm, int frame_vars, int32_t n_frames, double* frame_cov /* [n][fv][fv] */,
+                              int64_t n_points, double* point_cov /* [n][3][3] */);
+/* harness knob: the right-hand sides of the forward substitution are processed in batches of columns so that their buffer
+ * (handle-owned, grown lazily, freed by srk_ba_destroy) stays under 256 MB; max_columns > 0 caps a batch at that many columns
+ * instead (at least one block; tests force several batches at small sizes), 0 = the default. */
+int srk_ba_set_covariance_batch(srk_ba*, int64_t max_columns);
+
 /* device-time instrumentation of srk_ba_optimize / srk_ba_compute_inplace: 0 = none (default; report.ms_* stay 0
  * except ms_total), 1 = one HIP event pair per phase (fills report.ms_*), 2 = additionally event pairs around
  * every MFMA trailing-update launch (fills report.ms_solve_syrk / solve_mfma_flops).  Every event costs a few

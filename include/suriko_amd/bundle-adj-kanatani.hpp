@@ -113,6 +113,8 @@ public:
         f0_ = f0;
         points_count_ = f.ids.size();
         frames_count_ = inverse_orient_cams.size();
+        pnt_ind_of_.assign(map.SalientPointsCount(), -1); // for Covariances: salient point -> pnt_ind of the resident scene
+        for (size_t i = 0; i < f.ids.size(); ++i) pnt_ind_of_[map.SalientPointIndex(f.ids[i])] = (int64_t)i;
         // write back: points by salient-point id, cameras in place (K is never modified)
         for (size_t i = 0; i < f.ids.size(); ++i) {
             Point3& p = map.GetSalientPoint(f.ids[i]);
@@ -271,6 +273,42 @@ public:
         if (rc < 0) Raise(rc);
     }
 
+    /// EXTENSION: marginal covariances of the last ComputeInplace's result (srk_ba_covariances).  frames:
+    /// cameras; points: salient points of the map by their place in it (the order of AddSalientPoint) -- the adapter maps them
+    /// to pnt_ind as it maps the points themselves.  Any order, repeats allowed.  frame_cov receives one row-major FV x FV block
+    /// per camera (FV = 10, or 6 after SetFixedIntrinsics; variable order of bundle-adj-kanatani.h:113-118), point_cov one 3 x 3
+    /// block per point, for pixel noise sigma_pixels, in the coordinates of the map and the cameras.  Returns false (outputs
+    /// empty) when the undamped system is not positive definite -- with ten variables a frame on planar scenes the intrinsics
+    /// are close to unobservable: use SetFixedIntrinsics.  Throws std::invalid_argument for an index beyond the cameras / the
+    /// map, a salient point no track of the last ComputeInplace carried, and a sigma that is not finite and positive.
+    bool Covariances(const std::vector<size_t>& frames, const std::vector<size_t>& points, Scalar sigma_pixels,
+                     std::vector<Scalar>* frame_cov, std::vector<Scalar>* point_cov) {
+        std::vector<int32_t> fi;
+        std::vector<int64_t> pi;
+        for (size_t j : frames) {
+            if (j >= frames_count_) throw std::invalid_argument("covariances: a camera index is beyond the cameras");
+            fi.push_back((int32_t)j);
+        }
+        for (size_t k : points) {
+            if (k >= pnt_ind_of_.size() || pnt_ind_of_[k] < 0) throw std::invalid_argument("covariances: no track of the last ComputeInplace carries this salient point");
+            pi.push_back(pnt_ind_of_[k]);
+        }
+        const size_t fv = (size_t)srk_ba_frame_vars(h_);
+        std::vector<Scalar> fc(fv * fv * fi.size()), pc(9 * pi.size());
+        int rc = srk_ba_covariances(h_, (double)sigma_pixels, (int32_t)fi.size(), fi.empty() ? nullptr : fi.data(), fi.empty() ? nullptr : fc.data(),
+                                    (int64_t)pi.size(), pi.empty() ? nullptr : pi.data(), pi.empty() ? nullptr : pc.data(), 1);
+        if (rc < 0) Raise(rc);
+        if (rc != 0) { fc.clear(); pc.clear(); }
+        if (frame_cov) *frame_cov = std::move(fc);
+        if (point_cov) *point_cov = std::move(pc);
+        return rc == 0;
+    }
+    /// EXTENSION (harness knob): cap a batch of right-hand-side columns of Covariances (srk_ba_set_covariance_batch; 0 = default)
+    void SetCovarianceBatch(int64_t max_columns) {
+        int rc = srk_ba_set_covariance_batch(h_, max_columns);
+        if (rc < 0) Raise(rc);
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
@@ -387,6 +425,7 @@ private:
     bool prior_set_ = false, prior_keep_gauge_ = true;
     std::vector<PositionPrior> prior_points_, prior_frames_;
     std::vector<RelativePoseFactor> relpose_;
+    std::vector<int64_t> pnt_ind_of_;
 };
 
 } // namespace suriko_amd

@@ -65,6 +65,7 @@ EXPORTS = [
     "srk_ba_set_relative_pose_factors", "srk_ba_check_relative_pose_factors", "srk_ba_relative_pose_factor_count", "srk_ba_relative_pose_factors",
     "srk_ba_relative_pose_error", "srk_ba_relative_pose_residuals", "srk_ba_normalize_relative_pose_factors",
     "srk_ba_relative_pose_pass_ms",
+    "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
     "srk_ba_upload_scene", "srk_ba_optimize", "srk_ba_download_scene", "srk_ba_reset_scene", "srk_ba_phase_error",
     "srk_ba_phase_derivatives", "srk_ba_phase_schur", "srk_ba_phase_solve", "srk_ba_phase_backsub",
@@ -142,6 +143,10 @@ def lib():
     L.srk_ba_relative_pose_residuals.argtypes = [C.c_void_p, C.c_void_p]
     L.srk_ba_normalize_relative_pose_factors.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.srk_ba_relative_pose_pass_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.srk_ba_phase_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.srk_ba_covariances.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+    L.srk_ba_revert_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    L.srk_ba_set_covariance_batch.argtypes = [C.c_void_p, C.c_int64]
     L.srk_ba_revert_normalization.restype = None
     L.srk_circle_camera_shots.restype = None
     _lib = L

@@ -203,6 +203,22 @@ def normalize_position_priors(nrm, pos, info):
     return po, io
 
 
+def revert_covariances(nrm, frame_cov=None, point_cov=None):
+    """covariance blocks of the normalised scene's variables in the caller's coordinates (srk_ba_revert_covariances; host only):
+    frame_cov [n][fv][fv] (fv 6 or 10), point_cov [n][3][3]; either may be None.  Returns copies (frame_cov, point_cov)."""
+    fc = None if frame_cov is None else np.array(frame_cov, dtype=np.float64, order="C")
+    pc = None if point_cov is None else np.array(point_cov, dtype=np.float64, order="C").reshape(-1, 3, 3)
+    fv = 6 if fc is None else fc.shape[-1]
+    if fc is not None:
+        fc = fc.reshape(-1, fv, fv)
+    rc = lib().srk_ba_revert_covariances(C.byref(nrm), C.c_int(fv), C.c_int32(0 if fc is None else len(fc)),
+                                         _p(fc) if fc is not None and len(fc) else None, C.c_int64(0 if pc is None else len(pc)),
+                                         _p(pc) if pc is not None and len(pc) else None)
+    if rc != 0:
+        raise ValueError("srk_ba_revert_covariances: bad argument")
+    return fc, pc
+
+
 _RP_TRI = [(r, c) for r in range(6) for c in range(r, 6)]  # the 21 entries of the upper triangle of a 6 x 6, row by row
 
 
@@ -892,6 +908,45 @@ class BundleAdjustmentKanatani:
 
     def phase_accept(self):
         self._raise(self._lib.srk_ba_phase_accept(C.c_void_p(self._h)))
+
+    # ---- marginal covariances
+    def _cov_selection(self, frames, points):
+        M, N = self._scene.M, self._scene.N
+        fr = np.arange(M, dtype=np.int32) if frames is None else np.ascontiguousarray(np.asarray(frames).reshape(-1), dtype=np.int32)
+        pt = np.arange(N, dtype=np.int64) if points is None else np.ascontiguousarray(np.asarray(points).reshape(-1), dtype=np.int64)
+        fv = self.frame_vars()
+        return fr, pt, np.zeros((len(fr), fv, fv)), np.zeros((len(pt), 3, 3))
+
+    def set_covariance_batch(self, max_columns=0):
+        """cap a batch of right-hand-side columns of the covariance calls (harness knob; 0 = as many as fit 256 MB)"""
+        self._raise(self._lib.srk_ba_set_covariance_batch(C.c_void_p(self._h), C.c_int64(int(max_columns))))
+
+    def phase_covariance(self, frames=None, points=None):
+        """(frame_blocks [n][FV][FV], point_blocks [n][3][3]): the diagonal blocks of the inverse of the system phase_schur(c) left
+        in slot 0, in the resident (normalised) scene's variables; None = every frame / every landmark, an empty list = none.
+        Consumes the system.  Raises numpy.linalg.LinAlgError when it is not positive definite."""
+        fr, pt, fb, pb = self._cov_selection(frames, points)
+        rc = self._lib.srk_ba_phase_covariance(C.c_void_p(self._h), C.c_int32(len(fr)), _p(fr) if len(fr) else None,
+                                               _p(fb) if len(fr) else None, C.c_int64(len(pt)), _p(pt) if len(pt) else None,
+                                               _p(pb) if len(pt) else None)
+        self._raise(rc)
+        if rc != 0:
+            raise np.linalg.LinAlgError("srk_ba_phase_covariance: the system is not positive definite")
+        return fb, pb
+
+    def covariances(self, frames=None, points=None, sigma_pixels=1.0, caller_coordinates=True):
+        """(frame_cov [n][FV][FV], point_cov [n][3][3]): marginal covariances of the resident scene's current state for pixel
+        noise sigma_pixels, 2 (sigma_pixels / f0)^2 H^-1; in the coordinates of the uploaded arrays unless caller_coordinates is
+        False.  None = every frame / every landmark, an empty list = none.  Raises numpy.linalg.LinAlgError when the undamped
+        system is not positive definite (ten frame variables on a planar scene: use set_fixed_intrinsics)."""
+        fr, pt, fb, pb = self._cov_selection(frames, points)
+        rc = self._lib.srk_ba_covariances(C.c_void_p(self._h), C.c_double(float(sigma_pixels)), C.c_int32(len(fr)),
+                                          _p(fr) if len(fr) else None, _p(fb) if len(fr) else None, C.c_int64(len(pt)),
+                                          _p(pt) if len(pt) else None, _p(pb) if len(pt) else None, C.c_int(int(bool(caller_coordinates))))
+        self._raise(rc)
+        if rc != 0:
+            raise np.linalg.LinAlgError("srk_ba_covariances: the system is not positive definite")
+        return fb, pb
 
     def buffer(self, which):
         """flat download of a staged buffer; its layout follows frame_vars() (include/srk_ba.h SRK_BUF_*)"""

@@ -7,6 +7,7 @@
 // There is NO CPU fallback: every compute call needs a HIP device and fails loudly (SRK_E_DEVICE) without one.
 #include "../../include/srk_ba.h"
 #include "srk_dev.hpp"
+#include "srk_cov.hpp"
 #include "srk_geom.hpp"
 #include "srk_plan.hpp"
 
@@ -231,6 +232,12 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     // OUTSIDE the parts the next attempt rewrites (k_panel's dead rows: 0 * NaN).  The flag makes the next entry point
     // re-zero every slot's system and plan buffers (clear_poison) before anything is computed from them.
     bool poisoned = false;
+    // marginal covariances (srk_ba_phase_covariance): the right-hand sides Y of the forward substitution and
+    // the small tables of a call, grown lazily; cov_batch_cols: srk_ba_set_covariance_batch (0 = as many columns as fit 256 MB);
+    // cov_pt_frame0: the first internal frame of every internal landmark, fetched at the first call after an upload
+    DevBuf cov_Y, cov_grp, cov_blk, cov_out, cov_free, cov_colb;
+    int64_t cov_batch_cols = 0;
+    std::vector<int32_t> cov_pt_frame0;
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -394,7 +401,8 @@ void srk_ba_destroy(srk_ba* h)
                       &h->jr_first, &h->jr_count, &h->jr_jmin, &h->jr_group, &h->lg_item, &h->lg_np, &h->lg_nf, &h->lg_pts, &h->lg_frames,
                       &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk,
                       &h->info_q, &h->info_qf, &h->cst_pts, &h->cst_frames, &h->pri_pt_list, &h->pri_pt_val, &h->pri_fr_list, &h->pri_fr_val,
-                      &h->rp_fa, &h->rp_fb, &h->rp_val, &h->rp_fr_list, &h->rp_fr_ptr, &h->rp_fr_ent, &h->rp_tgt, &h->rp_cpl };
+                      &h->rp_fa, &h->rp_fb, &h->rp_val, &h->rp_fr_list, &h->rp_fr_ptr, &h->rp_fr_ent, &h->rp_tgt, &h->rp_cpl,
+                      &h->cov_Y, &h->cov_grp, &h->cov_blk, &h->cov_out, &h->cov_free, &h->cov_colb };
     for (DevBuf* b : all) dev_free(*b);
     for (auto& a : h->att) {
         for (DevBuf* b : { &a.S, &a.rhs, &a.wy, &a.dc, &a.acc, &a.dx, &a.err_partial, &a.info, &a.dinv, &a.packed, &a.sync_flags, &a.irr, &a.det_stage, &a.det_rhs,
@@ -1244,6 +1252,7 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     d.w_f32 = h->store_f32 ? 1 : 0;
     h->d = d;
     h->f0 = f0;
+    h->cov_pt_frame0.clear();
 
     // ---- the device buffers of the scene, each named once: allocated in this order, then filled from its host source (if any)
     struct Up { DevBuf& buf; const void* src; size_t bytes; }; // src NULL: nothing to copy
@@ -2161,6 +2170,244 @@ int srk_ba_phase_accept(srk_ba* h)
     if (!h || !h->have_scene) return SRK_E_STATE;
     std::swap(h->cur, h->att[0].trial); // slot 0's trial scene becomes current
     return SRK_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------ marginal covariances
+
+// the map of srk_ba_revert_covariances on one block: landmarks R0^T Sigma R0 / s^2; frames D Sigma D^T with
+// D = diag(I (intrinsics, fv = 10 only), R0^T / s, R0^T)
+static void cov_revert_frame(const srk_ba_normalizer& nrm, int fv, double* B)
+{
+    const int off = fv - 6;
+    const double is = 1.0 / nrm.world_scale;
+    double D[100] = {};
+    for (int i = 0; i < off; ++i) D[i * fv + i] = 1.0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            D[(off + a) * fv + off + b] = nrm.R0[3 * b + a] * is;
+            D[(off + 3 + a) * fv + off + 3 + b] = nrm.R0[3 * b + a];
+        }
+    double T[100];
+    for (int i = 0; i < fv; ++i)
+        for (int j = 0; j < fv; ++j) {
+            double v = 0;
+            for (int k = 0; k < fv; ++k) v += D[i * fv + k] * B[k * fv + j];
+            T[i * fv + j] = v;
+        }
+    for (int i = 0; i < fv; ++i)
+        for (int j = i; j < fv; ++j) {
+            double v = 0;
+            for (int k = 0; k < fv; ++k) v += T[i * fv + k] * D[j * fv + k];
+            B[i * fv + j] = B[j * fv + i] = v;
+        }
+}
+static void cov_revert_point(const srk_ba_normalizer& nrm, double* B)
+{
+    const double is2 = 1.0 / (nrm.world_scale * nrm.world_scale);
+    const double* R = nrm.R0;
+    double T[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) T[3 * i + j] = R[i] * B[j] + R[3 + i] * B[3 + j] + R[6 + i] * B[6 + j]; // R0^T Sigma
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) B[3 * i + j] = B[3 * j + i] = (T[3 * i] * R[j] + T[3 * i + 1] * R[3 + j] + T[3 * i + 2] * R[6 + j]) * is2;
+}
+
+static int cov_check_args(srk_ba* h, int32_t nf, const int32_t* frames, const double* fb, int64_t np, const int64_t* points, const double* pb)
+{
+    if (nf < 0 || np < 0 || (nf > 0 && (!frames || !fb)) || (np > 0 && (!points || !pb))) {
+        h->last_error = "covariance: a negative count, or a NULL array with a positive count";
+        return SRK_E_ARGS;
+    }
+    if (h->world > 1 || h->allreduce || h->comm) { h->last_error = "covariance: more than one rank is not supported"; return SRK_E_ARGS; }
+    if (h->shk_G > 0) { h->last_error = "covariance: intrinsic groups are not supported"; return SRK_E_ARGS; }
+    for (int32_t k = 0; k < nf; ++k)
+        if (frames[k] < 0 || frames[k] >= h->d.M) { h->last_error = "covariance: a frame index is out of range"; return SRK_E_ARGS; }
+    for (int64_t k = 0; k < np; ++k)
+        if (points[k] < 0 || points[k] >= h->d.N) { h->last_error = "covariance: a landmark index is out of range"; return SRK_E_ARGS; }
+    return SRK_OK;
+}
+
+// the blocks of the inverse of the system in slot 0 (built by phase_schur at h->last_hessian_factor); 0 ok, 1 not positive
+// definite / non-finite, negative on error.  Arguments checked by the caller.
+static int phase_covariance(srk_ba* h, int32_t nf, const int32_t* frames, double* frame_blocks, int64_t np, const int64_t* points,
+                            double* point_blocks)
+{
+    const SrkDims& d = h->d;
+    srk_ba::Attempt& a = h->att[0];
+    hipStream_t s = a.stream;
+    const int fv = d.fv;
+    const double c = h->last_hessian_factor;
+    const int64_t n_rows = fv * (int64_t)d.M;
+    const int32_t n_tiles = (int32_t)((n_rows + 63) / 64);
+    int rc;
+    // the factor: the single-chain solve with a zero right-hand side and the unfused launch sequence, whatever the rcs mode
+    HIPCHK(h, hipMemsetAsync(a.info.p, 0, 4, s));
+    HIPCHK(h, hipMemsetAsync(a.rhs.p, 0, (size_t)(8 * d.ld), s));
+    srk_chol_solve(s, d.ld, P<double>(a.S), P<double>(a.rhs), P<double>(a.wy), P<double>(a.dc), P<int>(a.info), h->row_end_h.data(),
+                   h->col_begin_h.data(), P<double>(a.dinv), nullptr, nullptr, n_rows);
+    HIPCHK(h, hipGetLastError());
+    int info = 0;
+    if ((rc = read_info(h, a, &info)) != SRK_OK) return rc;
+    if (info) { h->poisoned = true; return 1; }
+    if (nf == 0 && np == 0) return 0;
+
+    // which variables move
+    std::vector<uint8_t> free_var((size_t)d.ld, 0);
+    {
+        const int off = 10 - fv;
+        const int64_t b0 = fv * (int64_t)d.g0, v1 = fv * (int64_t)d.g1 + 4 - off + d.comp;
+        for (int64_t var = 0; var < n_rows; ++var) {
+            const bool gauge = (var >= b0 + 4 - off && var <= b0 + 9 - off) || var == v1;
+            const bool cst = !h->cst_frame_int.empty() && h->cst_frame_int[(size_t)(var / fv)];
+            free_var[(size_t)var] = gauge || cst ? 0 : 1;
+        }
+    }
+    if ((rc = dev_alloc(h, h->cov_free, (size_t)d.ld)) != SRK_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->cov_free.p, free_var.data(), (size_t)d.ld, hipMemcpyHostToDevice, s));
+    if ((rc = dev_alloc(h, h->cov_colb, (size_t)(8 * (d.ld / 64)))) != SRK_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->cov_colb.p, h->col_begin_h.data(), (size_t)(8 * (d.ld / 64)), hipMemcpyHostToDevice, s));
+    // landmarks: internal index and the first frame that sees them
+    std::vector<int64_t> pt_int;
+    if (np > 0) {
+        if (h->cov_pt_frame0.empty()) {
+            std::vector<int32_t> of((size_t)d.O);
+            HIPCHK(h, hipMemcpyAsync(of.data(), h->obs_frame.p, (size_t)(4 * d.O), hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipStreamSynchronize(s));
+            h->cov_pt_frame0.assign((size_t)d.N, 0);
+            for (int64_t i = 0; i < d.N; ++i) {
+                int32_t f0 = d.M - 1;
+                for (int64_t o = h->row_ptr_int[(size_t)i]; o < h->row_ptr_int[(size_t)i + 1]; ++o) f0 = std::min(f0, of[(size_t)o]);
+                h->cov_pt_frame0[(size_t)i] = f0;
+            }
+        }
+        pt_int.assign((size_t)d.N, 0);
+        for (int64_t i = 0; i < d.N; ++i) pt_int[(size_t)h->perm[(size_t)i]] = i;
+    }
+    // the selected blocks, sorted by their first non-zero row so that every column block starts late
+    struct Sel { SrkCovGroup g; int64_t dst; };
+    std::vector<Sel> sel;
+    sel.reserve((size_t)(nf + np));
+    for (int32_t k = 0; k < nf; ++k) {
+        const int32_t f = h->frame_int.empty() ? frames[k] : h->frame_int[(size_t)frames[k]];
+        sel.push_back(Sel{ SrkCovGroup{ f, 0, fv, (int32_t)(fv * (int64_t)f), 0 }, k });
+    }
+    std::vector<char> pt_zero((size_t)np, 0);
+    for (int64_t k = 0; k < np; ++k) {
+        if ((size_t)points[k] < h->cst_point_user.size() && h->cst_point_user[(size_t)points[k]]) { pt_zero[(size_t)k] = 1; continue; } // constant: a zero block
+        const int64_t i = pt_int[(size_t)points[k]];
+        sel.push_back(Sel{ SrkCovGroup{ i, 0, 3, (int32_t)(fv * (int64_t)h->cov_pt_frame0[(size_t)i]), 1 }, nf + k });
+    }
+    std::stable_sort(sel.begin(), sel.end(), [](const Sel& x, const Sel& y) { return x.g.first_row < y.g.first_row; });
+    // batches of columns: Y [ld][ncp] stays under the byte cap
+    int64_t max_cols = std::max<int64_t>(SRK_COV_CB, ((int64_t)256 << 20) / (8 * d.ld) / SRK_COV_CB * SRK_COV_CB);
+    if (h->cov_batch_cols > 0) max_cols = std::max<int64_t>(10, h->cov_batch_cols);
+    std::vector<double> res((size_t)(100 * sel.size()));
+    std::vector<SrkCovGroup> grp;
+    std::vector<int32_t> blk;
+    for (size_t b0 = 0; b0 < sel.size();) {
+        size_t b1 = b0;
+        int64_t cols = 0;
+        grp.clear();
+        while (b1 < sel.size() && cols + sel[b1].g.ncols <= max_cols) {
+            SrkCovGroup g = sel[b1].g;
+            g.col0 = (int32_t)cols;
+            cols += g.ncols;
+            grp.push_back(g);
+            ++b1;
+        }
+        const int64_t ncp = (cols + SRK_COV_CB - 1) / SRK_COV_CB * SRK_COV_CB;
+        blk.assign((size_t)(ncp / SRK_COV_CB), n_tiles);
+        for (const SrkCovGroup& g : grp)
+            for (int64_t q = g.col0 / SRK_COV_CB; q <= (g.col0 + g.ncols - 1) / SRK_COV_CB; ++q)
+                blk[(size_t)q] = std::min<int32_t>(blk[(size_t)q], g.first_row / 64);
+        const int32_t ng = (int32_t)grp.size();
+        if ((rc = dev_alloc(h, h->cov_Y, (size_t)(8 * d.ld * ncp))) != SRK_OK) return rc;
+        if ((rc = dev_alloc(h, h->cov_grp, sizeof(SrkCovGroup) * grp.size())) != SRK_OK) return rc;
+        if ((rc = dev_alloc(h, h->cov_blk, 4 * blk.size())) != SRK_OK) return rc;
+        if ((rc = dev_alloc(h, h->cov_out, (size_t)(800 * ng))) != SRK_OK) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->cov_grp.p, grp.data(), sizeof(SrkCovGroup) * grp.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->cov_blk.p, blk.data(), 4 * blk.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemsetAsync(h->cov_Y.p, 0, (size_t)(8 * 64 * (int64_t)n_tiles * ncp), s));
+        HIPCHK(h, hipMemsetAsync(h->cov_out.p, 0, (size_t)(800 * ng), s));
+        srk_launch_cov_rhs(s, d, c, P<SrkCovGroup>(h->cov_grp), ng, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W),
+                           P<double>(h->Vg), P<uint8_t>(h->cov_free), P<double>(h->cov_Y), ncp, P<int>(a.info));
+        srk_launch_cov_fwd(s, d.ld, P<double>(a.S), P<double>(a.dinv), P<int64_t>(h->cov_colb), n_tiles, P<int32_t>(h->cov_blk),
+                           P<double>(h->cov_Y), ncp);
+        srk_launch_cov_gram(s, d, c, P<SrkCovGroup>(h->cov_grp), ng, P<double>(h->Vg), P<double>(h->cov_Y), ncp, n_rows, P<double>(h->cov_out));
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(res.data() + 100 * b0, h->cov_out.p, (size_t)(800 * ng), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s)); // grp / blk are reused by the next batch
+        b0 = b1;
+    }
+    if ((rc = read_info(h, a, &info)) != SRK_OK) return rc;
+    if (info) return 1;
+    for (size_t k = 0; k < sel.size(); ++k) {
+        const int n = sel[k].g.ncols;
+        for (int e = 0; e < n * n; ++e)
+            if (!std::isfinite(res[100 * k + e])) return 1;
+    }
+    for (size_t k = 0; k < sel.size(); ++k) {
+        const int n = sel[k].g.ncols;
+        double* dst = sel[k].g.is_point ? point_blocks + 9 * (sel[k].dst - nf) : frame_blocks + (int64_t)fv * fv * sel[k].dst;
+        std::memcpy(dst, res.data() + 100 * k, sizeof(double) * (size_t)(n * n));
+    }
+    for (int64_t k = 0; k < np; ++k)
+        if (pt_zero[(size_t)k]) std::fill(point_blocks + 9 * k, point_blocks + 9 * k + 9, 0.0);
+    return 0;
+}
+
+extern "C" {
+
+int srk_ba_set_covariance_batch(srk_ba* h, int64_t max_columns)
+{
+    if (!h || max_columns < 0) return SRK_E_ARGS;
+    h->cov_batch_cols = max_columns;
+    return SRK_OK;
+}
+
+int srk_ba_phase_covariance(srk_ba* h, int32_t n_frames_sel, const int32_t* frames, double* frame_blocks, int64_t n_points_sel,
+                            const int64_t* points, double* point_blocks)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    int rc = cov_check_args(h, n_frames_sel, frames, frame_blocks, n_points_sel, points, point_blocks);
+    if (rc != SRK_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return phase_covariance(h, n_frames_sel, frames, frame_blocks, n_points_sel, points, point_blocks);
+}
+
+int srk_ba_revert_covariances(const srk_ba_normalizer* nrm, int frame_vars, int32_t n_frames, double* frame_cov, int64_t n_points,
+                              double* point_cov)
+{
+    if (!nrm || (frame_vars != 6 && frame_vars != 10) || n_frames < 0 || n_points < 0 || (n_frames > 0 && !frame_cov) ||
+        (n_points > 0 && !point_cov) || !(nrm->world_scale > 0) || !std::isfinite(nrm->world_scale))
+        return SRK_E_ARGS;
+    for (int32_t k = 0; k < n_frames; ++k) cov_revert_frame(*nrm, frame_vars, frame_cov + (int64_t)frame_vars * frame_vars * k);
+    for (int64_t k = 0; k < n_points; ++k) cov_revert_point(*nrm, point_cov + 9 * k);
+    return SRK_OK;
+}
+
+int srk_ba_covariances(srk_ba* h, double sigma_pixels, int32_t n_frames_sel, const int32_t* frames, double* frame_cov,
+                       int64_t n_points_sel, const int64_t* points, double* point_cov, int caller_coordinates)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    if (!(sigma_pixels > 0) || !std::isfinite(sigma_pixels)) { h->last_error = "covariances: sigma_pixels must be finite and positive"; return SRK_E_ARGS; }
+    int rc = cov_check_args(h, n_frames_sel, frames, frame_cov, n_points_sel, points, point_cov);
+    if (rc != SRK_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = clear_poison(h)) != SRK_OK) return rc;
+    if ((rc = phase_derivatives(h)) != SRK_OK) return rc;
+    h->last_slot = 0;
+    if ((rc = phase_schur(h, h->att[0], 0.0)) != SRK_OK) return rc;
+    rc = phase_covariance(h, n_frames_sel, frames, frame_cov, n_points_sel, points, point_cov);
+    if (rc != 0) return rc;
+    const int fv = h->d.fv;
+    const double k = 2.0 * (sigma_pixels / h->f0) * (sigma_pixels / h->f0);
+    for (int64_t e = 0; e < (int64_t)fv * fv * n_frames_sel; ++e) frame_cov[e] *= k;
+    for (int64_t e = 0; e < 9 * n_points_sel; ++e) point_cov[e] *= k;
+    if (caller_coordinates && h->normalized_on_upload) srk_ba_revert_covariances(&h->nrm, fv, n_frames_sel, frame_cov, n_points_sel, point_cov);
+    return 0;
 }
 
 } // extern "C"
