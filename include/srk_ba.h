@@ -625,7 +625,7 @@ int srk_ba_relative_pose_pass_ms(srk_ba*, double* derivative_ms, double* couple_
  * observations o: one forward substitution with many right-hand sides on the factor of S and a small Gram product per block.
  * Variables that do not move -- the seven gauge variables, constant frames, constant landmarks -- have covariance exactly 0:
  * their rows and columns of a frame block are exact zeros and a constant landmark returns a zero block.  Every block is exactly
- * symmetric.  Cross-covariances between two frames or two landmarks are not computed.
+ * symmetric.  The blocks between two different frames or landmarks are the next section's (srk_ba_cross_covariances).
  *
  * srk_ba_phase_covariance: the staged entry point, after srk_ba_phase_derivatives and srk_ba_phase_schur(c).  Returns the raw
  * blocks of the inverse of the system in slot 0, in the resident (normalised) scene's variables: frame_blocks [n][FV][FV]
@@ -666,6 +666,49 @@ int srk_ba_revert_covariances(const srk_ba_normalizer* nrm, int frame_vars, int3
  * (handle-owned, grown lazily, freed by srk_ba_destroy) stays under 256 MB; max_columns > 0 caps a batch at that many columns
  * instead (at least one block; tests force several batches at small sizes), 0 = the default. */
 int srk_ba_set_covariance_batch(srk_ba*, int64_t max_columns);
+
+/* ---- cross-covariances between blocks and relative-pose covariances (EXTENSION) ----
+ * The marginal blocks above do not answer "how well is the pose of frame b known relative to frame a?": that is
+ * J [[S_aa, S_ab], [S_ba, S_bb]] J^T and needs the block between the two frames, which far from the gauge frames is of the size
+ * of the marginals themselves.  With the notation above (Y_j = L^-1 E_j of a frame, Z_i = L^-1 B_i of a landmark):
+ *   frame a, frame b:        (H^-1)_ab =  Y_a^T Y_b   (FV x FV, rows a, columns b)
+ *   landmark i, frame j:     (H^-1)_ij = -Z_i^T Y_j   (3 x FV)
+ *   landmark i, landmark k:  (H^-1)_ik =  Z_i^T Z_k   (3 x 3; for i = k the marginal block, V_i^-1 added)
+ * from the same factor and the same forward substitution, followed by one small product per requested pair (k_cov_cross).
+ * Pairs are given in the caller's numbering, in any order; repeats are allowed, a == b is allowed and gives the marginal block
+ * with the bits of srk_ba_phase_covariance; block (b, a) is the transpose of block (a, b) to the bit; a pair's result does not
+ * depend on the batch cap (srk_ba_set_covariance_batch, here at least 20 columns) or on the other pairs of the call.  Rows and
+ * columns of variables that do not move are exact zeros and any pair with a constant landmark returns a zero block.
+ *
+ * srk_ba_phase_cross_covariance: the staged form, with the contract of srk_ba_phase_covariance (after srk_ba_phase_derivatives
+ * and srk_ba_phase_schur(c); consumes slot 0's system; blocks of the inverse of the damped matrix in the resident scene's
+ * variables; 1 = not positive definite or a result not finite, outputs untouched).
+ * srk_ba_cross_covariances: the convenience call: derivative pass, undamped system, blocks scaled by 2 (sigma_pixels / f0)^2 and,
+ * with caller_coordinates = 1, mapped as srk_ba_revert_cross_covariances maps them -- except a block with itself, which is mapped
+ * as srk_ba_revert_covariances maps it (exactly symmetric, with the bits of srk_ba_covariances), and a block (a, b) with a > b,
+ * which is mapped as the transpose of (b, a): the two stay transposes of one another to the bit in the caller's coordinates.
+ * srk_ba_revert_cross_covariances (host only): a block between p and q maps as D_p Sigma D_q^T, D of a frame
+ * diag(I (the four intrinsics, frame_vars = 10 only), R0^T / s, R0^T), D of a landmark R0^T / s; in place.
+ * srk_ba_relative_pose_covariances: for every pair a != b the 6 x 6 covariance, order [t; r], of the relative pose
+ * z = R_a (C_b - C_a), Z = R_a R_b^T in the perturbation [e_t; e_r] of srk_ba_set_relative_pose_factors at zero residual:
+ * J_a S_aa J_a^T + J_a S_ab J_b^T + J_b S_ba J_a^T + J_b S_bb J_b^T over the pose variables of the two frames (with ten variables
+ * a frame the intrinsics are marginalised), J_a = [[-R_a, R_a [d]x], [0, -R_b]], J_b = [[R_a, 0], [0, R_b]], d = C_b - C_a at the
+ * resident scene's current poses.  One factorisation serves all n pairs.  The result is in the caller's world units and
+ * radians (z and Z do not change under a rigid motion of the world and z scales with it: tt / s^2, tr / s, rr) and exactly
+ * symmetric.  A pair with a == b is refused.
+ *
+ * Refusals and return values are those of srk_ba_covariances.  Nothing is launched or allocated unless one of these calls is made. */
+int srk_ba_phase_cross_covariance(srk_ba*, int64_t n_ff, const int32_t* ff_a, const int32_t* ff_b,
+                                  double* ff_blocks /* [n][FV][FV]: rows a, columns b */, int64_t n_pf, const int64_t* pf_point,
+                                  const int32_t* pf_frame, double* pf_blocks /* [n][3][FV] */, int64_t n_pp, const int64_t* pp_a,
+                                  const int64_t* pp_b, double* pp_blocks /* [n][3][3] */);
+int srk_ba_cross_covariances(srk_ba*, double sigma_pixels, int64_t n_ff, const int32_t* ff_a, const int32_t* ff_b, double* ff_cov,
+                             int64_t n_pf, const int64_t* pf_point, const int32_t* pf_frame, double* pf_cov, int64_t n_pp,
+                             const int64_t* pp_a, const int64_t* pp_b, double* pp_cov, int caller_coordinates);
+int srk_ba_revert_cross_covariances(const srk_ba_normalizer* nrm, int frame_vars, int64_t n_ff, double* ff_blocks, int64_t n_pf,
+                                    double* pf_blocks, int64_t n_pp, double* pp_blocks);
+int srk_ba_relative_pose_covariances(srk_ba*, double sigma_pixels, int32_t n, const int32_t* frame_a, const int32_t* frame_b,
+                                     double* cov /* [n][6][6], [t; r], caller's world units and radians */);
 
 /* device-time instrumentation of srk_ba_optimize / srk_ba_compute_inplace: 0 = none (default; report.ms_* stay 0
  * except ms_total), 1 = one HIP event pair per phase (fills report.ms_*), 2 = additionally event pairs around

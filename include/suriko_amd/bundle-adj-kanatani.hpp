@@ -17,6 +17,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../srk_ba.h"
@@ -307,6 +308,60 @@ public:
     void SetCovarianceBatch(int64_t max_columns) {
         int rc = srk_ba_set_covariance_batch(h_, max_columns);
         if (rc < 0) Raise(rc);
+    }
+
+    /// EXTENSION: cross-covariances between blocks of the last ComputeInplace's result (srk_ba_cross_covariances; DESIGN.md
+    /// section 17).  frame_pairs: (camera a, camera b), the block has the rows of a and the columns of b; point_frame_pairs:
+    /// (salient point, camera); point_pairs: (salient point, salient point) -- salient points by their place in the map, as in
+    /// Covariances.  Any order, repeats allowed, a pair of one block with itself gives its marginal.  ff_cov receives one
+    /// row-major FV x FV block per frame pair, pf_cov one 3 x FV block, pp_cov one 3 x 3 block, for pixel noise sigma_pixels, in
+    /// the coordinates of the map and the cameras.  Returns false (outputs empty) when the undamped system is not positive
+    /// definite.  Throws std::invalid_argument as Covariances does.
+    bool CrossCovariances(const std::vector<std::pair<size_t, size_t>>& frame_pairs, const std::vector<std::pair<size_t, size_t>>& point_frame_pairs,
+                          const std::vector<std::pair<size_t, size_t>>& point_pairs, Scalar sigma_pixels, std::vector<Scalar>* ff_cov,
+                          std::vector<Scalar>* pf_cov, std::vector<Scalar>* pp_cov) {
+        const auto frame = [&](size_t j) {
+            if (j >= frames_count_) throw std::invalid_argument("cross-covariances: a camera index is beyond the cameras");
+            return (int32_t)j;
+        };
+        const auto point = [&](size_t k) {
+            if (k >= pnt_ind_of_.size() || pnt_ind_of_[k] < 0) throw std::invalid_argument("cross-covariances: no track of the last ComputeInplace carries this salient point");
+            return (int64_t)pnt_ind_of_[k];
+        };
+        std::vector<int32_t> fa, fb, pff;
+        std::vector<int64_t> pfp, pa, pb;
+        for (const auto& x : frame_pairs) { fa.push_back(frame(x.first)); fb.push_back(frame(x.second)); }
+        for (const auto& x : point_frame_pairs) { pfp.push_back(point(x.first)); pff.push_back(frame(x.second)); }
+        for (const auto& x : point_pairs) { pa.push_back(point(x.first)); pb.push_back(point(x.second)); }
+        const size_t fv = (size_t)srk_ba_frame_vars(h_);
+        std::vector<Scalar> ff(fv * fv * fa.size()), pf(3 * fv * pfp.size()), pp(9 * pa.size());
+        // (an empty vector's data() may be anything; the library wants NULL or a pointer, and reads neither with a count of 0)
+        int rc = srk_ba_cross_covariances(h_, (double)sigma_pixels, (int64_t)fa.size(), fa.data(), fb.data(), ff.data(), (int64_t)pfp.size(),
+                                          pfp.data(), pff.data(), pf.data(), (int64_t)pa.size(), pa.data(), pb.data(), pp.data(), 1);
+        if (rc < 0) Raise(rc);
+        if (rc != 0) { ff.clear(); pf.clear(); pp.clear(); }
+        if (ff_cov) *ff_cov = std::move(ff);
+        if (pf_cov) *pf_cov = std::move(pf);
+        if (pp_cov) *pp_cov = std::move(pp);
+        return rc == 0;
+    }
+    /// EXTENSION: the 6 x 6 covariance, order [t; r], of the relative pose z = R_a (C_b - C_a), Z = R_a R_b^T of every pair of
+    /// cameras (a, b), a != b, of the last ComputeInplace's result, cross term included (srk_ba_relative_pose_covariances), in the
+    /// units of the map and radians: what gates a loop closure.  cov receives one row-major block per pair.  Returns false
+    /// (cov empty) when the undamped system is not positive definite.
+    bool RelativePoseCovariances(const std::vector<std::pair<size_t, size_t>>& pairs, Scalar sigma_pixels, std::vector<Scalar>* cov) {
+        std::vector<int32_t> fa, fb;
+        for (const auto& x : pairs) {
+            if (x.first >= frames_count_ || x.second >= frames_count_) throw std::invalid_argument("relative-pose covariances: a camera index is beyond the cameras");
+            fa.push_back((int32_t)x.first);
+            fb.push_back((int32_t)x.second);
+        }
+        std::vector<Scalar> out(36 * fa.size());
+        int rc = srk_ba_relative_pose_covariances(h_, (double)sigma_pixels, (int32_t)fa.size(), fa.data(), fb.data(), out.data());
+        if (rc < 0) Raise(rc);
+        if (rc != 0) out.clear();
+        if (cov) *cov = std::move(out);
+        return rc == 0;
     }
 
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }

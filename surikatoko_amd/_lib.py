@@ -66,6 +66,7 @@ EXPORTS = [
     "srk_ba_relative_pose_error", "srk_ba_relative_pose_residuals", "srk_ba_normalize_relative_pose_factors",
     "srk_ba_relative_pose_pass_ms",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
+    "srk_ba_phase_cross_covariance", "srk_ba_cross_covariances", "srk_ba_revert_cross_covariances", "srk_ba_relative_pose_covariances",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
     "srk_ba_upload_scene", "srk_ba_optimize", "srk_ba_download_scene", "srk_ba_reset_scene", "srk_ba_phase_error",
     "srk_ba_phase_derivatives", "srk_ba_phase_schur", "srk_ba_phase_solve", "srk_ba_phase_backsub",
@@ -147,6 +148,11 @@ def lib():
     L.srk_ba_covariances.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.srk_ba_revert_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
     L.srk_ba_set_covariance_batch.argtypes = [C.c_void_p, C.c_int64]
+    _pairs = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] * 3
+    L.srk_ba_phase_cross_covariance.argtypes = [C.c_void_p] + _pairs
+    L.srk_ba_cross_covariances.argtypes = [C.c_void_p, C.c_double] + _pairs + [C.c_int]
+    L.srk_ba_revert_cross_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    L.srk_ba_relative_pose_covariances.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.srk_ba_revert_normalization.restype = None
     L.srk_circle_camera_shots.restype = None
     _lib = L

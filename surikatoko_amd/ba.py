@@ -219,6 +219,26 @@ def revert_covariances(nrm, frame_cov=None, point_cov=None):
     return fc, pc
 
 
+def revert_cross_covariances(nrm, frame_frame=None, point_frame=None, point_point=None):
+    """cross-covariance blocks of the normalised scene's variables in the caller's coordinates (srk_ba_revert_cross_covariances;
+    host only): frame_frame [n][fv][fv], point_frame [n][3][fv] (fv 6 or 10), point_point [n][3][3]; any may be None.  A block
+    between p and q maps as D_p Sigma D_q^T.  Returns copies (frame_frame, point_frame, point_point)."""
+    ff = None if frame_frame is None else np.array(frame_frame, dtype=np.float64, order="C")
+    pf = None if point_frame is None else np.array(point_frame, dtype=np.float64, order="C")
+    pp = None if point_point is None else np.array(point_point, dtype=np.float64, order="C").reshape(-1, 3, 3)
+    fv = ff.shape[-1] if ff is not None else (pf.shape[-1] if pf is not None else 6)
+    if ff is not None:
+        ff = ff.reshape(-1, fv, fv)
+    if pf is not None:
+        pf = pf.reshape(-1, 3, fv)
+    args = []
+    for a in (ff, pf, pp):
+        args += [C.c_int64(0 if a is None else len(a)), _p(a) if a is not None and len(a) else None]
+    if lib().srk_ba_revert_cross_covariances(C.byref(nrm), C.c_int(fv), *args) != 0:
+        raise ValueError("srk_ba_revert_cross_covariances: bad argument")
+    return ff, pf, pp
+
+
 _RP_TRI = [(r, c) for r in range(6) for c in range(r, 6)]  # the 21 entries of the upper triangle of a 6 x 6, row by row
 
 
@@ -947,6 +967,86 @@ class BundleAdjustmentKanatani:
         if rc != 0:
             raise np.linalg.LinAlgError("srk_ba_covariances: the system is not positive definite")
         return fb, pb
+
+    # ---- cross-covariances between blocks and relative-pose covariances
+    def _cross_args(self, frame_pairs, point_frame_pairs, point_pairs):
+        """the nine pair arguments of the C calls, and the three output arrays"""
+        fv = self.frame_vars()
+        ff = np.asarray([] if frame_pairs is None else frame_pairs, dtype=np.int32).reshape(-1, 2)
+        pf = np.asarray([] if point_frame_pairs is None else point_frame_pairs, dtype=np.int64).reshape(-1, 2)
+        pp = np.asarray([] if point_pairs is None else point_pairs, dtype=np.int64).reshape(-1, 2)
+        if pf.size and (pf[:, 1].min() < -2 ** 31 or pf[:, 1].max() >= 2 ** 31):
+            raise ValueError("cross-covariances: a frame index is out of range")
+        cols = [np.ascontiguousarray(ff[:, 0]), np.ascontiguousarray(ff[:, 1]), np.ascontiguousarray(pf[:, 0]),
+                np.ascontiguousarray(pf[:, 1], dtype=np.int32), np.ascontiguousarray(pp[:, 0]), np.ascontiguousarray(pp[:, 1])]
+        out = [np.zeros((len(ff), fv, fv)), np.zeros((len(pf), 3, fv)), np.zeros((len(pp), 3, 3))]
+        args = []
+        for k, o in enumerate(out):
+            n = len(o)
+            args += [C.c_int64(n), _p(cols[2 * k]) if n else None, _p(cols[2 * k + 1]) if n else None, _p(o) if n else None]
+        return args, out, cols
+
+    def phase_cross_covariance(self, frame_pairs=None, point_frame_pairs=None, point_pairs=None):
+        """(frame x frame [n][FV][FV], landmark x frame [n][3][FV], landmark x landmark [n][3][3]): the requested blocks of the
+        inverse of the system phase_schur(c) left in slot 0, in the resident (normalised) scene's variables.  frame_pairs
+        [n][2] = (a, b): rows a, columns b; point_frame_pairs [n][2] = (landmark, frame); point_pairs [n][2]; caller's
+        numbering, any order, repeats and a == b allowed.  Consumes the system.  Raises numpy.linalg.LinAlgError when it is
+        not positive definite."""
+        args, out, _keep = self._cross_args(frame_pairs, point_frame_pairs, point_pairs)
+        rc = self._lib.srk_ba_phase_cross_covariance(C.c_void_p(self._h), *args)
+        self._raise(rc)
+        if rc != 0:
+            raise np.linalg.LinAlgError("srk_ba_phase_cross_covariance: the system is not positive definite")
+        return tuple(out)
+
+    def cross_covariances(self, frame_pairs=None, point_frame_pairs=None, point_pairs=None, sigma_pixels=1.0, caller_coordinates=True):
+        """the blocks of phase_cross_covariance for the resident scene's current state and pixel noise sigma_pixels,
+        2 (sigma_pixels / f0)^2 H^-1; in the coordinates of the uploaded arrays unless caller_coordinates is False"""
+        args, out, _keep = self._cross_args(frame_pairs, point_frame_pairs, point_pairs)
+        rc = self._lib.srk_ba_cross_covariances(C.c_void_p(self._h), C.c_double(float(sigma_pixels)), *args,
+                                                C.c_int(int(bool(caller_coordinates))))
+        self._raise(rc)
+        if rc != 0:
+            raise np.linalg.LinAlgError("srk_ba_cross_covariances: the system is not positive definite")
+        return tuple(out)
+
+    def relative_pose_covariances(self, pairs, sigma_pixels=1.0):
+        """[n][6][6]: the covariance, order [t; r], of the relative pose z = R_a (C_b - C_a), Z = R_a R_b^T of every pair
+        (a, b), a != b, of the resident scene's current state, in the caller's world units and radians, cross term included"""
+        pr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        fa, fb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        out = np.zeros((len(pr), 6, 6))
+        rc = self._lib.srk_ba_relative_pose_covariances(C.c_void_p(self._h), C.c_double(float(sigma_pixels)), C.c_int32(len(pr)),
+                                                        _p(fa) if len(pr) else None, _p(fb) if len(pr) else None,
+                                                        _p(out) if len(pr) else None)
+        self._raise(rc)
+        if rc != 0:
+            raise np.linalg.LinAlgError("srk_ba_relative_pose_covariances: the system is not positive definite")
+        return out
+
+    def joint_covariance(self, frames, points, sigma_pixels=1.0, caller_coordinates=True):
+        """the dense symmetric covariance over [frames..., points...] (FV variables a frame, 3 a landmark), from one
+        cross_covariances call with all pairs of the selection; meant for windows of tens of blocks"""
+        fr = np.asarray(frames, dtype=np.int32).reshape(-1)
+        pt = np.asarray(points, dtype=np.int64).reshape(-1)
+        fv, nf, npt = self.frame_vars(), len(fr), len(pt)
+        fi, fj = np.triu_indices(nf)
+        pi, pj = np.triu_indices(npt)
+        gi, gj = np.meshgrid(np.arange(npt), np.arange(nf), indexing="ij")
+        ff, pf, pp = self.cross_covariances(np.stack([fr[fi], fr[fj]], axis=1), np.stack([pt[gi.ravel()], fr[gj.ravel()]], axis=1),
+                                            np.stack([pt[pi], pt[pj]], axis=1), sigma_pixels, caller_coordinates)
+        n = fv * nf + 3 * npt
+        J = np.zeros((n, n))
+        for k, (a, b) in enumerate(zip(fi, fj)):
+            J[fv * a:fv * a + fv, fv * b:fv * b + fv] = ff[k]
+            J[fv * b:fv * b + fv, fv * a:fv * a + fv] = ff[k].T
+        for k, (i, j) in enumerate(zip(gi.ravel(), gj.ravel())):
+            J[fv * nf + 3 * i:fv * nf + 3 * i + 3, fv * j:fv * j + fv] = pf[k]
+            J[fv * j:fv * j + fv, fv * nf + 3 * i:fv * nf + 3 * i + 3] = pf[k].T
+        for k, (a, b) in enumerate(zip(pi, pj)):
+            J[fv * nf + 3 * a:fv * nf + 3 * a + 3, fv * nf + 3 * b:fv * nf + 3 * b + 3] = pp[k]
+            J[fv * nf + 3 * b:fv * nf + 3 * b + 3, fv * nf + 3 * a:fv * nf + 3 * a + 3] = pp[k].T
+        return J
 
     def buffer(self, which):
         """flat download of a staged buffer; its layout follows frame_vars() (include/srk_ba.h SRK_BUF_*)"""

@@ -23,6 +23,7 @@
 #include <cstring>
 #include <string>
 #include <iterator>
+#include <map>
 #include <memory>
 #include <vector>
 #include <unordered_set>
@@ -236,6 +237,7 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     // the small tables of a call, grown lazily; cov_batch_cols: srk_ba_set_covariance_batch (0 = as many columns as fit 256 MB);
     // cov_pt_frame0: the first internal frame of every internal landmark, fetched at the first call after an upload
     DevBuf cov_Y, cov_grp, cov_blk, cov_out, cov_free, cov_colb;
+    DevBuf cov_pairs; // the pair table of a batch of cross-covariances (section 17)
     int64_t cov_batch_cols = 0;
     std::vector<int32_t> cov_pt_frame0;
 };
@@ -402,7 +404,7 @@ void srk_ba_destroy(srk_ba* h)
                       &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk,
                       &h->info_q, &h->info_qf, &h->cst_pts, &h->cst_frames, &h->pri_pt_list, &h->pri_pt_val, &h->pri_fr_list, &h->pri_fr_val,
                       &h->rp_fa, &h->rp_fb, &h->rp_val, &h->rp_fr_list, &h->rp_fr_ptr, &h->rp_fr_ent, &h->rp_tgt, &h->rp_cpl,
-                      &h->cov_Y, &h->cov_grp, &h->cov_blk, &h->cov_out, &h->cov_free, &h->cov_colb };
+                      &h->cov_Y, &h->cov_grp, &h->cov_blk, &h->cov_out, &h->cov_free, &h->cov_colb, &h->cov_pairs };
     for (DevBuf* b : all) dev_free(*b);
     for (auto& a : h->att) {
         for (DevBuf* b : { &a.S, &a.rhs, &a.wy, &a.dc, &a.acc, &a.dx, &a.err_partial, &a.info, &a.dinv, &a.packed, &a.sync_flags, &a.irr, &a.det_stage, &a.det_rhs,
@@ -2229,18 +2231,17 @@ static int cov_check_args(srk_ba* h, int32_t nf, const int32_t* frames, const do
     return SRK_OK;
 }
 
-// the blocks of the inverse of the system in slot 0 (built by phase_schur at h->last_hessian_factor); 0 ok, 1 not positive
-// definite / non-finite, negative on error.  Arguments checked by the caller.
-static int phase_covariance(srk_ba* h, int32_t nf, const int32_t* frames, double* frame_blocks, int64_t np, const int64_t* points,
-                            double* point_blocks)
+// the start the covariance calls share: slot 0's system (built by phase_schur at h->last_hessian_factor) is factorised in place;
+// with want_selection the mask of the variables that move and the skyline go to the device; with want_points pt_int receives
+// the internal index of every landmark of the caller (the first frame of every internal landmark is fetched at the first
+// such call after an upload).  0 ok, 1 not positive definite, negative on error.
+static int cov_prepare(srk_ba* h, bool want_selection, bool want_points, std::vector<int64_t>& pt_int)
 {
     const SrkDims& d = h->d;
     srk_ba::Attempt& a = h->att[0];
     hipStream_t s = a.stream;
     const int fv = d.fv;
-    const double c = h->last_hessian_factor;
     const int64_t n_rows = fv * (int64_t)d.M;
-    const int32_t n_tiles = (int32_t)((n_rows + 63) / 64);
     int rc;
     // the factor: the single-chain solve with a zero right-hand side and the unfused launch sequence, whatever the rcs mode
     HIPCHK(h, hipMemsetAsync(a.info.p, 0, 4, s));
@@ -2251,7 +2252,7 @@ static int phase_covariance(srk_ba* h, int32_t nf, const int32_t* frames, double
     int info = 0;
     if ((rc = read_info(h, a, &info)) != SRK_OK) return rc;
     if (info) { h->poisoned = true; return 1; }
-    if (nf == 0 && np == 0) return 0;
+    if (!want_selection) return 0;
 
     // which variables move
     std::vector<uint8_t> free_var((size_t)d.ld, 0);
@@ -2269,8 +2270,7 @@ static int phase_covariance(srk_ba* h, int32_t nf, const int32_t* frames, double
     if ((rc = dev_alloc(h, h->cov_colb, (size_t)(8 * (d.ld / 64)))) != SRK_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(h->cov_colb.p, h->col_begin_h.data(), (size_t)(8 * (d.ld / 64)), hipMemcpyHostToDevice, s));
     // landmarks: internal index and the first frame that sees them
-    std::vector<int64_t> pt_int;
-    if (np > 0) {
+    if (want_points) {
         if (h->cov_pt_frame0.empty()) {
             std::vector<int32_t> of((size_t)d.O);
             HIPCHK(h, hipMemcpyAsync(of.data(), h->obs_frame.p, (size_t)(4 * d.O), hipMemcpyDeviceToHost, s));
@@ -2285,6 +2285,32 @@ static int phase_covariance(srk_ba* h, int32_t nf, const int32_t* frames, double
         pt_int.assign((size_t)d.N, 0);
         for (int64_t i = 0; i < d.N; ++i) pt_int[(size_t)h->perm[(size_t)i]] = i;
     }
+    return 0;
+}
+
+// the column cap of a batch: Y [ld][columns] stays under 256 MB, or what srk_ba_set_covariance_batch asks for (at least floor)
+static int64_t cov_max_cols(const srk_ba* h, int64_t floor)
+{
+    if (h->cov_batch_cols > 0) return std::max<int64_t>(floor, h->cov_batch_cols);
+    return std::max<int64_t>(SRK_COV_CB, ((int64_t)256 << 20) / (8 * h->d.ld) / SRK_COV_CB * SRK_COV_CB);
+}
+
+// the blocks of the inverse of the system in slot 0 (built by phase_schur at h->last_hessian_factor); 0 ok, 1 not positive
+// definite / non-finite, negative on error.  Arguments checked by the caller.
+static int phase_covariance(srk_ba* h, int32_t nf, const int32_t* frames, double* frame_blocks, int64_t np, const int64_t* points,
+                            double* point_blocks)
+{
+    const SrkDims& d = h->d;
+    srk_ba::Attempt& a = h->att[0];
+    hipStream_t s = a.stream;
+    const int fv = d.fv;
+    const double c = h->last_hessian_factor;
+    const int64_t n_rows = fv * (int64_t)d.M;
+    const int32_t n_tiles = (int32_t)((n_rows + 63) / 64);
+    std::vector<int64_t> pt_int;
+    int rc = cov_prepare(h, nf > 0 || np > 0, np > 0, pt_int);
+    if (rc != 0 || (nf == 0 && np == 0)) return rc;
+    int info = 0;
     // the selected blocks, sorted by their first non-zero row so that every column block starts late
     struct Sel { SrkCovGroup g; int64_t dst; };
     std::vector<Sel> sel;
@@ -2301,8 +2327,7 @@ static int phase_covariance(srk_ba* h, int32_t nf, const int32_t* frames, double
     }
     std::stable_sort(sel.begin(), sel.end(), [](const Sel& x, const Sel& y) { return x.g.first_row < y.g.first_row; });
     // batches of columns: Y [ld][ncp] stays under the byte cap
-    int64_t max_cols = std::max<int64_t>(SRK_COV_CB, ((int64_t)256 << 20) / (8 * d.ld) / SRK_COV_CB * SRK_COV_CB);
-    if (h->cov_batch_cols > 0) max_cols = std::max<int64_t>(10, h->cov_batch_cols);
+    const int64_t max_cols = cov_max_cols(h, 10);
     std::vector<double> res((size_t)(100 * sel.size()));
     std::vector<SrkCovGroup> grp;
     std::vector<int32_t> blk;
@@ -2407,6 +2432,387 @@ int srk_ba_covariances(srk_ba* h, double sigma_pixels, int32_t n_frames_sel, con
     for (int64_t e = 0; e < (int64_t)fv * fv * n_frames_sel; ++e) frame_cov[e] *= k;
     for (int64_t e = 0; e < 9 * n_points_sel; ++e) point_cov[e] *= k;
     if (caller_coordinates && h->normalized_on_upload) srk_ba_revert_covariances(&h->nrm, fv, n_frames_sel, frame_cov, n_points_sel, point_cov);
+    return 0;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------ cross-covariances between blocks
+
+// the pairs of a call in the caller's numbering: frame x frame [n][FV][FV] (rows a, columns b), landmark x frame [n][3][FV],
+// landmark x landmark [n][3][3]
+struct CovPairArgs {
+    int64_t n_ff; const int32_t* ff_a; const int32_t* ff_b; double* ff_blocks;
+    int64_t n_pf; const int64_t* pf_point; const int32_t* pf_frame; double* pf_blocks;
+    int64_t n_pp; const int64_t* pp_a; const int64_t* pp_b; double* pp_blocks;
+};
+
+// D of a frame block, row-major fv x fv: diag(I (intrinsics, fv = 10 only), R0^T / s, R0^T); of a landmark block (fv = 0): R0^T / s
+static void cov_cross_map(const srk_ba_normalizer& nrm, int fv, double* D)
+{
+    const double is = 1.0 / nrm.world_scale;
+    const int n = fv ? fv : 3, off = fv ? fv - 6 : 0;
+    std::fill(D, D + n * n, 0.0);
+    for (int i = 0; i < off; ++i) D[i * n + i] = 1.0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            D[(off + a) * n + off + b] = nrm.R0[3 * b + a] * is;
+            if (fv) D[(off + 3 + a) * n + off + 3 + b] = nrm.R0[3 * b + a];
+        }
+}
+// B (np x nq, row-major) <- Dp B Dq^T
+static void cov_revert_cross(const double* Dp, int np, const double* Dq, int nq, double* B)
+{
+    double T[100];
+    for (int i = 0; i < np; ++i)
+        for (int j = 0; j < nq; ++j) {
+            double v = 0;
+            for (int k = 0; k < np; ++k) v += Dp[i * np + k] * B[k * nq + j];
+            T[i * nq + j] = v;
+        }
+    for (int i = 0; i < np; ++i)
+        for (int j = 0; j < nq; ++j) {
+            double v = 0;
+            for (int k = 0; k < nq; ++k) v += T[i * nq + k] * Dq[j * nq + k];
+            B[i * nq + j] = v;
+        }
+}
+
+static int cov_cross_check_args(srk_ba* h, const CovPairArgs& q)
+{
+    if (q.n_ff < 0 || q.n_pf < 0 || q.n_pp < 0 || (q.n_ff > 0 && (!q.ff_a || !q.ff_b || !q.ff_blocks)) ||
+        (q.n_pf > 0 && (!q.pf_point || !q.pf_frame || !q.pf_blocks)) || (q.n_pp > 0 && (!q.pp_a || !q.pp_b || !q.pp_blocks))) {
+        h->last_error = "cross-covariance: a negative count, or a NULL array with a positive count";
+        return SRK_E_ARGS;
+    }
+    if (q.n_ff + q.n_pf + q.n_pp > INT32_MAX / 2) { h->last_error = "cross-covariance: too many pairs in one call"; return SRK_E_ARGS; }
+    if (h->world > 1 || h->allreduce || h->comm) { h->last_error = "cross-covariance: more than one rank is not supported"; return SRK_E_ARGS; }
+    if (h->shk_G > 0) { h->last_error = "cross-covariance: intrinsic groups are not supported"; return SRK_E_ARGS; }
+    const auto bad_f = [&](int32_t f) { return f < 0 || f >= h->d.M; };
+    const auto bad_p = [&](int64_t i) { return i < 0 || i >= h->d.N; };
+    for (int64_t k = 0; k < q.n_ff; ++k)
+        if (bad_f(q.ff_a[k]) || bad_f(q.ff_b[k])) { h->last_error = "cross-covariance: a frame index is out of range"; return SRK_E_ARGS; }
+    for (int64_t k = 0; k < q.n_pf; ++k) {
+        if (bad_p(q.pf_point[k])) { h->last_error = "cross-covariance: a landmark index is out of range"; return SRK_E_ARGS; }
+        if (bad_f(q.pf_frame[k])) { h->last_error = "cross-covariance: a frame index is out of range"; return SRK_E_ARGS; }
+    }
+    for (int64_t k = 0; k < q.n_pp; ++k)
+        if (bad_p(q.pp_a[k]) || bad_p(q.pp_b[k])) { h->last_error = "cross-covariance: a landmark index is out of range"; return SRK_E_ARGS; }
+    return SRK_OK;
+}
+
+// the requested blocks of the inverse of the system in slot 0; 0 ok, 1 not positive definite / non-finite (outputs untouched),
+// negative on error.  Arguments checked by the caller.  The blocks the pairs name are deduplicated; the pairs are sorted by
+// (smaller first row, larger first row) and fill batches greedily so that both blocks of every pair of a batch lie in that
+// batch's Y, each block once (a block may come back in a later batch); per batch k_cov_rhs, k_cov_fwd, k_cov_cross.
+static int phase_cross_covariance(srk_ba* h, const CovPairArgs& q)
+{
+    const SrkDims& d = h->d;
+    srk_ba::Attempt& a = h->att[0];
+    hipStream_t s = a.stream;
+    const int fv = d.fv;
+    const double c = h->last_hessian_factor;
+    const int64_t n_rows = fv * (int64_t)d.M;
+    const int32_t n_tiles = (int32_t)((n_rows + 63) / 64);
+    const int64_t n_all = q.n_ff + q.n_pf + q.n_pp;
+    std::vector<int64_t> pt_int;
+    int rc = cov_prepare(h, n_all > 0, q.n_pf + q.n_pp > 0, pt_int);
+    if (rc != 0 || n_all == 0) return rc;
+
+    // the distinct blocks (key: internal frame, or M + internal landmark); a constant landmark has none: its pairs are zero blocks
+    std::vector<SrkCovGroup> blocks;
+    std::map<int64_t, int32_t> block_of;
+    const auto frame_block = [&](int32_t user) {
+        const int32_t f = h->frame_int.empty() ? user : h->frame_int[(size_t)user];
+        auto it = block_of.find(f);
+        if (it != block_of.end()) return it->second;
+        blocks.push_back(SrkCovGroup{ f, 0, fv, (int32_t)(fv * (int64_t)f), 0 });
+        return block_of[f] = (int32_t)blocks.size() - 1;
+    };
+    const auto point_block = [&](int64_t user) {
+        if ((size_t)user < h->cst_point_user.size() && h->cst_point_user[(size_t)user]) return (int32_t)-1;
+        const int64_t i = pt_int[(size_t)user];
+        auto it = block_of.find(d.M + i);
+        if (it != block_of.end()) return it->second;
+        blocks.push_back(SrkCovGroup{ i, 0, 3, (int32_t)(fv * (int64_t)h->cov_pt_frame0[(size_t)i]), 1 });
+        return block_of[d.M + i] = (int32_t)blocks.size() - 1;
+    };
+    struct Pair { int32_t p, q, kind; int64_t dst, res; }; // kind 0 frame x frame, 1 landmark x frame, 2 landmark x landmark
+    std::vector<Pair> pairs;
+    pairs.reserve((size_t)n_all);
+    for (int64_t k = 0; k < q.n_ff; ++k) pairs.push_back(Pair{ frame_block(q.ff_a[k]), frame_block(q.ff_b[k]), 0, k, -1 });
+    for (int64_t k = 0; k < q.n_pf; ++k) {
+        const int32_t p = point_block(q.pf_point[k]);
+        if (p >= 0) pairs.push_back(Pair{ p, frame_block(q.pf_frame[k]), 1, k, -1 });
+    }
+    for (int64_t k = 0; k < q.n_pp; ++k) {
+        const int32_t p = point_block(q.pp_a[k]), p2 = point_block(q.pp_b[k]);
+        if (p >= 0 && p2 >= 0) pairs.push_back(Pair{ p, p2, 2, k, -1 });
+    }
+    const auto rows_of = [&](const Pair& x) {
+        const int32_t rp = blocks[(size_t)x.p].first_row, rq = blocks[(size_t)x.q].first_row;
+        return std::make_pair(std::min(rp, rq), std::max(rp, rq));
+    };
+    std::stable_sort(pairs.begin(), pairs.end(), [&](const Pair& x, const Pair& y) { return rows_of(x) < rows_of(y); });
+
+    const int64_t max_cols = cov_max_cols(h, 20); // one pair of ten-variable frames always fits
+    std::vector<double> res((size_t)(100 * pairs.size()));
+    std::vector<int32_t> slot(blocks.size(), -1), members; // a block's place in the batch's group table
+    std::vector<SrkCovGroup> grp;
+    std::vector<SrkCovPair> tab;
+    std::vector<int32_t> blk;
+    for (size_t b0 = 0; b0 < pairs.size();) {
+        size_t b1 = b0;
+        int64_t cols = 0;
+        members.clear();
+        for (; b1 < pairs.size(); ++b1) {
+            const Pair& x = pairs[b1];
+            const int64_t need = (slot[(size_t)x.p] < 0 ? blocks[(size_t)x.p].ncols : 0) +
+                                 (x.q != x.p && slot[(size_t)x.q] < 0 ? blocks[(size_t)x.q].ncols : 0);
+            if (cols + need > max_cols) break; // (never the first pair of a batch: max_cols >= 20)
+            for (int32_t m : { x.p, x.q })
+                if (slot[(size_t)m] < 0) { slot[(size_t)m] = 0; members.push_back(m); }
+            cols += need;
+        }
+        // the batch's blocks by first row, so that every column block of k_cov_fwd starts late
+        std::stable_sort(members.begin(), members.end(), [&](int32_t x, int32_t y) { return blocks[(size_t)x].first_row < blocks[(size_t)y].first_row; });
+        grp.clear();
+        cols = 0;
+        for (int32_t m : members) {
+            SrkCovGroup g = blocks[(size_t)m];
+            g.col0 = (int32_t)cols;
+            cols += g.ncols;
+            slot[(size_t)m] = (int32_t)grp.size();
+            grp.push_back(g);
+        }
+        const int64_t ncp = (cols + SRK_COV_CB - 1) / SRK_COV_CB * SRK_COV_CB;
+        blk.assign((size_t)(ncp / SRK_COV_CB), n_tiles);
+        for (const SrkCovGroup& g : grp)
+            for (int64_t cb = g.col0 / SRK_COV_CB; cb <= (g.col0 + g.ncols - 1) / SRK_COV_CB; ++cb)
+                blk[(size_t)cb] = std::min<int32_t>(blk[(size_t)cb], g.first_row / 64);
+        // the pair table by kind: one launch per shape
+        tab.clear();
+        int32_t n_kind[3] = { 0, 0, 0 };
+        for (int kind = 0; kind < 3; ++kind)
+            for (size_t k = b0; k < b1; ++k)
+                if (pairs[k].kind == kind) {
+                    pairs[k].res = (int64_t)(b0 + tab.size());
+                    tab.push_back(SrkCovPair{ slot[(size_t)pairs[k].p], slot[(size_t)pairs[k].q] });
+                    ++n_kind[kind];
+                }
+        const int32_t ng = (int32_t)grp.size(), npr = (int32_t)tab.size();
+        if ((rc = dev_alloc(h, h->cov_Y, (size_t)(8 * d.ld * ncp))) != SRK_OK) return rc;
+        if ((rc = dev_alloc(h, h->cov_grp, sizeof(SrkCovGroup) * grp.size())) != SRK_OK) return rc;
+        if ((rc = dev_alloc(h, h->cov_blk, 4 * blk.size())) != SRK_OK) return rc;
+        if ((rc = dev_alloc(h, h->cov_pairs, sizeof(SrkCovPair) * tab.size())) != SRK_OK) return rc;
+        if ((rc = dev_alloc(h, h->cov_out, (size_t)(800 * (int64_t)npr))) != SRK_OK) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->cov_grp.p, grp.data(), sizeof(SrkCovGroup) * grp.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->cov_blk.p, blk.data(), 4 * blk.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->cov_pairs.p, tab.data(), sizeof(SrkCovPair) * tab.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemsetAsync(h->cov_Y.p, 0, (size_t)(8 * 64 * (int64_t)n_tiles * ncp), s));
+        HIPCHK(h, hipMemsetAsync(h->cov_out.p, 0, (size_t)(800 * (int64_t)npr), s));
+        srk_launch_cov_rhs(s, d, c, P<SrkCovGroup>(h->cov_grp), ng, P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W),
+                           P<double>(h->Vg), P<uint8_t>(h->cov_free), P<double>(h->cov_Y), ncp, P<int>(a.info));
+        srk_launch_cov_fwd(s, d.ld, P<double>(a.S), P<double>(a.dinv), P<int64_t>(h->cov_colb), n_tiles, P<int32_t>(h->cov_blk),
+                           P<double>(h->cov_Y), ncp);
+        srk_launch_cov_cross(s, d, c, P<SrkCovGroup>(h->cov_grp), P<SrkCovPair>(h->cov_pairs), n_kind[0], n_kind[1], n_kind[2], P<double>(h->Vg),
+                             P<double>(h->cov_Y), ncp, n_rows, P<double>(h->cov_out));
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(res.data() + 100 * b0, h->cov_out.p, (size_t)(800 * (int64_t)npr), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s)); // the tables are reused by the next batch
+        for (int32_t m : members) slot[(size_t)m] = -1;
+        b0 = b1;
+    }
+    int info = 0;
+    if ((rc = read_info(h, a, &info)) != SRK_OK) return rc;
+    if (info) return 1;
+    const int shape[3][2] = { { fv, fv }, { 3, fv }, { 3, 3 } };
+    for (const Pair& x : pairs)
+        for (int e = 0; e < shape[x.kind][0] * shape[x.kind][1]; ++e)
+            if (!std::isfinite(res[(size_t)(100 * x.res + e)])) return 1;
+    // pairs with a constant landmark stay zero
+    double* const outs[3] = { q.ff_blocks, q.pf_blocks, q.pp_blocks };
+    const int64_t counts[3] = { q.n_ff, q.n_pf, q.n_pp };
+    for (int kind = 0; kind < 3; ++kind)
+        if (counts[kind] > 0) std::fill(outs[kind], outs[kind] + counts[kind] * shape[kind][0] * shape[kind][1], 0.0);
+    for (const Pair& x : pairs) {
+        const int n = shape[x.kind][0] * shape[x.kind][1];
+        std::memcpy(outs[x.kind] + x.dst * n, res.data() + 100 * x.res, sizeof(double) * (size_t)n);
+    }
+    return 0;
+}
+
+// the derivative pass and the undamped system of the resident scene's current state in slot 0 (the convenience calls)
+static int cov_build_undamped(srk_ba* h)
+{
+    int rc;
+    if ((rc = clear_poison(h)) != SRK_OK) return rc;
+    if ((rc = phase_derivatives(h)) != SRK_OK) return rc;
+    h->last_slot = 0;
+    return phase_schur(h, h->att[0], 0.0);
+}
+
+extern "C" {
+
+int srk_ba_phase_cross_covariance(srk_ba* h, int64_t n_ff, const int32_t* ff_a, const int32_t* ff_b, double* ff_blocks, int64_t n_pf,
+                                  const int64_t* pf_point, const int32_t* pf_frame, double* pf_blocks, int64_t n_pp, const int64_t* pp_a,
+                                  const int64_t* pp_b, double* pp_blocks)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    const CovPairArgs q{ n_ff, ff_a, ff_b, ff_blocks, n_pf, pf_point, pf_frame, pf_blocks, n_pp, pp_a, pp_b, pp_blocks };
+    int rc = cov_cross_check_args(h, q);
+    if (rc != SRK_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return phase_cross_covariance(h, q);
+}
+
+int srk_ba_revert_cross_covariances(const srk_ba_normalizer* nrm, int frame_vars, int64_t n_ff, double* ff_blocks, int64_t n_pf,
+                                    double* pf_blocks, int64_t n_pp, double* pp_blocks)
+{
+    if (!nrm || (frame_vars != 6 && frame_vars != 10) || n_ff < 0 || n_pf < 0 || n_pp < 0 || (n_ff > 0 && !ff_blocks) ||
+        (n_pf > 0 && !pf_blocks) || (n_pp > 0 && !pp_blocks) || !(nrm->world_scale > 0) || !std::isfinite(nrm->world_scale))
+        return SRK_E_ARGS;
+    const int fv = frame_vars;
+    double Df[100], Dp[9];
+    cov_cross_map(*nrm, fv, Df);
+    cov_cross_map(*nrm, 0, Dp);
+    for (int64_t k = 0; k < n_ff; ++k) cov_revert_cross(Df, fv, Df, fv, ff_blocks + (int64_t)fv * fv * k);
+    for (int64_t k = 0; k < n_pf; ++k) cov_revert_cross(Dp, 3, Df, fv, pf_blocks + (int64_t)3 * fv * k);
+    for (int64_t k = 0; k < n_pp; ++k) cov_revert_cross(Dp, 3, Dp, 3, pp_blocks + 9 * k);
+    return SRK_OK;
+}
+
+int srk_ba_cross_covariances(srk_ba* h, double sigma_pixels, int64_t n_ff, const int32_t* ff_a, const int32_t* ff_b, double* ff_cov,
+                             int64_t n_pf, const int64_t* pf_point, const int32_t* pf_frame, double* pf_cov, int64_t n_pp,
+                             const int64_t* pp_a, const int64_t* pp_b, double* pp_cov, int caller_coordinates)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    if (!(sigma_pixels > 0) || !std::isfinite(sigma_pixels)) { h->last_error = "cross-covariances: sigma_pixels must be finite and positive"; return SRK_E_ARGS; }
+    const CovPairArgs q{ n_ff, ff_a, ff_b, ff_cov, n_pf, pf_point, pf_frame, pf_cov, n_pp, pp_a, pp_b, pp_cov };
+    int rc = cov_cross_check_args(h, q);
+    if (rc != SRK_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = cov_build_undamped(h)) != SRK_OK) return rc;
+    if ((rc = phase_cross_covariance(h, q)) != 0) return rc;
+    const int fv = h->d.fv;
+    const double k = 2.0 * (sigma_pixels / h->f0) * (sigma_pixels / h->f0);
+    for (int64_t e = 0; e < (int64_t)fv * fv * n_ff; ++e) ff_cov[e] *= k;
+    for (int64_t e = 0; e < (int64_t)3 * fv * n_pf; ++e) pf_cov[e] *= k;
+    for (int64_t e = 0; e < 9 * n_pp; ++e) pp_cov[e] *= k;
+    if (caller_coordinates && h->normalized_on_upload) {
+        // a block with itself is mapped as srk_ba_revert_covariances maps it: exactly symmetric, the bits of srk_ba_covariances;
+        // a block (a, b) with a > b is mapped as the transpose of (b, a), so that the two stay transposes of one another to the bit
+        double Df[100], Dp[9];
+        cov_cross_map(h->nrm, fv, Df);
+        cov_cross_map(h->nrm, 0, Dp);
+        const auto square = [](const double* D, int n, bool swapped, double* B) {
+            const auto transpose = [&] {
+                for (int i = 0; i < n; ++i)
+                    for (int j = i + 1; j < n; ++j) std::swap(B[i * n + j], B[j * n + i]);
+            };
+            if (swapped) transpose();
+            cov_revert_cross(D, n, D, n, B);
+            if (swapped) transpose();
+        };
+        for (int64_t e = 0; e < n_ff; ++e) {
+            double* B = ff_cov + (int64_t)fv * fv * e;
+            if (ff_a[e] == ff_b[e]) cov_revert_frame(h->nrm, fv, B);
+            else square(Df, fv, ff_a[e] > ff_b[e], B);
+        }
+        for (int64_t e = 0; e < n_pf; ++e) cov_revert_cross(Dp, 3, Df, fv, pf_cov + (int64_t)3 * fv * e);
+        for (int64_t e = 0; e < n_pp; ++e) {
+            if (pp_a[e] == pp_b[e]) cov_revert_point(h->nrm, pp_cov + 9 * e);
+            else square(Dp, 3, pp_a[e] > pp_b[e], pp_cov + 9 * e);
+        }
+    }
+    return 0;
+}
+
+int srk_ba_relative_pose_covariances(srk_ba* h, double sigma_pixels, int32_t n, const int32_t* frame_a, const int32_t* frame_b, double* cov)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    if (!(sigma_pixels > 0) || !std::isfinite(sigma_pixels)) { h->last_error = "relative-pose covariances: sigma_pixels must be finite and positive"; return SRK_E_ARGS; }
+    if (n < 0 || (n > 0 && (!frame_a || !frame_b || !cov))) {
+        h->last_error = "relative-pose covariances: a negative count, or a NULL array with a positive count";
+        return SRK_E_ARGS;
+    }
+    for (int32_t k = 0; k < n; ++k)
+        if (frame_a[k] >= 0 && frame_a[k] == frame_b[k]) { h->last_error = "relative-pose covariances: a pair names one frame twice"; return SRK_E_ARGS; }
+    // one factorisation for all: the marginal of every frame named, once, then the cross block of every pair
+    std::vector<int32_t> fa, fb;
+    std::map<int32_t, int64_t> marg;
+    for (int32_t k = 0; k < n; ++k)
+        for (int32_t f : { frame_a[k], frame_b[k] })
+            if (marg.emplace(f, (int64_t)fa.size()).second) { fa.push_back(f); fb.push_back(f); }
+    fa.insert(fa.end(), frame_a, frame_a + n);
+    fb.insert(fb.end(), frame_b, frame_b + n);
+    const int fv = h->d.fv, off = fv - 6;
+    const int64_t n_marg = (int64_t)marg.size();
+    std::vector<double> blk((size_t)(fv * fv) * fa.size());
+    const CovPairArgs q{ (int64_t)fa.size(), fa.data(), fb.data(), blk.data(), 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr };
+    int rc = cov_cross_check_args(h, q);
+    if (rc != SRK_OK) return rc;
+    if (n == 0) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = cov_build_undamped(h)) != SRK_OK) return rc;
+    if ((rc = phase_cross_covariance(h, q)) != 0) return rc;
+    // the resident scene's current poses (internal frame order)
+    const int32_t M = h->d.M;
+    std::vector<double> R(9 * (size_t)M), T(3 * (size_t)M);
+    hipStream_t s = h->att[0].stream;
+    HIPCHK(h, hipMemcpyAsync(R.data(), h->camR[h->cur].p, 72 * (int64_t)M, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(T.data(), h->camT[h->cur].p, 24 * (int64_t)M, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    const double kf = 2.0 * (sigma_pixels / h->f0) * (sigma_pixels / h->f0);
+    const double is = h->normalized_on_upload ? 1.0 / h->nrm.world_scale : 1.0; // z scales with the world, Z does not; no R0 enters
+    for (int32_t k = 0; k < n; ++k) {
+        const int32_t ia = h->frame_int.empty() ? frame_a[k] : h->frame_int[(size_t)frame_a[k]];
+        const int32_t ib = h->frame_int.empty() ? frame_b[k] : h->frame_int[(size_t)frame_b[k]];
+        const double *Ra = &R[9 * (size_t)ia], *Rb = &R[9 * (size_t)ib];
+        double Ca[3], Cb[3], dv[3], Rt[9];
+        srk::se3_inv(Ra, &T[3 * (size_t)ia], Rt, Ca); // the centre C = -R^T T
+        srk::se3_inv(Rb, &T[3 * (size_t)ib], Rt, Cb);
+        for (int e = 0; e < 3; ++e) dv[e] = Cb[e] - Ca[e];
+        const double dx[9] = { 0, -dv[2], dv[1], dv[2], 0, -dv[0], -dv[1], dv[0], 0 };
+        double RaDx[9];
+        srk::mat3_mul(Ra, dx, RaDx);
+        // J = [J_a J_b] (6 x 12), J_a = [[-R_a, R_a [d]x], [0, -R_b]], J_b = [[R_a, 0], [0, R_b]]
+        double J[6][12] = {};
+        for (int r = 0; r < 3; ++r)
+            for (int cc = 0; cc < 3; ++cc) {
+                J[r][cc] = -Ra[3 * r + cc];
+                J[r][3 + cc] = RaDx[3 * r + cc];
+                J[3 + r][3 + cc] = -Rb[3 * r + cc];
+                J[r][6 + cc] = Ra[3 * r + cc];
+                J[3 + r][9 + cc] = Rb[3 * r + cc];
+            }
+        // the joint covariance of the two frames' pose variables (with ten variables a frame: its variables 4..9)
+        const double* Saa = &blk[(size_t)(fv * fv) * (size_t)marg[frame_a[k]]];
+        const double* Sbb = &blk[(size_t)(fv * fv) * (size_t)marg[frame_b[k]]];
+        const double* Sab = &blk[(size_t)(fv * fv) * (size_t)(n_marg + k)];
+        double Sg[12][12];
+        for (int r = 0; r < 6; ++r)
+            for (int cc = 0; cc < 6; ++cc) {
+                Sg[r][cc] = Saa[(off + r) * fv + off + cc];
+                Sg[6 + r][6 + cc] = Sbb[(off + r) * fv + off + cc];
+                Sg[r][6 + cc] = Sg[6 + cc][r] = Sab[(off + r) * fv + off + cc];
+            }
+        double JS[6][12];
+        for (int r = 0; r < 6; ++r)
+            for (int cc = 0; cc < 12; ++cc) {
+                double v = 0;
+                for (int e = 0; e < 12; ++e) v += J[r][e] * Sg[e][cc];
+                JS[r][cc] = v;
+            }
+        double* out = cov + 36 * (int64_t)k;
+        for (int r = 0; r < 6; ++r)
+            for (int cc = r; cc < 6; ++cc) {
+                double v = 0;
+                for (int e = 0; e < 12; ++e) v += JS[r][e] * J[cc][e];
+                v *= kf * (r < 3 ? is : 1.0) * (cc < 3 ? is : 1.0); // tt / s^2, tr / s, rr
+                out[6 * r + cc] = out[6 * cc + r] = v;
+            }
+    }
     return 0;
 }
 

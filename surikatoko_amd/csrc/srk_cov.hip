@@ -10,6 +10,8 @@
 // last and reads nothing but L and the rows it wrote itself: no flags, no spins, no atomics, a fixed summation order.
 // Variables that do not move (gauge, constant frames, padding) get no unit column and no row of B: S holds identity rows
 // there, so every entry of their rows and columns comes out as an exact zero.
+// Cross-covariances (srk_ba_phase_cross_covariance; section 17) are products between two column groups of the same Y:
+// frame a, frame b: Y_a^T Y_b; landmark i, frame j: -Z_i^T Y_j; landmark i, landmark k: Z_i^T Z_k (k_cov_cross, at the end).
 #include "srk_cov.hpp"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -234,4 +236,79 @@ void srk_launch_cov_gram(hipStream_t s, const SrkDims& d, double c, const SrkCov
 {
     if (n_grp <= 0) return;
     hipLaunchKernelGGL(k_cov_gram, dim3((unsigned)n_grp), dim3(256), 0, s, d, c, grp, Vg, Y, ncp, n_rows, out);
+}
+
+// ------------------------------------------------------------------ cross products between two blocks
+// one workgroup per pair (p, q) of column groups of the same Y: the NP x NQ product Y_p^T Y_q over the rows
+// [max(first_row_p, first_row_q), n_rows) -- above that row one of the two groups holds exact zeros.  The summation scheme is
+// k_cov_gram's (thread t the rows r0 + t, + 256, ...; one fma per product; a shuffle tree per wave; the four waves' sums as
+// k_cov_gram adds them), so a pair (p, p) gives the bits of the marginal block and (q, p) the transpose of (p, q).  One
+// instantiation per shape keeps the NP NQ accumulators in registers.  A landmark x frame block is negated
+// ((H^-1)_ij = -Z_i^T Y_j); a landmark with itself adds V^-1.
+template <int NP, int NQ>
+__global__ __launch_bounds__(256) void k_cov_cross(SrkDims d, double c, const SrkCovGroup* __restrict__ grp, const SrkCovPair* __restrict__ pairs,
+                                                   const double* __restrict__ Vg, const double* __restrict__ Y, int64_t ncp, int64_t n_rows,
+                                                   double* __restrict__ out)
+{
+    __shared__ double sp[4][NP * NQ];
+    const SrkCovPair pr = pairs[blockIdx.x];
+    const SrkCovGroup gp = grp[pr.p], gq = grp[pr.q];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    double acc[NP * NQ];
+#pragma unroll
+    for (int e = 0; e < NP * NQ; ++e) acc[e] = 0;
+    const int64_t r0 = gp.first_row > gq.first_row ? gp.first_row : gq.first_row;
+    for (int64_t r = r0 + t; r < n_rows; r += 256) {
+        const double* yp = Y + r * ncp + gp.col0;
+        const double* yq = Y + r * ncp + gq.col0;
+        double a[NP], b[NQ];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) a[i] = yp[i];
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) b[j] = yq[j];
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) acc[i * NQ + j] = fma(a[i], b[j], acc[i * NQ + j]);
+    }
+#pragma unroll
+    for (int e = 0; e < NP * NQ; ++e) {
+        double v = acc[e];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) sp[wv][e] = v;
+    }
+    __syncthreads();
+    if (t < NP * NQ) {
+        const int i = t / NQ, j = t % NQ;
+        double v = (sp[0][t] + sp[1][t]) + (sp[2][t] + sp[3][t]);
+        if (NP == 3 && NQ == 3 && pr.p == pr.q) {
+            double iv[6];
+            const int lo = i < j ? i : j, hi = i < j ? j : i;
+            if (cv_point_inverse(Vg, d.Ns, gp.idx, c, iv)) v += iv[lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)];
+        }
+        if (NP == 3 && NQ != 3) v = -v;
+        out[(int64_t)blockIdx.x * 100 + t] = v;
+    }
+}
+
+template <int NP, int NQ>
+static void cov_cross_launch(hipStream_t s, const SrkDims& d, double c, const SrkCovGroup* grp, const SrkCovPair* pairs, int32_t n, const double* Vg,
+                             const double* Y, int64_t ncp, int64_t n_rows, double* out)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL((k_cov_cross<NP, NQ>), dim3((unsigned)n), dim3(256), 0, s, d, c, grp, pairs, Vg, Y, ncp, n_rows, out);
+}
+
+void srk_launch_cov_cross(hipStream_t s, const SrkDims& d, double c, const SrkCovGroup* grp, const SrkCovPair* pairs, int32_t n_ff, int32_t n_pf,
+                          int32_t n_pp, const double* Vg, const double* Y, int64_t ncp, int64_t n_rows, double* out)
+{
+    if (d.fv == 6) {
+        cov_cross_launch<6, 6>(s, d, c, grp, pairs, n_ff, Vg, Y, ncp, n_rows, out);
+        cov_cross_launch<3, 6>(s, d, c, grp, pairs + n_ff, n_pf, Vg, Y, ncp, n_rows, out + 100 * (int64_t)n_ff);
+    } else {
+        cov_cross_launch<10, 10>(s, d, c, grp, pairs, n_ff, Vg, Y, ncp, n_rows, out);
+        cov_cross_launch<3, 10>(s, d, c, grp, pairs + n_ff, n_pf, Vg, Y, ncp, n_rows, out + 100 * (int64_t)n_ff);
+    }
+    cov_cross_launch<3, 3>(s, d, c, grp, pairs + n_ff + n_pf, n_pp, Vg, Y, ncp, n_rows, out + 100 * ((int64_t)n_ff + n_pf));
 }

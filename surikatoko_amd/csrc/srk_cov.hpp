@@ -1,5 +1,5 @@
-// srk_cov.hpp -- marginal covariances of frames and landmarks (srk_ba_phase_covariance): the three
-// kernels of srk_cov.hip.  They work on the factor the single-chain solver (srk_chol_solve) leaves behind: the strictly
+// srk_cov.hpp -- marginal covariances of frames and landmarks (srk_ba_phase_covariance) and the blocks
+// between two of them (srk_ba_phase_cross_covariance; section 17): the kernels of srk_cov.hip.  They work on the factor the single-chain solver (srk_chol_solve) leaves behind: the strictly
 // lower 64 x 64 tiles of L in the slot's S and the inverses of the diagonal tiles in dinv.
 #pragma once
 #include "srk_dev.hpp"
@@ -31,3 +31,13 @@ void srk_launch_cov_fwd(hipStream_t s, int64_t ld, const double* L, const double
 // landmark V^-1 is added
 void srk_launch_cov_gram(hipStream_t s, const SrkDims& d, double c, const SrkCovGroup* grp, int32_t n_grp, const double* Vg,
                          const double* Y, int64_t ncp, int64_t n_rows, double* out);
+
+// one requested pair of blocks of a batch (k_cov_cross): indices into the batch's group table
+struct SrkCovPair {
+    int32_t p, q;
+};
+// out [n_ff + n_pf + n_pp][100]: the product Y_p^T Y_q over the rows [max(first_row_p, first_row_q), n_rows), row-major
+// n_p x n_q.  pairs holds the frame x frame pairs first, then the landmark x frame pairs (p the landmark; the block is
+// negated), then the landmark x landmark pairs (V^-1 is added where p == q).  One launch per kind that has pairs.
+void srk_launch_cov_cross(hipStream_t s, const SrkDims& d, double c, const SrkCovGroup* grp, const SrkCovPair* pairs, int32_t n_ff, int32_t n_pf,
+                          int32_t n_pp, const double* Vg, const double* Y, int64_t ncp, int64_t n_rows, double* out);
