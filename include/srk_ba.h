@@ -614,6 +614,79 @@ int srk_ba_normalize_relative_pose_factors(const srk_ba_normalizer* nrm, int32_t
  * launched or not timed.  One event pair a pass serves all attempt slots (tools/relpose_rate.py switches speculation off). */
 int srk_ba_relative_pose_pass_ms(srk_ba*, double* derivative_ms, double* couple_ms, double* error_ms);
 
+/* ---- joint Gaussian pose priors over sets of frames (EXTENSION) ----
+ * The prior a marginalised window leaves behind: a dense Gaussian over the poses of the k frames that shared landmarks with
+ * what was dropped, the inverse of a joint covariance block (srk_ba_cross_covariances).  With k = 1 it is the full pose prior:
+ * position and attitude of one frame with a 6 x 6 information matrix.  Set g holds k_g frames, 1 <= k_g <= 16: the slots
+ * set_ptr[g] .. set_ptr[g + 1] of frame[], caller's numbering, strictly ascending inside a set.  Slot i has a linearisation
+ * pose: the world -> camera rotation Rbar_i (lin_R, 3 x 3 row-major) and the centre Cbar_i (lin_C), in the caller's world
+ * coordinates.  The set has a mean m_g of 6 k_g values (mean; NULL = zeros for every set) and a symmetric positive semi-definite
+ * information matrix L_g, dense row-major (6 k_g)^2, the sets' matrices one behind the other in info[]; variable order slot by
+ * slot, [t; r] inside a slot.  With R_i, C_i = -R_i^T T_i the current pose:
+ *
+ *     r_i = [ C_i - Cbar_i ; Log(R_i^T Rbar_i) ]    (rotation vector of the direct rotation relative to the linearisation, angle < pi)
+ *     E = (everything E is without these priors) + sum_g (r_g - m_g)^T L_g (r_g - m_g)
+ *
+ * This is the pose perturbation of the covariance calls ([centre; rotation vector applied to the direct rotation from the
+ * left], srk_ba_revert_covariances), so the inverse of a joint covariance is usable as it comes.  L is in units of E,
+ * (pix / f0)^2, per squared world unit (tt), per world unit and radian (tr), per squared radian (rr): a Gaussian of covariance
+ * Sigma beside observations of pixel noise sigma_px is L = (sigma_px / f0)^2 Sigma^-1.  No robust loss and no observation
+ * information acts on it.  This E is what the accept / reject test, both termination tests, report.err_initial / err_final,
+ * srk_ba_iteration_log and srk_ba_phase_error use; srk_ba_reproj_error* stay the reprojection sums.  With J_i = diag(I,
+ * Jl^-1(r_r,i)) (the inverse left Jacobian of SO(3), exact, so the gradient is the gradient of E) a set adds 2 J_i^T L_ii J_i to
+ * the pose part of frame i's block (before the damping), 2 J_i^T (L (r - m))_i to its gradient and 2 J_i^T L_ij J_j as the
+ * pose x pose block (i, j) of the reduced camera system, undamped.  The intrinsic variables get nothing.
+ *
+ * A pair of slots whose 6 x 6 block L_ij is all zeros is no coupling; the other pairs enter the covisibility like the pairs of
+ * relative-pose factors: the frame renumbering, the skyline and the solver plans know them.  A set whose L is all zeros is
+ * switched off: the upload leaves it out, plan included.  Two sets may share at most one frame.  A pair may carry a
+ * relative-pose factor as well.
+ *
+ * keep_gauge as for position priors: 1 keeps the reference's seven gauge variables; 0 releases them -- the caller then asserts
+ * that the priors fix the seven freedoms (one full-rank pose prior fixes six, a second frame with a distinct centre the scale).
+ * The gauge is released when any of srk_ba_set_constant_blocks, srk_ba_set_position_priors and this call says 0.
+ *
+ * n_sets = 0 clears the setting (the default).  The handle keeps a copy (L symmetrised): it is applied by every later upload
+ * (srk_ba_compute_inplace and srk_ba_compute_inplace_f32 included) and is not touched by srk_ba_reset_scene.  The upload maps it
+ * to the normalised scene (srk_ba_normalize_joint_pose_priors).  An index beyond the uploaded scene's frames fails that upload
+ * with SRK_E_ARGS.
+ *
+ * SRK_E_ARGS (text in srk_ba_last_error), the previous setting staying in force: a set size outside 1..16, frames not strictly
+ * ascending or negative, two sets sharing more than one frame, a value that is not finite, a lin_R that is not a rotation to
+ * 1e-9, an L not symmetric to 1e-12 of its largest entry, an L that is not positive semi-definite, a NULL array (mean
+ * excepted), keep_gauge outside {0, 1}.  Refused with SRK_E_ARGS by whichever call comes second: intrinsic groups, more than one
+ * rank.  Everything else works unchanged.  Three small passes impose the priors (behind the derivative kernels, behind the
+ * assembly of the reduced camera system, beside the error kernel); none is launched without switched-on sets. */
+int srk_ba_set_joint_pose_priors(srk_ba*, int32_t n_sets, const int32_t* set_ptr /* [n_sets + 1] */, const int32_t* frame,
+                                 const double* lin_R /* [][9] */, const double* lin_C /* [][3] */, const double* mean /* [][6] or NULL */,
+                                 const double* info, int keep_gauge);
+/* host only, no device and no handle needed: the checks of the setter on their own.  SRK_OK, or SRK_E_ARGS with *why (may be
+ * NULL) pointing at a static text. */
+int srk_ba_check_joint_pose_priors(int32_t n_sets, const int32_t* set_ptr, const int32_t* frame, const double* lin_R,
+                                   const double* lin_C, const double* mean, const double* info, int keep_gauge, const char** why);
+/* the sizes of the stored setting: sets, slots (the length of frame[]) and doubles of info[]; returns 1 if a setting is stored,
+ * 0 if not */
+int srk_ba_joint_pose_prior_counts(srk_ba*, int32_t* n_sets, int32_t* n_frames, int64_t* n_info);
+/* the stored setting (what the NEXT upload applies) into arrays of the sizes the counts give; any pointer may be NULL.
+ * Returns 1 if a setting is stored, 0 if not. */
+int srk_ba_joint_pose_priors(srk_ba*, int32_t* set_ptr, int32_t* frame, double* lin_R, double* lin_C, double* mean, double* info,
+                             int* keep_gauge);
+/* the priors' sum of the resident scene's current state (0 without switched-on sets) */
+int srk_ba_joint_pose_prior_error(srk_ba*, double* e);
+/* r - m [slots][6] of the resident scene's current state in the caller's world units and radians, in the order of the setting.
+ * They belong to the setting the resident scene was uploaded with; if the stored setting has been changed since, the call fails
+ * with SRK_E_STATE until the scene is uploaded again. */
+int srk_ba_joint_pose_prior_residuals(srk_ba*, double* r);
+/* host only, no device needed: linearisation poses, means and information matrices through a normaliser, as the upload maps
+ * them.  With X_n = s (R0 X + T0): Cbar_n = s (R0 Cbar + T0), Rbar_n = Rbar R0^T, m_n = D m and L_n = D^-T L D^-1 with
+ * D = diag(s R0, R0) per slot; the energy is invariant.  Each in / out pair of arrays may be NULL.  SRK_OK or SRK_E_ARGS. */
+int srk_ba_normalize_joint_pose_priors(const srk_ba_normalizer* nrm, int32_t n_sets, const int32_t* set_ptr, const double* lin_R,
+                                       const double* lin_C, const double* mean, const double* info, double* lin_R_out,
+                                       double* lin_C_out, double* mean_out, double* info_out);
+/* device time in ms of the last launch of the three passes, taken with srk_ba_set_profile >= 1; 0 for a pass that was not
+ * launched or not timed.  One event pair a pass serves all attempt slots (tools/jointprior_rate.py switches speculation off). */
+int srk_ba_joint_pose_prior_pass_ms(srk_ba*, double* derivative_ms, double* couple_ms, double* error_ms);
+
 /* ---- marginal covariances of frames and landmarks (EXTENSION) ----
  * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
  * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior

@@ -104,6 +104,7 @@ public:
         ApplyConstantBlocks(map, f, inverse_orient_cams.size());
         ApplyPositionPriors(map, f);
         ApplyRelativePoseFactors();
+        ApplyJointPosePriors();
         Scalar a = term_crit.AllowedReprojErrRelativeChange().value_or(0), m = term_crit.MaxHessianFactor().value_or(0);
         int rc = srk_ba_compute_inplace(h_, f0, (int64_t)f.ids.size(), f.pts.data(), (int32_t)inverse_orient_cams.size(),
                                         f.R.data(), f.T.data(), f.K.data(), f.shared, f.row_ptr.data(), f.frames.data(),
@@ -364,6 +365,34 @@ public:
         return rc == 0;
     }
 
+    /// EXTENSION: joint Gaussian pose priors over sets of cameras from the next ComputeInplace on
+    /// (srk_ba_set_joint_pose_priors): what a marginalised window leaves behind, or with one camera a
+    /// full pose prior.  frames: 1 to 16 cameras, strictly ascending; lin_R / lin_C: per camera the linearisation pose, the
+    /// world -> camera rotation (row-major) and the centre; mean: 6 values a camera, or empty for zeros; info: the dense
+    /// row-major (6 k) x (6 k) information matrix, variable order camera by camera, [t; r] inside a camera, in units of the
+    /// error, (pix / f0)^2.  The residual of a camera is [C - lin_C; Log(R^T lin_R)].  keep_gauge = false releases the
+    /// reference's gauge: the priors must then fix the seven freedoms.  An empty vector clears the setting.  ComputeInplace
+    /// throws std::invalid_argument for a camera beyond the cameras, sizes that do not fit, values the library refuses, and
+    /// where it refuses the combination (intrinsic groups, more than one rank).
+    struct JointPosePrior {
+        std::vector<size_t> frames;
+        std::vector<std::array<Scalar, 9>> lin_R;
+        std::vector<Point3> lin_C;
+        std::vector<Scalar> mean;
+        std::vector<Scalar> info;
+    };
+    void SetJointPosePriors(const std::vector<JointPosePrior>& sets, bool keep_gauge = true) {
+        if (sets.empty()) { ClearJointPosePriors(); return; }
+        jprior_ = sets;
+        jprior_keep_gauge_ = keep_gauge;
+    }
+    void ClearJointPosePriors() {
+        jprior_.clear();
+        jprior_keep_gauge_ = true;
+        int rc = srk_ba_set_joint_pose_priors(h_, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1);
+        if (rc < 0) Raise(rc);
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
@@ -465,6 +494,29 @@ private:
         int rc = srk_ba_set_relative_pose_factors(h_, (int32_t)fa.size(), fa.data(), fb.data(), R.data(), t.data(), L.data());
         if (rc < 0) Raise(rc);
     }
+    // the stored sets as the flat arrays of the C ABI
+    void ApplyJointPosePriors() {
+        if (jprior_.empty()) return;
+        std::vector<int32_t> ptr(1, 0), fr;
+        std::vector<Scalar> R, Cc, m, L;
+        for (const JointPosePrior& s : jprior_) {
+            const size_t k = s.frames.size();
+            if (s.lin_R.size() != k || s.lin_C.size() != k || (!s.mean.empty() && s.mean.size() != 6 * k) || s.info.size() != 36 * k * k)
+                throw std::invalid_argument("joint pose priors: a set of k cameras needs k poses, 6 k mean values (or none) and (6 k)^2 information entries");
+            ptr.push_back(ptr.back() + (int32_t)k);
+            for (size_t i = 0; i < k; ++i) {
+                fr.push_back((int32_t)s.frames[i]);
+                R.insert(R.end(), s.lin_R[i].begin(), s.lin_R[i].end());
+                Cc.insert(Cc.end(), { s.lin_C[i].x, s.lin_C[i].y, s.lin_C[i].z });
+            }
+            if (s.mean.empty()) m.insert(m.end(), 6 * k, Scalar(0));
+            else m.insert(m.end(), s.mean.begin(), s.mean.end());
+            L.insert(L.end(), s.info.begin(), s.info.end());
+        }
+        int rc = srk_ba_set_joint_pose_priors(h_, (int32_t)jprior_.size(), ptr.data(), fr.data(), R.data(), Cc.data(), m.data(), L.data(),
+                                              jprior_keep_gauge_ ? 1 : 0);
+        if (rc < 0) Raise(rc);
+    }
     [[noreturn]] void Raise(int rc) const {
         std::string msg = srk_ba_last_error(h_);
         if (rc == SRK_E_ARGS) throw std::invalid_argument(msg);
@@ -480,6 +532,8 @@ private:
     bool prior_set_ = false, prior_keep_gauge_ = true;
     std::vector<PositionPrior> prior_points_, prior_frames_;
     std::vector<RelativePoseFactor> relpose_;
+    std::vector<JointPosePrior> jprior_;
+    bool jprior_keep_gauge_ = true;
     std::vector<int64_t> pnt_ind_of_;
 };
 

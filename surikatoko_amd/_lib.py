@@ -65,6 +65,9 @@ EXPORTS = [
     "srk_ba_set_relative_pose_factors", "srk_ba_check_relative_pose_factors", "srk_ba_relative_pose_factor_count", "srk_ba_relative_pose_factors",
     "srk_ba_relative_pose_error", "srk_ba_relative_pose_residuals", "srk_ba_normalize_relative_pose_factors",
     "srk_ba_relative_pose_pass_ms",
+    "srk_ba_set_joint_pose_priors", "srk_ba_check_joint_pose_priors", "srk_ba_joint_pose_prior_counts", "srk_ba_joint_pose_priors",
+    "srk_ba_joint_pose_prior_error", "srk_ba_joint_pose_prior_residuals", "srk_ba_normalize_joint_pose_priors",
+    "srk_ba_joint_pose_prior_pass_ms",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
     "srk_ba_phase_cross_covariance", "srk_ba_cross_covariances", "srk_ba_revert_cross_covariances", "srk_ba_relative_pose_covariances",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
@@ -144,6 +147,14 @@ def lib():
     L.srk_ba_relative_pose_residuals.argtypes = [C.c_void_p, C.c_void_p]
     L.srk_ba_normalize_relative_pose_factors.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.srk_ba_relative_pose_pass_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.srk_ba_set_joint_pose_priors.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int]
+    L.srk_ba_check_joint_pose_priors.argtypes = [C.c_int32] + [C.c_void_p] * 6 + [C.c_int, C.POINTER(C.c_char_p)]
+    L.srk_ba_joint_pose_prior_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.srk_ba_joint_pose_priors.argtypes = [C.c_void_p] * 7 + [C.POINTER(C.c_int)]
+    L.srk_ba_joint_pose_prior_error.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.srk_ba_joint_pose_prior_residuals.argtypes = [C.c_void_p, C.c_void_p]
+    L.srk_ba_normalize_joint_pose_priors.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
+    L.srk_ba_joint_pose_prior_pass_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.srk_ba_phase_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.srk_ba_covariances.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.srk_ba_revert_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]

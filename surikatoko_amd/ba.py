@@ -310,6 +310,101 @@ def normalize_relative_pose_factors(nrm, rel_t, info):
     return to, io
 
 
+def _joint_pose_prior_arrays(sets, sigma_pixels=None, f0=None):
+    """the flat arrays of the C ABI from a list of sets.  A set is a dict with frames (k, strictly ascending), R [k][3][3] and
+    C [k][3] (or poses=(R, C)): the linearisation poses, info= [6k][6k] or covariance= [6k][6k] (variable order frame by frame,
+    [t; r] inside a frame), and optionally mean= [6k]; or a tuple (frames, R, C, info[, mean]).  A covariance becomes
+    L = (sigma_pixels / f0)^2 Sigma^-1, as in relative_pose_information."""
+    ptr, frames, Rs, Cs, means, infos = [0], [], [], [], [], []
+    for st in sets:
+        if not isinstance(st, dict):
+            st = dict(zip(("frames", "R", "C", "info", "mean"), st))
+        fr = np.asarray(st["frames"]).astype(np.int32).reshape(-1)
+        k = fr.size
+        R, Cc = st["poses"] if "poses" in st else (st["R"], st["C"])
+        R = np.asarray(R, dtype=np.float64).reshape(-1, 9)
+        Cc = np.asarray(Cc, dtype=np.float64).reshape(-1, 3)
+        if R.shape[0] != k or Cc.shape[0] != k:
+            raise ValueError("joint pose priors: one linearisation pose (R, C) per frame of a set")
+        if st.get("info") is not None:
+            L = np.asarray(st["info"], dtype=np.float64)
+        elif st.get("covariance") is not None:
+            if not f0:
+                raise ValueError("joint pose priors: a covariance needs the scene's f0 (or pass info=)")
+            cov = np.asarray(st["covariance"], dtype=np.float64)
+            if cov.shape != (6 * k, 6 * k) or np.abs(cov - cov.T).max() > 1e-12 * np.abs(cov).max():
+                raise ValueError("joint pose priors: covariance= is a symmetric [6k][6k]")
+            cov = 0.5 * (cov + cov.T)
+            if not np.all(np.isfinite(cov)) or np.any(np.linalg.eigvalsh(cov) <= 0):
+                raise ValueError("joint pose priors: a covariance must be positive definite")
+            L = np.linalg.inv(cov) * (float(1.0 if sigma_pixels is None else sigma_pixels) / float(f0)) ** 2
+            L = 0.5 * (L + L.T)
+        else:
+            raise ValueError("joint pose priors: give info= or covariance= for every set")
+        if L.shape != (6 * k, 6 * k):
+            raise ValueError("joint pose priors: the information matrix of a set of k frames is [6k][6k]")
+        m = np.zeros(6 * k) if st.get("mean") is None else np.asarray(st["mean"], dtype=np.float64).reshape(-1)
+        if m.size != 6 * k:
+            raise ValueError("joint pose priors: the mean of a set of k frames has 6k values")
+        ptr.append(ptr[-1] + k)
+        frames.append(fr); Rs.append(R); Cs.append(Cc); means.append(m); infos.append(L.reshape(-1))
+    cat = lambda v, dt: np.ascontiguousarray(np.concatenate(v), dtype=dt)  # noqa: E731
+    return (np.asarray(ptr, dtype=np.int32), cat(frames, np.int32), cat(Rs, np.float64), cat(Cs, np.float64), cat(means, np.float64),
+            cat(infos, np.float64))
+
+
+def _joint_pose_prior_sets(ptr, fr, R, Cc, m, L):
+    """the inverse of _joint_pose_prior_arrays: a list of dicts frames, R, C, mean, info"""
+    out, at = [], 0
+    for g in range(len(ptr) - 1):
+        a, b = int(ptr[g]), int(ptr[g + 1])
+        n = 6 * (b - a)
+        out.append(dict(frames=fr[a:b].copy(), R=R.reshape(-1, 3, 3)[a:b].copy(), C=Cc.reshape(-1, 3)[a:b].copy(),
+                        mean=m.reshape(-1)[6 * a:6 * b].copy(), info=L[at:at + n * n].reshape(n, n).copy()))
+        at += n * n
+    return out
+
+
+def check_joint_pose_priors(sets, keep_gauge=True):
+    """the setter's checks on their own (srk_ba_check_joint_pose_priors; host only): None, or the text of the refusal"""
+    if len(sets) == 0:
+        return None
+    ptr, fr, R, Cc, m, L = _joint_pose_prior_arrays(sets)
+    why = C.c_char_p()
+    lib().srk_ba_check_joint_pose_priors(C.c_int32(len(ptr) - 1), _p(ptr), _p(fr), _p(R), _p(Cc), _p(m), _p(L), C.c_int(int(keep_gauge)),
+                                         C.byref(why))
+    return why.value.decode() if why.value else None
+
+
+def normalize_joint_pose_priors(nrm, sets):
+    """a list of sets through a Normalizer, as the upload maps them (srk_ba_normalize_joint_pose_priors; host only): with
+    X_n = s (R0 X + T0), Cbar_n = s (R0 Cbar + T0), Rbar_n = Rbar R0^T, m_n = D m, L_n = D^-T L D^-1, D = diag(s R0, R0)"""
+    ptr, fr, R, Cc, m, L = _joint_pose_prior_arrays(sets)
+    Ro, Co, mo, Lo = np.zeros_like(R), np.zeros_like(Cc), np.zeros_like(m), np.zeros_like(L)
+    rc = lib().srk_ba_normalize_joint_pose_priors(C.byref(nrm), C.c_int32(len(ptr) - 1), _p(ptr), _p(R), _p(Cc), _p(m), _p(L), _p(Ro), _p(Co),
+                                                  _p(mo), _p(Lo))
+    if rc != 0:
+        raise ValueError("srk_ba_normalize_joint_pose_priors: bad argument")
+    return _joint_pose_prior_sets(ptr, fr, Ro, Co, mo, Lo)
+
+
+def joint_pose_prior_from_covariance(frames, scene, joint_cov, frame_vars, sigma_pixels, f0):
+    """A ready set for set_joint_pose_priors from a joint_covariance(frames, []) result (computed at pixel noise sigma_pixels) and
+    the scene's current poses: the pose rows and columns of every frame are selected (which marginalises the intrinsics of
+    the ten-variable layout), then L = (sigma_pixels / f0)^2 Sigma^-1; mean zero, linearised at the scene's poses.  frames
+    must be strictly ascending, as joint_covariance was called."""
+    fr = np.asarray(frames).astype(np.int32).reshape(-1)
+    fv, k = int(frame_vars), fr.size
+    off = fv - 6
+    sel = np.concatenate([fv * i + off + np.arange(6) for i in range(k)])
+    cov = np.asarray(joint_cov, dtype=np.float64)[np.ix_(sel, sel)]
+    cov = 0.5 * (cov + cov.T)
+    L = np.linalg.inv(cov) * (float(sigma_pixels) / float(f0)) ** 2
+    R = np.asarray(scene.cam_R, dtype=np.float64).reshape(-1, 3, 3)[fr]
+    T = np.asarray(scene.cam_T, dtype=np.float64).reshape(-1, 3)[fr]
+    return dict(frames=fr, R=R.copy(), C=-np.einsum("kba,kb->ka", R, T), info=0.5 * (L + L.T), mean=np.zeros(6 * k))
+
+
 def check_world_is_normalized(scene, t1y=1.0, unity_comp_ind=1):
     """CheckWorldIsNormalized (.cpp:288-333)."""
     return bool(lib().srk_ba_check_world_is_normalized(C.c_int32(scene.M), _p(scene.cam_R), _p(scene.cam_T),
@@ -836,6 +931,57 @@ class BundleAdjustmentKanatani:
         """(derivative-side pass, coupling pass, error-side pass): device ms of the last launch, with set_profile >= 1"""
         a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
         self._raise(self._lib.srk_ba_relative_pose_pass_ms(C.c_void_p(self._h), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def set_joint_pose_priors(self, sets=None, keep_gauge=True, sigma_pixels=None):
+        """Joint Gaussian pose priors over sets of frames (next upload).  sets: a list of dicts with
+        frames (k <= 16, caller's numbering, strictly ascending), R [k][3][3] and C [k][3] (or poses=(R, C)): the
+        linearisation poses in the caller's world, info= [6k][6k] in units of the error or covariance= [6k][6k] (becomes
+        L = (sigma_pixels / f0)^2 Sigma^-1 with the f0 of the scene last passed to this object), and optionally mean= [6k];
+        joint_pose_prior_from_covariance builds one from a joint_covariance result.  The residual of a frame is
+        [C - Cbar; Log(R^T Rbar)].  keep_gauge False releases the reference's gauge: the priors must then fix the seven
+        freedoms.  None or empty clears the setting.  Not with intrinsic groups or more than one rank (ValueError)."""
+        if sets is None or len(sets) == 0:
+            self._raise(self._lib.srk_ba_set_joint_pose_priors(C.c_void_p(self._h), C.c_int32(0), None, None, None, None, None, None, C.c_int(1)))
+            return
+        ptr, fr, R, Cc, m, L = _joint_pose_prior_arrays(sets, sigma_pixels, self._f0)
+        self._raise(self._lib.srk_ba_set_joint_pose_priors(C.c_void_p(self._h), C.c_int32(len(ptr) - 1), _p(ptr), _p(fr), _p(R), _p(Cc), _p(m),
+                                                           _p(L), C.c_int(int(keep_gauge))))
+
+    def joint_pose_priors(self):
+        """None when no priors are set, else (sets, keep_gauge): the stored setting as a list of dicts frames, R, C, mean, info
+        in the caller's numbering and coordinates"""
+        ns, nq, ni = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        rc = self._lib.srk_ba_joint_pose_prior_counts(C.c_void_p(self._h), C.byref(ns), C.byref(nq), C.byref(ni))
+        self._raise(rc)
+        if rc == 0:
+            return None
+        ptr, fr = np.zeros(ns.value + 1, np.int32), np.zeros(nq.value, np.int32)
+        R, Cc, m, L = np.zeros((nq.value, 9)), np.zeros((nq.value, 3)), np.zeros(6 * nq.value), np.zeros(ni.value)
+        kg = C.c_int(1)
+        self._raise(self._lib.srk_ba_joint_pose_priors(C.c_void_p(self._h), _p(ptr), _p(fr), _p(R), _p(Cc), _p(m), _p(L), C.byref(kg)))
+        return _joint_pose_prior_sets(ptr, fr, R, Cc, m, L), bool(kg.value)
+
+    def joint_pose_prior_error(self):
+        """the priors' sum of the resident scene's current state"""
+        e = C.c_double(0)
+        self._raise(self._lib.srk_ba_joint_pose_prior_error(C.c_void_p(self._h), C.byref(e)))
+        return e.value
+
+    def joint_pose_prior_residuals(self):
+        """r - m per set (a list of [6k] arrays) of the resident scene's current state in the caller's world units and
+        radians, in the order of joint_pose_priors()"""
+        ns, nq, ni = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._raise(self._lib.srk_ba_joint_pose_prior_counts(C.c_void_p(self._h), C.byref(ns), C.byref(nq), C.byref(ni)))
+        ptr, r = np.zeros(ns.value + 1, np.int32), np.zeros(6 * nq.value)
+        self._raise(self._lib.srk_ba_joint_pose_priors(C.c_void_p(self._h), _p(ptr), None, None, None, None, None, None))
+        self._raise(self._lib.srk_ba_joint_pose_prior_residuals(C.c_void_p(self._h), _p(r) if nq.value else None))
+        return [r[6 * int(ptr[g]):6 * int(ptr[g + 1])].copy() for g in range(ns.value)]
+
+    def joint_pose_prior_pass_ms(self):
+        """(derivative-side passes, coupling pass, error-side pass): device ms of the last launch, with set_profile >= 1"""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._raise(self._lib.srk_ba_joint_pose_prior_pass_ms(C.c_void_p(self._h), C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
     def schur_fallback_landmarks(self):

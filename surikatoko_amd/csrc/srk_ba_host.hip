@@ -25,6 +25,7 @@
 #include <iterator>
 #include <map>
 #include <memory>
+#include <set>
 #include <vector>
 #include <unordered_set>
 #include <thread>
@@ -216,6 +217,23 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     int32_t n_rp = 0, n_rp_frames = 0;
     hipEvent_t ev_rp[6]{}; // profile level >= 1: around the last k_relpose_add / k_relpose_couple / k_relpose_error launch
     bool rp_timed[3] = { false, false, false };
+    // opt-in: joint Gaussian pose priors over sets of frames (srk_ba_set_joint_pose_priors).  jp_*: the
+    // setting in the caller's numbering and world coordinates (jp_info symmetrised, jp_mean zeros where none was given), kept
+    // across uploads and srk_ba_reset_scene.  The uploaded scene: jp_act = the sets that are switched on, jp_pair_a / jp_pair_b
+    // their coupled pairs in the internal numbering, and the device lists (SrkJointPrior).
+    bool jp_set = false;
+    int jp_keep_gauge = 1;
+    std::vector<int32_t> jp_ptr, jp_frame;
+    std::vector<double> jp_R, jp_C, jp_mean, jp_info;
+    std::vector<int32_t> jp_act, jp_pair_a, jp_pair_b;
+    std::vector<int32_t> app_jp_ptr, app_jp_frame; // what the resident scene was uploaded with (srk_ba_joint_pose_prior_residuals)
+    std::vector<double> app_jp_R, app_jp_C, app_jp_mean;
+    bool app_jp = false;
+    DevBuf jp_d_ptr, jp_d_frame, jp_d_lin, jp_d_mean, jp_d_iptr, jp_d_info, jp_d_pptr, jp_d_pslot, jp_d_tgt, jp_d_blk, jp_d_cpl, jp_d_fr_list,
+        jp_d_fr_ptr, jp_d_fr_ent;
+    int32_t n_jp = 0, n_jp_pairs = 0, n_jp_frames = 0;
+    hipEvent_t ev_jp[6]{}; // profile level >= 1: around the last k_jprior_form + k_jprior_add / k_jprior_couple / k_jprior_error launch
+    bool jp_timed[3] = { false, false, false };
     int profile_level = 0; // 0 = no events, 1 = phase events (report.ms_*), 2 = + event pairs around the MFMA updates
     bool chol_fused = true; // the solve's outer steps as one launch each (k_step256); srk_ba_set_solver_fusion
     // what the caller asked for.  A hand-off timeout switches chol_fused off for the rest of that call; the next upload /
@@ -404,6 +422,8 @@ void srk_ba_destroy(srk_ba* h)
                       &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk,
                       &h->info_q, &h->info_qf, &h->cst_pts, &h->cst_frames, &h->pri_pt_list, &h->pri_pt_val, &h->pri_fr_list, &h->pri_fr_val,
                       &h->rp_fa, &h->rp_fb, &h->rp_val, &h->rp_fr_list, &h->rp_fr_ptr, &h->rp_fr_ent, &h->rp_tgt, &h->rp_cpl,
+                      &h->jp_d_ptr, &h->jp_d_frame, &h->jp_d_lin, &h->jp_d_mean, &h->jp_d_iptr, &h->jp_d_info, &h->jp_d_pptr, &h->jp_d_pslot,
+                      &h->jp_d_tgt, &h->jp_d_blk, &h->jp_d_cpl, &h->jp_d_fr_list, &h->jp_d_fr_ptr, &h->jp_d_fr_ent,
                       &h->cov_Y, &h->cov_grp, &h->cov_blk, &h->cov_out, &h->cov_free, &h->cov_colb, &h->cov_pairs };
     for (DevBuf* b : all) dev_free(*b);
     for (auto& a : h->att) {
@@ -426,6 +446,8 @@ void srk_ba_destroy(srk_ba* h)
     for (auto& e : h->ev_pri)
         if (e) hipEventDestroy(e);
     for (auto& e : h->ev_rp)
+        if (e) hipEventDestroy(e);
+    for (auto& e : h->ev_jp)
         if (e) hipEventDestroy(e);
     if (h->ev_comm) hipEventDestroy(h->ev_comm);
     if (h->comm_stream) hipStreamDestroy(h->comm_stream);
@@ -517,6 +539,15 @@ static const char* relpose_conflict(bool factors, bool groups, int world)
     if (world > 1) return "relative-pose factors: not available with more than one rank";
     return nullptr;
 }
+// joint pose priors (srk_ba_set_joint_pose_priors) add to the pose part of the blocks and couple frames of one rank's system, as
+// the relative-pose factors do
+static const char* jprior_conflict(bool sets, bool groups, int world)
+{
+    if (!sets) return nullptr;
+    if (groups) return "joint pose priors: not available with intrinsic groups";
+    if (world > 1) return "joint pose priors: not available with more than one rank";
+    return nullptr;
+}
 static bool refuse_modes(srk_ba* h, bool fixed_k, bool deterministic, bool store_f32, bool schur_fp32, int world, bool groups)
 {
     const char* e = fixed_k_conflict(fixed_k, deterministic, store_f32, schur_fp32, world);
@@ -524,6 +555,7 @@ static bool refuse_modes(srk_ba* h, bool fixed_k, bool deterministic, bool store
     if (!e) e = constant_conflict(h->cst_set, groups, world);
     if (!e) e = prior_conflict(h->pri_set, groups, world);
     if (!e) e = relpose_conflict(h->rp_set, groups, world);
+    if (!e) e = jprior_conflict(h->jp_set, groups, world);
     if (e) h->last_error = e;
     return e != nullptr;
 }
@@ -727,6 +759,60 @@ int srk_ba_normalize_relative_pose_factors(const srk_ba_normalizer* nrm, int32_t
         int k = 0;
         for (int r = 0; r < 6; ++r)
             for (int c = r; c < 6; ++c, ++k) info_out[21 * i + k] = info[21 * i + k] * (r < 3 ? is : 1.0) * (c < 3 ? is : 1.0);
+    }
+    return SRK_OK;
+}
+
+// joint pose priors through a normaliser (host only).  With X_n = s (R0 X + T0): Cbar_n = s (R0 Cbar + T0), Rbar_n = Rbar R0^T,
+// and the residual of a frame maps as r_n = D r, D = diag(s R0, R0), so m_n = D m and L_n = D^-T L D^-1 keep the energy: block
+// (i, j) of L_n is G L_ij G^T with G = diag(R0 / s, R0).  The inverse of the map srk_ba_revert_covariances applies.
+int srk_ba_normalize_joint_pose_priors(const srk_ba_normalizer* nrm, int32_t n_sets, const int32_t* set_ptr, const double* lin_R,
+                                       const double* lin_C, const double* mean, const double* info, double* lin_R_out,
+                                       double* lin_C_out, double* mean_out, double* info_out)
+{
+    if (!nrm || n_sets < 0 || (n_sets > 0 && !set_ptr) || (lin_R != nullptr) != (lin_R_out != nullptr) ||
+        (lin_C != nullptr) != (lin_C_out != nullptr) || (mean != nullptr) != (mean_out != nullptr) || (info != nullptr) != (info_out != nullptr))
+        return SRK_E_ARGS;
+    for (int32_t g = 0; g < n_sets; ++g)
+        if (set_ptr[g + 1] < set_ptr[g] || set_ptr[0] != 0) return SRK_E_ARGS;
+    const double s = nrm->world_scale, is = 1.0 / s;
+    const double* R0 = nrm->R0;
+    const int64_t nq = n_sets > 0 ? set_ptr[n_sets] : 0;
+    double R0t[9];
+    srk::mat3_tr(R0, R0t);
+    for (int64_t q = 0; q < nq; ++q) {
+        if (lin_R) srk::mat3_mul(lin_R + 9 * q, R0t, lin_R_out + 9 * q);
+        if (lin_C) {
+            double y[3];
+            srk::se3_apply(R0, nrm->T0, lin_C + 3 * q, y);
+            for (int e = 0; e < 3; ++e) lin_C_out[3 * q + e] = s * y[e];
+        }
+        if (mean) {
+            double y[3];
+            srk::mat3_vec(R0, mean + 6 * q, y);
+            for (int e = 0; e < 3; ++e) mean_out[6 * q + e] = s * y[e];
+            srk::mat3_vec(R0, mean + 6 * q + 3, mean_out + 6 * q + 3);
+        }
+    }
+    int64_t at = 0;
+    for (int32_t g = 0; info && g < n_sets; ++g) {
+        const int64_t k = set_ptr[g + 1] - set_ptr[g], n = 6 * k;
+        const double* L = info + at;
+        double* o = info_out + at;
+        for (int64_t bi = 0; bi < 2 * k; ++bi)     // 3 x 3 blocks: even = translation, odd = rotation
+            for (int64_t bj = 0; bj < 2 * k; ++bj) {
+                double B[9], RB[9], RBR[9];
+                for (int a = 0; a < 3; ++a)
+                    for (int b = 0; b < 3; ++b) B[3 * a + b] = L[(3 * bi + a) * n + 3 * bj + b];
+                srk::mat3_mul(R0, B, RB);
+                srk::mat3_mul(RB, R0t, RBR);
+                const double f = ((bi & 1) ? 1.0 : is) * ((bj & 1) ? 1.0 : is);
+                for (int a = 0; a < 3; ++a)
+                    for (int b = 0; b < 3; ++b) o[(3 * bi + a) * n + 3 * bj + b] = f * RBR[3 * a + b];
+            }
+        for (int64_t r = 0; r < n; ++r) // the symmetric part: both triangles carry the same sum up to rounding
+            for (int64_t c = r + 1; c < n; ++c) o[r * n + c] = o[c * n + r] = 0.5 * (o[r * n + c] + o[c * n + r]);
+        at += n * n;
     }
     return SRK_OK;
 }
@@ -1090,6 +1176,25 @@ static int apply_information(srk_ba* h);
 static int apply_constant_blocks(srk_ba* h);
 static int apply_position_priors(srk_ba* h);
 static int apply_relative_pose_factors(srk_ba* h);
+static int apply_joint_pose_priors(srk_ba* h);
+// joint pose priors: the information matrix of set g of the stored setting (dense row-major, 6 k rows), and whether its 6 x 6
+// block (slot i, slot j) has a non-zero entry
+static const double* jp_info_of(const srk_ba* h, size_t g)
+{
+    int64_t at = 0;
+    for (size_t q = 0; q < g; ++q) {
+        const int64_t k = h->jp_ptr[q + 1] - h->jp_ptr[q];
+        at += 36 * k * k;
+    }
+    return h->jp_info.data() + at;
+}
+static bool jp_block_nonzero(const double* L, int64_t n, int32_t i, int32_t j)
+{
+    for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c)
+            if (L[(6 * i + r) * n + 6 * j + c] != 0.0) return true;
+    return false;
+}
 static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_in, int32_t M,
                              const double* cam_R_in, const double* cam_T_in, const double* K_in, int shared_k,
                              const int64_t* row_ptr, const int32_t* obs_frame, const double* obs_uv,
@@ -1166,6 +1271,31 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         h->rp_act.push_back((int32_t)k);
         rel_a.push_back(h->rp_a[k]);
         rel_b.push_back(h->rp_b[k]);
+    }
+    // joint pose priors: the switched-on sets; the pairs of slots whose 6 x 6 block of L is not all zeros join the factors'
+    // pairs, each unordered pair once
+    h->jp_act.clear();
+    if (h->jp_set) {
+        std::set<std::pair<int32_t, int32_t>> seen;
+        for (size_t k = 0; k < rel_a.size(); ++k) seen.insert({ std::min(rel_a[k], rel_b[k]), std::max(rel_a[k], rel_b[k]) });
+        for (size_t g = 0; g + 1 < h->jp_ptr.size(); ++g) {
+            const int32_t q0 = h->jp_ptr[g], k = h->jp_ptr[g + 1] - q0;
+            if (h->jp_frame[(size_t)(q0 + k - 1)] >= M) {
+                h->last_error = "joint pose priors: frame index " + std::to_string(h->jp_frame[(size_t)(q0 + k - 1)]) + ", the scene has " + std::to_string(M) + " frames";
+                return SRK_E_ARGS;
+            }
+            const double* L = jp_info_of(h, g);
+            bool off = true;
+            for (int64_t e = 0; e < 36 * (int64_t)k * k; ++e) off = off && L[e] == 0.0;
+            if (off) continue;
+            h->jp_act.push_back((int32_t)g);
+            for (int32_t i = 1; i < k; ++i)
+                for (int32_t j = 0; j < i; ++j)
+                    if (jp_block_nonzero(L, 6 * k, i, j) && seen.insert({ h->jp_frame[(size_t)(q0 + j)], h->jp_frame[(size_t)(q0 + i)] }).second) {
+                        rel_a.push_back(h->jp_frame[(size_t)(q0 + j)]);
+                        rel_b.push_back(h->jp_frame[(size_t)(q0 + i)]);
+                    }
+        }
     }
     rearm_fusion(h);
     stage("validate");
@@ -1251,6 +1381,8 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     if (h->cst_set && !h->cst_keep_gauge) d.g0 = d.g1 = -1;
     // position priors without the reference's gauge: the priors fix the similarity
     if (h->pri_set && !h->pri_keep_gauge) d.g0 = d.g1 = -1;
+    // joint pose priors without the reference's gauge: the caller asserts they fix the similarity
+    if (h->jp_set && !h->jp_keep_gauge) d.g0 = d.g1 = -1;
     d.w_f32 = h->store_f32 ? 1 : 0;
     h->d = d;
     h->f0 = f0;
@@ -1298,7 +1430,7 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         // (position priors: their partial sums sit behind the observation partials of either error kernel)
         add(a.err_partial, nullptr, 8 * (std::max<int64_t>(1024, srk_error_partials_staged(d)) +
                                          (h->pri_set ? srk_prior_partials((int64_t)h->pri_pt_idx.size(), (int64_t)h->pri_fr_idx.size()) : 0) +
-                                         srk_relpose_partials((int64_t)h->rp_act.size())));
+                                         srk_relpose_partials((int64_t)h->rp_act.size()) + srk_jprior_partials((int64_t)h->jp_act.size())));
         add(a.info, nullptr, 64);
         add(a.dinv, nullptr, 8 * 64 * d.ld);
         add(a.irr, nullptr, 4 * (N + 2));
@@ -1362,6 +1494,7 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     if ((rc = apply_constant_blocks(h)) != SRK_OK) return rc;
     if ((rc = apply_position_priors(h)) != SRK_OK) return rc;
     if ((rc = apply_relative_pose_factors(h)) != SRK_OK) return rc;
+    if ((rc = apply_joint_pose_priors(h)) != SRK_OK) return rc;
     h->have_scene = true;
     return SRK_OK;
 }
@@ -1442,6 +1575,108 @@ static const SrkRelPose* relpose_factors(const srk_ba* h, SrkRelPose& p)
 static bool rp_events(srk_ba* h)
 {
     for (auto& e : h->ev_rp)
+        if (!e && hipEventCreate(&e) != hipSuccess) return false;
+    return true;
+}
+
+// the switched-on sets (jp_act, checked at the start of the upload; the planner has seen their coupled pairs) -> the device
+// lists of the resident scene: frames through the renumbering (frame_int), poses, means and information matrices through the
+// normaliser of this upload, the coupled pairs with their places in S, the per-frame lists of slots in set order
+static int apply_joint_pose_priors(srk_ba* h)
+{
+    const SrkDims& d = h->d;
+    h->n_jp = h->n_jp_pairs = h->n_jp_frames = 0;
+    h->jp_timed[0] = h->jp_timed[1] = h->jp_timed[2] = false;
+    h->jp_pair_a.clear(); h->jp_pair_b.clear();
+    h->app_jp = h->jp_set;
+    h->app_jp_ptr = h->jp_ptr; h->app_jp_frame = h->jp_frame; h->app_jp_R = h->jp_R; h->app_jp_C = h->jp_C; h->app_jp_mean = h->jp_mean;
+    const size_t ns = h->jp_act.size();
+    if (ns == 0) return SRK_OK;
+    std::vector<double> Rn(h->jp_R.size()), Cn(h->jp_C.size()), mn(h->jp_mean.size()), Ln(h->jp_info.size());
+    srk_ba_normalize_joint_pose_priors(&h->nrm, (int32_t)h->jp_ptr.size() - 1, h->jp_ptr.data(), h->jp_R.data(), h->jp_C.data(),
+                                       h->jp_mean.data(), h->jp_info.data(), Rn.data(), Cn.data(), mn.data(), Ln.data());
+    std::vector<int32_t> ptr(1, 0), frame, pptr(1, 0), pslot;
+    std::vector<int64_t> iptr, tgt;
+    std::vector<double> lin, mean, info;
+    const int64_t t0 = 4 - (10 - d.fv); // first pose variable of a frame
+    for (size_t a = 0; a < ns; ++a) {
+        const size_t g = (size_t)h->jp_act[a];
+        const int32_t q0 = h->jp_ptr[g], k = h->jp_ptr[g + 1] - q0;
+        const int64_t n = 6 * (int64_t)k;
+        const double* L = Ln.data() + (jp_info_of(h, g) - h->jp_info.data());
+        iptr.push_back((int64_t)info.size());
+        info.insert(info.end(), L, L + n * n);
+        for (int32_t i = 0; i < k; ++i) {
+            const size_t q = (size_t)(q0 + i);
+            frame.push_back(h->frame_int.empty() ? h->jp_frame[q] : h->frame_int[(size_t)h->jp_frame[q]]);
+            lin.insert(lin.end(), &Rn[9 * q], &Rn[9 * q] + 9);
+            lin.insert(lin.end(), &Cn[3 * q], &Cn[3 * q] + 3);
+            mean.insert(mean.end(), &mn[6 * q], &mn[6 * q] + 6);
+        }
+        const int32_t* fr = frame.data() + ptr.back();
+        // (the stored matrix decides which pairs couple, as at the start of the upload: the normaliser maps a zero block to zeros)
+        for (int32_t i = 1; i < k; ++i)
+            for (int32_t j = 0; j < i; ++j)
+                if (jp_block_nonzero(jp_info_of(h, g), n, i, j)) {
+                    const int64_t hi = std::max(fr[i], fr[j]), lo = std::min(fr[i], fr[j]);
+                    pslot.push_back((i << 8) | j);
+                    tgt.push_back((d.fv * hi + t0) * d.ld + d.fv * lo + t0);
+                    h->jp_pair_a.push_back((int32_t)lo);
+                    h->jp_pair_b.push_back((int32_t)hi);
+                }
+        ptr.push_back(ptr.back() + k);
+        pptr.push_back((int32_t)pslot.size());
+    }
+    const size_t nq = frame.size(), np = pslot.size();
+    std::vector<int32_t> cnt((size_t)d.M, 0), list, fptr(1, 0), ent;
+    for (size_t q = 0; q < nq; ++q) ++cnt[(size_t)frame[q]];
+    std::vector<int32_t> at((size_t)d.M, -1);
+    for (int32_t j = 0; j < d.M; ++j)
+        if (cnt[(size_t)j]) {
+            at[(size_t)j] = (int32_t)list.size();
+            list.push_back(j);
+            fptr.push_back(fptr.back() + cnt[(size_t)j]);
+        }
+    ent.resize(nq);
+    std::vector<int32_t> fill(fptr.begin(), fptr.end() - 1);
+    for (size_t q = 0; q < nq; ++q) ent[(size_t)fill[(size_t)at[(size_t)frame[q]]]++] = (int32_t)q; // set order inside every frame's list
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &h->jp_d_ptr, ptr.data(), 4 * ptr.size() }, { &h->jp_d_frame, frame.data(), 4 * nq }, { &h->jp_d_lin, lin.data(), 8 * lin.size() },
+        { &h->jp_d_mean, mean.data(), 8 * mean.size() }, { &h->jp_d_iptr, iptr.data(), 8 * iptr.size() },
+        { &h->jp_d_info, info.data(), 8 * info.size() }, { &h->jp_d_pptr, pptr.data(), 4 * pptr.size() },
+        { &h->jp_d_pslot, pslot.data(), 4 * np }, { &h->jp_d_tgt, tgt.data(), 8 * np }, { &h->jp_d_fr_list, list.data(), 4 * list.size() },
+        { &h->jp_d_fr_ptr, fptr.data(), 4 * fptr.size() }, { &h->jp_d_fr_ent, ent.data(), 4 * ent.size() },
+    };
+    for (auto& u : up) {
+        if ((rc = dev_alloc(h, *u.b, std::max<size_t>(u.bytes, 8))) != SRK_OK) return rc;
+        if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((rc = dev_alloc(h, h->jp_d_blk, 8 * 42 * nq)) != SRK_OK) return rc;
+    HIPCHK(h, hipMemsetAsync(h->jp_d_blk.p, 0, 8 * 42 * nq, s));
+    if ((rc = dev_alloc(h, h->jp_d_cpl, 8 * 36 * std::max<size_t>(np, 1))) != SRK_OK) return rc;
+    HIPCHK(h, hipMemsetAsync(h->jp_d_cpl.p, 0, 8 * 36 * std::max<size_t>(np, 1), s));
+    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope
+    h->n_jp = (int32_t)ns;
+    h->n_jp_pairs = (int32_t)np;
+    h->n_jp_frames = (int32_t)list.size();
+    return SRK_OK;
+}
+// the lists of the resident scene for the kernels: NULL without switched-on sets, so that none of the passes is launched
+static const SrkJointPrior* joint_priors(const srk_ba* h, SrkJointPrior& p)
+{
+    if (h->n_jp == 0) return nullptr;
+    p = SrkJointPrior{ h->n_jp, P<int32_t>(h->jp_d_ptr), P<int32_t>(h->jp_d_frame), P<double>(h->jp_d_lin), P<double>(h->jp_d_mean),
+                       P<int64_t>(h->jp_d_iptr), P<double>(h->jp_d_info), P<int32_t>(h->jp_d_pptr), P<int32_t>(h->jp_d_pslot),
+                       P<int64_t>(h->jp_d_tgt), h->n_jp_pairs, P<double>(h->jp_d_blk), P<double>(h->jp_d_cpl), P<int32_t>(h->jp_d_fr_list),
+                       P<int32_t>(h->jp_d_fr_ptr), P<int32_t>(h->jp_d_fr_ent), h->n_jp_frames };
+    return &p;
+}
+static bool jp_events(srk_ba* h)
+{
+    for (auto& e : h->ev_jp)
         if (!e && hipEventCreate(&e) != hipSuccess) return false;
     return true;
 }
@@ -1839,11 +2074,16 @@ static int phase_error(srk_ba* h, srk_ba::Attempt& a, int which, double* err_hos
     const SrkRelPose* relpose = relpose_factors(h, rpl); // the factor sum of the scene being scored
     const bool rp_timed = relpose && h->profile_level >= 1 && rp_events(h);
     if (relpose) h->rp_timed[2] = rp_timed;
+    SrkJointPrior jpl;
+    const SrkJointPrior* jprior = joint_priors(h, jpl); // the joint pose priors' sum of the scene being scored
+    const bool jp_timed = jprior && h->profile_level >= 1 && jp_events(h);
+    if (jprior) h->jp_timed[2] = jp_timed;
     srk_launch_error(s, d, P<double>(h->pts[which]), P<double>(h->cam[which]), P<int32_t>(h->obs_frame),
                      P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(a.err_partial), np, a.err_dst,
                      h->jac_fused ? P<int32_t>(h->wg_jmin) : nullptr, with_status ? P<int>(a.info) : nullptr,
                      with_status ? reinterpret_cast<int*>(reinterpret_cast<char*>(a.acc.p) + 8 * 3 * d.Ns) : nullptr,
-                     robust_loss(h, L), prior, timed ? &h->ev_pri[2] : nullptr, relpose, rp_timed ? &h->ev_rp[4] : nullptr);
+                     robust_loss(h, L), prior, timed ? &h->ev_pri[2] : nullptr, relpose, rp_timed ? &h->ev_rp[4] : nullptr,
+                     jprior, jp_timed ? &h->ev_jp[4] : nullptr);
     HIPCHK(h, hipGetLastError());
     int rc = no_exchange ? SRK_OK : exchange(h, a, a.err_dst, with_status ? 3 : 1);
     if (rc != SRK_OK) return rc;
@@ -1912,6 +2152,15 @@ static int phase_derivatives(srk_ba* h)
         srk_launch_relpose_add(s, d, P<double>(h->cam[c]), *relpose, P<double>(h->Ug));
         if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[1], s));
         h->rp_timed[0] = timed;
+        HIPCHK(h, hipGetLastError());
+    }
+    SrkJointPrior jpl;
+    if (const SrkJointPrior* jprior = joint_priors(h, jpl)) { // the sets' terms into Ug, the coupling blocks aside
+        const bool timed = h->profile_level >= 1 && jp_events(h);
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_jp[0], s));
+        srk_launch_jprior_add(s, d, P<double>(h->cam[c]), *jprior, P<double>(h->Ug));
+        if (timed) HIPCHK(h, hipEventRecord(h->ev_jp[1], s));
+        h->jp_timed[0] = timed;
         HIPCHK(h, hipGetLastError());
     }
     if (h->n_cst_pts > 0) { // constant landmarks: identity block, zero gradient, zero point-frame blocks
@@ -1992,6 +2241,17 @@ static int phase_schur(srk_ba* h, srk_ba::Attempt& a, double c, bool local_only)
         if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[3], s));
         h->rp_timed[1] = timed;
         HIPCHK(h, hipGetLastError());
+    }
+    SrkJointPrior jpl;
+    if (const SrkJointPrior* jprior = joint_priors(h, jpl)) { // the sets' coupling blocks, before the constant frames are masked
+        if (jprior->n_pairs > 0) {
+            const bool timed = h->profile_level >= 1 && jp_events(h);
+            if (timed) HIPCHK(h, hipEventRecord(h->ev_jp[2], s));
+            srk_launch_jprior_couple(s, d, *jprior, P<double>(a.S));
+            if (timed) HIPCHK(h, hipEventRecord(h->ev_jp[3], s));
+            h->jp_timed[1] = timed;
+            HIPCHK(h, hipGetLastError());
+        }
     }
     if (h->n_cst_frames > 0) { // constant frames: identity rows and columns, zero rhs
         const bool timed = h->profile_level >= 1 && cst_events(h);
@@ -4021,6 +4281,8 @@ int srk_ba_set_covisibility(srk_ba* h, const int32_t* min_cv)
             const int32_t hi = std::max(h->rp_int_a[i], h->rp_int_b[i]), lo = std::min(h->rp_int_a[i], h->rp_int_b[i]);
             h->min_cv[(size_t)hi] = std::min(h->min_cv[(size_t)hi], lo);
         }
+        for (size_t i = 0; i < h->jp_pair_a.size(); ++i) // so are the coupled pairs of the joint pose priors (lo, hi)
+            h->min_cv[(size_t)h->jp_pair_b[i]] = std::min(h->min_cv[(size_t)h->jp_pair_b[i]], h->jp_pair_a[i]);
     } else {
         std::fill(h->min_cv.begin(), h->min_cv.end(), 0);
     }
@@ -4633,6 +4895,220 @@ int srk_ba_relative_pose_pass_ms(srk_ba* h, double* derivative_ms, double* coupl
         float ms = 0;
         if (h->rp_timed[k] && hipEventElapsedTime(&ms, h->ev_rp[2 * k], h->ev_rp[2 * k + 1]) != hipSuccess) ms = 0;
         if (outs[k]) *outs[k] = h->rp_timed[k] ? (double)ms : 0.0;
+    }
+    return SRK_OK;
+}
+// joint Gaussian pose priors over sets of frames.  Next upload.
+// positive semi-definite n x n (full symmetric A, destroyed): the pivot rule of relpose_info_psd at n variables
+static bool jprior_info_psd(std::vector<double>& A, int64_t n)
+{
+    double m = 0;
+    for (double v : A) m = std::max(m, std::fabs(v));
+    if (m == 0) return true;
+    for (int64_t k = 0; k < n; ++k) {
+        int64_t p = k;
+        for (int64_t i = k + 1; i < n; ++i)
+            if (A[(n + 1) * i] > A[(n + 1) * p]) p = i;
+        if (A[(n + 1) * p] <= 1e-12 * m) {
+            for (int64_t i = k; i < n; ++i)
+                for (int64_t j = k; j < n; ++j)
+                    if (i == j ? A[(n + 1) * i] < -1e-12 * m : std::fabs(A[n * i + j]) > 1e-11 * m) return false;
+            return true;
+        }
+        for (int64_t j = 0; j < n; ++j) std::swap(A[n * k + j], A[n * p + j]);
+        for (int64_t i = 0; i < n; ++i) std::swap(A[n * i + k], A[n * i + p]);
+        for (int64_t i = k + 1; i < n; ++i) {
+            const double f = A[n * i + k] / A[(n + 1) * k];
+            for (int64_t j = k + 1; j < n; ++j) A[n * i + j] -= f * A[n * k + j];
+        }
+    }
+    return true;
+}
+static const char* check_jprior(int32_t n_sets, const int32_t* set_ptr, const int32_t* frame, const double* lin_R, const double* lin_C,
+                                const double* mean, const double* info, int keep_gauge)
+{
+    if (keep_gauge != 0 && keep_gauge != 1) return "joint pose priors: keep_gauge must be 0 or 1";
+    if (set_ptr[0] != 0) return "joint pose priors: set_ptr must start at 0";
+    int64_t at = 0;
+    std::map<int32_t, std::vector<int32_t>> sets_of; // frame -> the sets that hold it
+    for (int32_t g = 0; g < n_sets; ++g) {
+        const int64_t k = (int64_t)set_ptr[g + 1] - set_ptr[g], n = 6 * k;
+        if (k < 1 || k > SRK_JP_MAX_FRAMES_HOST) return "joint pose priors: a set holds 1 to 16 frames";
+        for (int64_t i = 0; i < k; ++i) {
+            const int64_t q = set_ptr[g] + i;
+            if (frame[q] < 0) return "joint pose priors: negative frame index";
+            if (i > 0 && frame[q - 1] >= frame[q]) return "joint pose priors: the frames of a set must be strictly ascending";
+            const double* z = lin_R + 9 * q;
+            for (int e = 0; e < 9; ++e)
+                if (!std::isfinite(z[e])) return "joint pose priors: a linearisation rotation is not finite";
+            for (int e = 0; e < 3; ++e)
+                if (!std::isfinite(lin_C[3 * q + e])) return "joint pose priors: a linearisation centre is not finite";
+            for (int e = 0; mean && e < 6; ++e)
+                if (!std::isfinite(mean[6 * q + e])) return "joint pose priors: a mean is not finite";
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) {
+                    const double gm = z[a] * z[b] + z[3 + a] * z[3 + b] + z[6 + a] * z[6 + b] - (a == b ? 1.0 : 0.0);
+                    if (std::fabs(gm) > 1e-9) return "joint pose priors: a linearisation rotation is not orthogonal to 1e-9";
+                }
+            const double det = z[0] * (z[4] * z[8] - z[5] * z[7]) - z[1] * (z[3] * z[8] - z[5] * z[6]) + z[2] * (z[3] * z[7] - z[4] * z[6]);
+            if (std::fabs(det - 1.0) > 1e-9) return "joint pose priors: a linearisation rotation has determinant != 1";
+            // two sets may share one frame: every coupling block of the system then has one owner among the sets
+            std::vector<int32_t>& in = sets_of[frame[q]];
+            for (int32_t other : in)
+                for (int64_t i2 = 0; i2 < i; ++i2) {
+                    const std::vector<int32_t>& in2 = sets_of[frame[set_ptr[g] + i2]];
+                    if (std::find(in2.begin(), in2.end(), other) != in2.end()) return "joint pose priors: two sets share more than one frame";
+                }
+            in.push_back(g);
+        }
+        const double* L = info + at;
+        double m = 0;
+        for (int64_t e = 0; e < n * n; ++e) {
+            if (!std::isfinite(L[e])) return "joint pose priors: an information matrix is not finite";
+            m = std::max(m, std::fabs(L[e]));
+        }
+        std::vector<double> A((size_t)(n * n));
+        for (int64_t r = 0; r < n; ++r)
+            for (int64_t c = 0; c < n; ++c) {
+                if (std::fabs(L[r * n + c] - L[c * n + r]) > 1e-12 * m) return "joint pose priors: an information matrix is not symmetric to 1e-12 of its largest entry";
+                A[(size_t)(r * n + c)] = 0.5 * (L[r * n + c] + L[c * n + r]);
+            }
+        if (!jprior_info_psd(A, n)) return "joint pose priors: an information matrix is not positive semi-definite";
+        at += n * n;
+    }
+    return nullptr;
+}
+int srk_ba_check_joint_pose_priors(int32_t n_sets, const int32_t* set_ptr, const int32_t* frame, const double* lin_R, const double* lin_C,
+                                   const double* mean, const double* info, int keep_gauge, const char** why)
+{
+    const char* e = nullptr;
+    if (n_sets < 0) e = "joint pose priors: negative count";
+    else if (n_sets > 0 && (!set_ptr || !frame || !lin_R || !lin_C || !info)) e = "joint pose priors: null array";
+    else if (n_sets > 0) e = check_jprior(n_sets, set_ptr, frame, lin_R, lin_C, mean, info, keep_gauge);
+    if (why) *why = e;
+    return e ? SRK_E_ARGS : SRK_OK;
+}
+int srk_ba_set_joint_pose_priors(srk_ba* h, int32_t n_sets, const int32_t* set_ptr, const int32_t* frame, const double* lin_R,
+                                 const double* lin_C, const double* mean, const double* info, int keep_gauge)
+{
+    if (!h) return SRK_E_ARGS;
+    if (n_sets == 0) {
+        h->jp_set = false;
+        h->jp_keep_gauge = 1;
+        h->jp_ptr.clear(); h->jp_frame.clear(); h->jp_R.clear(); h->jp_C.clear(); h->jp_mean.clear(); h->jp_info.clear();
+        return SRK_OK;
+    }
+    const char* e = nullptr;
+    if (srk_ba_check_joint_pose_priors(n_sets, set_ptr, frame, lin_R, lin_C, mean, info, keep_gauge, &e) != SRK_OK) { h->last_error = e; return SRK_E_ARGS; }
+    if ((e = jprior_conflict(true, !h->igroup_user.empty(), h->world))) { h->last_error = e; return SRK_E_ARGS; }
+    const int64_t nq = set_ptr[n_sets];
+    int64_t ni = 0;
+    for (int32_t g = 0; g < n_sets; ++g) ni += 36 * (int64_t)(set_ptr[g + 1] - set_ptr[g]) * (set_ptr[g + 1] - set_ptr[g]);
+    h->jp_ptr.assign(set_ptr, set_ptr + n_sets + 1);
+    h->jp_frame.assign(frame, frame + nq);
+    h->jp_R.assign(lin_R, lin_R + 9 * nq);
+    h->jp_C.assign(lin_C, lin_C + 3 * nq);
+    if (mean) h->jp_mean.assign(mean, mean + 6 * nq);
+    else h->jp_mean.assign((size_t)(6 * nq), 0.0);
+    h->jp_info.assign(info, info + ni);
+    int64_t at = 0;
+    for (int32_t g = 0; g < n_sets; ++g) { // stored symmetrised
+        const int64_t n = 6 * (int64_t)(set_ptr[g + 1] - set_ptr[g]);
+        double* L = h->jp_info.data() + at;
+        for (int64_t r = 0; r < n; ++r)
+            for (int64_t c = r + 1; c < n; ++c) L[r * n + c] = L[c * n + r] = 0.5 * (L[r * n + c] + L[c * n + r]);
+        at += n * n;
+    }
+    h->jp_keep_gauge = keep_gauge;
+    h->jp_set = true;
+    return SRK_OK;
+}
+int srk_ba_joint_pose_prior_counts(srk_ba* h, int32_t* n_sets, int32_t* n_frames, int64_t* n_info)
+{
+    if (!h) return SRK_E_ARGS;
+    if (n_sets) *n_sets = h->jp_set ? (int32_t)h->jp_ptr.size() - 1 : 0;
+    if (n_frames) *n_frames = (int32_t)h->jp_frame.size();
+    if (n_info) *n_info = (int64_t)h->jp_info.size();
+    return h->jp_set ? 1 : 0;
+}
+int srk_ba_joint_pose_priors(srk_ba* h, int32_t* set_ptr, int32_t* frame, double* lin_R, double* lin_C, double* mean, double* info,
+                             int* keep_gauge)
+{
+    if (!h) return SRK_E_ARGS;
+    auto out = [](auto* dst, const auto& v) {
+        if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
+    };
+    out(set_ptr, h->jp_ptr); out(frame, h->jp_frame); out(lin_R, h->jp_R); out(lin_C, h->jp_C); out(mean, h->jp_mean); out(info, h->jp_info);
+    if (keep_gauge) *keep_gauge = h->jp_keep_gauge;
+    return h->jp_set ? 1 : 0;
+}
+int srk_ba_joint_pose_prior_error(srk_ba* h, double* e_out)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    if (e_out) *e_out = 0;
+    SrkJointPrior jp;
+    if (!joint_priors(h, jp)) return SRK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    HIPCHK(h, hipStreamSynchronize(s));
+    const int32_t nb = srk_jprior_partials(jp.n_sets);
+    DevBuf part;
+    int rc = dev_alloc(h, part, 8 * ((size_t)nb + 1));
+    if (rc != SRK_OK) return rc;
+    double out = 0;
+    srk_launch_jprior_error(s, P<double>(h->cam[h->cur]), jp, P<double>(part), P<double>(part) + nb);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&out, P<double>(part) + nb, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    dev_free(part);
+    HIPCHK(h, e);
+    if (e_out) *e_out = out;
+    return SRK_OK;
+}
+int srk_ba_joint_pose_prior_residuals(srk_ba* h, double* r_out)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    // the residuals belong to the setting the resident scene was uploaded with: a setter call since then has not reached it
+    if (h->app_jp != h->jp_set || h->app_jp_ptr != h->jp_ptr || h->app_jp_frame != h->jp_frame || h->app_jp_R != h->jp_R ||
+        h->app_jp_C != h->jp_C || h->app_jp_mean != h->jp_mean) {
+        h->last_error = "joint_pose_prior_residuals: the priors were changed after the upload; upload the scene again";
+        return SRK_E_STATE;
+    }
+    if (h->app_jp_frame.empty() || !r_out) return SRK_OK;
+    const SrkDims& d = h->d;
+    std::vector<double> p((size_t)(3 * d.N)), R((size_t)(9 * (int64_t)d.M)), T((size_t)(3 * (int64_t)d.M));
+    int rc = srk_ba_download_scene(h, p.data(), R.data(), T.data(), 1); // the caller's world coordinates
+    if (rc != SRK_OK) return rc;
+    for (size_t q = 0; q < h->app_jp_frame.size(); ++q) {
+        const double* r = &R[9 * (size_t)h->app_jp_frame[q]];
+        const double* t = &T[3 * (size_t)h->app_jp_frame[q]];
+        const double* Rb = &h->app_jp_R[9 * q];
+        double* e = r_out + 6 * q;
+        double M[9];
+        for (int c = 0; c < 3; ++c) e[c] = -(r[c] * t[0] + r[3 + c] * t[1] + r[6 + c] * t[2]) - h->app_jp_C[3 * q + (size_t)c];
+        for (int a = 0; a < 3; ++a) // M = R^T Rbar
+            for (int b = 0; b < 3; ++b) M[3 * a + b] = r[a] * Rb[b] + r[3 + a] * Rb[3 + b] + r[6 + a] * Rb[6 + b];
+        // Log as the kernels take it (k_jprior_error)
+        const double v[3] = { 0.5 * (M[7] - M[5]), 0.5 * (M[2] - M[6]), 0.5 * (M[3] - M[1]) };
+        const double s2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], sn = std::sqrt(s2), cs = 0.5 * (M[0] + M[4] + M[8] - 1.0);
+        const double f = (sn < 1e-4 && cs > 0) ? 1.0 + s2 / 6.0 + 3.0 * s2 * s2 / 40.0 : std::atan2(sn, cs) / sn;
+        for (int c = 0; c < 3; ++c) e[3 + c] = f * v[c];
+        for (int c = 0; c < 6; ++c) e[c] -= h->app_jp_mean[6 * q + (size_t)c];
+    }
+    return SRK_OK;
+}
+int srk_ba_joint_pose_prior_pass_ms(srk_ba* h, double* derivative_ms, double* couple_ms, double* error_ms)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
+    for (int sl = 1; sl < SRK_SLOTS; ++sl)
+        if (h->att[sl].stream) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
+    double* outs[3] = { derivative_ms, couple_ms, error_ms };
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0;
+        if (h->jp_timed[k] && hipEventElapsedTime(&ms, h->ev_jp[2 * k], h->ev_jp[2 * k + 1]) != hipSuccess) ms = 0;
+        if (outs[k]) *outs[k] = h->jp_timed[k] ? (double)ms : 0.0;
     }
     return SRK_OK;
 }

@@ -2976,10 +2976,78 @@ void srk_launch_relpose_error(hipStream_t s, const double* cam, const SrkRelPose
     hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, nb, partial, out, (int*)nullptr, (int*)nullptr);
 }
 
+// ------------------------------------------------------------------ joint Gaussian pose priors: residual, Jacobian, energy pass
+// (srk_ba_set_joint_pose_priors)
+static_assert(SRK_JP_MAX_FRAMES_HOST == 16, "the shared arrays of the joint-prior kernels hold 16 frames");
+#define SRK_JP_ROWS (6 * SRK_JP_MAX_FRAMES_HOST)
+// inverse left Jacobian of SO(3) at phi: I - [phi]x / 2 + k [phi]x^2, k as in rp_jrinv
+__device__ __forceinline__ void jp_jlinv(const double p[3], double J[9])
+{
+    const double t2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+    double k;
+    if (t2 < 1e-6) k = 1.0 / 12.0 + t2 / 720.0;
+    else {
+        const double t = sqrt(t2);
+        k = 1.0 / t2 - (1.0 + cos(t)) / (2.0 * t * sin(t));
+    }
+    J[0] = 1.0 + k * (p[0] * p[0] - t2); J[1] = 0.5 * p[2] + k * p[0] * p[1]; J[2] = -0.5 * p[1] + k * p[0] * p[2];
+    J[3] = -0.5 * p[2] + k * p[0] * p[1]; J[4] = 1.0 + k * (p[1] * p[1] - t2); J[5] = 0.5 * p[0] + k * p[1] * p[2];
+    J[6] = 0.5 * p[1] + k * p[0] * p[2]; J[7] = -0.5 * p[0] + k * p[1] * p[2]; J[8] = 1.0 + k * (p[2] * p[2] - t2);
+}
+// slot q: r = [C - Cbar; Log(R^T Rbar)] of its frame from the camera pack
+__device__ __forceinline__ void jp_residual(const double* __restrict__ cam, const SrkJointPrior& p, int32_t q, double r[6])
+{
+    const double* c = cam + (int64_t)SRK_CAM_PACK * p.frame[q];
+    const double* lin = p.lin + 12 * (int64_t)q;
+    double Cn[3], M[9];
+    prior_centre(c, Cn);
+    for (int e = 0; e < 3; ++e) r[e] = Cn[e] - lin[9 + e];
+    for (int a = 0; a < 3; ++a) // M = R^T Rbar
+        for (int b = 0; b < 3; ++b) M[3 * a + b] = c[a] * lin[b] + c[3 + a] * lin[3 + b] + c[6 + a] * lin[6 + b];
+    rp_log(M, r + 3);
+}
+// One workgroup per set.  Lane t < k forms r - m of slot t; lane t < 6 k then takes row t of L (r - m) in the order of the
+// columns (L is stored symmetric, so the lanes read along a row of the matrix) and the workgroup sums (r - m)_t (L (r - m))_t
+// in the fixed order of err_block_sum: one partial per set, no atomics, the same bits from run to run.
+__global__ __launch_bounds__(256) void k_jprior_error(const double* __restrict__ cam, SrkJointPrior p, double* __restrict__ partial)
+{
+    __shared__ double sr[SRK_JP_ROWS];
+    const int32_t g = blockIdx.x, q0 = p.set_ptr[g], k = min(p.set_ptr[g + 1] - q0, SRK_JP_MAX_FRAMES_HOST), n = 6 * k;
+    const int t = threadIdx.x;
+    if (t < k) {
+        double r[6];
+        jp_residual(cam, p, q0 + t, r);
+        for (int e = 0; e < 6; ++e) sr[6 * t + e] = r[e] - p.mean[6 * (int64_t)(q0 + t) + e];
+    }
+    __syncthreads();
+    double sum = 0;
+    if (t < n) {
+        const double* L = p.info + p.info_ptr[g];
+        double y = 0;
+        for (int c = 0; c < n; ++c) y += L[(int64_t)c * n + t] * sr[c];
+        sum = sr[t] * y;
+    }
+    err_block_sum(sum, partial + g);
+}
+static int32_t launch_jprior_partials(hipStream_t s, const double* cam, const SrkJointPrior& p, double* partial, const hipEvent_t* ev)
+{
+    const int32_t nb = srk_jprior_partials(p.n_sets);
+    if (ev) (void)hipEventRecord(ev[0], s);
+    hipLaunchKernelGGL(k_jprior_error, dim3((unsigned)nb), dim3(256), 0, s, cam, p, partial);
+    if (ev) (void)hipEventRecord(ev[1], s);
+    return nb;
+}
+void srk_launch_jprior_error(hipStream_t s, const double* cam, const SrkJointPrior& p, double* partial, double* out)
+{
+    const int32_t nb = launch_jprior_partials(s, cam, p, partial, nullptr);
+    hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, nb, partial, out, (int*)nullptr, (int*)nullptr);
+}
+
 void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const double* cam,
                       const int32_t* obs_frame, const int32_t* obs_pt, const double* obs_uv, double* partial,
                       int32_t n_partial, double* err_out, const int32_t* wg_jmin, int* info, int* info2, const SrkLoss* loss,
-                      const SrkPrior* prior, const hipEvent_t* prior_ev, const SrkRelPose* relpose, const hipEvent_t* relpose_ev)
+                      const SrkPrior* prior, const hipEvent_t* prior_ev, const SrkRelPose* relpose, const hipEvent_t* relpose_ev,
+                      const SrkJointPrior* jprior, const hipEvent_t* jprior_ev)
 {
     const bool robust = srk_robust_side(loss);
     const bool staged = wg_jmin && d.O > 0; // staged cameras: one partial sum per run of SRK_JF_OBS observations
@@ -2999,6 +3067,8 @@ void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const 
     if (prior) nb += launch_prior_partials(s, pts, cam, *prior, partial + nb, prior_ev);
     // relative-pose factors: their partials behind the priors' 
     if (relpose) nb += launch_relpose_partials(s, cam, *relpose, partial + nb, relpose_ev);
+    // joint pose priors: their partials behind the factors' 
+    if (jprior) nb += launch_jprior_partials(s, cam, *jprior, partial + nb, jprior_ev);
     hipLaunchKernelGGL(k_error_final, dim3(1), dim3(256), 0, s, nb, partial, err_out, info, info2);
 }
 
@@ -3561,4 +3631,115 @@ void srk_launch_relpose_couple(hipStream_t s, const SrkDims& d, const SrkRelPose
 {
     if (rp.n <= 0) return;
     hipLaunchKernelGGL(k_relpose_couple, dim3((unsigned)rp.n), dim3(64), 0, s, d, rp, S);
+}
+
+// ------------------------------------------------------------------ joint Gaussian pose priors: the derivative-side passes and the coupling pass
+// (srk_ba_set_joint_pose_priors).  The Jacobian of slot i over its frame's pose variables [Tx Ty Tz Wx Wy Wz]
+// is J_i = diag(I, A_i), A_i = Jl^-1(r_r,i): the translation correction is added to the centre, the rotation correction
+// multiplies the direct rotation R^T from the left (k_cam_apply).
+// entry (a, b) of J_i^T B J_j for the 6 x 6 block B = L[ro .. ro + 6][co .. co + 6] of the n x n matrix L, in a fixed order
+__device__ __forceinline__ double jp_jtbj(const double* __restrict__ L, int n, int ro, int co, const double* Ai, const double* Aj, int a, int b)
+{
+    const int x0 = a < 3 ? a : 3, x1 = a < 3 ? a + 1 : 6, y0 = b < 3 ? b : 3, y1 = b < 3 ? b + 1 : 6;
+    double sum = 0;
+    for (int x = x0; x < x1; ++x) {
+        double z = 0;
+        for (int y = y0; y < y1; ++y) z += L[(int64_t)(ro + x) * n + co + y] * (b < 3 ? 1.0 : Aj[3 * (y - 3) + (b - 3)]);
+        sum += (a < 3 ? 1.0 : Ai[3 * (x - 3) + (a - 3)]) * z;
+    }
+    return sum;
+}
+// k_jprior_form: one workgroup per set, behind k_relpose_add.  Lane t < k forms r - m and A of slot t; lane t < 6 k then row t of
+// v = L (r - m) in the order of the columns; then the workgroup strides over the set's outputs: the 36 entries of
+// 2 J_i^T L_ii J_i and the 6 of 2 J_i^T v_i for every slot (blk), and the 36 entries of 2 J_i^T L_ij J_j for every coupled pair
+// (cpl), rows belonging to the frame with the larger internal index.  The damping does not enter: formed once per derivative
+// pass, read by both attempt slots.  Every output has one owner.
+__global__ __launch_bounds__(256) void k_jprior_form(const double* __restrict__ cam, SrkJointPrior p)
+{
+    __shared__ double sr[SRK_JP_ROWS], sv[SRK_JP_ROWS], sA[SRK_JP_MAX_FRAMES_HOST][9];
+    const int32_t g = blockIdx.x, q0 = p.set_ptr[g], k = min(p.set_ptr[g + 1] - q0, SRK_JP_MAX_FRAMES_HOST), n = 6 * k;
+    const int t = threadIdx.x;
+    const double* L = p.info + p.info_ptr[g];
+    if (t < k) {
+        double r[6];
+        jp_residual(cam, p, q0 + t, r);
+        jp_jlinv(r + 3, sA[t]);
+        for (int e = 0; e < 6; ++e) sr[6 * t + e] = r[e] - p.mean[6 * (int64_t)(q0 + t) + e];
+    }
+    __syncthreads();
+    if (t < n) {
+        double y = 0;
+        for (int c = 0; c < n; ++c) y += L[(int64_t)c * n + t] * sr[c];
+        sv[t] = y;
+    }
+    __syncthreads();
+    const int32_t p0 = p.pair_ptr[g], np = p.pair_ptr[g + 1] - p0;
+    for (int e = t; e < 42 * k + 36 * np; e += 256) {
+        if (e < 42 * k) {
+            const int i = e / 42, w = e - 42 * i;
+            double y;
+            if (w < 36) y = jp_jtbj(L, n, 6 * i, 6 * i, sA[i], sA[i], w / 6, w % 6);
+            else {
+                const int a = w - 36;
+                if (a < 3) y = sv[6 * i + a];
+                else y = sA[i][a - 3] * sv[6 * i + 3] + sA[i][3 + a - 3] * sv[6 * i + 4] + sA[i][6 + a - 3] * sv[6 * i + 5];
+            }
+            p.blk[42 * (int64_t)(q0 + i) + w] = 2.0 * y;
+        } else {
+            const int pr = (e - 42 * k) / 36, w = (e - 42 * k) - 36 * pr, a = w / 6, b = w - 6 * a;
+            const int32_t ij = p.pair_slot[p0 + pr], i = ij >> 8, j = ij & 255;
+            if (i >= k || j >= k) continue;
+            const double y = 2.0 * jp_jtbj(L, n, 6 * i, 6 * j, sA[i], sA[j], a, b);
+            p.cpl[36 * (int64_t)(p0 + pr) + (p.frame[q0 + i] > p.frame[q0 + j] ? 6 * a + b : 6 * b + a)] = y;
+        }
+    }
+}
+// k_jprior_add: behind k_jprior_form and before k_const_points.  Lane t: the t-th frame with incident sets adds the blocks and
+// gradient terms of its slots, in set order, to the upper triangle of the pose part of its block in Ug (variables 4..9 of ten,
+// 0..5 of six) and to those gradient entries.  One owner per entry, a fixed order of additions: no atomics.
+__global__ __launch_bounds__(64) void k_jprior_add(SrkDims d, SrkJointPrior p, double* __restrict__ Ug)
+{
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= p.n_frames) return;
+    const int64_t j = p.fr_list[t];
+    if (j < 0 || j >= d.M) return;
+    const int fv = d.fv, ut = fv * (fv + 1) / 2, t0 = 4 - SRK_FV_OFF(fv); // first pose variable of the frame
+    double* u = Ug + (int64_t)SRK_UGS(fv) * j;
+    for (int32_t q = p.fr_ptr[t]; q < p.fr_ptr[t + 1]; ++q) {
+        const double* blk = p.blk + 42 * (int64_t)p.fr_ent[q];
+        for (int a = 0; a < 6; ++a) {
+            const int va = t0 + a, row = va * fv - va * (va - 1) / 2; // row va of the upper triangle starts at its diagonal entry
+            for (int b = a; b < 6; ++b) u[row + (b - a)] += blk[6 * a + b];
+            u[ut + va] += blk[36 + a];
+        }
+    }
+}
+void srk_launch_jprior_add(hipStream_t s, const SrkDims& d, const double* cam, const SrkJointPrior& jp, double* Ug)
+{
+    if (jp.n_sets <= 0) return;
+    hipLaunchKernelGGL(k_jprior_form, dim3((unsigned)jp.n_sets), dim3(256), 0, s, cam, jp);
+    hipLaunchKernelGGL(k_jprior_add, dim3((unsigned)((jp.n_frames + 63) / 64)), dim3(64), 0, s, d, jp, Ug);
+}
+
+// k_jprior_couple: behind k_relpose_couple and before k_const_frames.  One wave per coupled pair; lane e < 36 adds entry
+// (e / 6, e % 6) of the pair's block to S at the pair's target, inside the lower triangle and the skyline (the planner put the
+// pair into min_cv).  A gauge-fixed variable keeps its identity row and column.  The damping does not enter.  One owner per
+// entry among the sets; a relative-pose factor on the same pair has added its block in the launch before.
+__global__ __launch_bounds__(64) void k_jprior_couple(SrkDims d, SrkJointPrior p, double* __restrict__ S)
+{
+    const int64_t k = blockIdx.x;
+    const int e = threadIdx.x;
+    if (k >= p.n_pairs || e >= 36) return;
+    const int r = e / 6, c = e - 6 * r;
+    const int64_t at = p.tgt[k], row = at / d.ld + r, col = at % d.ld + c;
+    if (row >= d.ld || col >= row) return;
+    const bool fixed = d.fv == 6 ? (srk_is_fixed_var_fv<6>(row, d) || srk_is_fixed_var_fv<6>(col, d))
+                                 : (srk_is_fixed_var_fv<10>(row, d) || srk_is_fixed_var_fv<10>(col, d));
+    if (fixed) return;
+    S[row * d.ld + col] += p.cpl[36 * k + e];
+}
+void srk_launch_jprior_couple(hipStream_t s, const SrkDims& d, const SrkJointPrior& jp, double* S)
+{
+    if (jp.n_pairs <= 0) return;
+    hipLaunchKernelGGL(k_jprior_couple, dim3((unsigned)jp.n_pairs), dim3(64), 0, s, d, jp, S);
 }

@@ -202,6 +202,40 @@ void srk_launch_relpose_add(hipStream_t s, const SrkDims& d, const double* cam, 
 void srk_launch_relpose_couple(hipStream_t s, const SrkDims& d, const SrkRelPose& rp, double* S);
 // the factor sum of a scene on its own (srk_ba_relative_pose_error): partial [srk_relpose_partials], out = the sum
 void srk_launch_relpose_error(hipStream_t s, const double* cam, const SrkRelPose& rp, double* partial, double* out);
+// joint Gaussian pose priors over sets of frames (srk_ba_set_joint_pose_priors): the lists of the resident
+// scene.  Set g owns the slots set_ptr[g] .. set_ptr[g + 1] (at most SRK_JP_MAX_FRAMES_HOST); slot q is the internal frame
+// frame[q] with the linearisation pose lin[12 q] (Rbar row-major, then Cbar, normalised world) and the mean mean[6 q]; the
+// set's information matrix is the dense symmetric row-major (6 k)^2 block at info[info_ptr[g]].  Its coupled pairs (slots
+// i > j whose block L_ij is not all zeros) are pair_ptr[g] .. pair_ptr[g + 1].  Two sets share at most one frame, so every
+// entry of S the passes touch has one owner.
+struct SrkJointPrior {
+    int32_t n_sets;
+    const int32_t* set_ptr;   // [n_sets + 1]
+    const int32_t* frame;     // [n_slots] internal frame of each slot
+    const double* lin;        // [n_slots][12]
+    const double* mean;       // [n_slots][6]
+    const int64_t* info_ptr;  // [n_sets]
+    const double* info;
+    const int32_t* pair_ptr;  // [n_sets + 1]
+    const int32_t* pair_slot; // [n_pairs] (slot i of the set << 8) | slot j, i > j
+    const int64_t* tgt;       // [n_pairs] offset in S of entry (0, 0) of the pair's block: row = first pose variable of the frame
+                              // with the larger internal index, column = that of the other
+    int32_t n_pairs;
+    double* blk;              // [n_slots][42] 2 J_i^T L_ii J_i (6 x 6 row-major) and 2 J_i^T (L (r - m))_i, written by k_jprior_form
+    double* cpl;              // [n_pairs][36] 2 J_i^T L_ij J_j, rows belonging to the frame with the larger internal index
+    const int32_t* fr_list;   // [n_frames] internal frames with incident sets, ascending
+    const int32_t* fr_ptr;    // [n_frames + 1] CSR into fr_ent
+    const int32_t* fr_ent;    // slots of the frame, in set order
+    int32_t n_frames;
+};
+// partial sums the joint-prior energy pass writes: one per set
+inline int32_t srk_jprior_partials(int64_t n_sets) { return (int32_t)n_sets; }
+// behind srk_launch_relpose_add, before srk_launch_const_points: blk and cpl from the current poses, then blk into Ug
+void srk_launch_jprior_add(hipStream_t s, const SrkDims& d, const double* cam, const SrkJointPrior& jp, double* Ug);
+// behind srk_launch_relpose_couple, before srk_launch_const_frames: jp.cpl into the lower triangle of S, fixed variables skipped
+void srk_launch_jprior_couple(hipStream_t s, const SrkDims& d, const SrkJointPrior& jp, double* S);
+// the prior sum of a scene on its own (srk_ba_joint_pose_prior_error): partial [srk_jprior_partials], out = the sum
+void srk_launch_jprior_error(hipStream_t s, const double* cam, const SrkJointPrior& jp, double* partial, double* out);
 void srk_launch_backsub(hipStream_t s, const SrkDims& d, double c, const int32_t* obs_frame, const int32_t* obs_pt,
                         const double* W, const double* Vg, const double* dc, double* acc, const double* pts,
                         double* pts_trial, double* dx);
@@ -219,7 +253,10 @@ void srk_launch_error(hipStream_t s, const SrkDims& d, const double* pts, const 
                       const hipEvent_t* prior_ev = nullptr /* given: two events recorded around the prior pass */,
                       const SrkRelPose* relpose = nullptr /* given: the factor sum as srk_relpose_partials more partials behind
                                                              the priors' */,
-                      const hipEvent_t* relpose_ev = nullptr /* given: two events recorded around that pass */);
+                      const hipEvent_t* relpose_ev = nullptr /* given: two events recorded around that pass */,
+                      const SrkJointPrior* jprior = nullptr /* given: the joint pose priors' sum as srk_jprior_partials more
+                                                               partials behind the factors' */,
+                      const hipEvent_t* jprior_ev = nullptr /* given: two events recorded around that pass */);
 // the IRLS weights w = rho'(s) of the resident scene, one per observation in the internal order (srk_ba_observation_weights)
 void srk_launch_obs_weights(hipStream_t s, const SrkDims& d, const double* pts, const double* cam, const int32_t* obs_frame,
                             const int32_t* obs_pt, const double* obs_uv, const SrkLoss& loss, double* w);

@@ -23,3 +23,5 @@
 #define SRK_LONG_PTS_HOST 128
 #define SRK_LONG_MAXNF_HOST 4096
 #define SRK_LONG_FB_HOST 8
+// joint Gaussian pose priors (srk_ba_set_joint_pose_priors): frames of one set; its information matrix has 6 x that many rows
+#define SRK_JP_MAX_FRAMES_HOST 16
