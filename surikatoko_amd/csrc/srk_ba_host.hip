@@ -10,6 +10,7 @@
 #include "srk_cov.hpp"
 #include "srk_geom.hpp"
 #include "srk_plan.hpp"
+#include "srk_factors.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -36,6 +37,55 @@ struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
 };
+
+// one event pair around the last launch of a pass (profile level >= 1), created on first use
+struct TimedPass { hipEvent_t ev[2]{}; bool timed = false; };
+// The factor settings, one struct per family (srk_factors.hpp has the host half): what the setter stored, the snapshot of the last
+// upload, the host tables kept from it, the device tables (srk_dev.hpp: SrkLoss, SrkPrior, SrkRelPose, SrkJointPrior) and the
+// timed passes.  All counts 0 = none of the family's passes is launched.
+struct InfoFamily {
+    SrkInfoSetting set;
+    bool on = false; // the resident scene runs with it
+    enum { Q, QF, NBUF };
+    DevBuf buf[NBUF];
+};
+struct ConstFamily { // section 13
+    SrkConstSetting set;
+    std::vector<uint8_t> frame_int; // the frames' flags by internal index (SRK_BUF_GRAD, the covariances)
+    enum { PTS, FRAMES, NBUF };
+    DevBuf buf[NBUF];
+    int64_t n_pts = 0;
+    int32_t n_frames = 0;
+    TimedPass pass[2]; // k_const_points, k_const_frames
+};
+struct PriorFamily { // section 14
+    SrkPriorSetting set;
+    SrkPriorApplied app;
+    enum { PT_LIST, PT_VAL, FR_LIST, FR_VAL, NBUF };
+    DevBuf buf[NBUF];
+    int64_t n_pts = 0;
+    int32_t n_frames = 0;
+    TimedPass pass[2]; // k_prior_add, k_prior_error
+};
+struct RelPoseFamily { // section 15
+    SrkRelPoseSetting set;
+    SrkRelPoseApplied app;
+    std::vector<int32_t> int_a, int_b; // the internal frames of the active factors (srk_ba_set_covisibility)
+    enum { FA, FB, VAL, FR_LIST, FR_PTR, FR_ENT, TGT, CPL, NBUF };
+    DevBuf buf[NBUF];
+    int32_t n = 0, n_frames = 0;
+    TimedPass pass[3]; // k_relpose_add, k_relpose_couple, k_relpose_error
+};
+struct JPriorFamily { // section 18
+    SrkJPriorSetting set;
+    SrkJPriorApplied app;
+    std::vector<int32_t> pair_a, pair_b; // the coupled pairs (lo, hi) in the internal numbering (srk_ba_set_covisibility)
+    enum { PTR, FRAME, LIN, MEAN, IPTR, INFO, PPTR, PSLOT, TGT, FR_LIST, FR_PTR, FR_ENT, BLK, CPL, NBUF };
+    DevBuf buf[NBUF];
+    int32_t n = 0, n_pairs = 0, n_frames = 0;
+    TimedPass pass[3]; // k_jprior_form + k_jprior_add, k_jprior_couple, k_jprior_error
+};
+static_assert(SRK_RP_PLANES_HOST == SRK_RP_PLANES, "srk_factors.hpp and srk_dev.hpp disagree about the planes of a relative-pose factor");
 
 } // namespace
 
@@ -164,76 +214,13 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     std::vector<int64_t> shk_row_end, shk_col_begin; // skyline of the compact pose system (host, for the solve)
     int loss_kind = SRK_LOSS_NONE; // opt-in: robust loss (srk_ba_set_robust_loss); takes effect at the next optimise / phase call
     double loss_delta_pix = 0;     // its scale in pixels; the kernels get delta / f0 (robust_loss below)
-    // opt-in: per-observation information (srk_ba_set_observation_information).  info_user: the values in
-    // the caller's observation order, empty = none; kept across uploads and srk_ba_reset_scene.  info_on: the resident scene
-    // runs with them -- info_q holds them in the internal order, info_qf in the frame-major order of fobs_* (two-kernel
-    // derivative path only: fobs_of[internal observation] = its place there)
-    std::vector<double> info_user;
-    bool info_on = false;
-    DevBuf info_q, info_qf;
-    // opt-in: constant parameter blocks (srk_ba_set_constant_blocks).  cst_frame_user / cst_point_user: the
-    // flags in the caller's numbering (either may be empty = none of that kind), kept across uploads and srk_ba_reset_scene.
-    // The uploaded scene: the constant landmarks in the internal order and the constant internal frames (ascending) on the
-    // device, the frames' flags by internal index on the host (SRK_BUF_GRAD).  Both counts 0 = no masking pass is launched.
-    bool cst_set = false;
-    int cst_keep_gauge = 1;
-    std::vector<uint8_t> cst_frame_user, cst_point_user;
-    DevBuf cst_pts, cst_frames;
-    int64_t n_cst_pts = 0;
-    int32_t n_cst_frames = 0;
-    std::vector<uint8_t> cst_frame_int;
-    hipEvent_t ev_cst[4]{}; // profile level >= 1: around the last k_const_points / k_const_frames launch (created on first use)
-    bool cst_timed[2] = { false, false };
-    // opt-in: Gaussian position priors (srk_ba_set_position_priors).  pri_*_idx / _pos / _info: the setting
-    // in the caller's numbering and world coordinates, kept across uploads and srk_ba_reset_scene.  The uploaded scene: the
-    // lists in the internal order with the values mapped to the normalised world (SrkPrior), on the device.  Both counts 0 =
-    // neither prior pass is launched.
-    bool pri_set = false;
-    int pri_keep_gauge = 1;
-    std::vector<int64_t> pri_pt_idx;
-    std::vector<int32_t> pri_fr_idx;
-    std::vector<double> pri_pt_pos, pri_pt_info, pri_fr_pos, pri_fr_info;
-    DevBuf pri_pt_list, pri_pt_val, pri_fr_list, pri_fr_val;
-    // what the resident scene was uploaded with (indices and positions): srk_ba_prior_residuals answers for that setting only
-    std::vector<int64_t> app_pt_idx;
-    std::vector<int32_t> app_fr_idx;
-    std::vector<double> app_pt_pos, app_fr_pos;
-    int64_t n_pri_pts = 0;
-    int32_t n_pri_frames = 0;
-    hipEvent_t ev_pri[4]{}; // profile level >= 1: around the last k_prior_add / k_prior_error launch (created on first use)
-    bool pri_timed[2] = { false, false };
-    // opt-in: relative-pose factors between frames (srk_ba_set_relative_pose_factors).  rp_a / rp_b / rp_R /
-    // rp_t / rp_info: the setting in the caller's numbering and world coordinates, kept across uploads and srk_ba_reset_scene.
-    // The uploaded scene: rp_act = the factors of the setting that are switched on (the planner has their pairs), and the
-    // device lists in the internal numbering with the values mapped to the normalised world (SrkRelPose).
-    bool rp_set = false;
-    std::vector<int32_t> rp_a, rp_b;
-    std::vector<double> rp_R, rp_t, rp_info;
-    std::vector<int32_t> rp_act, rp_int_a, rp_int_b; // active factors: place in the setting, internal frames
-    std::vector<int32_t> app_rp_a, app_rp_b;         // what the resident scene was uploaded with (srk_ba_relative_pose_residuals)
-    std::vector<double> app_rp_R, app_rp_t;
-    bool app_rp = false;
-    DevBuf rp_fa, rp_fb, rp_val, rp_fr_list, rp_fr_ptr, rp_fr_ent, rp_tgt, rp_cpl;
-    int32_t n_rp = 0, n_rp_frames = 0;
-    hipEvent_t ev_rp[6]{}; // profile level >= 1: around the last k_relpose_add / k_relpose_couple / k_relpose_error launch
-    bool rp_timed[3] = { false, false, false };
-    // opt-in: joint Gaussian pose priors over sets of frames (srk_ba_set_joint_pose_priors).  jp_*: the
-    // setting in the caller's numbering and world coordinates (jp_info symmetrised, jp_mean zeros where none was given), kept
-    // across uploads and srk_ba_reset_scene.  The uploaded scene: jp_act = the sets that are switched on, jp_pair_a / jp_pair_b
-    // their coupled pairs in the internal numbering, and the device lists (SrkJointPrior).
-    bool jp_set = false;
-    int jp_keep_gauge = 1;
-    std::vector<int32_t> jp_ptr, jp_frame;
-    std::vector<double> jp_R, jp_C, jp_mean, jp_info;
-    std::vector<int32_t> jp_act, jp_pair_a, jp_pair_b;
-    std::vector<int32_t> app_jp_ptr, app_jp_frame; // what the resident scene was uploaded with (srk_ba_joint_pose_prior_residuals)
-    std::vector<double> app_jp_R, app_jp_C, app_jp_mean;
-    bool app_jp = false;
-    DevBuf jp_d_ptr, jp_d_frame, jp_d_lin, jp_d_mean, jp_d_iptr, jp_d_info, jp_d_pptr, jp_d_pslot, jp_d_tgt, jp_d_blk, jp_d_cpl, jp_d_fr_list,
-        jp_d_fr_ptr, jp_d_fr_ent;
-    int32_t n_jp = 0, n_jp_pairs = 0, n_jp_frames = 0;
-    hipEvent_t ev_jp[6]{}; // profile level >= 1: around the last k_jprior_form + k_jprior_add / k_jprior_couple / k_jprior_error launch
-    bool jp_timed[3] = { false, false, false };
+    // opt-in: the factor settings, each kept across uploads and srk_ba_reset_scene and applied by the next upload
+    InfoFamily obs_info;
+    ConstFamily cst;
+    PriorFamily pri;
+    RelPoseFamily rp;
+    JPriorFamily jp;
+    SrkFactorSelection sel; // what the last upload switched on of them (the planner has seen sel.rel_a / rel_b)
     int profile_level = 0; // 0 = no events, 1 = phase events (report.ms_*), 2 = + event pairs around the MFMA updates
     bool chol_fused = true; // the solve's outer steps as one launch each (k_step256); srk_ba_set_solver_fusion
     // what the caller asked for.  A hand-off timeout switches chol_fused off for the rest of that call; the next upload /
@@ -335,6 +322,13 @@ static void dev_free(DevBuf& b)
     b.p = nullptr;
     b.bytes = 0;
 }
+static void release(DevBuf* b, int nb, TimedPass* p, int np) // the device tables and event pairs of a family of factor settings
+{
+    for (int i = 0; i < nb; ++i) dev_free(b[i]);
+    for (int k = 0; k < np; ++k)
+        for (hipEvent_t& e : p[k].ev)
+            if (e) hipEventDestroy(e);
+}
 template <typename T> static T* P(const DevBuf& b) { return reinterpret_cast<T*>(b.p); }
 
 extern "C" {
@@ -420,10 +414,6 @@ void srk_ba_destroy(srk_ba* h)
                       &h->jd_nf, &h->jd_frames, &h->jd_mask,
                       &h->jr_first, &h->jr_count, &h->jr_jmin, &h->jr_group, &h->lg_item, &h->lg_np, &h->lg_nf, &h->lg_pts, &h->lg_frames,
                       &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk,
-                      &h->info_q, &h->info_qf, &h->cst_pts, &h->cst_frames, &h->pri_pt_list, &h->pri_pt_val, &h->pri_fr_list, &h->pri_fr_val,
-                      &h->rp_fa, &h->rp_fb, &h->rp_val, &h->rp_fr_list, &h->rp_fr_ptr, &h->rp_fr_ent, &h->rp_tgt, &h->rp_cpl,
-                      &h->jp_d_ptr, &h->jp_d_frame, &h->jp_d_lin, &h->jp_d_mean, &h->jp_d_iptr, &h->jp_d_info, &h->jp_d_pptr, &h->jp_d_pslot,
-                      &h->jp_d_tgt, &h->jp_d_blk, &h->jp_d_cpl, &h->jp_d_fr_list, &h->jp_d_fr_ptr, &h->jp_d_fr_ent,
                       &h->cov_Y, &h->cov_grp, &h->cov_blk, &h->cov_out, &h->cov_free, &h->cov_colb, &h->cov_pairs };
     for (DevBuf* b : all) dev_free(*b);
     for (auto& a : h->att) {
@@ -441,14 +431,11 @@ void srk_ba_destroy(srk_ba* h)
         if (e) hipEventDestroy(e);
     for (auto& e : h->chol_ev) hipEventDestroy(e);
     if (h->ev_jac) hipEventDestroy(h->ev_jac);
-    for (auto& e : h->ev_cst)
-        if (e) hipEventDestroy(e);
-    for (auto& e : h->ev_pri)
-        if (e) hipEventDestroy(e);
-    for (auto& e : h->ev_rp)
-        if (e) hipEventDestroy(e);
-    for (auto& e : h->ev_jp)
-        if (e) hipEventDestroy(e);
+    release(h->obs_info.buf, InfoFamily::NBUF, nullptr, 0);
+    release(h->cst.buf, ConstFamily::NBUF, h->cst.pass, 2);
+    release(h->pri.buf, PriorFamily::NBUF, h->pri.pass, 2);
+    release(h->rp.buf, RelPoseFamily::NBUF, h->rp.pass, 3);
+    release(h->jp.buf, JPriorFamily::NBUF, h->jp.pass, 3);
     if (h->ev_comm) hipEventDestroy(h->ev_comm);
     if (h->comm_stream) hipStreamDestroy(h->comm_stream);
     for (int sl = 1; sl < SRK_SLOTS; ++sl)
@@ -512,52 +499,17 @@ static const char* groups_conflict(bool groups, bool fixed_k, bool store_f32, bo
     if (world > 1) return "intrinsic groups: not available with more than one rank";
     return nullptr;
 }
-// constant parameter blocks (srk_ba_set_constant_blocks) mask the 10- or 6-variable system of one rank: the fold of shared
-// intrinsics would drop a constant frame's observations from its group's K, and the mask would have to follow the exchange
-static const char* constant_conflict(bool constant, bool groups, int world)
-{
-    if (!constant) return nullptr;
-    if (groups) return "constant blocks: not available with intrinsic groups";
-    if (world > 1) return "constant blocks: not available with more than one rank";
-    return nullptr;
-}
-// position priors (srk_ba_set_position_priors) add to the 10- or 6-variable blocks of one rank: the fold of shared intrinsics and
-// the exchange of the ranks' partial frame sums (a frame prior would have to come from rank 0 alone) can follow later
-static const char* prior_conflict(bool priors, bool groups, int world)
-{
-    if (!priors) return nullptr;
-    if (groups) return "position priors: not available with intrinsic groups";
-    if (world > 1) return "position priors: not available with more than one rank";
-    return nullptr;
-}
-// relative-pose factors (srk_ba_set_relative_pose_factors) add to the pose part of the 10- or 6-variable blocks and couple two
-// frames of one rank's system: the fold of shared intrinsics and the exchange of the ranks' partial sums can follow later
-static const char* relpose_conflict(bool factors, bool groups, int world)
-{
-    if (!factors) return nullptr;
-    if (groups) return "relative-pose factors: not available with intrinsic groups";
-    if (world > 1) return "relative-pose factors: not available with more than one rank";
-    return nullptr;
-}
-// joint pose priors (srk_ba_set_joint_pose_priors) add to the pose part of the blocks and couple frames of one rank's system, as
-// the relative-pose factors do
-static const char* jprior_conflict(bool sets, bool groups, int world)
-{
-    if (!sets) return nullptr;
-    if (groups) return "joint pose priors: not available with intrinsic groups";
-    if (world > 1) return "joint pose priors: not available with more than one rank";
-    return nullptr;
-}
 static bool refuse_modes(srk_ba* h, bool fixed_k, bool deterministic, bool store_f32, bool schur_fp32, int world, bool groups)
 {
-    const char* e = fixed_k_conflict(fixed_k, deterministic, store_f32, schur_fp32, world);
-    if (!e) e = groups_conflict(groups, fixed_k, store_f32, schur_fp32, world);
-    if (!e) e = constant_conflict(h->cst_set, groups, world);
-    if (!e) e = prior_conflict(h->pri_set, groups, world);
-    if (!e) e = relpose_conflict(h->rp_set, groups, world);
-    if (!e) e = jprior_conflict(h->jp_set, groups, world);
-    if (e) h->last_error = e;
-    return e != nullptr;
+    const char* c = fixed_k_conflict(fixed_k, deterministic, store_f32, schur_fp32, world);
+    if (!c) c = groups_conflict(groups, fixed_k, store_f32, schur_fp32, world);
+    std::string e = c ? c : "";
+    if (e.empty()) e = srk_setting_conflict("constant blocks", h->cst.set.set, groups, world);
+    if (e.empty()) e = srk_setting_conflict("position priors", h->pri.set.set, groups, world);
+    if (e.empty()) e = srk_setting_conflict("relative-pose factors", h->rp.set.set, groups, world);
+    if (e.empty()) e = srk_setting_conflict("joint pose priors", h->jp.set.set, groups, world);
+    if (!e.empty()) h->last_error = e;
+    return !e.empty();
 }
 
 int srk_ba_set_allreduce(srk_ba* h, srk_allreduce_fn fn, void* ctx, int rank, int world_size)
@@ -718,103 +670,6 @@ void srk_ba_revert_normalization(int64_t N, double* pts, int32_t M, double* cam_
         for (int i = 0; i < 3; ++i) T[i] = T[i] / s + u[i];
         std::memcpy(R, RR, sizeof RR);
     }
-}
-
-// position priors through a normaliser (host only): pos_n = s (R0 pos + T0), L_n = R0 L R0^T / s^2, so that
-// (x_n - pos_n)^T L_n (x_n - pos_n) = (x - pos)^T L (x - pos) for x_n = s (R0 x + T0)
-int srk_ba_normalize_position_priors(const srk_ba_normalizer* nrm, int64_t n, const double* pos, const double* info,
-                                     double* pos_out, double* info_out)
-{
-    if (!nrm || n < 0 || (pos != nullptr) != (pos_out != nullptr) || (info != nullptr) != (info_out != nullptr)) return SRK_E_ARGS;
-    const double s = nrm->world_scale, is2 = 1.0 / (s * s);
-    const double* R = nrm->R0;
-    for (int64_t i = 0; pos && i < n; ++i) {
-        double y[3];
-        srk::se3_apply(nrm->R0, nrm->T0, pos + 3 * i, y);
-        for (int e = 0; e < 3; ++e) pos_out[3 * i + e] = y[e] * s;
-    }
-    for (int64_t i = 0; info && i < n; ++i) {
-        const double* l = info + 6 * i;
-        const double L[9] = { l[0], l[1], l[2], l[1], l[3], l[4], l[2], l[4], l[5] };
-        double RL[9], o[9];
-        srk::mat3_mul(R, L, RL);
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) o[3 * a + b] = (RL[3 * a] * R[3 * b] + RL[3 * a + 1] * R[3 * b + 1] + RL[3 * a + 2] * R[3 * b + 2]) * is2;
-        double* q = info_out + 6 * i; // the symmetric part: both triangles carry the same sum up to rounding
-        q[0] = o[0]; q[1] = 0.5 * (o[1] + o[3]); q[2] = 0.5 * (o[2] + o[6]);
-        q[3] = o[4]; q[4] = 0.5 * (o[5] + o[7]); q[5] = o[8];
-    }
-    return SRK_OK;
-}
-
-// relative-pose factors through a normaliser (host only).  A relative pose is invariant under R0 and T0 and scales with s:
-// z_n = s z, L_tt / s^2, L_tr / s, L_rr as it is, so that [e_t; e_r]^T L [e_t; e_r] is the same number in both worlds
-int srk_ba_normalize_relative_pose_factors(const srk_ba_normalizer* nrm, int32_t n, const double* rel_t, const double* info,
-                                           double* rel_t_out, double* info_out)
-{
-    if (!nrm || n < 0 || (rel_t != nullptr) != (rel_t_out != nullptr) || (info != nullptr) != (info_out != nullptr)) return SRK_E_ARGS;
-    const double s = nrm->world_scale, is = 1.0 / s;
-    for (int64_t i = 0; rel_t && i < 3 * (int64_t)n; ++i) rel_t_out[i] = s * rel_t[i];
-    for (int64_t i = 0; info && i < n; ++i) {
-        int k = 0;
-        for (int r = 0; r < 6; ++r)
-            for (int c = r; c < 6; ++c, ++k) info_out[21 * i + k] = info[21 * i + k] * (r < 3 ? is : 1.0) * (c < 3 ? is : 1.0);
-    }
-    return SRK_OK;
-}
-
-// joint pose priors through a normaliser (host only).  With X_n = s (R0 X + T0): Cbar_n = s (R0 Cbar + T0), Rbar_n = Rbar R0^T,
-// and the residual of a frame maps as r_n = D r, D = diag(s R0, R0), so m_n = D m and L_n = D^-T L D^-1 keep the energy: block
-// (i, j) of L_n is G L_ij G^T with G = diag(R0 / s, R0).  The inverse of the map srk_ba_revert_covariances applies.
-int srk_ba_normalize_joint_pose_priors(const srk_ba_normalizer* nrm, int32_t n_sets, const int32_t* set_ptr, const double* lin_R,
-                                       const double* lin_C, const double* mean, const double* info, double* lin_R_out,
-                                       double* lin_C_out, double* mean_out, double* info_out)
-{
-    if (!nrm || n_sets < 0 || (n_sets > 0 && !set_ptr) || (lin_R != nullptr) != (lin_R_out != nullptr) ||
-        (lin_C != nullptr) != (lin_C_out != nullptr) || (mean != nullptr) != (mean_out != nullptr) || (info != nullptr) != (info_out != nullptr))
-        return SRK_E_ARGS;
-    for (int32_t g = 0; g < n_sets; ++g)
-        if (set_ptr[g + 1] < set_ptr[g] || set_ptr[0] != 0) return SRK_E_ARGS;
-    const double s = nrm->world_scale, is = 1.0 / s;
-    const double* R0 = nrm->R0;
-    const int64_t nq = n_sets > 0 ? set_ptr[n_sets] : 0;
-    double R0t[9];
-    srk::mat3_tr(R0, R0t);
-    for (int64_t q = 0; q < nq; ++q) {
-        if (lin_R) srk::mat3_mul(lin_R + 9 * q, R0t, lin_R_out + 9 * q);
-        if (lin_C) {
-            double y[3];
-            srk::se3_apply(R0, nrm->T0, lin_C + 3 * q, y);
-            for (int e = 0; e < 3; ++e) lin_C_out[3 * q + e] = s * y[e];
-        }
-        if (mean) {
-            double y[3];
-            srk::mat3_vec(R0, mean + 6 * q, y);
-            for (int e = 0; e < 3; ++e) mean_out[6 * q + e] = s * y[e];
-            srk::mat3_vec(R0, mean + 6 * q + 3, mean_out + 6 * q + 3);
-        }
-    }
-    int64_t at = 0;
-    for (int32_t g = 0; info && g < n_sets; ++g) {
-        const int64_t k = set_ptr[g + 1] - set_ptr[g], n = 6 * k;
-        const double* L = info + at;
-        double* o = info_out + at;
-        for (int64_t bi = 0; bi < 2 * k; ++bi)     // 3 x 3 blocks: even = translation, odd = rotation
-            for (int64_t bj = 0; bj < 2 * k; ++bj) {
-                double B[9], RB[9], RBR[9];
-                for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) B[3 * a + b] = L[(3 * bi + a) * n + 3 * bj + b];
-                srk::mat3_mul(R0, B, RB);
-                srk::mat3_mul(RB, R0t, RBR);
-                const double f = ((bi & 1) ? 1.0 : is) * ((bj & 1) ? 1.0 : is);
-                for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) o[(3 * bi + a) * n + 3 * bj + b] = f * RBR[3 * a + b];
-            }
-        for (int64_t r = 0; r < n; ++r) // the symmetric part: both triangles carry the same sum up to rounding
-            for (int64_t c = r + 1; c < n; ++c) o[r * n + c] = o[c * n + r] = 0.5 * (o[r * n + c] + o[c * n + r]);
-        at += n * n;
-    }
-    return SRK_OK;
 }
 
 } // extern "C"
@@ -1172,29 +1027,220 @@ static int check_information(srk_ba* h, const char* who, const double* q, int64_
     }
     return SRK_OK;
 }
-static int apply_information(srk_ba* h);
-static int apply_constant_blocks(srk_ba* h);
-static int apply_position_priors(srk_ba* h);
-static int apply_relative_pose_factors(srk_ba* h);
-static int apply_joint_pose_priors(srk_ba* h);
-// joint pose priors: the information matrix of set g of the stored setting (dense row-major, 6 k rows), and whether its 6 x 6
-// block (slot i, slot j) has a non-zero entry
-static const double* jp_info_of(const srk_ba* h, size_t g)
+// ---- the factor settings -> the device tables of the resident scene: srk_factors.cpp builds them, upload_tables allocates and
+// copies.  A table: bytes from src (or zeros) in a buffer of max(bytes, at_least) bytes; nothing at all when that is 0.
+struct TableUp { DevBuf* buf; const void* src; size_t bytes, at_least; bool zero; };
+template <typename T> static TableUp table_of(DevBuf& b, const std::vector<T>& v, size_t at_least = 0)
 {
-    int64_t at = 0;
-    for (size_t q = 0; q < g; ++q) {
-        const int64_t k = h->jp_ptr[q + 1] - h->jp_ptr[q];
-        at += 36 * k * k;
+    return { &b, v.data(), sizeof(T) * v.size(), at_least, false };
+}
+static TableUp zeros_of(DevBuf& b, size_t bytes) { return { &b, nullptr, bytes, 0, true }; }
+static int upload_tables(srk_ba* h, std::initializer_list<TableUp> tables)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    int rc;
+    for (const TableUp& u : tables) {
+        const size_t size = std::max(u.bytes, u.at_least);
+        if (size == 0) continue;
+        if ((rc = dev_alloc(h, *u.buf, size)) != SRK_OK) return rc;
+        if (u.zero) HIPCHK(h, hipMemsetAsync(u.buf->p, 0, size, s));
+        else if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.buf->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
     }
-    return h->jp_info.data() + at;
+    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope; every attempt stream starts behind this call
+    return SRK_OK;
 }
-static bool jp_block_nonzero(const double* L, int64_t n, int32_t i, int32_t j)
+static SrkFactorDims factor_dims(const srk_ba* h) { return { h->d.N, h->d.M, h->d.O, h->d.fv, h->d.ld }; }
+
+static int apply_information(srk_ba* h)
 {
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c)
-            if (L[(6 * i + r) * n + 6 * j + c] != 0.0) return true;
-    return false;
+    InfoFamily& f = h->obs_info;
+    f.on = false;
+    const SrkInfoTables t = srk_build_information(f.set, *h, factor_dims(h));
+    if (!t.on) return SRK_OK;
+    const int rc = upload_tables(h, { table_of(f.buf[f.Q], t.q), table_of(f.buf[f.QF], t.qf) });
+    f.on = rc == SRK_OK;
+    return rc;
 }
+static int apply_constant_blocks(srk_ba* h)
+{
+    ConstFamily& f = h->cst;
+    f.n_pts = 0;
+    f.n_frames = 0;
+    f.frame_int.clear();
+    if (!f.set.set) return SRK_OK;
+    SrkConstTables t = srk_build_constant(f.set, *h, factor_dims(h));
+    f.frame_int.swap(t.frame_int);
+    const int rc = upload_tables(h, { table_of(f.buf[f.PTS], t.pts), table_of(f.buf[f.FRAMES], t.frames) });
+    if (rc != SRK_OK) return rc;
+    f.n_pts = (int64_t)t.pts.size();
+    f.n_frames = (int32_t)t.frames.size();
+    return SRK_OK;
+}
+static int apply_position_priors(srk_ba* h)
+{
+    PriorFamily& f = h->pri;
+    f.n_pts = 0;
+    f.n_frames = 0;
+    f.app.take(f.set);
+    if (!f.set.set) return SRK_OK;
+    const SrkPriorTables t = srk_build_priors(f.set, h->nrm, *h, factor_dims(h));
+    const int rc = upload_tables(h, { table_of(f.buf[f.PT_LIST], t.pt_list), table_of(f.buf[f.PT_VAL], t.pt_val),
+                                      table_of(f.buf[f.FR_LIST], t.fr_list), table_of(f.buf[f.FR_VAL], t.fr_val) });
+    if (rc != SRK_OK) return rc;
+    f.n_pts = (int64_t)t.pt_list.size();
+    f.n_frames = (int32_t)t.fr_list.size();
+    return SRK_OK;
+}
+static int apply_relative_pose_factors(srk_ba* h)
+{
+    RelPoseFamily& f = h->rp;
+    f.n = f.n_frames = 0;
+    f.int_a.clear(); f.int_b.clear();
+    f.app.take(f.set);
+    SrkRelPoseTables t = srk_build_relpose(f.set, h->sel, h->nrm, *h, factor_dims(h));
+    const size_t n = t.fa.size();
+    if (n == 0) return SRK_OK;
+    const int rc = upload_tables(h, { table_of(f.buf[f.FA], t.fa), table_of(f.buf[f.FB], t.fb), table_of(f.buf[f.VAL], t.val),
+                                      table_of(f.buf[f.FR_LIST], t.fr_list), table_of(f.buf[f.FR_PTR], t.fr_ptr),
+                                      table_of(f.buf[f.FR_ENT], t.fr_ent), table_of(f.buf[f.TGT], t.tgt), zeros_of(f.buf[f.CPL], 8 * 36 * n) });
+    if (rc != SRK_OK) return rc;
+    f.int_a.swap(t.fa);
+    f.int_b.swap(t.fb);
+    f.n = (int32_t)n;
+    f.n_frames = (int32_t)t.fr_list.size();
+    return SRK_OK;
+}
+static int apply_joint_pose_priors(srk_ba* h)
+{
+    JPriorFamily& f = h->jp;
+    f.n = f.n_pairs = f.n_frames = 0;
+    for (TimedPass& p : f.pass) p.timed = false;
+    f.pair_a.clear(); f.pair_b.clear();
+    f.app.take(f.set);
+    SrkJPriorTables t = srk_build_jprior(f.set, h->sel, h->nrm, *h, factor_dims(h));
+    const size_t nq = t.frame.size(), np = t.pslot.size();
+    if (nq == 0) return SRK_OK;
+    f.pair_a.swap(t.pair_a);
+    f.pair_b.swap(t.pair_b);
+    const int rc = upload_tables(h, { table_of(f.buf[f.PTR], t.ptr, 8), table_of(f.buf[f.FRAME], t.frame, 8), table_of(f.buf[f.LIN], t.lin, 8),
+                                      table_of(f.buf[f.MEAN], t.mean, 8), table_of(f.buf[f.IPTR], t.iptr, 8), table_of(f.buf[f.INFO], t.info, 8),
+                                      table_of(f.buf[f.PPTR], t.pptr, 8), table_of(f.buf[f.PSLOT], t.pslot, 8), table_of(f.buf[f.TGT], t.tgt, 8),
+                                      table_of(f.buf[f.FR_LIST], t.fr_list, 8), table_of(f.buf[f.FR_PTR], t.fr_ptr, 8),
+                                      table_of(f.buf[f.FR_ENT], t.fr_ent, 8), zeros_of(f.buf[f.BLK], 8 * 42 * nq),
+                                      zeros_of(f.buf[f.CPL], 8 * 36 * std::max<size_t>(np, 1)) });
+    if (rc != SRK_OK) return rc;
+    f.n = (int32_t)t.iptr.size();
+    f.n_pairs = (int32_t)np;
+    f.n_frames = (int32_t)t.fr_list.size();
+    return SRK_OK;
+}
+
+// the lists of the resident scene for the kernels: NULL without switched-on entries, so that none of a family's passes is launched
+static const SrkPrior* position_priors(const srk_ba* h, SrkPrior& p)
+{
+    const PriorFamily& f = h->pri;
+    if (f.n_pts == 0 && f.n_frames == 0) return nullptr;
+    p = SrkPrior{ P<int32_t>(f.buf[f.PT_LIST]), P<double>(f.buf[f.PT_VAL]), f.n_pts, P<int32_t>(f.buf[f.FR_LIST]), P<double>(f.buf[f.FR_VAL]), f.n_frames };
+    return &p;
+}
+static const SrkRelPose* relpose_factors(const srk_ba* h, SrkRelPose& p)
+{
+    const RelPoseFamily& f = h->rp;
+    if (f.n == 0) return nullptr;
+    p = SrkRelPose{ P<int32_t>(f.buf[f.FA]), P<int32_t>(f.buf[f.FB]), P<double>(f.buf[f.VAL]), f.n, P<int32_t>(f.buf[f.FR_LIST]),
+                    P<int32_t>(f.buf[f.FR_PTR]), P<int32_t>(f.buf[f.FR_ENT]), f.n_frames, P<int64_t>(f.buf[f.TGT]), P<double>(f.buf[f.CPL]) };
+    return &p;
+}
+static const SrkJointPrior* joint_priors(const srk_ba* h, SrkJointPrior& p)
+{
+    const JPriorFamily& f = h->jp;
+    if (f.n == 0) return nullptr;
+    p = SrkJointPrior{ f.n, P<int32_t>(f.buf[f.PTR]), P<int32_t>(f.buf[f.FRAME]), P<double>(f.buf[f.LIN]), P<double>(f.buf[f.MEAN]),
+                       P<int64_t>(f.buf[f.IPTR]), P<double>(f.buf[f.INFO]), P<int32_t>(f.buf[f.PPTR]), P<int32_t>(f.buf[f.PSLOT]),
+                       P<int64_t>(f.buf[f.TGT]), f.n_pairs, P<double>(f.buf[f.BLK]), P<double>(f.buf[f.CPL]), P<int32_t>(f.buf[f.FR_LIST]),
+                       P<int32_t>(f.buf[f.FR_PTR]), P<int32_t>(f.buf[f.FR_ENT]), f.n_frames };
+    return &p;
+}
+
+// ---- the timed passes (profile level >= 1; the *_pass_ms calls read them)
+static bool pass_events(TimedPass& p)
+{
+    for (hipEvent_t& e : p.ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) return false;
+    return true;
+}
+// a launch between the two events of its pass
+template <typename Launch> static int timed_launch(srk_ba* h, TimedPass& p, hipStream_t s, Launch launch)
+{
+    const bool timed = h->profile_level >= 1 && pass_events(p);
+    if (timed) HIPCHK(h, hipEventRecord(p.ev[0], s));
+    launch();
+    if (timed) HIPCHK(h, hipEventRecord(p.ev[1], s));
+    p.timed = timed;
+    HIPCHK(h, hipGetLastError());
+    return SRK_OK;
+}
+// for srk_launch_error, which records the pair around a family's pass itself: the pair, or NULL when the pass is not timed
+static const hipEvent_t* error_pass_events(srk_ba* h, TimedPass& p, bool launched)
+{
+    if (!launched) return nullptr;
+    p.timed = h->profile_level >= 1 && pass_events(p);
+    return p.timed ? p.ev : nullptr;
+}
+// the milliseconds of a family's n passes, 0 where a pass was not timed (every slot's stream has drained first)
+static int pass_ms(srk_ba* h, const TimedPass* pass, int n, double* const* out)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
+    for (int sl = 1; sl < SRK_SLOTS; ++sl)
+        if (h->att[sl].stream) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
+    for (int k = 0; k < n; ++k) {
+        float ms = 0;
+        if (pass[k].timed && hipEventElapsedTime(&ms, pass[k].ev[0], pass[k].ev[1]) != hipSuccess) ms = 0;
+        if (out[k]) *out[k] = pass[k].timed ? (double)ms : 0.0;
+    }
+    return SRK_OK;
+}
+
+// ---- shared by the entry points of the factor settings
+// a pass on its own (a family's energy, the observations' weights or residuals): nb partial sums and the n_out results behind them
+// in a buffer of the call's own; launch(stream, partials, results) starts the pass, the results come back to out
+template <typename Launch> static int error_pass(srk_ba* h, int32_t nb, int64_t n_out, double* out, Launch launch)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->main_stream;
+    HIPCHK(h, hipStreamSynchronize(s));
+    DevBuf part;
+    int rc = dev_alloc(h, part, 8 * ((size_t)nb + (size_t)n_out));
+    if (rc != SRK_OK) return rc;
+    launch(s, P<double>(part), P<double>(part) + nb);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, P<double>(part) + nb, 8 * (size_t)n_out, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    dev_free(part);
+    HIPCHK(h, e);
+    return SRK_OK;
+}
+// a setter of the named family against the modes already set
+static bool refuse_setting(srk_ba* h, const char* family)
+{
+    const std::string e = srk_setting_conflict(family, true, !h->igroup_user.empty(), h->world);
+    if (!e.empty()) h->last_error = e;
+    return !e.empty();
+}
+template <typename T> static void copy_out(T* dst, const std::vector<T>& v)
+{
+    if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(T));
+}
+// the resident scene in the caller's world coordinates, for the residual calls
+struct WorldScene {
+    std::vector<double> pts, R, T;
+    int rc;
+    explicit WorldScene(srk_ba* h) : pts((size_t)(3 * h->d.N)), R((size_t)(9 * (int64_t)h->d.M)), T((size_t)(3 * (int64_t)h->d.M)),
+                                     rc(srk_ba_download_scene(h, pts.data(), R.data(), T.data(), 1)) {}
+};
 static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_in, int32_t M,
                              const double* cam_R_in, const double* cam_T_in, const double* K_in, int shared_k,
                              const int64_t* row_ptr, const int32_t* obs_frame, const double* obs_uv,
@@ -1233,70 +1279,12 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     int rc = validate_scene(h, f0, N, pts_in, M, cam_R_in, cam_T_in, K_in, row_ptr, obs_frame, obs_uv);
     if (rc != SRK_OK) return rc;
     if (refuse_modes(h, h->fixed_k, h->deterministic, h->store_f32, h->schur_fp32, h->world, !h->igroup_user.empty())) return SRK_E_ARGS;
-    if (!h->info_user.empty() &&
-        check_information(h, "upload", h->info_user.data(), (int64_t)h->info_user.size(), N, row_ptr) != SRK_OK)
+    if (!h->obs_info.set.q.empty() &&
+        check_information(h, "upload", h->obs_info.set.q.data(), (int64_t)h->obs_info.set.q.size(), N, row_ptr) != SRK_OK)
         return SRK_E_ARGS;
-    if (h->cst_set) {
-        if (!h->cst_frame_user.empty() && (int64_t)h->cst_frame_user.size() != (int64_t)M) {
-            h->last_error = "constant blocks: set for " + std::to_string(h->cst_frame_user.size()) + " frames, the scene has " + std::to_string(M);
-            return SRK_E_ARGS;
-        }
-        if (!h->cst_point_user.empty() && (int64_t)h->cst_point_user.size() != N) {
-            h->last_error = "constant blocks: set for " + std::to_string(h->cst_point_user.size()) + " landmarks, the scene has " + std::to_string(N);
-            return SRK_E_ARGS;
-        }
-    }
-    if (h->pri_set) {
-        if (!h->pri_pt_idx.empty() && h->pri_pt_idx.back() >= N) {
-            h->last_error = "position priors: landmark index " + std::to_string(h->pri_pt_idx.back()) + ", the scene has " + std::to_string(N) + " landmarks";
-            return SRK_E_ARGS;
-        }
-        if (!h->pri_fr_idx.empty() && h->pri_fr_idx.back() >= M) {
-            h->last_error = "position priors: frame index " + std::to_string(h->pri_fr_idx.back()) + ", the scene has " + std::to_string(M) + " frames";
-            return SRK_E_ARGS;
-        }
-    }
-    // relative-pose factors: the switched-on ones (an all-zero information matrix is left out, plan included, so that the
-    // run has the bits of the run without it); their pairs go to the planner in the caller's numbering
-    h->rp_act.clear();
-    std::vector<int32_t> rel_a, rel_b;
-    for (size_t k = 0; h->rp_set && k < h->rp_a.size(); ++k) {
-        if (h->rp_a[k] >= M || h->rp_b[k] >= M) {
-            h->last_error = "relative-pose factors: frame index " + std::to_string(std::max(h->rp_a[k], h->rp_b[k])) + ", the scene has " + std::to_string(M) + " frames";
-            return SRK_E_ARGS;
-        }
-        bool off = true;
-        for (int e = 0; e < 21; ++e) off = off && h->rp_info[21 * k + (size_t)e] == 0.0;
-        if (off) continue;
-        h->rp_act.push_back((int32_t)k);
-        rel_a.push_back(h->rp_a[k]);
-        rel_b.push_back(h->rp_b[k]);
-    }
-    // joint pose priors: the switched-on sets; the pairs of slots whose 6 x 6 block of L is not all zeros join the factors'
-    // pairs, each unordered pair once
-    h->jp_act.clear();
-    if (h->jp_set) {
-        std::set<std::pair<int32_t, int32_t>> seen;
-        for (size_t k = 0; k < rel_a.size(); ++k) seen.insert({ std::min(rel_a[k], rel_b[k]), std::max(rel_a[k], rel_b[k]) });
-        for (size_t g = 0; g + 1 < h->jp_ptr.size(); ++g) {
-            const int32_t q0 = h->jp_ptr[g], k = h->jp_ptr[g + 1] - q0;
-            if (h->jp_frame[(size_t)(q0 + k - 1)] >= M) {
-                h->last_error = "joint pose priors: frame index " + std::to_string(h->jp_frame[(size_t)(q0 + k - 1)]) + ", the scene has " + std::to_string(M) + " frames";
-                return SRK_E_ARGS;
-            }
-            const double* L = jp_info_of(h, g);
-            bool off = true;
-            for (int64_t e = 0; e < 36 * (int64_t)k * k; ++e) off = off && L[e] == 0.0;
-            if (off) continue;
-            h->jp_act.push_back((int32_t)g);
-            for (int32_t i = 1; i < k; ++i)
-                for (int32_t j = 0; j < i; ++j)
-                    if (jp_block_nonzero(L, 6 * k, i, j) && seen.insert({ h->jp_frame[(size_t)(q0 + j)], h->jp_frame[(size_t)(q0 + i)] }).second) {
-                        rel_a.push_back(h->jp_frame[(size_t)(q0 + j)]);
-                        rel_b.push_back(h->jp_frame[(size_t)(q0 + i)]);
-                    }
-        }
-    }
+    // the settings against this scene, the switched-on factors and sets, and their pairs for the planner (srk_factors.cpp)
+    const std::string refused = srk_select_factors(h->cst.set, h->pri.set, h->rp.set, h->jp.set, N, M, h->sel);
+    if (!refused.empty()) { h->last_error = refused; return SRK_E_ARGS; }
     rearm_fusion(h);
     stage("validate");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1353,9 +1341,9 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     if (const char* e = getenv("SRK_SCHUR_RUN_SPLIT")) opt.run_split = std::max(1, std::min(16, atoi(e))); // development: fixed cut
     opt.no_long = getenv("SRK_SCHUR_NO_LONG") != nullptr; // development: everything through the per-landmark kernel
 #endif
-    opt.rel_a = rel_a.data();
-    opt.rel_b = rel_b.data();
-    opt.n_rel = (int64_t)rel_a.size();
+    opt.rel_a = h->sel.rel_a.data();
+    opt.rel_b = h->sel.rel_b.data();
+    opt.n_rel = (int64_t)h->sel.rel_a.size();
     SrkScenePlan plan;
     srk_plan_scene({ N, M, row_ptr, obs_frame, obs_uv, pts.data(), camR.data(), camT.data(), Kexp.data() }, opt, plan, stage);
     if (!h->igroup_user.empty()) {
@@ -1376,13 +1364,10 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     d.comp = 1;
     d.g0 = plan.g0;
     d.g1 = plan.g1;
-    // constant blocks without the reference's gauge: no frame index matches, so srk_is_fixed_var is false for every variable
-    // and the masking passes are the only source of identity rows besides the padding
-    if (h->cst_set && !h->cst_keep_gauge) d.g0 = d.g1 = -1;
-    // position priors without the reference's gauge: the priors fix the similarity
-    if (h->pri_set && !h->pri_keep_gauge) d.g0 = d.g1 = -1;
-    // joint pose priors without the reference's gauge: the caller asserts they fix the similarity
-    if (h->jp_set && !h->jp_keep_gauge) d.g0 = d.g1 = -1;
+    // a setting without the reference's gauge: no frame index matches, so srk_is_fixed_var is false for every variable.  The
+    // constant blocks' masking passes are then the only source of identity rows besides the padding;
+    // position priors, or joint pose priors as the caller asserts, fix the similarity (sections 14 and 18)
+    if ((h->cst.set.set && !h->cst.set.keep_gauge) || (h->pri.set.set && !h->pri.set.keep_gauge) || (h->jp.set.set && !h->jp.set.keep_gauge)) d.g0 = d.g1 = -1;
     d.w_f32 = h->store_f32 ? 1 : 0;
     h->d = d;
     h->f0 = f0;
@@ -1429,8 +1414,8 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
         add(a.dx, nullptr, 24 * N);
         // (position priors: their partial sums sit behind the observation partials of either error kernel)
         add(a.err_partial, nullptr, 8 * (std::max<int64_t>(1024, srk_error_partials_staged(d)) +
-                                         (h->pri_set ? srk_prior_partials((int64_t)h->pri_pt_idx.size(), (int64_t)h->pri_fr_idx.size()) : 0) +
-                                         srk_relpose_partials((int64_t)h->rp_act.size()) + srk_jprior_partials((int64_t)h->jp_act.size())));
+                                         (h->pri.set.set ? srk_prior_partials((int64_t)h->pri.set.pt_idx.size(), (int64_t)h->pri.set.fr_idx.size()) : 0) +
+                                         srk_relpose_partials((int64_t)h->sel.rp_act.size()) + srk_jprior_partials((int64_t)h->sel.jp_act.size())));
         add(a.info, nullptr, 64);
         add(a.dinv, nullptr, 8 * 64 * d.ld);
         add(a.irr, nullptr, 4 * (N + 2));
@@ -1499,349 +1484,6 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     return SRK_OK;
 }
 
-// the switched-on factors (rp_act, checked at the start of the upload; the planner has seen their pairs) -> the device lists of
-// the resident scene: frames through the renumbering (frame_int), values through the normaliser of this upload, the per-frame
-// lists of incident factors in factor order, and each factor's place in S
-static int apply_relative_pose_factors(srk_ba* h)
-{
-    const SrkDims& d = h->d;
-    h->n_rp = 0;
-    h->n_rp_frames = 0;
-    h->rp_int_a.clear(); h->rp_int_b.clear();
-    h->app_rp = h->rp_set;
-    h->app_rp_a = h->rp_a; h->app_rp_b = h->rp_b; h->app_rp_R = h->rp_R; h->app_rp_t = h->rp_t;
-    const size_t n = h->rp_act.size();
-    if (n == 0) return SRK_OK;
-    std::vector<double> tn(h->rp_t.size()), ln(h->rp_info.size());
-    srk_ba_normalize_relative_pose_factors(&h->nrm, (int32_t)h->rp_a.size(), h->rp_t.data(), h->rp_info.data(), tn.data(), ln.data());
-    std::vector<int32_t> fa(n), fb(n);
-    std::vector<double> val((size_t)SRK_RP_PLANES * n);
-    std::vector<int64_t> tgt(n);
-    const int64_t t0 = 4 - (10 - d.fv); // first pose variable of a frame
-    for (size_t i = 0; i < n; ++i) {
-        const size_t k = (size_t)h->rp_act[i];
-        fa[i] = h->frame_int.empty() ? h->rp_a[k] : h->frame_int[(size_t)h->rp_a[k]];
-        fb[i] = h->frame_int.empty() ? h->rp_b[k] : h->frame_int[(size_t)h->rp_b[k]];
-        for (int e = 0; e < 9; ++e) val[(size_t)e * n + i] = h->rp_R[9 * k + (size_t)e];
-        for (int e = 0; e < 3; ++e) val[(size_t)(9 + e) * n + i] = tn[3 * k + (size_t)e];
-        for (int e = 0; e < 21; ++e) val[(size_t)(12 + e) * n + i] = ln[21 * k + (size_t)e];
-        const int64_t hi = std::max(fa[i], fb[i]), lo = std::min(fa[i], fb[i]);
-        tgt[i] = (d.fv * hi + t0) * d.ld + d.fv * lo + t0;
-    }
-    std::vector<int32_t> cnt((size_t)d.M, 0), list, ptr(1, 0), ent;
-    for (size_t i = 0; i < n; ++i) { ++cnt[(size_t)fa[i]]; ++cnt[(size_t)fb[i]]; }
-    std::vector<int32_t> at((size_t)d.M, -1);
-    for (int32_t j = 0; j < d.M; ++j)
-        if (cnt[(size_t)j]) {
-            at[(size_t)j] = (int32_t)list.size();
-            list.push_back(j);
-            ptr.push_back(ptr.back() + cnt[(size_t)j]);
-        }
-    ent.resize((size_t)ptr.back());
-    std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-    for (size_t i = 0; i < n; ++i) { // factor order inside every frame's list
-        ent[(size_t)fill[(size_t)at[(size_t)fa[i]]]++] = (int32_t)(2 * i);
-        ent[(size_t)fill[(size_t)at[(size_t)fb[i]]]++] = (int32_t)(2 * i + 1);
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    int rc;
-    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
-        { &h->rp_fa, fa.data(), 4 * n }, { &h->rp_fb, fb.data(), 4 * n }, { &h->rp_val, val.data(), 8 * val.size() },
-        { &h->rp_fr_list, list.data(), 4 * list.size() }, { &h->rp_fr_ptr, ptr.data(), 4 * ptr.size() },
-        { &h->rp_fr_ent, ent.data(), 4 * ent.size() }, { &h->rp_tgt, tgt.data(), 8 * n },
-    };
-    for (auto& u : up) {
-        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
-    }
-    if ((rc = dev_alloc(h, h->rp_cpl, 8 * 36 * n)) != SRK_OK) return rc;
-    HIPCHK(h, hipMemsetAsync(h->rp_cpl.p, 0, 8 * 36 * n, s));
-    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope
-    h->rp_int_a = fa;
-    h->rp_int_b = fb;
-    h->n_rp = (int32_t)n;
-    h->n_rp_frames = (int32_t)list.size();
-    return SRK_OK;
-}
-// the factor lists of the resident scene for the kernels: NULL without factors, so that none of the three passes is launched
-static const SrkRelPose* relpose_factors(const srk_ba* h, SrkRelPose& p)
-{
-    if (h->n_rp == 0) return nullptr;
-    p = SrkRelPose{ P<int32_t>(h->rp_fa), P<int32_t>(h->rp_fb), P<double>(h->rp_val), h->n_rp, P<int32_t>(h->rp_fr_list),
-                    P<int32_t>(h->rp_fr_ptr), P<int32_t>(h->rp_fr_ent), h->n_rp_frames, P<int64_t>(h->rp_tgt), P<double>(h->rp_cpl) };
-    return &p;
-}
-static bool rp_events(srk_ba* h)
-{
-    for (auto& e : h->ev_rp)
-        if (!e && hipEventCreate(&e) != hipSuccess) return false;
-    return true;
-}
-
-// the switched-on sets (jp_act, checked at the start of the upload; the planner has seen their coupled pairs) -> the device
-// lists of the resident scene: frames through the renumbering (frame_int), poses, means and information matrices through the
-// normaliser of this upload, the coupled pairs with their places in S, the per-frame lists of slots in set order
-static int apply_joint_pose_priors(srk_ba* h)
-{
-    const SrkDims& d = h->d;
-    h->n_jp = h->n_jp_pairs = h->n_jp_frames = 0;
-    h->jp_timed[0] = h->jp_timed[1] = h->jp_timed[2] = false;
-    h->jp_pair_a.clear(); h->jp_pair_b.clear();
-    h->app_jp = h->jp_set;
-    h->app_jp_ptr = h->jp_ptr; h->app_jp_frame = h->jp_frame; h->app_jp_R = h->jp_R; h->app_jp_C = h->jp_C; h->app_jp_mean = h->jp_mean;
-    const size_t ns = h->jp_act.size();
-    if (ns == 0) return SRK_OK;
-    std::vector<double> Rn(h->jp_R.size()), Cn(h->jp_C.size()), mn(h->jp_mean.size()), Ln(h->jp_info.size());
-    srk_ba_normalize_joint_pose_priors(&h->nrm, (int32_t)h->jp_ptr.size() - 1, h->jp_ptr.data(), h->jp_R.data(), h->jp_C.data(),
-                                       h->jp_mean.data(), h->jp_info.data(), Rn.data(), Cn.data(), mn.data(), Ln.data());
-    std::vector<int32_t> ptr(1, 0), frame, pptr(1, 0), pslot;
-    std::vector<int64_t> iptr, tgt;
-    std::vector<double> lin, mean, info;
-    const int64_t t0 = 4 - (10 - d.fv); // first pose variable of a frame
-    for (size_t a = 0; a < ns; ++a) {
-        const size_t g = (size_t)h->jp_act[a];
-        const int32_t q0 = h->jp_ptr[g], k = h->jp_ptr[g + 1] - q0;
-        const int64_t n = 6 * (int64_t)k;
-        const double* L = Ln.data() + (jp_info_of(h, g) - h->jp_info.data());
-        iptr.push_back((int64_t)info.size());
-        info.insert(info.end(), L, L + n * n);
-        for (int32_t i = 0; i < k; ++i) {
-            const size_t q = (size_t)(q0 + i);
-            frame.push_back(h->frame_int.empty() ? h->jp_frame[q] : h->frame_int[(size_t)h->jp_frame[q]]);
-            lin.insert(lin.end(), &Rn[9 * q], &Rn[9 * q] + 9);
-            lin.insert(lin.end(), &Cn[3 * q], &Cn[3 * q] + 3);
-            mean.insert(mean.end(), &mn[6 * q], &mn[6 * q] + 6);
-        }
-        const int32_t* fr = frame.data() + ptr.back();
-        // (the stored matrix decides which pairs couple, as at the start of the upload: the normaliser maps a zero block to zeros)
-        for (int32_t i = 1; i < k; ++i)
-            for (int32_t j = 0; j < i; ++j)
-                if (jp_block_nonzero(jp_info_of(h, g), n, i, j)) {
-                    const int64_t hi = std::max(fr[i], fr[j]), lo = std::min(fr[i], fr[j]);
-                    pslot.push_back((i << 8) | j);
-                    tgt.push_back((d.fv * hi + t0) * d.ld + d.fv * lo + t0);
-                    h->jp_pair_a.push_back((int32_t)lo);
-                    h->jp_pair_b.push_back((int32_t)hi);
-                }
-        ptr.push_back(ptr.back() + k);
-        pptr.push_back((int32_t)pslot.size());
-    }
-    const size_t nq = frame.size(), np = pslot.size();
-    std::vector<int32_t> cnt((size_t)d.M, 0), list, fptr(1, 0), ent;
-    for (size_t q = 0; q < nq; ++q) ++cnt[(size_t)frame[q]];
-    std::vector<int32_t> at((size_t)d.M, -1);
-    for (int32_t j = 0; j < d.M; ++j)
-        if (cnt[(size_t)j]) {
-            at[(size_t)j] = (int32_t)list.size();
-            list.push_back(j);
-            fptr.push_back(fptr.back() + cnt[(size_t)j]);
-        }
-    ent.resize(nq);
-    std::vector<int32_t> fill(fptr.begin(), fptr.end() - 1);
-    for (size_t q = 0; q < nq; ++q) ent[(size_t)fill[(size_t)at[(size_t)frame[q]]]++] = (int32_t)q; // set order inside every frame's list
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    int rc;
-    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
-        { &h->jp_d_ptr, ptr.data(), 4 * ptr.size() }, { &h->jp_d_frame, frame.data(), 4 * nq }, { &h->jp_d_lin, lin.data(), 8 * lin.size() },
-        { &h->jp_d_mean, mean.data(), 8 * mean.size() }, { &h->jp_d_iptr, iptr.data(), 8 * iptr.size() },
-        { &h->jp_d_info, info.data(), 8 * info.size() }, { &h->jp_d_pptr, pptr.data(), 4 * pptr.size() },
-        { &h->jp_d_pslot, pslot.data(), 4 * np }, { &h->jp_d_tgt, tgt.data(), 8 * np }, { &h->jp_d_fr_list, list.data(), 4 * list.size() },
-        { &h->jp_d_fr_ptr, fptr.data(), 4 * fptr.size() }, { &h->jp_d_fr_ent, ent.data(), 4 * ent.size() },
-    };
-    for (auto& u : up) {
-        if ((rc = dev_alloc(h, *u.b, std::max<size_t>(u.bytes, 8))) != SRK_OK) return rc;
-        if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
-    }
-    if ((rc = dev_alloc(h, h->jp_d_blk, 8 * 42 * nq)) != SRK_OK) return rc;
-    HIPCHK(h, hipMemsetAsync(h->jp_d_blk.p, 0, 8 * 42 * nq, s));
-    if ((rc = dev_alloc(h, h->jp_d_cpl, 8 * 36 * std::max<size_t>(np, 1))) != SRK_OK) return rc;
-    HIPCHK(h, hipMemsetAsync(h->jp_d_cpl.p, 0, 8 * 36 * std::max<size_t>(np, 1), s));
-    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope
-    h->n_jp = (int32_t)ns;
-    h->n_jp_pairs = (int32_t)np;
-    h->n_jp_frames = (int32_t)list.size();
-    return SRK_OK;
-}
-// the lists of the resident scene for the kernels: NULL without switched-on sets, so that none of the passes is launched
-static const SrkJointPrior* joint_priors(const srk_ba* h, SrkJointPrior& p)
-{
-    if (h->n_jp == 0) return nullptr;
-    p = SrkJointPrior{ h->n_jp, P<int32_t>(h->jp_d_ptr), P<int32_t>(h->jp_d_frame), P<double>(h->jp_d_lin), P<double>(h->jp_d_mean),
-                       P<int64_t>(h->jp_d_iptr), P<double>(h->jp_d_info), P<int32_t>(h->jp_d_pptr), P<int32_t>(h->jp_d_pslot),
-                       P<int64_t>(h->jp_d_tgt), h->n_jp_pairs, P<double>(h->jp_d_blk), P<double>(h->jp_d_cpl), P<int32_t>(h->jp_d_fr_list),
-                       P<int32_t>(h->jp_d_fr_ptr), P<int32_t>(h->jp_d_fr_ent), h->n_jp_frames };
-    return &p;
-}
-static bool jp_events(srk_ba* h)
-{
-    for (auto& e : h->ev_jp)
-        if (!e && hipEventCreate(&e) != hipSuccess) return false;
-    return true;
-}
-
-// the stored priors (indices checked at the start of the upload) -> the device lists of the resident scene: values through the
-// normaliser of this upload (the identity for a scene uploaded as already normalised), landmarks through the internal order
-// (perm), frames through the renumbering (frame_int), both ascending in the internal numbering
-static int apply_position_priors(srk_ba* h)
-{
-    const SrkDims& d = h->d;
-    h->n_pri_pts = 0;
-    h->n_pri_frames = 0;
-    h->app_pt_idx.clear(); h->app_pt_pos.clear(); h->app_fr_idx.clear(); h->app_fr_pos.clear();
-    if (!h->pri_set) return SRK_OK;
-    h->app_pt_idx = h->pri_pt_idx; h->app_pt_pos = h->pri_pt_pos;
-    h->app_fr_idx = h->pri_fr_idx; h->app_fr_pos = h->pri_fr_pos;
-    const size_t np = h->pri_pt_idx.size(), nf = h->pri_fr_idx.size();
-    std::vector<double> pn(3 * np), ln(6 * np), cn(3 * nf), fn(6 * nf);
-    srk_ba_normalize_position_priors(&h->nrm, (int64_t)np, np ? h->pri_pt_pos.data() : nullptr, np ? h->pri_pt_info.data() : nullptr,
-                                     np ? pn.data() : nullptr, np ? ln.data() : nullptr);
-    srk_ba_normalize_position_priors(&h->nrm, (int64_t)nf, nf ? h->pri_fr_pos.data() : nullptr, nf ? h->pri_fr_info.data() : nullptr,
-                                     nf ? cn.data() : nullptr, nf ? fn.data() : nullptr);
-    // an all-zero information matrix is a switched-off prior: it is left out of the lists, so that the sums (and their bits) are
-    // those of the setting without it
-    auto off = [](const double* info) {
-        for (int e = 0; e < 6; ++e)
-            if (info[e] != 0.0) return false;
-        return true;
-    };
-    std::vector<int32_t> pl, fl; // the lists, and each entry's place in the setting
-    std::vector<size_t> pk, fk;
-    if (np) {
-        std::vector<int64_t> slot((size_t)d.N, -1); // caller's landmark -> its place in the setting
-        for (size_t k = 0; k < np; ++k) slot[(size_t)h->pri_pt_idx[k]] = (int64_t)k;
-        for (int64_t i = 0; i < d.N; ++i) {
-            const int64_t k = slot[(size_t)h->perm[(size_t)i]];
-            if (k < 0 || off(&h->pri_pt_info[6 * (size_t)k])) continue;
-            pl.push_back((int32_t)i);
-            pk.push_back((size_t)k);
-        }
-    }
-    if (nf) {
-        std::vector<int32_t> slot((size_t)d.M, -1); // internal frame -> its place in the setting
-        for (size_t k = 0; k < nf; ++k) {
-            const int32_t j = h->pri_fr_idx[k];
-            slot[(size_t)(h->frame_int.empty() ? j : h->frame_int[(size_t)j])] = (int32_t)k;
-        }
-        for (int32_t j = 0; j < d.M; ++j) {
-            const int32_t k = slot[(size_t)j];
-            if (k < 0 || off(&h->pri_fr_info[6 * (size_t)k])) continue;
-            fl.push_back(j);
-            fk.push_back((size_t)k);
-        }
-    }
-    // the values as SoA planes over the list (SrkPrior)
-    auto planes = [](const std::vector<size_t>& at, const std::vector<double>& pos, const std::vector<double>& info) {
-        const size_t n = at.size();
-        std::vector<double> val(9 * n);
-        for (size_t i = 0; i < n; ++i) {
-            for (int e = 0; e < 3; ++e) val[(size_t)e * n + i] = pos[3 * at[i] + (size_t)e];
-            for (int e = 0; e < 6; ++e) val[(size_t)(3 + e) * n + i] = info[6 * at[i] + (size_t)e];
-        }
-        return val;
-    };
-    const std::vector<double> pv = planes(pk, pn, ln), fvv = planes(fk, cn, fn);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    int rc;
-    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
-        { &h->pri_pt_list, pl.data(), 4 * pl.size() }, { &h->pri_pt_val, pv.data(), 8 * pv.size() },
-        { &h->pri_fr_list, fl.data(), 4 * fl.size() }, { &h->pri_fr_val, fvv.data(), 8 * fvv.size() },
-    };
-    for (auto& u : up) {
-        if (!u.bytes) continue;
-        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope
-    h->n_pri_pts = (int64_t)pl.size();
-    h->n_pri_frames = (int32_t)fl.size();
-    return SRK_OK;
-}
-// the prior lists of the resident scene for the kernels: NULL without priors, so that neither pass is launched
-static const SrkPrior* position_priors(const srk_ba* h, SrkPrior& p)
-{
-    if (h->n_pri_pts == 0 && h->n_pri_frames == 0) return nullptr;
-    p = SrkPrior{ P<int32_t>(h->pri_pt_list), P<double>(h->pri_pt_val), h->n_pri_pts,
-                  P<int32_t>(h->pri_fr_list), P<double>(h->pri_fr_val), h->n_pri_frames };
-    return &p;
-}
-// the event pairs around the two prior passes (srk_ba_prior_pass_ms), created on first use
-static bool pri_events(srk_ba* h)
-{
-    for (auto& e : h->ev_pri)
-        if (!e && hipEventCreate(&e) != hipSuccess) return false;
-    return true;
-}
-
-// cst_frame_user / cst_point_user (counts checked at the start of the upload) -> the device lists of the resident scene: the
-// constant landmarks in the internal order (perm), the constant frames through the renumbering (frame_int), ascending
-static int apply_constant_blocks(srk_ba* h)
-{
-    const SrkDims& d = h->d;
-    h->n_cst_pts = 0;
-    h->n_cst_frames = 0;
-    h->cst_frame_int.clear();
-    if (!h->cst_set) return SRK_OK;
-    std::vector<int32_t> pl, fl;
-    if (!h->cst_point_user.empty())
-        for (int64_t i = 0; i < d.N; ++i)
-            if (h->cst_point_user[(size_t)h->perm[(size_t)i]]) pl.push_back((int32_t)i);
-    if (!h->cst_frame_user.empty()) {
-        h->cst_frame_int.assign((size_t)d.M, 0);
-        for (int32_t j = 0; j < d.M; ++j)
-            if (h->cst_frame_user[(size_t)j]) h->cst_frame_int[(size_t)(h->frame_int.empty() ? j : h->frame_int[(size_t)j])] = 1;
-        for (int32_t j = 0; j < d.M; ++j)
-            if (h->cst_frame_int[(size_t)j]) fl.push_back(j);
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    int rc;
-    if (!pl.empty()) {
-        if ((rc = dev_alloc(h, h->cst_pts, 4 * pl.size())) != SRK_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->cst_pts.p, pl.data(), 4 * pl.size(), hipMemcpyHostToDevice, s));
-    }
-    if (!fl.empty()) {
-        if ((rc = dev_alloc(h, h->cst_frames, 4 * fl.size())) != SRK_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->cst_frames.p, fl.data(), 4 * fl.size(), hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope
-    h->n_cst_pts = (int64_t)pl.size();
-    h->n_cst_frames = (int32_t)fl.size();
-    return SRK_OK;
-}
-
-// info_user (checked against the resident scene's rows) -> the device, in the internal order: landmark perm and observation
-// rank inside the landmark, the inverse of the mapping at the end of srk_ba_observation_weights; the frame-major copy beside it
-static int apply_information(srk_ba* h)
-{
-    const SrkDims& d = h->d;
-    h->info_on = false;
-    if (h->info_user.empty() || d.O == 0) return SRK_OK;
-    std::vector<double> qi((size_t)d.O), qf(h->fobs_of.size());
-    for (int64_t i = 0; i < d.N; ++i) {
-        const int64_t oi = h->row_ptr_int[(size_t)i], ou = h->row_ptr_user[(size_t)h->perm[(size_t)i]];
-        const int64_t cnt = h->row_ptr_int[(size_t)i + 1] - oi;
-        for (int64_t a = 0; a < cnt; ++a) {
-            const int64_t ai = h->obs_rank.empty() ? a : h->obs_rank[(size_t)(ou + a)];
-            qi[(size_t)(oi + ai)] = h->info_user[(size_t)(ou + a)];
-        }
-    }
-    for (size_t o = 0; o < qf.size(); ++o) qf[(size_t)h->fobs_of[o]] = qi[o];
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    int rc;
-    if ((rc = dev_alloc(h, h->info_q, (size_t)(8 * d.O))) != SRK_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->info_q.p, qi.data(), (size_t)(8 * d.O), hipMemcpyHostToDevice, s));
-    if (!qf.empty()) {
-        if ((rc = dev_alloc(h, h->info_qf, 8 * qf.size())) != SRK_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->info_qf.p, qf.data(), 8 * qf.size(), hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(h, hipStreamSynchronize(s)); // the staging vectors go out of scope; every attempt stream starts behind this call
-    h->info_on = true;
-    return SRK_OK;
-}
 
 // entry of an upload / optimise call: the fused outer steps again after an earlier call's hand-off timeout (see chol_fused_wanted).
 // Every rank of a sharded run counts the same timeouts (the status words are exchanged), so all re-arm together.
@@ -2050,12 +1692,12 @@ static int coll_group(srk_ba* h, int op, int G, double* const* ptrs, const int64
 // the plain least-squares kernels run
 static const SrkLoss* robust_loss(const srk_ba* h, SrkLoss& L)
 {
-    if (h->loss_kind == SRK_LOSS_NONE && !h->info_on) return nullptr;
+    if (h->loss_kind == SRK_LOSS_NONE && !h->obs_info.on) return nullptr;
     L.kind = h->loss_kind;
     L.d = h->loss_delta_pix / h->f0;
     L.d2 = L.d * L.d;
-    L.q = h->info_on ? P<double>(h->info_q) : nullptr;
-    L.qf = h->info_on && !h->fobs_of.empty() ? P<double>(h->info_qf) : nullptr;
+    L.q = h->obs_info.on ? P<double>(h->obs_info.buf[InfoFamily::Q]) : nullptr;
+    L.qf = h->obs_info.on && !h->fobs_of.empty() ? P<double>(h->obs_info.buf[InfoFamily::QF]) : nullptr;
     return &L;
 }
 
@@ -2067,23 +1709,17 @@ static int phase_error(srk_ba* h, srk_ba::Attempt& a, int which, double* err_hos
     SrkLoss L;
     SrkPrior pr;
     const SrkPrior* prior = position_priors(h, pr); // the prior sums of the scene being scored
-    // (one event pair for all attempt slots: with speculation on, srk_ba_prior_pass_ms reports the attempt that recorded last)
-    const bool timed = prior && h->profile_level >= 1 && pri_events(h);
-    if (prior) h->pri_timed[1] = timed;
     SrkRelPose rpl;
     const SrkRelPose* relpose = relpose_factors(h, rpl); // the factor sum of the scene being scored
-    const bool rp_timed = relpose && h->profile_level >= 1 && rp_events(h);
-    if (relpose) h->rp_timed[2] = rp_timed;
     SrkJointPrior jpl;
     const SrkJointPrior* jprior = joint_priors(h, jpl); // the joint pose priors' sum of the scene being scored
-    const bool jp_timed = jprior && h->profile_level >= 1 && jp_events(h);
-    if (jprior) h->jp_timed[2] = jp_timed;
+    // (one event pair for all attempt slots: with speculation on, the *_pass_ms calls report the attempt that recorded last)
     srk_launch_error(s, d, P<double>(h->pts[which]), P<double>(h->cam[which]), P<int32_t>(h->obs_frame),
                      P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(a.err_partial), np, a.err_dst,
                      h->jac_fused ? P<int32_t>(h->wg_jmin) : nullptr, with_status ? P<int>(a.info) : nullptr,
                      with_status ? reinterpret_cast<int*>(reinterpret_cast<char*>(a.acc.p) + 8 * 3 * d.Ns) : nullptr,
-                     robust_loss(h, L), prior, timed ? &h->ev_pri[2] : nullptr, relpose, rp_timed ? &h->ev_rp[4] : nullptr,
-                     jprior, jp_timed ? &h->ev_jp[4] : nullptr);
+                     robust_loss(h, L), prior, error_pass_events(h, h->pri.pass[1], prior != nullptr), relpose,
+                     error_pass_events(h, h->rp.pass[2], relpose != nullptr), jprior, error_pass_events(h, h->jp.pass[2], jprior != nullptr));
     HIPCHK(h, hipGetLastError());
     int rc = no_exchange ? SRK_OK : exchange(h, a, a.err_dst, with_status ? 3 : 1);
     if (rc != SRK_OK) return rc;
@@ -2092,14 +1728,6 @@ static int phase_error(srk_ba* h, srk_ba::Attempt& a, int which, double* err_hos
         HIPCHK(h, hipStreamSynchronize(s));
     }
     return SRK_OK;
-}
-
-// the event pairs around the masking passes of the constant blocks (srk_ba_constant_pass_ms), created on first use
-static bool cst_events(srk_ba* h)
-{
-    for (auto& e : h->ev_cst)
-        if (!e && hipEventCreate(&e) != hipSuccess) return false;
-    return true;
 }
 
 static int phase_derivatives(srk_ba* h)
@@ -2136,41 +1764,18 @@ static int phase_derivatives(srk_ba* h)
                               P<int64_t>(h->col_ptr), P<int32_t>(h->fobs_pt), P<double>(h->fobs_uv), P<double>(h->Ug), L);
     }
     HIPCHK(h, hipGetLastError());
+    int rc;
     SrkPrior pr;
-    if (const SrkPrior* prior = position_priors(h, pr)) { // 2 L into the blocks, 2 L (x - xbar) into the gradients
-        const bool timed = h->profile_level >= 1 && pri_events(h);
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_pri[0], s));
-        srk_launch_prior_add(s, d, P<double>(h->pts[c]), P<double>(h->cam[c]), *prior, P<double>(h->Vg), P<double>(h->Ug));
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_pri[1], s));
-        h->pri_timed[0] = timed;
-        HIPCHK(h, hipGetLastError());
-    }
+    if (const SrkPrior* prior = position_priors(h, pr)) // 2 L into the blocks, 2 L (x - xbar) into the gradients
+        if ((rc = timed_launch(h, h->pri.pass[0], s, [&] { srk_launch_prior_add(s, d, P<double>(h->pts[c]), P<double>(h->cam[c]), *prior, P<double>(h->Vg), P<double>(h->Ug)); })) != SRK_OK) return rc;
     SrkRelPose rpl;
-    if (const SrkRelPose* relpose = relpose_factors(h, rpl)) { // the factors' terms into Ug, the coupling blocks aside
-        const bool timed = h->profile_level >= 1 && rp_events(h);
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[0], s));
-        srk_launch_relpose_add(s, d, P<double>(h->cam[c]), *relpose, P<double>(h->Ug));
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[1], s));
-        h->rp_timed[0] = timed;
-        HIPCHK(h, hipGetLastError());
-    }
+    if (const SrkRelPose* relpose = relpose_factors(h, rpl)) // the factors' terms into Ug, the coupling blocks aside
+        if ((rc = timed_launch(h, h->rp.pass[0], s, [&] { srk_launch_relpose_add(s, d, P<double>(h->cam[c]), *relpose, P<double>(h->Ug)); })) != SRK_OK) return rc;
     SrkJointPrior jpl;
-    if (const SrkJointPrior* jprior = joint_priors(h, jpl)) { // the sets' terms into Ug, the coupling blocks aside
-        const bool timed = h->profile_level >= 1 && jp_events(h);
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_jp[0], s));
-        srk_launch_jprior_add(s, d, P<double>(h->cam[c]), *jprior, P<double>(h->Ug));
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_jp[1], s));
-        h->jp_timed[0] = timed;
-        HIPCHK(h, hipGetLastError());
-    }
-    if (h->n_cst_pts > 0) { // constant landmarks: identity block, zero gradient, zero point-frame blocks
-        const bool timed = h->profile_level >= 1 && cst_events(h);
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[0], s));
-        srk_launch_const_points(s, d, P<int32_t>(h->cst_pts), h->n_cst_pts, P<int64_t>(h->row_ptr), P<double>(h->W), P<double>(h->Vg));
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[1], s));
-        h->cst_timed[0] = timed;
-        HIPCHK(h, hipGetLastError());
-    }
+    if (const SrkJointPrior* jprior = joint_priors(h, jpl)) // the sets' terms into Ug, the coupling blocks aside
+        if ((rc = timed_launch(h, h->jp.pass[0], s, [&] { srk_launch_jprior_add(s, d, P<double>(h->cam[c]), *jprior, P<double>(h->Ug)); })) != SRK_OK) return rc;
+    if (h->cst.n_pts > 0) // constant landmarks: identity block, zero gradient, zero point-frame blocks
+        if ((rc = timed_launch(h, h->cst.pass[0], s, [&] { srk_launch_const_points(s, d, P<int32_t>(h->cst.buf[ConstFamily::PTS]), h->cst.n_pts, P<int64_t>(h->row_ptr), P<double>(h->W), P<double>(h->Vg)); })) != SRK_OK) return rc;
     // landmark shards: Ug stays this rank's partial sum; it enters the reduced camera system before that is summed
     return SRK_OK;
 }
@@ -2233,34 +1838,16 @@ static int phase_schur(srk_ba* h, srk_ba::Attempt& a, double c, bool local_only)
     srk_launch_assemble(s, d, c, P<double>(h->Ug), P<double>(a.S), P<double>(a.rhs), h->rank == 0 ? 1.0 : 0.0,
                         P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->W), P<double>(h->Vg), P<int32_t>(a.irr));
     HIPCHK(h, hipGetLastError());
+    int rc;
     SrkRelPose rpl;
-    if (const SrkRelPose* relpose = relpose_factors(h, rpl)) { // the coupling blocks, before the constant frames are masked
-        const bool timed = h->profile_level >= 1 && rp_events(h);
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[2], s));
-        srk_launch_relpose_couple(s, d, *relpose, P<double>(a.S));
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_rp[3], s));
-        h->rp_timed[1] = timed;
-        HIPCHK(h, hipGetLastError());
-    }
+    if (const SrkRelPose* relpose = relpose_factors(h, rpl)) // the coupling blocks, before the constant frames are masked
+        if ((rc = timed_launch(h, h->rp.pass[1], s, [&] { srk_launch_relpose_couple(s, d, *relpose, P<double>(a.S)); })) != SRK_OK) return rc;
     SrkJointPrior jpl;
-    if (const SrkJointPrior* jprior = joint_priors(h, jpl)) { // the sets' coupling blocks, before the constant frames are masked
-        if (jprior->n_pairs > 0) {
-            const bool timed = h->profile_level >= 1 && jp_events(h);
-            if (timed) HIPCHK(h, hipEventRecord(h->ev_jp[2], s));
-            srk_launch_jprior_couple(s, d, *jprior, P<double>(a.S));
-            if (timed) HIPCHK(h, hipEventRecord(h->ev_jp[3], s));
-            h->jp_timed[1] = timed;
-            HIPCHK(h, hipGetLastError());
-        }
-    }
-    if (h->n_cst_frames > 0) { // constant frames: identity rows and columns, zero rhs
-        const bool timed = h->profile_level >= 1 && cst_events(h);
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[2], s));
-        srk_launch_const_frames(s, d, P<int32_t>(h->cst_frames), h->n_cst_frames, P<int64_t>(h->env_col), P<double>(a.S), P<double>(a.rhs));
-        if (timed) HIPCHK(h, hipEventRecord(h->ev_cst[3], s));
-        h->cst_timed[1] = timed;
-        HIPCHK(h, hipGetLastError());
-    }
+    const SrkJointPrior* jprior = joint_priors(h, jpl);
+    if (jprior && jprior->n_pairs > 0) // the sets' coupling blocks, before the constant frames are masked
+        if ((rc = timed_launch(h, h->jp.pass[1], s, [&] { srk_launch_jprior_couple(s, d, *jprior, P<double>(a.S)); })) != SRK_OK) return rc;
+    if (h->cst.n_frames > 0) // constant frames: identity rows and columns, zero rhs
+        if ((rc = timed_launch(h, h->cst.pass[1], s, [&] { srk_launch_const_frames(s, d, P<int32_t>(h->cst.buf[ConstFamily::FRAMES]), h->cst.n_frames, P<int64_t>(h->env_col), P<double>(a.S), P<double>(a.rhs)); })) != SRK_OK) return rc;
     if (h->shk_G > 0) { // shared intrinsics: S_sh = P^T S10 P, rhs_sh = P^T rhs10 (one rank only)
         srk_launch_rcs_fold(s, shk_args(h, a), P<double>(a.S), P<double>(a.rhs), P<double>(a.Ssh), P<double>(a.rsh));
         HIPCHK(h, hipGetLastError());
@@ -2346,7 +1933,7 @@ static int phase_cam_apply(srk_ba* h, srk_ba::Attempt& a)
     srk_launch_cam_apply(a.stream, h->d.M, P<double>(h->camR[cur]), P<double>(h->camT[cur]), P<double>(a.dc),
                          P<double>(h->camR[tr]), P<double>(h->camT[tr]), kbuf(h, tr), h->f0, P<double>(h->cam[tr]), h->d.fv);
     // constant frames: a zero correction does not return T bit for bit (it goes through R^T), so their trial pose is copied
-    srk_launch_const_cam_keep(a.stream, P<int32_t>(h->cst_frames), h->n_cst_frames, P<double>(h->camR[cur]), P<double>(h->camT[cur]),
+    srk_launch_const_cam_keep(a.stream, P<int32_t>(h->cst.buf[ConstFamily::FRAMES]), h->cst.n_frames, P<double>(h->camR[cur]), P<double>(h->camT[cur]),
                               P<double>(h->cam[cur]), P<double>(h->camR[tr]), P<double>(h->camT[tr]), P<double>(h->cam[tr]));
     HIPCHK(h, hipGetLastError());
     return SRK_OK;
@@ -2521,7 +2108,7 @@ static int cov_prepare(srk_ba* h, bool want_selection, bool want_points, std::ve
         const int64_t b0 = fv * (int64_t)d.g0, v1 = fv * (int64_t)d.g1 + 4 - off + d.comp;
         for (int64_t var = 0; var < n_rows; ++var) {
             const bool gauge = (var >= b0 + 4 - off && var <= b0 + 9 - off) || var == v1;
-            const bool cst = !h->cst_frame_int.empty() && h->cst_frame_int[(size_t)(var / fv)];
+            const bool cst = !h->cst.frame_int.empty() && h->cst.frame_int[(size_t)(var / fv)];
             free_var[(size_t)var] = gauge || cst ? 0 : 1;
         }
     }
@@ -2581,7 +2168,7 @@ static int phase_covariance(srk_ba* h, int32_t nf, const int32_t* frames, double
     }
     std::vector<char> pt_zero((size_t)np, 0);
     for (int64_t k = 0; k < np; ++k) {
-        if ((size_t)points[k] < h->cst_point_user.size() && h->cst_point_user[(size_t)points[k]]) { pt_zero[(size_t)k] = 1; continue; } // constant: a zero block
+        if ((size_t)points[k] < h->cst.set.points.size() && h->cst.set.points[(size_t)points[k]]) { pt_zero[(size_t)k] = 1; continue; } // constant: a zero block
         const int64_t i = pt_int[(size_t)points[k]];
         sel.push_back(Sel{ SrkCovGroup{ i, 0, 3, (int32_t)(fv * (int64_t)h->cov_pt_frame0[(size_t)i]), 1 }, nf + k });
     }
@@ -2790,7 +2377,7 @@ static int phase_cross_covariance(srk_ba* h, const CovPairArgs& q)
         return block_of[f] = (int32_t)blocks.size() - 1;
     };
     const auto point_block = [&](int64_t user) {
-        if ((size_t)user < h->cst_point_user.size() && h->cst_point_user[(size_t)user]) return (int32_t)-1;
+        if ((size_t)user < h->cst.set.points.size() && h->cst.set.points[(size_t)user]) return (int32_t)-1;
         const int64_t i = pt_int[(size_t)user];
         auto it = block_of.find(d.M + i);
         if (it != block_of.end()) return it->second;
@@ -3643,7 +3230,7 @@ int srk_ba_compute_inplace(srk_ba* h, double f0, int64_t N, double* pts, int32_t
     if (rc != SRK_OK) return rc;
     int result = srk_ba_optimize(h, allowed_err_change, max_hessian_factor, max_iterations, rep);
     if (result < 0) return result;
-    if (!h->cst_set) {
+    if (!h->cst.set.set) {
         rc = srk_ba_download_scene(h, pts, cam_R, cam_T, 1);
         if (rc != SRK_OK) return rc;
         return result;
@@ -3653,9 +3240,9 @@ int srk_ba_compute_inplace(srk_ba* h, double f0, int64_t N, double* pts, int32_t
     rc = srk_ba_download_scene(h, p2.data(), r2.data(), t2.data(), 1);
     if (rc != SRK_OK) return rc;
     for (int64_t i = 0; i < N; ++i)
-        if (h->cst_point_user.empty() || !h->cst_point_user[(size_t)i]) std::memcpy(pts + 3 * i, &p2[(size_t)(3 * i)], 24);
+        if (h->cst.set.points.empty() || !h->cst.set.points[(size_t)i]) std::memcpy(pts + 3 * i, &p2[(size_t)(3 * i)], 24);
     for (int32_t j = 0; j < M; ++j)
-        if (h->cst_frame_user.empty() || !h->cst_frame_user[(size_t)j]) {
+        if (h->cst.set.frames.empty() || !h->cst.set.frames[(size_t)j]) {
             std::memcpy(cam_R + 9 * (int64_t)j, &r2[9 * (size_t)j], 72);
             std::memcpy(cam_T + 3 * (int64_t)j, &t2[3 * (size_t)j], 24);
         }
@@ -4059,7 +3646,7 @@ int srk_ba_download(srk_ba* h, int which, double* dst, int64_t count)
         if ((rc = d2h(ug.data(), h->Ug.p, ug.size() * 8)) != SRK_OK) return rc;
         for (int32_t j = 0; j < d.M; ++j)
             for (int e = 0; e < d.fv; ++e) // (constant frames report 0: their sums in Ug stay unmasked)
-                dst[3 * d.N + d.fv * (int64_t)j + e] = (!h->cst_frame_int.empty() && h->cst_frame_int[(size_t)j]) ? 0.0 : ug[(size_t)(ugs * (int64_t)j + ut + e)];
+                dst[3 * d.N + d.fv * (int64_t)j + e] = (!h->cst.frame_int.empty() && h->cst.frame_int[(size_t)j]) ? 0.0 : ug[(size_t)(ugs * (int64_t)j + ut + e)];
         frames_to_user(h, dst + 3 * d.N, d.fv);
         return SRK_OK;
     }
@@ -4277,12 +3864,12 @@ int srk_ba_set_covisibility(srk_ba* h, const int32_t* min_cv)
             if (min_cv[j] < 0 || min_cv[j] > j) { h->last_error = "min_cv[j] must be in [0, j]"; return SRK_E_ARGS; }
             h->min_cv[(size_t)j] = min_cv[j];
         }
-        for (size_t i = 0; i < h->rp_int_a.size(); ++i) { // the pairs of the relative-pose factors are part of the skyline
-            const int32_t hi = std::max(h->rp_int_a[i], h->rp_int_b[i]), lo = std::min(h->rp_int_a[i], h->rp_int_b[i]);
+        for (size_t i = 0; i < h->rp.int_a.size(); ++i) { // the pairs of the relative-pose factors are part of the skyline
+            const int32_t hi = std::max(h->rp.int_a[i], h->rp.int_b[i]), lo = std::min(h->rp.int_a[i], h->rp.int_b[i]);
             h->min_cv[(size_t)hi] = std::min(h->min_cv[(size_t)hi], lo);
         }
-        for (size_t i = 0; i < h->jp_pair_a.size(); ++i) // so are the coupled pairs of the joint pose priors (lo, hi)
-            h->min_cv[(size_t)h->jp_pair_b[i]] = std::min(h->min_cv[(size_t)h->jp_pair_b[i]], h->jp_pair_a[i]);
+        for (size_t i = 0; i < h->jp.pair_a.size(); ++i) // so are the coupled pairs of the joint pose priors (lo, hi)
+            h->min_cv[(size_t)h->jp.pair_b[i]] = std::min(h->min_cv[(size_t)h->jp.pair_b[i]], h->jp.pair_a[i]);
     } else {
         std::fill(h->min_cv.begin(), h->min_cv.end(), 0);
     }
@@ -4513,91 +4100,56 @@ int srk_ba_set_constant_blocks(srk_ba* h, const uint8_t* frame_const, int32_t n_
 {
     if (!h) return SRK_E_ARGS;
     if (!frame_const && !point_const) {
-        h->cst_set = false;
-        h->cst_keep_gauge = 1;
-        h->cst_frame_user.clear();
-        h->cst_point_user.clear();
+        h->cst.set = SrkConstSetting{};
         return SRK_OK;
     }
     if (keep_gauge != 0 && keep_gauge != 1) { h->last_error = "constant blocks: keep_gauge must be 0 or 1"; return SRK_E_ARGS; }
     if (frame_const && n_frames < 1) { h->last_error = "constant blocks: need at least one frame"; return SRK_E_ARGS; }
     if (point_const && n_points < 0) { h->last_error = "constant blocks: negative number of landmarks"; return SRK_E_ARGS; }
-    if (const char* e = constant_conflict(true, !h->igroup_user.empty(), h->world)) { h->last_error = e; return SRK_E_ARGS; }
+    if (refuse_setting(h, "constant blocks")) return SRK_E_ARGS;
     bool all_frames = frame_const != nullptr, all_points = point_const != nullptr;
     for (int32_t j = 0; frame_const && j < n_frames; ++j) all_frames = all_frames && frame_const[j] != 0;
     for (int64_t i = 0; point_const && i < n_points; ++i) all_points = all_points && point_const[i] != 0;
     if (all_frames && all_points) { h->last_error = "constant blocks: every frame and every landmark is constant, nothing is left to solve"; return SRK_E_ARGS; }
-    h->cst_frame_user.clear();
-    h->cst_point_user.clear();
-    if (frame_const) h->cst_frame_user.assign(frame_const, frame_const + n_frames);
-    if (point_const) h->cst_point_user.assign(point_const, point_const + n_points);
-    for (auto& f : h->cst_frame_user) f = f ? 1 : 0;
-    for (auto& f : h->cst_point_user) f = f ? 1 : 0;
-    h->cst_keep_gauge = keep_gauge;
-    h->cst_set = true;
+    SrkConstSetting& s = h->cst.set;
+    s.frames.clear();
+    s.points.clear();
+    if (frame_const) s.frames.assign(frame_const, frame_const + n_frames);
+    if (point_const) s.points.assign(point_const, point_const + n_points);
+    for (auto& f : s.frames) f = f ? 1 : 0;
+    for (auto& f : s.points) f = f ? 1 : 0;
+    s.keep_gauge = keep_gauge;
+    s.set = true;
     return SRK_OK;
 }
 int srk_ba_constant_blocks(srk_ba* h, uint8_t* frame_const, uint8_t* point_const, int* keep_gauge)
 {
     if (!h) return SRK_E_ARGS;
-    if (keep_gauge) *keep_gauge = h->cst_keep_gauge;
-    if (frame_const && !h->cst_frame_user.empty()) std::memcpy(frame_const, h->cst_frame_user.data(), h->cst_frame_user.size());
-    if (point_const && !h->cst_point_user.empty()) std::memcpy(point_const, h->cst_point_user.data(), h->cst_point_user.size());
-    return h->cst_set ? 1 : 0;
+    if (keep_gauge) *keep_gauge = h->cst.set.keep_gauge;
+    copy_out(frame_const, h->cst.set.frames);
+    copy_out(point_const, h->cst.set.points);
+    return h->cst.set.set ? 1 : 0;
 }
 int srk_ba_constant_counts(srk_ba* h, int32_t* n_frames, int64_t* n_points)
 {
     if (!h) return SRK_E_ARGS;
-    if (n_frames) *n_frames = (int32_t)h->cst_frame_user.size();
-    if (n_points) *n_points = (int64_t)h->cst_point_user.size();
-    return h->cst_set ? 1 : 0;
+    if (n_frames) *n_frames = (int32_t)h->cst.set.frames.size();
+    if (n_points) *n_points = (int64_t)h->cst.set.points.size();
+    return h->cst.set.set ? 1 : 0;
 }
 int srk_ba_constant_pass_ms(srk_ba* h, double* points_ms, double* frames_ms)
 {
-    if (!h || !h->have_scene) return SRK_E_STATE;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->main_stream));
-    for (int sl = 1; sl < SRK_SLOTS; ++sl)
-        if (h->att[sl].stream) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
-    for (int k = 0; k < 2; ++k) {
-        float ms = 0;
-        if (h->cst_timed[k] && hipEventElapsedTime(&ms, h->ev_cst[2 * k], h->ev_cst[2 * k + 1]) != hipSuccess) ms = 0;
-        double* out = k == 0 ? points_ms : frames_ms;
-        if (out) *out = h->cst_timed[k] ? (double)ms : 0.0;
-    }
-    return SRK_OK;
+    double* const out[2] = { points_ms, frames_ms };
+    return pass_ms(h, h ? h->cst.pass : nullptr, 2, out);
 }
 // position priors.  Next upload.
-static const char* check_prior_values(int64_t n, const double* pos, const double* info)
-{
-    for (int64_t i = 0; i < n; ++i) {
-        for (int e = 0; e < 3; ++e)
-            if (!std::isfinite(pos[3 * i + e])) return "position priors: a position is not finite";
-        const double* l = info + 6 * i;
-        double m = 0;
-        for (int e = 0; e < 6; ++e) {
-            if (!std::isfinite(l[e])) return "position priors: an information matrix is not finite";
-            m = std::max(m, std::fabs(l[e]));
-        }
-        // positive semi-definite: every principal minor >= 0 (up to the rounding of a rank-deficient matrix)
-        const double xx = l[0], xy = l[1], xz = l[2], yy = l[3], yz = l[4], zz = l[5];
-        const double t2 = 1e-12 * m * m, t3 = 1e-12 * m * m * m;
-        const double det = xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz);
-        if (xx < 0 || yy < 0 || zz < 0 || xx * yy - xy * xy < -t2 || xx * zz - xz * xz < -t2 || yy * zz - yz * yz < -t2 || det < -t3)
-            return "position priors: an information matrix is not positive semi-definite";
-    }
-    return nullptr;
-}
 int srk_ba_set_position_priors(srk_ba* h, int64_t n_point_priors, const int64_t* point_index, const double* point_pos,
                                const double* point_info, int32_t n_frame_priors, const int32_t* frame_index,
                                const double* frame_centre, const double* frame_info, int keep_gauge)
 {
     if (!h) return SRK_E_ARGS;
     if (n_point_priors == 0 && n_frame_priors == 0) {
-        h->pri_set = false;
-        h->pri_keep_gauge = 1;
-        h->pri_pt_idx.clear(); h->pri_pt_pos.clear(); h->pri_pt_info.clear();
-        h->pri_fr_idx.clear(); h->pri_fr_pos.clear(); h->pri_fr_info.clear();
+        h->pri.set = SrkPriorSetting{};
         return SRK_OK;
     }
     if (keep_gauge != 0 && keep_gauge != 1) { h->last_error = "position priors: keep_gauge must be 0 or 1"; return SRK_E_ARGS; }
@@ -4606,7 +4158,7 @@ int srk_ba_set_position_priors(srk_ba* h, int64_t n_point_priors, const int64_t*
         h->last_error = "position priors: null array";
         return SRK_E_ARGS;
     }
-    if (const char* e = prior_conflict(true, !h->igroup_user.empty(), h->world)) { h->last_error = e; return SRK_E_ARGS; }
+    if (refuse_setting(h, "position priors")) return SRK_E_ARGS;
     for (int64_t i = 0; i < n_point_priors; ++i)
         if (point_index[i] < 0 || point_index[i] > 2147483000LL || (i > 0 && point_index[i - 1] >= point_index[i])) {
             h->last_error = "position priors: landmark indices must be non-negative and strictly ascending";
@@ -4617,37 +4169,36 @@ int srk_ba_set_position_priors(srk_ba* h, int64_t n_point_priors, const int64_t*
             h->last_error = "position priors: frame indices must be non-negative and strictly ascending";
             return SRK_E_ARGS;
         }
-    const char* e = check_prior_values(n_point_priors, point_pos, point_info);
-    if (!e) e = check_prior_values(n_frame_priors, frame_centre, frame_info);
+    const char* e = srk_check_prior_values(n_point_priors, point_pos, point_info);
+    if (!e) e = srk_check_prior_values(n_frame_priors, frame_centre, frame_info);
     if (e) { h->last_error = e; return SRK_E_ARGS; }
-    h->pri_pt_idx.assign(point_index, point_index + n_point_priors);
-    h->pri_pt_pos.assign(point_pos, point_pos + 3 * n_point_priors);
-    h->pri_pt_info.assign(point_info, point_info + 6 * n_point_priors);
-    h->pri_fr_idx.assign(frame_index, frame_index + n_frame_priors);
-    h->pri_fr_pos.assign(frame_centre, frame_centre + 3 * (int64_t)n_frame_priors);
-    h->pri_fr_info.assign(frame_info, frame_info + 6 * (int64_t)n_frame_priors);
-    h->pri_keep_gauge = keep_gauge;
-    h->pri_set = true;
+    SrkPriorSetting& s = h->pri.set;
+    s.pt_idx.assign(point_index, point_index + n_point_priors);
+    s.pt_pos.assign(point_pos, point_pos + 3 * n_point_priors);
+    s.pt_info.assign(point_info, point_info + 6 * n_point_priors);
+    s.fr_idx.assign(frame_index, frame_index + n_frame_priors);
+    s.fr_pos.assign(frame_centre, frame_centre + 3 * (int64_t)n_frame_priors);
+    s.fr_info.assign(frame_info, frame_info + 6 * (int64_t)n_frame_priors);
+    s.keep_gauge = keep_gauge;
+    s.set = true;
     return SRK_OK;
 }
 int srk_ba_position_prior_counts(srk_ba* h, int64_t* n_point_priors, int32_t* n_frame_priors)
 {
     if (!h) return SRK_E_ARGS;
-    if (n_point_priors) *n_point_priors = (int64_t)h->pri_pt_idx.size();
-    if (n_frame_priors) *n_frame_priors = (int32_t)h->pri_fr_idx.size();
-    return h->pri_set ? 1 : 0;
+    if (n_point_priors) *n_point_priors = (int64_t)h->pri.set.pt_idx.size();
+    if (n_frame_priors) *n_frame_priors = (int32_t)h->pri.set.fr_idx.size();
+    return h->pri.set.set ? 1 : 0;
 }
 int srk_ba_position_priors(srk_ba* h, int64_t* point_index, double* point_pos, double* point_info, int32_t* frame_index,
                            double* frame_centre, double* frame_info, int* keep_gauge)
 {
     if (!h) return SRK_E_ARGS;
-    auto out = [](auto* dst, const auto& v) {
-        if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
-    };
-    out(point_index, h->pri_pt_idx); out(point_pos, h->pri_pt_pos); out(point_info, h->pri_pt_info);
-    out(frame_index, h->pri_fr_idx); out(frame_centre, h->pri_fr_pos); out(frame_info, h->pri_fr_info);
-    if (keep_gauge) *keep_gauge = h->pri_keep_gauge;
-    return h->pri_set ? 1 : 0;
+    const SrkPriorSetting& s = h->pri.set;
+    copy_out(point_index, s.pt_idx); copy_out(point_pos, s.pt_pos); copy_out(point_info, s.pt_info);
+    copy_out(frame_index, s.fr_idx); copy_out(frame_centre, s.fr_pos); copy_out(frame_info, s.fr_info);
+    if (keep_gauge) *keep_gauge = s.keep_gauge;
+    return s.set ? 1 : 0;
 }
 int srk_ba_prior_error(srk_ba* h, double* e_points, double* e_frames)
 {
@@ -4655,22 +4206,12 @@ int srk_ba_prior_error(srk_ba* h, double* e_points, double* e_frames)
     if (e_points) *e_points = 0;
     if (e_frames) *e_frames = 0;
     SrkPrior pr;
-    const SrkPrior* prior = position_priors(h, pr);
-    if (!prior) return SRK_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    HIPCHK(h, hipStreamSynchronize(s));
-    const int32_t nb = srk_prior_partials(pr.n_pts, pr.n_frames);
-    DevBuf part;
-    int rc = dev_alloc(h, part, 8 * ((size_t)nb + 2));
-    if (rc != SRK_OK) return rc;
+    if (!position_priors(h, pr)) return SRK_OK;
     double out2[2] = { 0, 0 };
-    srk_launch_prior_error(s, P<double>(h->pts[h->cur]), P<double>(h->cam[h->cur]), pr, P<double>(part), P<double>(part) + nb);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out2, P<double>(part) + nb, 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(part);
-    HIPCHK(h, e);
+    const int rc = error_pass(h, srk_prior_partials(pr.n_pts, pr.n_frames), 2, out2, [&](hipStream_t s, double* partial, double* sums) {
+        srk_launch_prior_error(s, P<double>(h->pts[h->cur]), P<double>(h->cam[h->cur]), pr, partial, sums);
+    });
+    if (rc != SRK_OK) return rc;
     if (e_points) *e_points = out2[0];
     if (e_frames) *e_frames = out2[1];
     return SRK_OK;
@@ -4680,108 +4221,29 @@ int srk_ba_prior_residuals(srk_ba* h, double* d_points, double* d_frames)
     if (!h || !h->have_scene) return SRK_E_STATE;
     // the offsets belong to the setting the resident scene was uploaded with: a setter call since then has not reached the
     // scene (srk_ba_prior_error still sums the uploaded lists), so the two must not be mixed
-    if (h->app_pt_idx != h->pri_pt_idx || h->app_fr_idx != h->pri_fr_idx || h->app_pt_pos != h->pri_pt_pos || h->app_fr_pos != h->pri_fr_pos) {
+    if (!h->pri.app.is(h->pri.set)) {
         h->last_error = "prior_residuals: the position priors were changed after the upload; upload the scene again";
         return SRK_E_STATE;
     }
-    if (h->app_pt_idx.empty() && h->app_fr_idx.empty()) return SRK_OK;
-    const SrkDims& d = h->d;
-    std::vector<double> p((size_t)(3 * d.N)), R((size_t)(9 * (int64_t)d.M)), T((size_t)(3 * (int64_t)d.M));
-    int rc = srk_ba_download_scene(h, p.data(), R.data(), T.data(), 1); // the caller's world coordinates
-    if (rc != SRK_OK) return rc;
-    for (size_t k = 0; d_points && k < h->app_pt_idx.size(); ++k)
-        for (int e = 0; e < 3; ++e) d_points[3 * k + e] = p[(size_t)(3 * h->app_pt_idx[k] + e)] - h->app_pt_pos[3 * k + e];
-    for (size_t k = 0; d_frames && k < h->app_fr_idx.size(); ++k) {
-        const double* r = &R[9 * (size_t)h->app_fr_idx[k]];
-        const double* t = &T[3 * (size_t)h->app_fr_idx[k]];
-        for (int e = 0; e < 3; ++e) d_frames[3 * k + e] = -(r[e] * t[0] + r[3 + e] * t[1] + r[6 + e] * t[2]) - h->app_fr_pos[3 * k + e];
-    }
+    if (h->pri.app.pt_idx.empty() && h->pri.app.fr_idx.empty()) return SRK_OK;
+    WorldScene w(h);
+    if (w.rc != SRK_OK) return w.rc;
+    srk_prior_residuals(h->pri.app, w.pts.data(), w.R.data(), w.T.data(), d_points, d_frames);
     return SRK_OK;
 }
 int srk_ba_prior_pass_ms(srk_ba* h, double* derivative_ms, double* error_ms)
 {
-    if (!h || !h->have_scene) return SRK_E_STATE;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->main_stream));
-    for (int sl = 1; sl < SRK_SLOTS; ++sl)
-        if (h->att[sl].stream) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
-    for (int k = 0; k < 2; ++k) {
-        float ms = 0;
-        if (h->pri_timed[k] && hipEventElapsedTime(&ms, h->ev_pri[2 * k], h->ev_pri[2 * k + 1]) != hipSuccess) ms = 0;
-        double* out = k == 0 ? derivative_ms : error_ms;
-        if (out) *out = h->pri_timed[k] ? (double)ms : 0.0;
-    }
-    return SRK_OK;
+    double* const out[2] = { derivative_ms, error_ms };
+    return pass_ms(h, h ? h->pri.pass : nullptr, 2, out);
 }
 // relative-pose factors.  Next upload.
-// positive semi-definite 6 x 6 (full symmetric A, destroyed): elimination with diagonal pivoting; every pivot must be >= 0 up to
-// the rounding of a rank-deficient matrix, and once the largest remaining diagonal entry is ~0 so must be everything left
-static bool relpose_info_psd(double* A)
-{
-    double m = 0;
-    for (int e = 0; e < 36; ++e) m = std::max(m, std::fabs(A[e]));
-    if (m == 0) return true;
-    for (int k = 0; k < 6; ++k) {
-        int p = k;
-        for (int i = k + 1; i < 6; ++i)
-            if (A[7 * i] > A[7 * p]) p = i;
-        if (A[7 * p] <= 1e-12 * m) {
-            for (int i = k; i < 6; ++i)
-                for (int j = k; j < 6; ++j)
-                    if (i == j ? A[7 * i] < -1e-12 * m : std::fabs(A[6 * i + j]) > 1e-11 * m) return false;
-            return true;
-        }
-        for (int j = 0; j < 6; ++j) std::swap(A[6 * k + j], A[6 * p + j]);
-        for (int i = 0; i < 6; ++i) std::swap(A[6 * i + k], A[6 * i + p]);
-        for (int i = k + 1; i < 6; ++i) {
-            const double f = A[6 * i + k] / A[7 * k];
-            for (int j = k + 1; j < 6; ++j) A[6 * i + j] -= f * A[6 * k + j];
-        }
-    }
-    return true;
-}
-static const char* check_relpose(int32_t n, const int32_t* fa, const int32_t* fb, const double* R, const double* t, const double* info)
-{
-    for (int32_t i = 0; i < n; ++i) {
-        if (fa[i] < 0 || fb[i] < 0) return "relative-pose factors: negative frame index";
-        if (fa[i] == fb[i]) return "relative-pose factors: a factor needs two different frames";
-        if (i > 0) {
-            const int32_t lo0 = std::min(fa[i - 1], fb[i - 1]), hi0 = std::max(fa[i - 1], fb[i - 1]);
-            const int32_t lo1 = std::min(fa[i], fb[i]), hi1 = std::max(fa[i], fb[i]);
-            if (lo0 == lo1 && hi0 == hi1) return "relative-pose factors: a pair of frames is given twice";
-            if (lo1 < lo0 || (lo1 == lo0 && hi1 < hi0)) return "relative-pose factors: pairs must be sorted by (min, max) of their frames";
-        }
-        const double* z = R + 9 * (int64_t)i;
-        for (int e = 0; e < 9; ++e)
-            if (!std::isfinite(z[e])) return "relative-pose factors: a rotation is not finite";
-        for (int e = 0; e < 3; ++e)
-            if (!std::isfinite(t[3 * (int64_t)i + e])) return "relative-pose factors: a translation is not finite";
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) {
-                const double g = z[a] * z[b] + z[3 + a] * z[3 + b] + z[6 + a] * z[6 + b] - (a == b ? 1.0 : 0.0);
-                if (std::fabs(g) > 1e-9) return "relative-pose factors: a measured rotation is not orthogonal to 1e-9";
-            }
-        const double det = z[0] * (z[4] * z[8] - z[5] * z[7]) - z[1] * (z[3] * z[8] - z[5] * z[6]) + z[2] * (z[3] * z[7] - z[4] * z[6]);
-        if (std::fabs(det - 1.0) > 1e-9) return "relative-pose factors: a measured rotation has determinant != 1";
-        double A[36];
-        int k = 0;
-        for (int r = 0; r < 6; ++r)
-            for (int c = r; c < 6; ++c, ++k) {
-                const double v = info[21 * (int64_t)i + k];
-                if (!std::isfinite(v)) return "relative-pose factors: an information matrix is not finite";
-                A[6 * r + c] = A[6 * c + r] = v;
-            }
-        if (!relpose_info_psd(A)) return "relative-pose factors: an information matrix is not positive semi-definite";
-    }
-    return nullptr;
-}
 int srk_ba_check_relative_pose_factors(int32_t n, const int32_t* frame_a, const int32_t* frame_b, const double* rel_R,
                                        const double* rel_t, const double* info, const char** why)
 {
     const char* e = nullptr;
     if (n < 0) e = "relative-pose factors: negative count";
     else if (n > 0 && (!frame_a || !frame_b || !rel_R || !rel_t || !info)) e = "relative-pose factors: null array";
-    else e = check_relpose(n, frame_a, frame_b, rel_R, rel_t, info);
+    else e = srk_check_relpose(n, frame_a, frame_b, rel_R, rel_t, info);
     if (why) *why = e;
     return e ? SRK_E_ARGS : SRK_OK;
 }
@@ -4790,35 +4252,33 @@ int srk_ba_set_relative_pose_factors(srk_ba* h, int32_t n, const int32_t* frame_
 {
     if (!h) return SRK_E_ARGS;
     if (n == 0) {
-        h->rp_set = false;
-        h->rp_a.clear(); h->rp_b.clear(); h->rp_R.clear(); h->rp_t.clear(); h->rp_info.clear();
+        h->rp.set = SrkRelPoseSetting{};
         return SRK_OK;
     }
     const char* e = nullptr;
     if (srk_ba_check_relative_pose_factors(n, frame_a, frame_b, rel_R, rel_t, info, &e) != SRK_OK) { h->last_error = e; return SRK_E_ARGS; }
-    if ((e = relpose_conflict(true, !h->igroup_user.empty(), h->world))) { h->last_error = e; return SRK_E_ARGS; }
-    h->rp_a.assign(frame_a, frame_a + n);
-    h->rp_b.assign(frame_b, frame_b + n);
-    h->rp_R.assign(rel_R, rel_R + 9 * (int64_t)n);
-    h->rp_t.assign(rel_t, rel_t + 3 * (int64_t)n);
-    h->rp_info.assign(info, info + 21 * (int64_t)n);
-    h->rp_set = true;
+    if (refuse_setting(h, "relative-pose factors")) return SRK_E_ARGS;
+    SrkRelPoseSetting& s = h->rp.set;
+    s.a.assign(frame_a, frame_a + n);
+    s.b.assign(frame_b, frame_b + n);
+    s.R.assign(rel_R, rel_R + 9 * (int64_t)n);
+    s.t.assign(rel_t, rel_t + 3 * (int64_t)n);
+    s.info.assign(info, info + 21 * (int64_t)n);
+    s.set = true;
     return SRK_OK;
 }
 int srk_ba_relative_pose_factor_count(srk_ba* h, int32_t* n)
 {
     if (!h) return SRK_E_ARGS;
-    if (n) *n = (int32_t)h->rp_a.size();
-    return h->rp_set ? 1 : 0;
+    if (n) *n = (int32_t)h->rp.set.a.size();
+    return h->rp.set.set ? 1 : 0;
 }
 int srk_ba_relative_pose_factors(srk_ba* h, int32_t* frame_a, int32_t* frame_b, double* rel_R, double* rel_t, double* info)
 {
     if (!h) return SRK_E_ARGS;
-    auto out = [](auto* dst, const auto& v) {
-        if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
-    };
-    out(frame_a, h->rp_a); out(frame_b, h->rp_b); out(rel_R, h->rp_R); out(rel_t, h->rp_t); out(info, h->rp_info);
-    return h->rp_set ? 1 : 0;
+    const SrkRelPoseSetting& s = h->rp.set;
+    copy_out(frame_a, s.a); copy_out(frame_b, s.b); copy_out(rel_R, s.R); copy_out(rel_t, s.t); copy_out(info, s.info);
+    return s.set ? 1 : 0;
 }
 int srk_ba_relative_pose_error(srk_ba* h, double* e_out)
 {
@@ -4826,20 +4286,11 @@ int srk_ba_relative_pose_error(srk_ba* h, double* e_out)
     if (e_out) *e_out = 0;
     SrkRelPose rp;
     if (!relpose_factors(h, rp)) return SRK_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    HIPCHK(h, hipStreamSynchronize(s));
-    const int32_t nb = srk_relpose_partials(rp.n);
-    DevBuf part;
-    int rc = dev_alloc(h, part, 8 * ((size_t)nb + 1));
-    if (rc != SRK_OK) return rc;
     double out = 0;
-    srk_launch_relpose_error(s, P<double>(h->cam[h->cur]), rp, P<double>(part), P<double>(part) + nb);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&out, P<double>(part) + nb, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(part);
-    HIPCHK(h, e);
+    const int rc = error_pass(h, srk_relpose_partials(rp.n), 1, &out, [&](hipStream_t s, double* partial, double* sum) {
+        srk_launch_relpose_error(s, P<double>(h->cam[h->cur]), rp, partial, sum);
+    });
+    if (rc != SRK_OK) return rc;
     if (e_out) *e_out = out;
     return SRK_OK;
 }
@@ -4847,144 +4298,29 @@ int srk_ba_relative_pose_residuals(srk_ba* h, double* r_out)
 {
     if (!h || !h->have_scene) return SRK_E_STATE;
     // the residuals belong to the setting the resident scene was uploaded with: a setter call since then has not reached it
-    if (h->app_rp != h->rp_set || h->app_rp_a != h->rp_a || h->app_rp_b != h->rp_b || h->app_rp_R != h->rp_R || h->app_rp_t != h->rp_t) {
+    if (!h->rp.app.is(h->rp.set)) {
         h->last_error = "relative_pose_residuals: the factors were changed after the upload; upload the scene again";
         return SRK_E_STATE;
     }
-    if (h->app_rp_a.empty() || !r_out) return SRK_OK;
-    const SrkDims& d = h->d;
-    std::vector<double> p((size_t)(3 * d.N)), R((size_t)(9 * (int64_t)d.M)), T((size_t)(3 * (int64_t)d.M));
-    int rc = srk_ba_download_scene(h, p.data(), R.data(), T.data(), 1); // the caller's world coordinates
-    if (rc != SRK_OK) return rc;
-    auto centre = [&](int32_t j, double* C) {
-        const double* r = &R[9 * (size_t)j];
-        const double* t = &T[3 * (size_t)j];
-        for (int e = 0; e < 3; ++e) C[e] = -(r[e] * t[0] + r[3 + e] * t[1] + r[6 + e] * t[2]);
-    };
-    for (size_t k = 0; k < h->app_rp_a.size(); ++k) {
-        const double* ra = &R[9 * (size_t)h->app_rp_a[k]];
-        const double* rb = &R[9 * (size_t)h->app_rp_b[k]];
-        const double* Z = &h->app_rp_R[9 * k];
-        double Ca[3], Cb[3], Pm[9], M[9];
-        centre(h->app_rp_a[k], Ca);
-        centre(h->app_rp_b[k], Cb);
-        double* e = r_out + 6 * k;
-        for (int r = 0; r < 3; ++r)
-            e[r] = ra[3 * r] * (Cb[0] - Ca[0]) + ra[3 * r + 1] * (Cb[1] - Ca[1]) + ra[3 * r + 2] * (Cb[2] - Ca[2]) - h->app_rp_t[3 * k + (size_t)r];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) Pm[3 * r + c] = ra[3 * r] * rb[3 * c] + ra[3 * r + 1] * rb[3 * c + 1] + ra[3 * r + 2] * rb[3 * c + 2];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) M[3 * r + c] = Z[r] * Pm[c] + Z[3 + r] * Pm[3 + c] + Z[6 + r] * Pm[6 + c];
-        // Log as the kernels take it (k_relpose_error)
-        const double v[3] = { 0.5 * (M[7] - M[5]), 0.5 * (M[2] - M[6]), 0.5 * (M[3] - M[1]) };
-        const double s2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], sn = std::sqrt(s2), cs = 0.5 * (M[0] + M[4] + M[8] - 1.0);
-        const double f = (sn < 1e-4 && cs > 0) ? 1.0 + s2 / 6.0 + 3.0 * s2 * s2 / 40.0 : std::atan2(sn, cs) / sn;
-        for (int c = 0; c < 3; ++c) e[3 + c] = f * v[c];
-    }
+    if (h->rp.app.a.empty() || !r_out) return SRK_OK;
+    WorldScene w(h);
+    if (w.rc != SRK_OK) return w.rc;
+    srk_relpose_residuals(h->rp.app, w.R.data(), w.T.data(), r_out);
     return SRK_OK;
 }
 int srk_ba_relative_pose_pass_ms(srk_ba* h, double* derivative_ms, double* couple_ms, double* error_ms)
 {
-    if (!h || !h->have_scene) return SRK_E_STATE;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->main_stream));
-    for (int sl = 1; sl < SRK_SLOTS; ++sl)
-        if (h->att[sl].stream) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
-    double* outs[3] = { derivative_ms, couple_ms, error_ms };
-    for (int k = 0; k < 3; ++k) {
-        float ms = 0;
-        if (h->rp_timed[k] && hipEventElapsedTime(&ms, h->ev_rp[2 * k], h->ev_rp[2 * k + 1]) != hipSuccess) ms = 0;
-        if (outs[k]) *outs[k] = h->rp_timed[k] ? (double)ms : 0.0;
-    }
-    return SRK_OK;
+    double* const out[3] = { derivative_ms, couple_ms, error_ms };
+    return pass_ms(h, h ? h->rp.pass : nullptr, 3, out);
 }
 // joint Gaussian pose priors over sets of frames.  Next upload.
-// positive semi-definite n x n (full symmetric A, destroyed): the pivot rule of relpose_info_psd at n variables
-static bool jprior_info_psd(std::vector<double>& A, int64_t n)
-{
-    double m = 0;
-    for (double v : A) m = std::max(m, std::fabs(v));
-    if (m == 0) return true;
-    for (int64_t k = 0; k < n; ++k) {
-        int64_t p = k;
-        for (int64_t i = k + 1; i < n; ++i)
-            if (A[(n + 1) * i] > A[(n + 1) * p]) p = i;
-        if (A[(n + 1) * p] <= 1e-12 * m) {
-            for (int64_t i = k; i < n; ++i)
-                for (int64_t j = k; j < n; ++j)
-                    if (i == j ? A[(n + 1) * i] < -1e-12 * m : std::fabs(A[n * i + j]) > 1e-11 * m) return false;
-            return true;
-        }
-        for (int64_t j = 0; j < n; ++j) std::swap(A[n * k + j], A[n * p + j]);
-        for (int64_t i = 0; i < n; ++i) std::swap(A[n * i + k], A[n * i + p]);
-        for (int64_t i = k + 1; i < n; ++i) {
-            const double f = A[n * i + k] / A[(n + 1) * k];
-            for (int64_t j = k + 1; j < n; ++j) A[n * i + j] -= f * A[n * k + j];
-        }
-    }
-    return true;
-}
-static const char* check_jprior(int32_t n_sets, const int32_t* set_ptr, const int32_t* frame, const double* lin_R, const double* lin_C,
-                                const double* mean, const double* info, int keep_gauge)
-{
-    if (keep_gauge != 0 && keep_gauge != 1) return "joint pose priors: keep_gauge must be 0 or 1";
-    if (set_ptr[0] != 0) return "joint pose priors: set_ptr must start at 0";
-    int64_t at = 0;
-    std::map<int32_t, std::vector<int32_t>> sets_of; // frame -> the sets that hold it
-    for (int32_t g = 0; g < n_sets; ++g) {
-        const int64_t k = (int64_t)set_ptr[g + 1] - set_ptr[g], n = 6 * k;
-        if (k < 1 || k > SRK_JP_MAX_FRAMES_HOST) return "joint pose priors: a set holds 1 to 16 frames";
-        for (int64_t i = 0; i < k; ++i) {
-            const int64_t q = set_ptr[g] + i;
-            if (frame[q] < 0) return "joint pose priors: negative frame index";
-            if (i > 0 && frame[q - 1] >= frame[q]) return "joint pose priors: the frames of a set must be strictly ascending";
-            const double* z = lin_R + 9 * q;
-            for (int e = 0; e < 9; ++e)
-                if (!std::isfinite(z[e])) return "joint pose priors: a linearisation rotation is not finite";
-            for (int e = 0; e < 3; ++e)
-                if (!std::isfinite(lin_C[3 * q + e])) return "joint pose priors: a linearisation centre is not finite";
-            for (int e = 0; mean && e < 6; ++e)
-                if (!std::isfinite(mean[6 * q + e])) return "joint pose priors: a mean is not finite";
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) {
-                    const double gm = z[a] * z[b] + z[3 + a] * z[3 + b] + z[6 + a] * z[6 + b] - (a == b ? 1.0 : 0.0);
-                    if (std::fabs(gm) > 1e-9) return "joint pose priors: a linearisation rotation is not orthogonal to 1e-9";
-                }
-            const double det = z[0] * (z[4] * z[8] - z[5] * z[7]) - z[1] * (z[3] * z[8] - z[5] * z[6]) + z[2] * (z[3] * z[7] - z[4] * z[6]);
-            if (std::fabs(det - 1.0) > 1e-9) return "joint pose priors: a linearisation rotation has determinant != 1";
-            // two sets may share one frame: every coupling block of the system then has one owner among the sets
-            std::vector<int32_t>& in = sets_of[frame[q]];
-            for (int32_t other : in)
-                for (int64_t i2 = 0; i2 < i; ++i2) {
-                    const std::vector<int32_t>& in2 = sets_of[frame[set_ptr[g] + i2]];
-                    if (std::find(in2.begin(), in2.end(), other) != in2.end()) return "joint pose priors: two sets share more than one frame";
-                }
-            in.push_back(g);
-        }
-        const double* L = info + at;
-        double m = 0;
-        for (int64_t e = 0; e < n * n; ++e) {
-            if (!std::isfinite(L[e])) return "joint pose priors: an information matrix is not finite";
-            m = std::max(m, std::fabs(L[e]));
-        }
-        std::vector<double> A((size_t)(n * n));
-        for (int64_t r = 0; r < n; ++r)
-            for (int64_t c = 0; c < n; ++c) {
-                if (std::fabs(L[r * n + c] - L[c * n + r]) > 1e-12 * m) return "joint pose priors: an information matrix is not symmetric to 1e-12 of its largest entry";
-                A[(size_t)(r * n + c)] = 0.5 * (L[r * n + c] + L[c * n + r]);
-            }
-        if (!jprior_info_psd(A, n)) return "joint pose priors: an information matrix is not positive semi-definite";
-        at += n * n;
-    }
-    return nullptr;
-}
 int srk_ba_check_joint_pose_priors(int32_t n_sets, const int32_t* set_ptr, const int32_t* frame, const double* lin_R, const double* lin_C,
                                    const double* mean, const double* info, int keep_gauge, const char** why)
 {
     const char* e = nullptr;
     if (n_sets < 0) e = "joint pose priors: negative count";
     else if (n_sets > 0 && (!set_ptr || !frame || !lin_R || !lin_C || !info)) e = "joint pose priors: null array";
-    else if (n_sets > 0) e = check_jprior(n_sets, set_ptr, frame, lin_R, lin_C, mean, info, keep_gauge);
+    else if (n_sets > 0) e = srk_check_jprior(n_sets, set_ptr, frame, lin_R, lin_C, mean, info, keep_gauge);
     if (why) *why = e;
     return e ? SRK_E_ARGS : SRK_OK;
 }
@@ -4993,54 +4329,46 @@ int srk_ba_set_joint_pose_priors(srk_ba* h, int32_t n_sets, const int32_t* set_p
 {
     if (!h) return SRK_E_ARGS;
     if (n_sets == 0) {
-        h->jp_set = false;
-        h->jp_keep_gauge = 1;
-        h->jp_ptr.clear(); h->jp_frame.clear(); h->jp_R.clear(); h->jp_C.clear(); h->jp_mean.clear(); h->jp_info.clear();
+        h->jp.set = SrkJPriorSetting{};
         return SRK_OK;
     }
     const char* e = nullptr;
     if (srk_ba_check_joint_pose_priors(n_sets, set_ptr, frame, lin_R, lin_C, mean, info, keep_gauge, &e) != SRK_OK) { h->last_error = e; return SRK_E_ARGS; }
-    if ((e = jprior_conflict(true, !h->igroup_user.empty(), h->world))) { h->last_error = e; return SRK_E_ARGS; }
+    if (refuse_setting(h, "joint pose priors")) return SRK_E_ARGS;
     const int64_t nq = set_ptr[n_sets];
     int64_t ni = 0;
     for (int32_t g = 0; g < n_sets; ++g) ni += 36 * (int64_t)(set_ptr[g + 1] - set_ptr[g]) * (set_ptr[g + 1] - set_ptr[g]);
-    h->jp_ptr.assign(set_ptr, set_ptr + n_sets + 1);
-    h->jp_frame.assign(frame, frame + nq);
-    h->jp_R.assign(lin_R, lin_R + 9 * nq);
-    h->jp_C.assign(lin_C, lin_C + 3 * nq);
-    if (mean) h->jp_mean.assign(mean, mean + 6 * nq);
-    else h->jp_mean.assign((size_t)(6 * nq), 0.0);
-    h->jp_info.assign(info, info + ni);
-    int64_t at = 0;
-    for (int32_t g = 0; g < n_sets; ++g) { // stored symmetrised
-        const int64_t n = 6 * (int64_t)(set_ptr[g + 1] - set_ptr[g]);
-        double* L = h->jp_info.data() + at;
-        for (int64_t r = 0; r < n; ++r)
-            for (int64_t c = r + 1; c < n; ++c) L[r * n + c] = L[c * n + r] = 0.5 * (L[r * n + c] + L[c * n + r]);
-        at += n * n;
-    }
-    h->jp_keep_gauge = keep_gauge;
-    h->jp_set = true;
+    SrkJPriorSetting& s = h->jp.set;
+    s.ptr.assign(set_ptr, set_ptr + n_sets + 1);
+    s.frame.assign(frame, frame + nq);
+    s.R.assign(lin_R, lin_R + 9 * nq);
+    s.C.assign(lin_C, lin_C + 3 * nq);
+    if (mean) s.mean.assign(mean, mean + 6 * nq);
+    else s.mean.assign((size_t)(6 * nq), 0.0);
+    s.info.assign(info, info + ni);
+    for (int32_t g = 0; g < n_sets; ++g) // stored symmetrised
+        srk_symmetrise(const_cast<double*>(s.info_of((size_t)g)), 6 * (int64_t)(set_ptr[g + 1] - set_ptr[g]));
+    s.keep_gauge = keep_gauge;
+    s.set = true;
     return SRK_OK;
 }
 int srk_ba_joint_pose_prior_counts(srk_ba* h, int32_t* n_sets, int32_t* n_frames, int64_t* n_info)
 {
     if (!h) return SRK_E_ARGS;
-    if (n_sets) *n_sets = h->jp_set ? (int32_t)h->jp_ptr.size() - 1 : 0;
-    if (n_frames) *n_frames = (int32_t)h->jp_frame.size();
-    if (n_info) *n_info = (int64_t)h->jp_info.size();
-    return h->jp_set ? 1 : 0;
+    const SrkJPriorSetting& s = h->jp.set;
+    if (n_sets) *n_sets = s.set ? (int32_t)s.ptr.size() - 1 : 0;
+    if (n_frames) *n_frames = (int32_t)s.frame.size();
+    if (n_info) *n_info = (int64_t)s.info.size();
+    return s.set ? 1 : 0;
 }
 int srk_ba_joint_pose_priors(srk_ba* h, int32_t* set_ptr, int32_t* frame, double* lin_R, double* lin_C, double* mean, double* info,
                              int* keep_gauge)
 {
     if (!h) return SRK_E_ARGS;
-    auto out = [](auto* dst, const auto& v) {
-        if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
-    };
-    out(set_ptr, h->jp_ptr); out(frame, h->jp_frame); out(lin_R, h->jp_R); out(lin_C, h->jp_C); out(mean, h->jp_mean); out(info, h->jp_info);
-    if (keep_gauge) *keep_gauge = h->jp_keep_gauge;
-    return h->jp_set ? 1 : 0;
+    const SrkJPriorSetting& s = h->jp.set;
+    copy_out(set_ptr, s.ptr); copy_out(frame, s.frame); copy_out(lin_R, s.R); copy_out(lin_C, s.C); copy_out(mean, s.mean); copy_out(info, s.info);
+    if (keep_gauge) *keep_gauge = s.keep_gauge;
+    return s.set ? 1 : 0;
 }
 int srk_ba_joint_pose_prior_error(srk_ba* h, double* e_out)
 {
@@ -5048,20 +4376,11 @@ int srk_ba_joint_pose_prior_error(srk_ba* h, double* e_out)
     if (e_out) *e_out = 0;
     SrkJointPrior jp;
     if (!joint_priors(h, jp)) return SRK_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    HIPCHK(h, hipStreamSynchronize(s));
-    const int32_t nb = srk_jprior_partials(jp.n_sets);
-    DevBuf part;
-    int rc = dev_alloc(h, part, 8 * ((size_t)nb + 1));
-    if (rc != SRK_OK) return rc;
     double out = 0;
-    srk_launch_jprior_error(s, P<double>(h->cam[h->cur]), jp, P<double>(part), P<double>(part) + nb);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&out, P<double>(part) + nb, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(part);
-    HIPCHK(h, e);
+    const int rc = error_pass(h, srk_jprior_partials(jp.n_sets), 1, &out, [&](hipStream_t s, double* partial, double* sum) {
+        srk_launch_jprior_error(s, P<double>(h->cam[h->cur]), jp, partial, sum);
+    });
+    if (rc != SRK_OK) return rc;
     if (e_out) *e_out = out;
     return SRK_OK;
 }
@@ -5069,48 +4388,20 @@ int srk_ba_joint_pose_prior_residuals(srk_ba* h, double* r_out)
 {
     if (!h || !h->have_scene) return SRK_E_STATE;
     // the residuals belong to the setting the resident scene was uploaded with: a setter call since then has not reached it
-    if (h->app_jp != h->jp_set || h->app_jp_ptr != h->jp_ptr || h->app_jp_frame != h->jp_frame || h->app_jp_R != h->jp_R ||
-        h->app_jp_C != h->jp_C || h->app_jp_mean != h->jp_mean) {
+    if (!h->jp.app.is(h->jp.set)) {
         h->last_error = "joint_pose_prior_residuals: the priors were changed after the upload; upload the scene again";
         return SRK_E_STATE;
     }
-    if (h->app_jp_frame.empty() || !r_out) return SRK_OK;
-    const SrkDims& d = h->d;
-    std::vector<double> p((size_t)(3 * d.N)), R((size_t)(9 * (int64_t)d.M)), T((size_t)(3 * (int64_t)d.M));
-    int rc = srk_ba_download_scene(h, p.data(), R.data(), T.data(), 1); // the caller's world coordinates
-    if (rc != SRK_OK) return rc;
-    for (size_t q = 0; q < h->app_jp_frame.size(); ++q) {
-        const double* r = &R[9 * (size_t)h->app_jp_frame[q]];
-        const double* t = &T[3 * (size_t)h->app_jp_frame[q]];
-        const double* Rb = &h->app_jp_R[9 * q];
-        double* e = r_out + 6 * q;
-        double M[9];
-        for (int c = 0; c < 3; ++c) e[c] = -(r[c] * t[0] + r[3 + c] * t[1] + r[6 + c] * t[2]) - h->app_jp_C[3 * q + (size_t)c];
-        for (int a = 0; a < 3; ++a) // M = R^T Rbar
-            for (int b = 0; b < 3; ++b) M[3 * a + b] = r[a] * Rb[b] + r[3 + a] * Rb[3 + b] + r[6 + a] * Rb[6 + b];
-        // Log as the kernels take it (k_jprior_error)
-        const double v[3] = { 0.5 * (M[7] - M[5]), 0.5 * (M[2] - M[6]), 0.5 * (M[3] - M[1]) };
-        const double s2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], sn = std::sqrt(s2), cs = 0.5 * (M[0] + M[4] + M[8] - 1.0);
-        const double f = (sn < 1e-4 && cs > 0) ? 1.0 + s2 / 6.0 + 3.0 * s2 * s2 / 40.0 : std::atan2(sn, cs) / sn;
-        for (int c = 0; c < 3; ++c) e[3 + c] = f * v[c];
-        for (int c = 0; c < 6; ++c) e[c] -= h->app_jp_mean[6 * q + (size_t)c];
-    }
+    if (h->jp.app.frame.empty() || !r_out) return SRK_OK;
+    WorldScene w(h);
+    if (w.rc != SRK_OK) return w.rc;
+    srk_jprior_residuals(h->jp.app, w.R.data(), w.T.data(), r_out);
     return SRK_OK;
 }
 int srk_ba_joint_pose_prior_pass_ms(srk_ba* h, double* derivative_ms, double* couple_ms, double* error_ms)
 {
-    if (!h || !h->have_scene) return SRK_E_STATE;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->main_stream));
-    for (int sl = 1; sl < SRK_SLOTS; ++sl)
-        if (h->att[sl].stream) HIPCHK(h, hipStreamSynchronize(h->att[sl].stream));
-    double* outs[3] = { derivative_ms, couple_ms, error_ms };
-    for (int k = 0; k < 3; ++k) {
-        float ms = 0;
-        if (h->jp_timed[k] && hipEventElapsedTime(&ms, h->ev_jp[2 * k], h->ev_jp[2 * k + 1]) != hipSuccess) ms = 0;
-        if (outs[k]) *outs[k] = h->jp_timed[k] ? (double)ms : 0.0;
-    }
-    return SRK_OK;
+    double* const out[3] = { derivative_ms, couple_ms, error_ms };
+    return pass_ms(h, h ? h->jp.pass : nullptr, 3, out);
 }
 int64_t srk_ba_schur_fallback_landmarks(srk_ba* h)
 {
@@ -5153,29 +4444,14 @@ int srk_ba_observation_weights(srk_ba* h, double* w, int64_t count)
         std::fill(w, w + d.O, 1.0);
         return SRK_OK;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    HIPCHK(h, hipStreamSynchronize(s));
-    DevBuf wd;
-    int rc = dev_alloc(h, wd, (size_t)(8 * d.O));
-    if (rc != SRK_OK) return rc;
     std::vector<double> wi((size_t)d.O);
-    srk_launch_obs_weights(s, d, P<double>(h->pts[h->cur]), P<double>(h->cam[h->cur]), P<int32_t>(h->obs_frame),
-                           P<int32_t>(h->obs_pt), P<double>(h->obs_uv), *L, P<double>(wd));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(wi.data(), wd.p, (size_t)(8 * d.O), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(wd);
-    HIPCHK(h, e);
-    // internal order -> the caller's: landmark perm, observation rank inside the landmark (as SRK_BUF_POINT_FRAME)
-    for (int64_t i = 0; i < d.N; ++i) {
-        const int64_t oi = h->row_ptr_int[(size_t)i], ou = h->row_ptr_user[(size_t)h->perm[(size_t)i]];
-        const int64_t cnt = h->row_ptr_int[(size_t)i + 1] - oi;
-        for (int64_t a = 0; a < cnt; ++a) {
-            const int64_t ai = h->obs_rank.empty() ? a : h->obs_rank[(size_t)(ou + a)];
-            w[ou + a] = wi[(size_t)(oi + ai)];
-        }
-    }
+    const int rc = error_pass(h, 0, (int64_t)d.O, wi.data(), [&](hipStream_t s, double*, double* out) {
+        srk_launch_obs_weights(s, d, P<double>(h->pts[h->cur]), P<double>(h->cam[h->cur]), P<int32_t>(h->obs_frame),
+                               P<int32_t>(h->obs_pt), P<double>(h->obs_uv), *L, out);
+    });
+    if (rc != SRK_OK) return rc;
+    const std::vector<int64_t> at = srk_observation_places(*h, d.N, d.O); // internal order -> the caller's
+    for (int64_t o = 0; o < d.O; ++o) w[o] = wi[(size_t)at[(size_t)o]];
     return SRK_OK;
 }
 
@@ -5187,8 +4463,8 @@ int srk_ba_set_observation_information(srk_ba* h, const double* q, int64_t count
 {
     if (!h) return SRK_E_ARGS;
     if (!q) {
-        h->info_user.clear();
-        h->info_on = false;
+        h->obs_info.set.q.clear();
+        h->obs_info.on = false;
         return SRK_OK;
     }
     try {
@@ -5204,17 +4480,17 @@ int srk_ba_set_observation_information(srk_ba* h, const double* q, int64_t count
         }
         std::vector<double> keep(q, q + count);
         if (!h->have_scene) {
-            h->info_user.swap(keep);
+            h->obs_info.set.q.swap(keep);
             return SRK_OK;
         }
         for (auto& a : h->att) // nothing of an earlier call may still read the values on the device
             if (a.allocated && a.stream) HIPCHK(h, hipStreamSynchronize(a.stream));
-        h->info_user.swap(keep);
-        const bool was_on = h->info_on;
+        h->obs_info.set.q.swap(keep);
+        const bool was_on = h->obs_info.on;
         const int rc = apply_information(h);
         if (rc != SRK_OK) { // (device failure: back to the previous values)
-            h->info_user.swap(keep);
-            h->info_on = false;
+            h->obs_info.set.q.swap(keep);
+            h->obs_info.on = false;
             if (was_on) apply_information(h);
         }
         return rc;
@@ -5227,10 +4503,10 @@ int srk_ba_set_observation_information(srk_ba* h, const double* q, int64_t count
 int srk_ba_observation_information(srk_ba* h, double* q, int64_t count)
 {
     if (!h || !q) return SRK_E_ARGS;
-    const int64_t want = !h->info_user.empty() ? (int64_t)h->info_user.size() : (h->have_scene ? h->d.O : count);
+    const int64_t want = !h->obs_info.set.q.empty() ? (int64_t)h->obs_info.set.q.size() : (h->have_scene ? h->d.O : count);
     if (count != want) { h->last_error = "observation_information: count must be the number of observations"; return SRK_E_ARGS; }
-    if (h->info_user.empty()) std::fill(q, q + count, 1.0);
-    else std::copy(h->info_user.begin(), h->info_user.end(), q);
+    if (h->obs_info.set.q.empty()) std::fill(q, q + count, 1.0);
+    else std::copy(h->obs_info.set.q.begin(), h->obs_info.set.q.end(), q);
     return SRK_OK;
 }
 // the raw residuals f0 (ex, ey) in pixels of the resident scene's observations, [count][2] in the caller's order; neither
@@ -5241,29 +4517,14 @@ int srk_ba_observation_residuals(srk_ba* h, double* exy_pixels, int64_t count)
     const SrkDims& d = h->d;
     if (count != d.O) { h->last_error = "observation_residuals: count must be the number of observations"; return SRK_E_ARGS; }
     if (d.O == 0) return SRK_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->main_stream;
-    HIPCHK(h, hipStreamSynchronize(s));
-    DevBuf ed;
-    int rc = dev_alloc(h, ed, (size_t)(16 * d.O));
-    if (rc != SRK_OK) return rc;
     std::vector<double> ei((size_t)(2 * d.O));
-    srk_launch_obs_residuals(s, d, P<double>(h->pts[h->cur]), P<double>(h->cam[h->cur]), P<int32_t>(h->obs_frame),
-                             P<int32_t>(h->obs_pt), P<double>(h->obs_uv), P<double>(ed));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(ei.data(), ed.p, (size_t)(16 * d.O), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(ed);
-    HIPCHK(h, e);
-    for (int64_t i = 0; i < d.N; ++i) { // internal order -> the caller's, as srk_ba_observation_weights
-        const int64_t oi = h->row_ptr_int[(size_t)i], ou = h->row_ptr_user[(size_t)h->perm[(size_t)i]];
-        const int64_t cnt = h->row_ptr_int[(size_t)i + 1] - oi;
-        for (int64_t a = 0; a < cnt; ++a) {
-            const int64_t ai = h->obs_rank.empty() ? a : h->obs_rank[(size_t)(ou + a)];
-            exy_pixels[2 * (ou + a)] = ei[(size_t)(2 * (oi + ai))];
-            exy_pixels[2 * (ou + a) + 1] = ei[(size_t)(2 * (oi + ai) + 1)];
-        }
-    }
+    const int rc = error_pass(h, 0, 2 * (int64_t)d.O, ei.data(), [&](hipStream_t s, double*, double* out) {
+        srk_launch_obs_residuals(s, d, P<double>(h->pts[h->cur]), P<double>(h->cam[h->cur]), P<int32_t>(h->obs_frame),
+                                 P<int32_t>(h->obs_pt), P<double>(h->obs_uv), out);
+    });
+    if (rc != SRK_OK) return rc;
+    const std::vector<int64_t> at = srk_observation_places(*h, d.N, d.O); // internal order -> the caller's
+    for (int64_t o = 0; o < d.O; ++o) std::memcpy(exy_pixels + 2 * o, &ei[(size_t)(2 * at[(size_t)o])], 16);
     return SRK_OK;
 }
 
