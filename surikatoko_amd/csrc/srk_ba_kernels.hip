@@ -2880,25 +2880,41 @@ void srk_launch_prior_error(hipStream_t s, const double* pts, const double* cam,
 
 // ------------------------------------------------------------------ relative-pose factors: residual, Jacobians, energy pass
 // (srk_ba_set_relative_pose_factors)
-// rotation vector of the rotation M (angle < pi): the antisymmetric part is sin(angle) axis; the series of asin(x) / x where
-// the angle is small
+// rotation vector of the rotation M (angle <= pi): the antisymmetric part is sin(angle) axis; the series of asin(x) / x where
+// the angle is small.  Towards pi that part vanishes, so where the cosine is below -0.9 the axis comes from the symmetric part,
+// (M + M^T) / 2 = cos I + (1 - cos) a a^T: the column of the largest diagonal entry (there (1 - cos) a_c^2 >= 1.9 / 3),
+// normalised, with the sign of the antisymmetric part (at pi itself either sign is the same rotation)
 __device__ __forceinline__ void rp_log(const double M[9], double phi[3])
 {
     const double v[3] = { 0.5 * (M[7] - M[5]), 0.5 * (M[2] - M[6]), 0.5 * (M[3] - M[1]) };
     const double s2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], sn = sqrt(s2), cs = 0.5 * (M[0] + M[4] + M[8] - 1.0);
+    if (cs < -0.9) {
+        double a[3];
+        if (M[0] >= M[4] && M[0] >= M[8]) { a[0] = M[0] - cs; a[1] = 0.5 * (M[3] + M[1]); a[2] = 0.5 * (M[6] + M[2]); }
+        else if (M[4] >= M[8]) { a[0] = 0.5 * (M[1] + M[3]); a[1] = M[4] - cs; a[2] = 0.5 * (M[7] + M[5]); }
+        else { a[0] = 0.5 * (M[2] + M[6]); a[1] = 0.5 * (M[5] + M[7]); a[2] = M[8] - cs; }
+        const double t = atan2(sn, cs);
+        const double f = (a[0] * v[0] + a[1] * v[1] + a[2] * v[2] < 0 ? -t : t) / sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        for (int e = 0; e < 3; ++e) phi[e] = f * a[e];
+        return;
+    }
     const double k = (sn < 1e-4 && cs > 0) ? 1.0 + s2 / 6.0 + 3.0 * s2 * s2 / 40.0 : atan2(sn, cs) / sn;
     for (int e = 0; e < 3; ++e) phi[e] = k * v[e];
 }
-// inverse right Jacobian of SO(3) at phi: I + [phi]x / 2 + k [phi]x^2, k = 1 / t^2 - (1 + cos t) / (2 t sin t) -> 1 / 12 + t^2 / 720
+// the coefficient of [phi]x^2 in the inverse Jacobians of SO(3) at the squared angle t2: 1 / t^2 - (1 + cos t) / (2 t sin t)
+// -> 1 / 12 + t^2 / 720; from 1.5 rad on in the half-angle form 1 / t^2 - 1 / (2 t tan(t / 2)), which does not cancel
+// towards pi (at pi it is 1 / pi^2)
+__device__ __forceinline__ double rp_jk(double t2)
+{
+    if (t2 < 1e-6) return 1.0 / 12.0 + t2 / 720.0;
+    const double t = sqrt(t2);
+    if (t2 >= 2.25) return 1.0 / t2 - 1.0 / (2.0 * t * tan(0.5 * t));
+    return 1.0 / t2 - (1.0 + cos(t)) / (2.0 * t * sin(t));
+}
+// inverse right Jacobian of SO(3) at phi: I + [phi]x / 2 + k [phi]x^2
 __device__ __forceinline__ void rp_jrinv(const double p[3], double J[9])
 {
-    const double t2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
-    double k;
-    if (t2 < 1e-6) k = 1.0 / 12.0 + t2 / 720.0;
-    else {
-        const double t = sqrt(t2);
-        k = 1.0 / t2 - (1.0 + cos(t)) / (2.0 * t * sin(t));
-    }
+    const double t2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2], k = rp_jk(t2);
     // [p]x^2 = p p^T - t2 I
     J[0] = 1.0 + k * (p[0] * p[0] - t2); J[1] = -0.5 * p[2] + k * p[0] * p[1]; J[2] = 0.5 * p[1] + k * p[0] * p[2];
     J[3] = 0.5 * p[2] + k * p[0] * p[1]; J[4] = 1.0 + k * (p[1] * p[1] - t2); J[5] = -0.5 * p[0] + k * p[1] * p[2];
@@ -2983,13 +2999,7 @@ static_assert(SRK_JP_MAX_FRAMES_HOST == 16, "the shared arrays of the joint-prio
 // inverse left Jacobian of SO(3) at phi: I - [phi]x / 2 + k [phi]x^2, k as in rp_jrinv
 __device__ __forceinline__ void jp_jlinv(const double p[3], double J[9])
 {
-    const double t2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
-    double k;
-    if (t2 < 1e-6) k = 1.0 / 12.0 + t2 / 720.0;
-    else {
-        const double t = sqrt(t2);
-        k = 1.0 / t2 - (1.0 + cos(t)) / (2.0 * t * sin(t));
-    }
+    const double t2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2], k = rp_jk(t2);
     J[0] = 1.0 + k * (p[0] * p[0] - t2); J[1] = 0.5 * p[2] + k * p[0] * p[1]; J[2] = -0.5 * p[1] + k * p[0] * p[2];
     J[3] = -0.5 * p[2] + k * p[0] * p[1]; J[4] = 1.0 + k * (p[1] * p[1] - t2); J[5] = 0.5 * p[0] + k * p[1] * p[2];
     J[6] = 0.5 * p[1] + k * p[0] * p[2]; J[7] = -0.5 * p[0] + k * p[1] * p[2]; J[8] = 1.0 + k * (p[2] * p[2] - t2);

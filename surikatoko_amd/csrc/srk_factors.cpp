@@ -532,11 +532,22 @@ static void centre(const double* R, const double* T, int32_t j, double* C)
     const double* t = T + 3 * (size_t)j;
     for (int e = 0; e < 3; ++e) C[e] = -(r[e] * t[0] + r[3 + e] * t[1] + r[6 + e] * t[2]);
 }
-// Log of a rotation matrix as the kernels take it (k_relpose_error, k_jprior_error): must stay in step with theirs
+// Log of a rotation matrix as the kernels take it (rp_log of k_relpose_error, k_jprior_error): must stay in step with theirs,
+// the path near pi (cosine below -0.9: the axis from the symmetric part) included
 static void so3_log(const double* M, double* w)
 {
     const double v[3] = { 0.5 * (M[7] - M[5]), 0.5 * (M[2] - M[6]), 0.5 * (M[3] - M[1]) };
     const double s2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], sn = std::sqrt(s2), cs = 0.5 * (M[0] + M[4] + M[8] - 1.0);
+    if (cs < -0.9) {
+        double a[3];
+        if (M[0] >= M[4] && M[0] >= M[8]) { a[0] = M[0] - cs; a[1] = 0.5 * (M[3] + M[1]); a[2] = 0.5 * (M[6] + M[2]); }
+        else if (M[4] >= M[8]) { a[0] = 0.5 * (M[1] + M[3]); a[1] = M[4] - cs; a[2] = 0.5 * (M[7] + M[5]); }
+        else { a[0] = 0.5 * (M[2] + M[6]); a[1] = 0.5 * (M[5] + M[7]); a[2] = M[8] - cs; }
+        const double t = std::atan2(sn, cs);
+        const double f = (a[0] * v[0] + a[1] * v[1] + a[2] * v[2] < 0 ? -t : t) / std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        for (int c = 0; c < 3; ++c) w[c] = f * a[c];
+        return;
+    }
     const double f = (sn < 1e-4 && cs > 0) ? 1.0 + s2 / 6.0 + 3.0 * s2 * s2 / 40.0 : std::atan2(sn, cs) / sn;
     for (int c = 0; c < 3; ++c) w[c] = f * v[c];
 }

@@ -132,7 +132,8 @@ SrkJPriorTables srk_build_jprior(const SrkJPriorSetting& s, const SrkFactorSelec
                                  const SrkPlanKept& plan, const SrkFactorDims& d);
 
 // ---- residuals in the caller's units, from a downloaded scene (the caller's world coordinates) and the snapshot of its upload.
-// The SO(3) logarithm is the kernels' (k_relpose_error, k_jprior_error): series below sin = 1e-4 at a positive cosine, atan2 else.
+// The SO(3) logarithm is the kernels' (k_relpose_error, k_jprior_error): series below sin = 1e-4 at a positive cosine, the axis
+// from the symmetric part at a cosine below -0.9 (valid up to and at pi), atan2 over the antisymmetric part else.
 void srk_prior_residuals(const SrkPriorApplied& s, const double* pts, const double* R, const double* T, double* d_points /* [n][3] or NULL */,
                          double* d_frames /* [n][3] or NULL */);
 void srk_relpose_residuals(const SrkRelPoseApplied& s, const double* R, const double* T, double* r_out /* [n][6] */);

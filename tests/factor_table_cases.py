@@ -20,6 +20,7 @@ import prior_cases as pc
 import prior_ref as pref
 import relpose_cases as rc
 import relpose_ref as rr
+import so3_ref as so3
 
 
 def _case(sc, f0, fv=10, reorder=-1, info=None, const=None, pri=None, fac=None, sets=None):
@@ -175,11 +176,40 @@ BUILDERS = {
 NAMES = list(BUILDERS)
 _cache = {}
 
+# The residual functions over the whole range of rotation angles (tests/test_so3_cpu.py): every angle of so3_ref.SWEEP about
+# eight axes, 15 (angle, axis) combinations a case -- one factor on each of the 15 pairs of the six frames of nf2_short_runs in
+# a rotated world, every third pair given backwards, and one slot each in the sets of jointprior_cases.sets_for_slots, with a
+# mean.  These cases have no entry in the parent commit's golden tables and are not in NAMES.
+SO3_AXES = 8
+SO3_PER_CASE = 15
+
+
+def so3_combinations():
+    """[(angle, axis)]: so3_ref.SWEEP x so3_ref.axes(SO3_AXES), angle-major"""
+    return [(ang, ax) for ang in so3.SWEEP for ax in so3.axes(SO3_AXES)]
+
+
+def _so3_sweep(part):
+    combos = so3_combinations()[SO3_PER_CASE * part:SO3_PER_CASE * (part + 1)]
+    sc, f0 = cc.scene(rc.SWEEP_SCENE)
+    sc = pc.rotated(sc)
+    n = len(combos)
+    pairs = [(a, b) for a in range(sc.M) for b in range(a + 1, sc.M)][:n]
+    pairs = [(b, a) if k % 3 == 2 else (a, b) for k, (a, b) in enumerate(pairs)]
+    fac = rc.factors_for(sc, pairs, "diag", angle=0.0)
+    for k, (ang, ax) in enumerate(combos):  # (the pairs above are already in the order factors_for sorts them into)
+        fac.Z[k] = rr.relative_pose(sc, int(fac.a[k]), int(fac.b[k]))[0] @ so3.exp(ang * ax).T
+    return _case(sc, f0, fac=fac, sets=(jc.sets_for_slots(sc, [ang * ax for ang, ax in combos]), 1))
+
+
+SO3_NAMES = [f"so3_sweep_{part:02d}" for part in range(-(-len(so3.SWEEP) * SO3_AXES // SO3_PER_CASE))]
+SO3_BUILDERS = {name: (lambda part=part: _so3_sweep(part)) for part, name in enumerate(SO3_NAMES)}
+
 
 def case(name):
     """built once, not to be changed by the caller"""
     if name not in _cache:
-        _cache[name] = BUILDERS[name]()
+        _cache[name] = (BUILDERS[name] if name in BUILDERS else SO3_BUILDERS[name])()
     return _cache[name]
 
 

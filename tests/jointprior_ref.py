@@ -22,11 +22,12 @@ import constant_ref as kref
 import lm_ref
 import prior_ref as pref
 import relpose_ref as rr
+import so3_ref as so3
 
 
 def jl_inv(phi):
-    """inverse left Jacobian of SO(3): Log(Exp(d) Exp(phi)) = phi + Jl^-1(phi) d + O(d^2)"""
-    return rr.jr_inv(phi).T
+    """inverse left Jacobian of SO(3): Log(Exp(d) Exp(phi)) = phi + Jl^-1(phi) d + O(d^2) (tests/so3_ref.py)"""
+    return so3.jl_inv(phi)
 
 
 class Sets:

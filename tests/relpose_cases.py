@@ -12,13 +12,15 @@ Information: E is in (pix / f0)^2 with f0 = 600, and the scenes' extent is about
 block (hundreds of observations) is of order 1000 and its rotation block of the same order times the squared distance to the
 landmarks.  L_tt = 100 per squared extent and L_rr = 100 put 2 J^T L J at a tenth of the blocks they are added to: neither term
 drowns the other in the sums the comparisons look at.  The measurements are the scene's own relative poses moved by a seeded
-offset of up to 5e-3 (of the extent, and radians), so that every factor gradient is non-zero."""
+offset of up to 5e-3 (of the extent, and radians), so that every factor gradient is non-zero.  Those residual rotations sit
+between 1e-3 and 9e-3 rad; sweep_case, pi_case and residual_sweep put them at every angle of so3_ref.SWEEP and at pi."""
 import numpy as np
 
 import surikatoko_amd as sa
 import constant_cases as cc
 import prior_cases as pc
 import relpose_ref as rr
+import so3_ref as so3
 
 L_T = 100.0
 L_R = 100.0
@@ -44,9 +46,12 @@ def chain(M):
     return [(j, j + 1) for j in range(M - 1)]
 
 
-def factors_for(sc, pairs, kind="diag", seed=29, offset=OFFSET):
+def factors_for(sc, pairs, kind="diag", seed=29, offset=OFFSET, angle=None, axes=None):
     """factors on the given pairs (each as given: (a, b) in that direction), sorted by (min, max), measuring the scene's own
-    relative poses moved by a seeded offset; in the scene's coordinates"""
+    relative poses moved by a seeded offset; in the scene's coordinates.  With angle the rotation is not moved by that offset:
+    Z = P Exp(phi)^T with P the scene's own R_a R_b^T and |phi| = angle about a seeded axis per factor (or axes[k]), so the
+    rotation residual Log(Z^T P) is phi up to the rounding of the two products, in any world coordinates; the translation
+    parts are moved as without angle."""
     pairs = sorted(pairs, key=lambda p: (min(p), max(p)))
     rs = np.random.RandomState(seed)
     n = len(pairs)
@@ -56,6 +61,10 @@ def factors_for(sc, pairs, kind="diag", seed=29, offset=OFFSET):
         Zk, zk = rr.relative_pose(sc, a, b)
         Z[k] = Zk @ pc.rodrigues(rs.uniform(-offset, offset, size=3))
         z[k] = zk + ext * rs.uniform(-offset, offset, size=3)
+    if angle is not None:
+        ax = so3.axes(n + 1, seed)[1:] if axes is None else np.asarray(axes, dtype=np.float64).reshape(n, 3)
+        for k, (a, b) in enumerate(pairs):
+            Z[k] = rr.relative_pose(sc, a, b)[0] @ so3.exp(angle * ax[k]).T
     info = _full(n, ext) if kind == "full" else _diag(n, ext)
     return rr.Factors([p[0] for p in pairs], [p[1] for p in pairs], Z, z, info)
 
@@ -87,6 +96,8 @@ _extra = {}
 
 def case(name):
     """(scene copy, f0, factors in the scene's coordinates, fv, constant-frame mask, keep_gauge)"""
+    if name in SWEEP_CASES:
+        return pi_case() if name == PI_CASE else sweep_case(SWEEP_CASES[name])
     sname, pf, kind, fv, rot, fc, keep_gauge = CASES[name]
     if sname in pc.EXTRA_SCENES:
         if sname not in _extra:
@@ -100,6 +111,49 @@ def case(name):
     if fc is not None:
         fconst[fc] = True
     return sc, f0, factors_for(sc, pf(sc), kind), fv, fconst, keep_gauge
+
+
+# ------------------------------------------------------------------ the whole range of residual angles (so3_ref.SWEEP)
+# Three factors with full information on the smallest scene: one on the gauge frames, one on (2, 4), one given backwards.
+SWEEP = so3.SWEEP
+SWEEP_SCENE = "nf2_short_runs"
+SWEEP_PAIRS = [(0, 1), (2, 4), (5, 3)]
+
+
+def sweep_case(angle, fv=10):
+    """(scene copy, f0, factors whose rotation residuals all have the given angle, fv, constant-frame mask, keep_gauge)"""
+    sc, f0 = cc.scene(SWEEP_SCENE)
+    return sc, f0, factors_for(sc, SWEEP_PAIRS, "full", angle=angle), fv, np.zeros(sc.M, dtype=bool), 1
+
+
+def pi_case(fv=10):
+    """two factors whose measurements are half a turn away from the scene's relative rotations: (2, 4) about a coordinate
+    axis, Z = P diag(1, -1, -1) exactly, and (5, 3) about a seeded axis.  The rounding of the normalisation and of the two
+    products puts the residual on either side of pi, so Log may return +pi a or -pi a: the information matrix is diagonal with
+    a multiple of I as its rotation part, for which the energy does not depend on that sign."""
+    sc, f0 = cc.scene(SWEEP_SCENE)
+    fac = factors_for(sc, SWEEP_PAIRS[1:], "diag", angle=np.pi)
+    fac.Z[0] = rr.relative_pose(sc, int(fac.a[0]), int(fac.b[0]))[0] @ np.diag([1.0, -1.0, -1.0])
+    return sc, f0, fac, fv, np.zeros(sc.M, dtype=bool), 1
+
+
+PI_CASE = "sweep_exactly_pi"
+# name -> angle: what tests/test_relpose_cpu.py checks for conditioning beside CASES
+SWEEP_CASES = {**{f"sweep_{a:.12g}": a for a in SWEEP}, PI_CASE: np.pi}
+
+
+def residual_sweep(part):
+    """factors for the residual getter: all 15 pairs of the six frames, every third one given backwards, factor k at the angle
+    SWEEP[15 * part + k] (part 0 or 1: a pair carries one factor, so the sweep takes two settings)"""
+    sc, f0 = cc.scene(SWEEP_SCENE)
+    angles = SWEEP[15 * part:15 * part + 15]
+    pairs = [(a, b) for a in range(sc.M) for b in range(a + 1, sc.M)][:len(angles)]
+    pairs = [(b, a) if k % 3 == 2 else (a, b) for k, (a, b) in enumerate(pairs)]
+    fac = factors_for(sc, pairs, "diag", angle=0.0)
+    ax = so3.axes(len(pairs) + 1, 31 + part)[1:]
+    for k in range(fac.n):
+        fac.Z[k] = rr.relative_pose(sc, int(fac.a[k]), int(fac.b[k]))[0] @ so3.exp(angles[k] * ax[k]).T
+    return sc, f0, fac, np.asarray(angles)
 
 
 CHUNKED = sa.SceneSpec(n_frames=330, grid_nx=60, grid_ny=40, vis_window=8)  # the smallest scene of test_chunked_solve_equals_single_chain

@@ -12,7 +12,8 @@ multiplies the direct rotation R^T from the left and leaves the centre alone.  W
 
     d e_t / d(T_a, W_a, T_b, W_b) = -R_a, R_a [d]x, R_a, 0        d e_r / d(...) = 0, -J R_b, 0, J R_b
 
-Everything here is numpy on factors that are already in the coordinates of the scene they are used with.  The step forms the
+Log and Jr^-1 are those of tests/so3_ref.py (mpmath; no formula shared with the kernels).  Everything else here is numpy on
+factors that are already in the coordinates of the scene they are used with.  The step forms the
 damped reduced camera system densely over all 10 M frame variables (constant_ref.schur), adds the couplings, restricts it to
 the free variables and solves (constant_ref.solve) -- with the gauge kept as well, because orc.two_phase has no place for a
 block between two frames.  The LM loop is lm_ref.loop.
@@ -22,6 +23,7 @@ import numpy as np
 import constant_ref as kref
 import lm_ref
 import prior_ref as pref
+import so3_ref as so3
 
 TRI = [(r, c) for r in range(6) for c in range(r, 6)]  # the 21 entries of the upper triangle, row by row
 
@@ -46,26 +48,13 @@ def skew(v):
 
 
 def log_so3(M):
-    """rotation vector of the rotation M, angle < pi; the series of asin(x) / x where the angle is small"""
-    v = 0.5 * np.array([M[2, 1] - M[1, 2], M[0, 2] - M[2, 0], M[1, 0] - M[0, 1]])
-    sn = float(np.sqrt(v @ v))
-    cs = 0.5 * (M[0, 0] + M[1, 1] + M[2, 2] - 1.0)
-    if sn < 1e-4 and cs > 0:
-        s2 = sn * sn
-        return v * (1.0 + s2 / 6.0 + 3.0 * s2 * s2 / 40.0)
-    return v * (np.arctan2(sn, cs) / sn)
+    """rotation vector of the rotation M, angle in [0, pi] (tests/so3_ref.py: mpmath, nothing shared with the kernels)"""
+    return so3.log(M)
 
 
 def jr_inv(phi):
-    """inverse right Jacobian of SO(3): Log(Exp(phi) Exp(d)) = phi + Jr^-1(phi) d + O(d^2)"""
-    th2 = float(phi @ phi)
-    if th2 < 1e-6:
-        k = 1.0 / 12.0 + th2 / 720.0
-    else:
-        th = np.sqrt(th2)
-        k = 1.0 / th2 - (1.0 + np.cos(th)) / (2.0 * th * np.sin(th))
-    P = skew(phi)
-    return np.eye(3) + 0.5 * P + k * (P @ P)
+    """inverse right Jacobian of SO(3): Log(Exp(phi) Exp(d)) = phi + Jr^-1(phi) d + O(d^2) (tests/so3_ref.py)"""
+    return so3.jr_inv(phi)
 
 
 class Factors:

@@ -28,6 +28,7 @@ import prior_ref as pref
 import relpose_ref as rr
 import jointprior_cases as jc
 import jointprior_ref as jr
+import so3_ref as so3
 import weighted_ref as wr
 from test_jointprior_cpu import DOUBLING_FRAMES, doubling_reference
 from gpu_common import orc_scene as _orc_scene, handle as _handle, run_lm as _run, compare_runs as _compare_runs
@@ -228,6 +229,102 @@ def test_jointprior_phases_in_every_mode(orc, mode):
             b = _phases(orc, h, sc, f0, 1e-4, sets, keep_gauge, fv)
             for k in ("S", "rhs", "corr", "points", "cam_R", "cam_T", "err", "V", "U", "g"):
                 assert np.array_equal(a[k], b[k]), k
+    finally:
+        h.close()
+
+
+# ------------------------------------------------------------------ the whole range of residual angles
+
+def _finite(*arrays):
+    return all(np.all(np.isfinite(a)) for a in arrays)
+
+
+@pytest.mark.parametrize("angle", jc.SWEEP, ids=lambda a: f"{a:.12g}")
+def test_jointprior_phases_over_the_angle_range(orc, angle):
+    """jointprior_cases.sweep_case: one set of three frames, dense 18 x 18 information, a non-zero mean, every slot's rotation
+    residual at the given angle, through _phases at c = 1e-4 with its tolerances as they are, ten and six variables a frame,
+    and with jacobian_mode 0 (per-observation derivative kernels) at one angle on either side of every switch of the three
+    formulas.  The yardstick's Log and
+    Jl^-1 are those of tests/so3_ref.py.  The prior sum itself is held to rel 1e-10 here, as
+    tests/test_gpu_relpose.py::test_relpose_phases_over_the_angle_range holds the factor sum."""
+    for fv in (10, 6):
+        for kw in [{}] + ([dict(jacobian_mode=0)] if angle in so3.AT_SWITCHES else []):
+            sc, f0, sets, fv, fconst, keep_gauge, fac = jc.sweep_case(angle, fv)
+            h = _handle(fv, **kw)
+            try:
+                sets.set_on(h, keep_gauge)
+                assert h.upload(f0, sc)
+                so = _orc_scene(orc, sc)
+                ok, nrm = orc.normalize(so)
+                assert ok
+                sn = jr.normalised(sets, nrm)
+                r = (jr.residuals(sn, so)[0] + sn.sets[0]["mean"]).reshape(-1, 6)
+                assert np.linalg.norm(r, axis=1).min() > 2e-3 and np.abs(np.linalg.norm(r[:, 3:], axis=1) - angle).max() < 1e-13
+                want, got = jr.energy(sn, so), h.joint_pose_prior_error()
+                out = _phases(orc, h, sc, f0, 1e-4, sets, keep_gauge, fv)
+                assert h.jacobian_kernel() in ((0, 1) if kw else (1, 2, 3))
+                Uo = out["ref"]["blocks"][2][:, 10 - fv:, 10 - fv:]
+                dU = np.sqrt(np.abs(np.einsum("mii->mi", Uo)))
+                print(f"angle {angle:.12g} fv {fv} {kw}: prior sum off by {abs(got - want) / want:.2e}, frame blocks by "
+                      f"{sym_scaled_err(out['U'], Uo, dU):.2e} (scaled)")
+                assert got == pytest.approx(want, rel=1e-10)
+            finally:
+                h.close()
+
+
+def test_joint_pose_prior_residuals_over_the_angle_range():
+    """the host getter at every angle of the sweep, one slot each, one upload: rotation rows within 1e-13 of the reference's on
+    the downloaded scene (tests/test_so3_cpu.py derives the bound), translation rows within 1e-10 of the extent"""
+    sc, f0, sets, angles = jc.residual_sweep()
+    h = _handle(10)
+    try:
+        sets.set_on(h)
+        assert h.upload(f0, sc)
+        world = sc.copy()
+        h.download(world)
+        want = np.concatenate(jr.residuals(sets, world)).reshape(-1, 6)
+        got = np.concatenate(h.joint_pose_prior_residuals()).reshape(-1, 6)
+        mean = np.concatenate([s["mean"] for s in sets.sets]).reshape(-1, 6)
+        assert got.shape == want.shape == (angles.size, 6)
+        assert np.abs(np.linalg.norm(want[:, 3:] + mean[:, 3:], axis=1) - angles).max() < 1e-13
+        for k, a in enumerate(angles):
+            print(f"angle {a:.12g}: rotation rows off by {np.abs(got[k, 3:] - want[k, 3:]).max():.2e}")
+        assert np.abs(got[:, :3] - want[:, :3]).max() < 1e-10 * jc.extent(sc)
+        assert np.abs(got[:, 3:] - want[:, 3:]).max() < 1e-13
+    finally:
+        h.close()
+
+
+def test_jointprior_at_exactly_pi():
+    """jointprior_cases.pi_case: slots half a turn about a coordinate axis and about a seeded one.  The rounding of the
+    normalisation lands on either side of pi, so only what both signs of the residual share is held: everything downloaded is
+    finite, the solve succeeds, the residuals have the length pi, and the prior sum (rotation information a multiple of I, no
+    coupling to it, a zero mean) is the yardstick's."""
+    sc, f0, sets, fv, fconst, keep_gauge, fac = jc.pi_case()
+    h = _handle(fv)
+    try:
+        sets.set_on(h, keep_gauge)
+        assert h.upload(f0, sc)
+        nsc = sc.copy()
+        ok, nrm = sa.normalize_scene_inplace(nsc)
+        assert ok
+        sn = jr.normalised(sets, nrm)
+        want, got = jr.energy(sn, nsc), h.joint_pose_prior_error()
+        err = h.phase_error()[0]
+        h.phase_derivatives()
+        V, U, W, g = (h.buffer(b).copy() for b in (B.BUF_POINT_BLOCKS, B.BUF_FRAME_BLOCKS, B.BUF_POINT_FRAME, B.BUF_GRAD))
+        h.phase_schur(1e-4)
+        S, rhs = h.buffer(B.BUF_RCS).copy(), h.buffer(B.BUF_RCS_RHS).copy()
+        assert _finite(V, U, W, g, S, rhs) and np.isfinite(err) and np.isfinite(got)
+        assert h.phase_solve()
+        h.phase_backsub(1e-4)
+        assert _finite(h.buffer(B.BUF_CORRECTIONS))
+        res = h.joint_pose_prior_residuals()[0].reshape(-1, 6)
+        ang = np.linalg.norm(res[:, 3:], axis=1)
+        print(f"half a turn: residual angles - pi {ang[:2] - np.pi}, prior sum {got:.17g}, yardstick {want:.17g}")
+        assert _finite(res) and np.abs(ang[:2] - np.pi).max() < 1e-13 and abs(ang[2] - 0.05) < 1e-13
+        assert np.abs(np.abs(res[0, 3:]) - [np.pi, 0, 0]).max() < 1e-13  # about the first axis of R^T Rbar = diag(1, -1, -1)
+        assert got == pytest.approx(want, rel=1e-10) and err > got
     finally:
         h.close()
 

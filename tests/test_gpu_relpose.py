@@ -26,6 +26,7 @@ import prior_cases as pc
 import prior_ref as pref
 import relpose_cases as rc
 import relpose_ref as rr
+import so3_ref as so3
 import weighted_ref as wr
 from gpu_common import orc_scene as _orc_scene, handle as _handle, run_lm as _run, compare_runs as _compare_runs
 
@@ -242,6 +243,107 @@ def test_relpose_phases_in_every_mode(orc, mode):
             b = _phases(orc, h, sc, f0, 1e-4, fac, keep_gauge, fv)
             for k in ("S", "rhs", "corr", "points", "cam_R", "cam_T", "err", "V", "U", "g"):
                 assert np.array_equal(a[k], b[k]), k
+    finally:
+        h.close()
+
+
+# ------------------------------------------------------------------ the whole range of residual angles
+
+def _finite(*arrays):
+    return all(np.all(np.isfinite(a)) for a in arrays)
+
+
+@pytest.mark.parametrize("angle", rc.SWEEP, ids=lambda a: f"{a:.12g}")
+def test_relpose_phases_over_the_angle_range(orc, angle):
+    """relpose_cases.sweep_case: three factors with full information whose rotation residuals all have the given angle, on the
+    gauge frames, on (2, 4) and given backwards on (5, 3), through _phases at c = 1e-4 with its tolerances as they are, ten
+    and six variables a frame, and with jacobian_mode 0 (per-observation derivative kernels, of which this six-frame scene
+    takes the fused one; the two-kernel path needs the 60 frames of relpose_cases.TWO_KERNEL_CASE, whose own test runs it) at one
+    angle on either side of every switch of the three formulas.  The yardstick's Log and Jr^-1 are those of tests/so3_ref.py.  The
+    factor sum itself is held to rel 1e-10 here: the residuals are within 1e-13 of the yardstick's and no factor's residual is
+    shorter than 2e-3 (the translation offsets see to that)."""
+    for fv in (10, 6):
+        for kw in [{}] + ([dict(jacobian_mode=0)] if angle in so3.AT_SWITCHES else []):
+            sc, f0, fac, fv, fconst, keep_gauge = rc.sweep_case(angle, fv)
+            h = _handle(fv, **kw)
+            try:
+                fac.set_on(h)
+                assert h.upload(f0, sc)
+                so = _orc_scene(orc, sc)
+                ok, nrm = orc.normalize(so)
+                assert ok
+                fn = rr.normalised(fac, nrm)
+                e = rr.residuals(fn, so)
+                assert np.linalg.norm(e, axis=1).min() > 2e-3 and np.abs(np.linalg.norm(e[:, 3:], axis=1) - angle).max() < 1e-13
+                want, got = rr.energy(fn, so), h.relative_pose_error()
+                out = _phases(orc, h, sc, f0, 1e-4, fac, keep_gauge, fv)
+                assert h.jacobian_kernel() in ((0, 1) if kw else (1, 2, 3))
+                Uo = out["ref"]["blocks"][2][:, 10 - fv:, 10 - fv:]
+                dU = np.sqrt(np.abs(np.einsum("mii->mi", Uo)))
+                print(f"angle {angle:.12g} fv {fv} {kw}: factor sum off by {abs(got - want) / want:.2e}, frame blocks by "
+                      f"{sym_scaled_err(out['U'], Uo, dU):.2e} (scaled)")
+                assert got == pytest.approx(want, rel=1e-10)
+            finally:
+                h.close()
+
+
+def test_relative_pose_residuals_over_the_angle_range():
+    """the host getter at every angle of the sweep: rotation rows within 1e-13 of the reference's on the downloaded scene
+    (tests/test_so3_cpu.py derives the bound), translation rows within 1e-10 of the extent.  A pair carries one factor and the
+    scene has 15 pairs, so the sweep takes two settings on one handle."""
+    h = _handle(10)
+    try:
+        seen = []
+        for part in (0, 1):
+            sc, f0, fac, angles = rc.residual_sweep(part)
+            fac.set_on(h)
+            assert h.upload(f0, sc)
+            world = sc.copy()
+            h.download(world)
+            want, got = rr.residuals(fac, world), h.relative_pose_residuals()
+            extent = float(np.abs(sc.points - sc.points.mean(axis=0)).max())
+            assert got.shape == want.shape == (angles.size, 6)
+            assert np.abs(np.linalg.norm(want[:, 3:], axis=1) - angles).max() < 1e-13
+            for k, a in enumerate(angles):
+                print(f"angle {a:.12g}: rotation rows off by {np.abs(got[k, 3:] - want[k, 3:]).max():.2e}")
+            assert np.abs(got[:, :3] - want[:, :3]).max() < 1e-10 * extent
+            assert np.abs(got[:, 3:] - want[:, 3:]).max() < 1e-13
+            seen += list(angles)
+        assert seen == list(rc.SWEEP)
+    finally:
+        h.close()
+
+
+def test_relpose_at_exactly_pi():
+    """relpose_cases.pi_case: half a turn about a coordinate axis and about a seeded one.  The rounding of the normalisation
+    lands on either side of pi, so only what both signs of the residual share is held: everything downloaded is finite, the
+    solve succeeds, the residuals have the length pi, and the factor sum (a rotation information that is a multiple of I) is
+    the yardstick's."""
+    sc, f0, fac, fv, fconst, keep_gauge = rc.pi_case()
+    h = _handle(fv)
+    try:
+        fac.set_on(h)
+        assert h.upload(f0, sc)
+        nsc = sc.copy()
+        ok, nrm = sa.normalize_scene_inplace(nsc)
+        assert ok
+        fn = rr.normalised(fac, nrm)
+        want, got = rr.energy(fn, nsc), h.relative_pose_error()
+        err = h.phase_error()[0]
+        h.phase_derivatives()
+        V, U, W, g = (h.buffer(b).copy() for b in (B.BUF_POINT_BLOCKS, B.BUF_FRAME_BLOCKS, B.BUF_POINT_FRAME, B.BUF_GRAD))
+        h.phase_schur(1e-4)
+        S, rhs = h.buffer(B.BUF_RCS).copy(), h.buffer(B.BUF_RCS_RHS).copy()
+        assert _finite(V, U, W, g, S, rhs) and np.isfinite(err) and np.isfinite(got)
+        assert h.phase_solve()
+        h.phase_backsub(1e-4)
+        assert _finite(h.buffer(B.BUF_CORRECTIONS))
+        res = h.relative_pose_residuals()
+        ang = np.linalg.norm(res[:, 3:], axis=1)
+        print(f"half a turn: residual angles - pi {ang - np.pi}, factor sum {got:.17g}, yardstick {want:.17g}")
+        assert _finite(res) and np.abs(ang - np.pi).max() < 1e-13
+        assert np.abs(np.abs(res[0, 3:]) - [np.pi, 0, 0]).max() < 1e-13  # about the first axis of Z^T P = diag(1, -1, -1)
+        assert got == pytest.approx(want, rel=1e-10) and err > got
     finally:
         h.close()
 

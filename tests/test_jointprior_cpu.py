@@ -299,8 +299,10 @@ def test_planner_sees_the_coupled_pairs_of_a_set_and_nothing_else(plan):
 # ------------------------------------------------------------------ conditioning of every compared case
 
 @pytest.mark.parametrize("c", [1e-4, 1.0])
-@pytest.mark.parametrize("name", list(jc.CASES))
+@pytest.mark.parametrize("name", list(jc.CASES) + list(jc.SWEEP_CASES))
 def test_every_gpu_case_is_positive_definite_and_well_conditioned(orc, name, c):
+    """jc.CASES keep their residual rotations below 1 rad; the cases over the whole range of residual angles
+    (jointprior_cases.SWEEP_CASES, half a turn among them) have the angle their name says"""
     sc, f0, sets_w, fv, fconst, keep_gauge, fac_w = jc.case(name)
     so, nrm = _orc_scene(orc, sc)
     sets = jr.normalised(sets_w, nrm)
@@ -309,7 +311,10 @@ def test_every_gpu_case_is_positive_definite_and_well_conditioned(orc, name, c):
     cond = kref.system_check(ref["S"], ref["fixed"], 1e10)
     rot = max(float(np.linalg.norm((r + s["mean"]).reshape(-1, 6)[:, 3:], axis=1).max()) for s, r in zip(sets.sets, jr.residuals(sets, so)))
     print(f"{name} c={c:g}: cond {cond:.3e}, largest residual rotation {rot:.3e} rad")
-    assert rot <= 1.0
+    if name in jc.SWEEP_CASES:
+        assert abs(rot - jc.SWEEP_CASES[name]) < 1e-14
+    else:
+        assert rot <= 1.0
     for s in sets_w.sets:
         assert np.linalg.eigvalsh(s["info"]).min() > 0
 

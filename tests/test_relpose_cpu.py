@@ -337,10 +337,11 @@ def _system(orc, name, c, weighted=False, with_factors=True):
 
 
 @pytest.mark.parametrize("c", [1e-4, 1e-1])
-@pytest.mark.parametrize("name", list(rc.CASES))
+@pytest.mark.parametrize("name", list(rc.CASES) + list(rc.SWEEP_CASES))
 def test_every_gpu_case_is_positive_definite_and_well_conditioned(orc, name, c):
     """np.linalg.cholesky of the reference system's free part succeeds and its condition number after symmetric diagonal
-    scaling is below 1e10, for every case the GPU tests use, the loss + information variant of the mode case included"""
+    scaling is below 1e10, for every case the GPU tests use, the loss + information variant of the mode case and the cases
+    over the whole range of residual angles (relpose_cases.SWEEP_CASES, half a turn among them) included"""
     for weighted in (False, True) if name == rc.MODE_CASE else (False,):
         S, fixed, V = _system(orc, name, c, weighted)
         cond = kref.system_check(S, fixed, 1e10)
