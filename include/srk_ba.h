@@ -687,6 +687,78 @@ int srk_ba_normalize_joint_pose_priors(const srk_ba_normalizer* nrm, int32_t n_s
  * launched or not timed.  One event pair a pass serves all attempt slots (tools/jointprior_rate.py switches speculation off). */
 int srk_ba_joint_pose_prior_pass_ms(srk_ba*, double* derivative_ms, double* couple_ms, double* error_ms);
 
+/* ---- marginalisation priors in information form (EXTENSION) ----
+ * The operation a sliding window needs: drop a few frames D of the resident scene and the landmarks P that go with them, and get
+ * the Gaussian that exactly the factors touching them leave on the poses of the frames that stay -- in information form,
+ * linearised at the current poses, ready for srk_ba_set_joint_pose_priors on the reduced scene.  A joint pose prior set that
+ * contains a dropped frame is absorbed, mean included, so a window can slide again and again.
+ *
+ * drop [n_drop]: frames, the caller's numbering, strictly ascending, n_drop <= 8.  points [n_points]: landmarks, the caller's
+ * numbering, strictly ascending.  One of the lists may be empty.  The involved factors F are: every observation with information
+ * q > 0 of a landmark of P; the position priors of the landmarks of P and of the centres of the frames of D; every switched-on
+ * relative-pose factor with an end in D; every switched-on joint set that contains a frame of D (the whole set).  A landmark of
+ * P with fewer than two weighted observations is left out with its prior (one view constrains no pose).  The kept frames K are
+ * the frames outside D that F touches, ascending, at most 32; a result over at most 16 can be set as one joint set as it comes.
+ *
+ * With x the pose perturbations of sections 16 to 18 ([centre; rotation vector applied to the direct rotation from the left]; at
+ * the linearisation the solver's [Tx Ty Tz Wx Wy Wz] step) of D, then K, the Gauss-Newton model of the sum of F at the current
+ * scene is E_F(x) ~ E_0 + 2 b^T x + x^T A x: robust and information weights frozen at the current residuals, the relative-pose and
+ * joint-set terms with their exact Jacobians, the intrinsics constants (ten-variable layout too), the gauge ignored.  The
+ * landmarks of P are eliminated first, then D:
+ *     Lam = A_KK - A_KD A_DD^-1 A_DK,   eta = b_K - A_KD A_DD^-1 b_D,   Lam m = -eta
+ * so that (r - m)^T Lam (r - m) is E_F on K up to a constant.  A and b are HALF of what the reduced camera system and its
+ * right-hand side carry in the library's factor-2 convention.  Lam is singular along whatever F does not determine; m is the
+ * basic solution of a diagonally pivoted elimination (components of null pivots are zero).
+ *
+ * Refused with SRK_E_ARGS (text in srk_ba_last_error), nothing written: a weighted observation in a frame of D whose landmark is
+ * not in P (the result would be a prior on a landmark: put it into P, or switch the observation off with
+ * srk_ba_set_observation_information); constant blocks; intrinsic groups; more than one rank; an index beyond the scene; a list
+ * not strictly ascending; both lists empty; more than 8 dropped or more than 32 kept frames (the text names the count); kept_cap
+ * smaller than the number of kept frames.  None of the calls changes the resident scene, its systems or any setting, and no other
+ * call launches their kernels. */
+typedef struct srk_ba_marg_counts {
+    int32_t n_drop, n_kept;
+    int64_t n_landmarks;          /* landmarks of P that enter */
+    int64_t n_landmarks_skipped;  /* landmarks of P with fewer than two weighted observations */
+    int64_t n_observations;       /* observations (weighted or not) of the entering landmarks */
+    int32_t n_factors, n_sets, n_frame_priors; /* involved relative-pose factors, joint sets, priors on centres of D */
+} srk_ba_marg_counts;
+typedef struct srk_ba_marg_report {
+    int64_t landmarks_used;       /* landmarks of P that entered the sum */
+    int64_t landmarks_skipped;    /* fewer than two weighted observations, or an undamped 3 x 3 block that fails the pivot test */
+    int32_t factors, sets, frame_priors; /* absorbed relative-pose factors, joint sets, priors on centres of D */
+    double defect;                /* |Lam m + eta|_inf / |eta|_inf in the normalised variables (0 when eta is zero) */
+    double ms_rows, ms_gram;      /* device ms of the two kernels with their small second passes, from event pairs */
+    double ms_host;               /* host ms of the factor terms, the elimination and the map into the caller's coordinates */
+} srk_ba_marg_report;
+/* The plan of a call on the resident scene, for sizing: no kernel is launched.  kept (may be NULL: counts only) receives the kept
+ * frames when kept_cap holds them.  SRK_OK, SRK_E_STATE without a scene, SRK_E_ARGS for every refusal above. */
+int srk_ba_marginalization_plan(srk_ba*, int32_t n_drop, const int32_t* drop, int64_t n_points, const int64_t* points, int32_t kept_cap,
+                                int32_t* kept, srk_ba_marg_counts* counts);
+/* The staged form, in the variables of the resident (normalised) scene, n = n_drop + n_kept slots, D first: A0 [(6 n)^2], b0 [6 n]
+ * what the two kernels give (observations and landmark priors, P eliminated), A1, b1 the same plus the host's terms (priors on
+ * centres of D, relative-pose factors, joint sets), before the elimination of D.  Any output may be NULL.  Returns as the plan. */
+int srk_ba_phase_marginalization(srk_ba*, int32_t n_drop, const int32_t* drop, int64_t n_points, const int64_t* points, int32_t kept_cap,
+                                 int32_t* kept, int32_t* n_kept, double* A0, double* b0, double* A1, double* b1, srk_ba_marg_report* report);
+/* The whole operation.  Outputs over the k kept frames, in the coordinates of the uploaded arrays and the units
+ * srk_ba_set_joint_pose_priors takes (through srk_ba_revert_marginalization_prior when the upload normalised the scene): lin_R
+ * [k][9], lin_C [k][3] the current poses, info [(6 k)^2] Lam (symmetric), eta [6 k], mean [6 k].  Any output may be NULL.  Returns
+ * SRK_OK; 1 when A_DD is not positive definite (a lone kept frame cannot fix a dropped frame's scale, for instance), nothing
+ * written; else as the plan. */
+int srk_ba_marginalization_prior(srk_ba*, int32_t n_drop, const int32_t* drop, int64_t n_points, const int64_t* points, int32_t kept_cap,
+                                 int32_t* kept, int32_t* n_kept, double* lin_R, double* lin_C, double* info, double* eta, double* mean,
+                                 srk_ba_marg_report* report);
+/* host only, no device and no handle needed: the dense elimination on caller-given A [(6 (d + k))^2] (symmetric) and b, D first.
+ * A_DD is eliminated with diagonal pivoting and the threshold of the positive-semi-definite check of the setters (a pivot
+ * <= 1e-12 of its largest entry is not positive: returns 1, nothing written); mean is the basic solution of the same elimination
+ * of Lam.  Any output may be NULL.  SRK_OK, 1, or SRK_E_ARGS. */
+int srk_ba_marginalize_dense(const double* A, const double* b, int32_t d, int32_t k, double* info, double* eta, double* mean, double* defect);
+/* host only: the inverse of the map of srk_ba_normalize_joint_pose_priors on one result over k frames, in place; any array may be
+ * NULL.  lin_R = lin_R_n R0, lin_C = R0^T (lin_C_n / s - T0), Lam = D^T Lam_n D, eta = D^T eta_n, m = D^-1 m_n with
+ * D = diag(s R0, R0) per frame; the energy is invariant.  SRK_OK or SRK_E_ARGS. */
+int srk_ba_revert_marginalization_prior(const srk_ba_normalizer* nrm, int32_t k, double* lin_R, double* lin_C, double* info, double* eta,
+                                        double* mean);
+
 /* ---- marginal covariances of frames and landmarks (EXTENSION) ----
  * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
  * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior

@@ -393,6 +393,55 @@ public:
         if (rc < 0) Raise(rc);
     }
 
+    /// EXTENSION: the prior a sliding window leaves behind, from the last ComputeInplace's result
+    /// (srk_ba_marginalization_prior): the cameras `frames` (strictly ascending, at most 8) and the salient
+    /// points `points` (by their place in the map, as in Covariances; ascending in the tracks' order) are marginalised, and the
+    /// Gaussian that exactly the factors touching them leave on the cameras that stay comes back in information form as a
+    /// JointPosePrior over those cameras (numbered as in this scene), linearised at the current poses, with eta (optional) and
+    /// the library's report (optional).  Every observation of a dropped camera must belong to a marginalised point.  Returns
+    /// false (outputs untouched) when the block of the dropped cameras is not positive definite.  Throws std::invalid_argument
+    /// for every refusal of the library and as Covariances does.
+    bool MarginalizationPrior(const std::vector<size_t>& frames, const std::vector<size_t>& points, JointPosePrior* prior,
+                              std::vector<Scalar>* eta = nullptr, srk_ba_marg_report* report = nullptr) {
+        std::vector<int32_t> fi;
+        std::vector<int64_t> pi;
+        for (size_t j : frames) {
+            if (j >= frames_count_) throw std::invalid_argument("marginalization: a camera index is beyond the cameras");
+            fi.push_back((int32_t)j);
+        }
+        for (size_t k : points) {
+            if (k >= pnt_ind_of_.size() || pnt_ind_of_[k] < 0) throw std::invalid_argument("marginalization: no track of the last ComputeInplace carries this salient point");
+            pi.push_back(pnt_ind_of_[k]);
+        }
+        std::sort(pi.begin(), pi.end());
+        srk_ba_marg_counts cnt{};
+        int rc = srk_ba_marginalization_plan(h_, (int32_t)fi.size(), fi.data(), (int64_t)pi.size(), pi.data(), 0, nullptr, &cnt);
+        if (rc < 0) Raise(rc);
+        const size_t k = (size_t)cnt.n_kept;
+        std::vector<int32_t> kept(k + 1);
+        std::vector<Scalar> R(9 * k + 1), Cc(3 * k + 1), L(36 * k * k + 1), e(6 * k + 1), m(6 * k + 1);
+        int32_t nk = 0;
+        srk_ba_marg_report rep{};
+        rc = srk_ba_marginalization_prior(h_, (int32_t)fi.size(), fi.data(), (int64_t)pi.size(), pi.data(), (int32_t)k, kept.data(), &nk, R.data(),
+                                          Cc.data(), L.data(), e.data(), m.data(), &rep);
+        if (rc < 0) Raise(rc);
+        if (rc != 0) return false;
+        if (prior) {
+            prior->frames.assign(kept.begin(), kept.begin() + nk);
+            prior->lin_R.resize(k);
+            prior->lin_C.resize(k);
+            for (size_t q = 0; q < k; ++q) {
+                std::copy(R.begin() + 9 * q, R.begin() + 9 * q + 9, prior->lin_R[q].begin());
+                prior->lin_C[q] = Point3{ Cc[3 * q], Cc[3 * q + 1], Cc[3 * q + 2] };
+            }
+            prior->mean.assign(m.begin(), m.begin() + 6 * k);
+            prior->info.assign(L.begin(), L.begin() + 36 * k * k);
+        }
+        if (eta) eta->assign(e.begin(), e.begin() + 6 * k);
+        if (report) *report = rep;
+        return true;
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }

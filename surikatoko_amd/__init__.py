@@ -7,6 +7,6 @@ fallback: every compute entry point needs libsrk_ba.so and a HIP device.
 from ._lib import lib, library_path, build_library, LibraryNotBuilt  # noqa: F401
 from .ba import (BundleAdjustmentKanatani, BundleAdjustmentKanataniTermCriteria, Report, Scene,  # noqa: F401
                  normalize_scene_inplace, check_world_is_normalized, status_string, device_count, revert_covariances,
-                 revert_cross_covariances)
+                 revert_cross_covariances, marginalize_dense, revert_marginalization_prior, marginalization_landmarks)
 from .scene import (SceneSpec, generate_scene, config_scene, drop_observations, renumber_frames, loop_scene,  # noqa: F401
                     CONFIGS)

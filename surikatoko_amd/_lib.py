@@ -49,6 +49,23 @@ class SceneSpecC(C.Structure):
                 ("seed", C.c_uint32)]
 
 
+class MargCounts(C.Structure):
+    _fields_ = [("n_drop", C.c_int32), ("n_kept", C.c_int32), ("n_landmarks", C.c_int64), ("n_landmarks_skipped", C.c_int64),
+                ("n_observations", C.c_int64), ("n_factors", C.c_int32), ("n_sets", C.c_int32), ("n_frame_priors", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class MargReport(C.Structure):
+    _fields_ = [("landmarks_used", C.c_int64), ("landmarks_skipped", C.c_int64), ("factors", C.c_int32), ("sets", C.c_int32),
+                ("frame_priors", C.c_int32), ("defect", C.c_double), ("ms_rows", C.c_double), ("ms_gram", C.c_double),
+                ("ms_host", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 # every symbol include/srk_ba.h declares (checked by tests/test_abi.py)
@@ -68,6 +85,8 @@ EXPORTS = [
     "srk_ba_set_joint_pose_priors", "srk_ba_check_joint_pose_priors", "srk_ba_joint_pose_prior_counts", "srk_ba_joint_pose_priors",
     "srk_ba_joint_pose_prior_error", "srk_ba_joint_pose_prior_residuals", "srk_ba_normalize_joint_pose_priors",
     "srk_ba_joint_pose_prior_pass_ms",
+    "srk_ba_marginalization_plan", "srk_ba_phase_marginalization", "srk_ba_marginalization_prior", "srk_ba_marginalize_dense",
+    "srk_ba_revert_marginalization_prior",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
     "srk_ba_phase_cross_covariance", "srk_ba_cross_covariances", "srk_ba_revert_cross_covariances", "srk_ba_relative_pose_covariances",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
@@ -155,6 +174,12 @@ def lib():
     L.srk_ba_joint_pose_prior_residuals.argtypes = [C.c_void_p, C.c_void_p]
     L.srk_ba_normalize_joint_pose_priors.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
     L.srk_ba_joint_pose_prior_pass_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    _marg = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+    L.srk_ba_marginalization_plan.argtypes = _marg + [C.POINTER(MargCounts)]
+    L.srk_ba_phase_marginalization.argtypes = _marg + [C.POINTER(C.c_int32)] + [C.c_void_p] * 4 + [C.POINTER(MargReport)]
+    L.srk_ba_marginalization_prior.argtypes = _marg + [C.POINTER(C.c_int32)] + [C.c_void_p] * 5 + [C.POINTER(MargReport)]
+    L.srk_ba_marginalize_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+    L.srk_ba_revert_marginalization_prior.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5
     L.srk_ba_phase_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.srk_ba_covariances.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.srk_ba_revert_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]

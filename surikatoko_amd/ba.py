@@ -15,7 +15,7 @@ import math
 
 import numpy as np
 
-from ._lib import Normalizer, Report, lib
+from ._lib import MargCounts, MargReport, Normalizer, Report, lib
 
 BUF_GRAD, BUF_POINT_BLOCKS, BUF_FRAME_BLOCKS, BUF_POINT_FRAME, BUF_RCS, BUF_RCS_RHS, BUF_CORRECTIONS, BUF_POINTS, \
     BUF_CAM_R, BUF_CAM_T = range(10)
@@ -403,6 +403,72 @@ def joint_pose_prior_from_covariance(frames, scene, joint_cov, frame_vars, sigma
     R = np.asarray(scene.cam_R, dtype=np.float64).reshape(-1, 3, 3)[fr]
     T = np.asarray(scene.cam_T, dtype=np.float64).reshape(-1, 3)[fr]
     return dict(frames=fr, R=R.copy(), C=-np.einsum("kba,kb->ka", R, T), info=0.5 * (L + L.T), mean=np.zeros(6 * k))
+
+
+def marginalize_dense(A, b, d, k):
+    """the dense elimination of a marginalisation prior on caller-given A [6(d+k)][6(d+k)] and b, dropped slots first
+    (srk_ba_marginalize_dense; host only): (info, eta, mean, defect).  Raises numpy.linalg.LinAlgError when A_DD is not positive
+    definite."""
+    n = 6 * (int(d) + int(k))
+    A = np.ascontiguousarray(np.asarray(A, dtype=np.float64).reshape(n, n))
+    b = np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(n))
+    L, eta, m = np.zeros((6 * k, 6 * k)), np.zeros(6 * k), np.zeros(6 * k)
+    defect = C.c_double(0)
+    rc = lib().srk_ba_marginalize_dense(_p(A), _p(b), C.c_int32(int(d)), C.c_int32(int(k)), _p(L), _p(eta), _p(m), C.byref(defect))
+    if rc < 0:
+        raise ValueError("srk_ba_marginalize_dense: bad argument")
+    if rc != 0:
+        raise np.linalg.LinAlgError("srk_ba_marginalize_dense: the block of the dropped frames is not positive definite")
+    return L, eta, m, defect.value
+
+
+def revert_marginalization_prior(nrm, R=None, C_=None, info=None, eta=None, mean=None):
+    """a marginalisation prior in the normalised variables back into the caller's coordinates
+    (srk_ba_revert_marginalization_prior; host only): copies of the arrays given, None where None was given"""
+    cp = lambda a, shape: None if a is None else np.ascontiguousarray(np.array(a, dtype=np.float64).reshape(shape))  # noqa: E731
+    sizes = [np.asarray(a).size // s for a, s in ((R, 9), (C_, 3), (eta, 6), (mean, 6)) if a is not None]
+    if info is not None:
+        sizes.append(int(round(math.sqrt(np.asarray(info).size))) // 6)
+    if not sizes or len(set(sizes)) != 1:
+        raise ValueError("revert_marginalization_prior: arrays over one and the same number of frames")
+    k = sizes[0]
+    out = [cp(R, (k, 3, 3)), cp(C_, (k, 3)), cp(info, (6 * k, 6 * k)), cp(eta, 6 * k), cp(mean, 6 * k)]
+    rc = lib().srk_ba_revert_marginalization_prior(C.byref(nrm), C.c_int32(k), *[None if a is None else _p(a) for a in out])
+    if rc != 0:
+        raise ValueError("srk_ba_revert_marginalization_prior: bad argument")
+    return tuple(out)
+
+
+def marginalization_landmarks(scene, frames, max_kept=16, q=None):
+    """Which landmarks to marginalise with the frames dropped, so that the prior ties at most max_kept frames: the landmarks seen
+    from a dropped frame are taken in the order of their track length as long as the union of their other frames stays within
+    max_kept.  Returns (points, q): the chosen landmarks (ascending) and the observation information that switches off the
+    dropped frames' observations of the others (the given q, or ones, with zeros there) -- what set_observation_information
+    takes before marginalization_prior."""
+    rp = np.asarray(scene.row_ptr)
+    fr = np.asarray(scene.obs_frame)
+    O = int(rp[-1])
+    q = np.ones(O) if q is None else np.array(q, dtype=np.float64).reshape(O)
+    drop = np.zeros(scene.M, dtype=bool)
+    drop[np.asarray(frames, dtype=np.int64)] = True
+    pt = np.repeat(np.arange(scene.N), np.diff(rp))
+    hit = np.zeros(scene.N, dtype=bool)
+    hit[pt[drop[fr] & (q > 0)]] = True
+    cand = np.flatnonzero(hit)
+    cand = cand[np.argsort(np.diff(rp)[cand], kind="stable")]
+    kept = np.zeros(scene.M, dtype=bool)
+    chosen = []
+    for i in cand:
+        f = fr[rp[i]:rp[i + 1]][q[rp[i]:rp[i + 1]] > 0]
+        new = kept.copy()
+        new[f[~drop[f]]] = True
+        if new.sum() <= max_kept:
+            kept = new
+            chosen.append(int(i))
+    take = np.zeros(scene.N, dtype=bool)
+    take[chosen] = True
+    q[drop[fr] & ~take[pt]] = 0.0
+    return np.asarray(sorted(chosen), dtype=np.int64), q
 
 
 def check_world_is_normalized(scene, t1y=1.0, unity_comp_ind=1):
@@ -1193,6 +1259,59 @@ class BundleAdjustmentKanatani:
             J[fv * nf + 3 * a:fv * nf + 3 * a + 3, fv * nf + 3 * b:fv * nf + 3 * b + 3] = pp[k]
             J[fv * nf + 3 * b:fv * nf + 3 * b + 3, fv * nf + 3 * a:fv * nf + 3 * a + 3] = pp[k].T
         return J
+
+    # ---- marginalisation priors in information form
+    def _marg_args(self, frames, points):
+        fr = np.ascontiguousarray(np.asarray([] if frames is None else frames).reshape(-1), dtype=np.int32)
+        pt = np.ascontiguousarray(np.asarray([] if points is None else points).reshape(-1), dtype=np.int64)
+        return fr, pt, [C.c_void_p(self._h), C.c_int32(len(fr)), _p(fr) if len(fr) else None, C.c_int64(len(pt)), _p(pt) if len(pt) else None]
+
+    def marginalization_plan(self, frames, points):
+        """the plan of marginalising the frames and landmarks given (caller's numbering, strictly ascending) on the resident
+        scene, no kernel launched: (kept frames, counts dict).  Every refusal of the operation is a ValueError here."""
+        fr, pt, args = self._marg_args(frames, points)
+        cnt = MargCounts()
+        kept = np.zeros(max(self._scene.M, 1), np.int32)
+        self._raise(self._lib.srk_ba_marginalization_plan(*args, C.c_int32(kept.size), _p(kept), C.byref(cnt)))
+        return kept[:cnt.n_kept].copy(), cnt.as_dict()
+
+    def phase_marginalization(self, frames, points):
+        """the staged form in the resident (normalised) scene's variables, dropped slots first, then the kept frames: a dict with
+        kept, A0 / b0 (what the kernels give: observations and landmark priors, the landmarks eliminated), A1 / b1 (plus the
+        host's factor terms) and report"""
+        fr, pt, args = self._marg_args(frames, points)
+        kept, _ = self.marginalization_plan(fr, pt)
+        n = 6 * (len(fr) + len(kept))
+        A0, b0, A1, b1 = np.zeros((n, n)), np.zeros(n), np.zeros((n, n)), np.zeros(n)
+        nk, rep = C.c_int32(0), MargReport()
+        kb = np.zeros(max(len(kept), 1), np.int32)
+        self._raise(self._lib.srk_ba_phase_marginalization(*args, C.c_int32(len(kept)), _p(kb), C.byref(nk), _p(A0), _p(b0), _p(A1), _p(b1),
+                                                           C.byref(rep)))
+        return dict(kept=kb[:nk.value].copy(), A0=A0, b0=b0, A1=A1, b1=b1, report=rep.as_dict())
+
+    def marginalization_prior(self, frames, points=None, sigma_pixels=None):
+        """The Gaussian the factors touching the dropped frames and the marginalised landmarks leave on the frames that stay, in
+        information form at the current poses (srk_ba_marginalization_prior).  points None: every landmark with a weighted
+        observation in a dropped frame.  Returns a dict that set_joint_pose_priors accepts as a set (frames, R, C, info, mean; the
+        frames in THIS scene's numbering -- renumber them for the reduced scene) plus eta and report; with sigma_pixels also
+        information_metric = info / (sigma_pixels / f0)^2, the inverse covariance in world units.  Raises
+        numpy.linalg.LinAlgError when the block of the dropped frames is not positive definite."""
+        if points is None:
+            points, _ = marginalization_landmarks(self._scene, frames, max_kept=self._scene.M, q=self.observation_information())
+        fr, pt, args = self._marg_args(frames, points)
+        kept, _ = self.marginalization_plan(fr, pt)
+        k = len(kept)
+        R, Cc, L, eta, m = np.zeros((k, 3, 3)), np.zeros((k, 3)), np.zeros((6 * k, 6 * k)), np.zeros(6 * k), np.zeros(6 * k)
+        nk, rep = C.c_int32(0), MargReport()
+        kb = np.zeros(max(k, 1), np.int32)
+        rc = self._lib.srk_ba_marginalization_prior(*args, C.c_int32(k), _p(kb), C.byref(nk), _p(R), _p(Cc), _p(L), _p(eta), _p(m), C.byref(rep))
+        self._raise(rc)
+        if rc != 0:
+            raise np.linalg.LinAlgError("srk_ba_marginalization_prior: " + self.last_error())
+        out = dict(frames=kb[:nk.value].copy(), R=R, C=Cc, info=L, mean=m, eta=eta, report=rep.as_dict())
+        if sigma_pixels is not None:
+            out["information_metric"] = L / (float(sigma_pixels) / float(self._f0)) ** 2
+        return out
 
     def buffer(self, which):
         """flat download of a staged buffer; its layout follows frame_vars() (include/srk_ba.h SRK_BUF_*)"""

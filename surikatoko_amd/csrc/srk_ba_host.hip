@@ -11,6 +11,8 @@
 #include "srk_geom.hpp"
 #include "srk_plan.hpp"
 #include "srk_factors.hpp"
+#include "srk_marg.hpp"
+#include "srk_marg_dev.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -245,6 +247,14 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     DevBuf cov_pairs; // the pair table of a batch of cross-covariances (section 17)
     int64_t cov_batch_cols = 0;
     std::vector<int32_t> cov_pt_frame0;
+    // marginalisation priors (srk_ba_marginalization_prior): the tables of a call's plan, the dense strip Z,
+    // the observations' staging rows, the chunks' partial Gram products and the result, grown lazily; two event pairs (the strip
+    // and the frames' sums; the Gram product and its reduction), created at the first call; mg_obs_frame: the frames of the
+    // observations in the internal order, fetched at the first call after an upload
+    enum { MG_LM, MG_LM_STAGE, MG_LM_PRIOR, MG_FRAME_SLOT, MG_SLOT_PTR, MG_SLOT_ENT, MG_Z, MG_STAGE, MG_SKIP, MG_US, MG_PART, MG_OUT, MG_NBUF };
+    DevBuf mg[MG_NBUF];
+    hipEvent_t mg_ev[4]{};
+    std::vector<int32_t> mg_obs_frame;
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -416,6 +426,9 @@ void srk_ba_destroy(srk_ba* h)
                       &h->lg_obs_off, &h->lg_obs, &h->shk_grp, &h->shk_lo, &h->shk_hi, &h->shk_mptr, &h->shk_mem, &h->shk_env, &h->dp_chk,
                       &h->cov_Y, &h->cov_grp, &h->cov_blk, &h->cov_out, &h->cov_free, &h->cov_colb, &h->cov_pairs };
     for (DevBuf* b : all) dev_free(*b);
+    for (DevBuf& b : h->mg) dev_free(b);
+    for (hipEvent_t& e : h->mg_ev)
+        if (e) hipEventDestroy(e);
     for (auto& a : h->att) {
         for (DevBuf* b : { &a.S, &a.rhs, &a.wy, &a.dc, &a.acc, &a.dx, &a.err_partial, &a.info, &a.dinv, &a.packed, &a.sync_flags, &a.irr, &a.det_stage, &a.det_rhs,
                           &a.Ssh, &a.rsh, &a.ysh, &a.dcsh, &a.dinvsh, &a.Tsh }) dev_free(*b);
@@ -1372,6 +1385,7 @@ static int upload_scene_impl(srk_ba* h, double f0, int64_t N, const double* pts_
     h->d = d;
     h->f0 = f0;
     h->cov_pt_frame0.clear();
+    h->mg_obs_frame.clear();
 
     // ---- the device buffers of the scene, each named once: allocated in this order, then filled from its host source (if any)
     struct Up { DevBuf& buf; const void* src; size_t bytes; }; // src NULL: nothing to copy
@@ -2661,6 +2675,345 @@ int srk_ba_relative_pose_covariances(srk_ba* h, double sigma_pixels, int32_t n, 
             }
     }
     return 0;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------ marginalisation priors
+
+namespace {
+// what a call carries from its plan to its result, in the variables of the resident (normalised) scene
+struct MargCall {
+    SrkMargPlan plan;
+    std::vector<int32_t> set_ptr, set_frame; // the switched-on joint sets as the device holds them
+    std::vector<double> R, T;                // the current poses, internal order
+    std::vector<double> A0, b0, A1, b1;
+    srk_ba_marg_report rep{};
+};
+template <typename T> int marg_fetch(srk_ba* h, hipStream_t s, const DevBuf& b, size_t n, std::vector<T>& out)
+{
+    out.assign(n, T());
+    if (n == 0) return SRK_OK;
+    HIPCHK(h, hipMemcpyAsync(out.data(), b.p, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return SRK_OK;
+}
+template <typename T> int marg_put(srk_ba* h, hipStream_t s, DevBuf& b, const std::vector<T>& v)
+{
+    const int rc = dev_alloc(h, b, v.size() * sizeof(T));
+    if (rc != SRK_OK || v.empty()) return rc;
+    HIPCHK(h, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    return SRK_OK;
+}
+} // namespace
+
+// the plan of a call: the checks and tables of srk_marg_plan on the resident scene.  The only device traffic is the download of
+// small index tables (the observations' frames once per upload).
+static int marg_plan(srk_ba* h, int32_t nd, const int32_t* drop, int64_t np, const int64_t* points, MargCall& mc)
+{
+    const SrkDims& d = h->d;
+    hipStream_t s = h->main_stream;
+    int rc;
+    for (auto& a : h->att) // nothing of an earlier call is still writing the scene
+        if (a.allocated && a.stream) HIPCHK(h, hipStreamSynchronize(a.stream));
+    if (h->mg_obs_frame.empty() && d.O > 0 && (rc = marg_fetch(h, s, h->obs_frame, (size_t)d.O, h->mg_obs_frame)) != SRK_OK) return rc;
+    SrkInfoTables qt;
+    if (h->obs_info.on) qt = srk_build_information(h->obs_info.set, *h, factor_dims(h));
+    std::vector<int32_t> pt_prior, fr_prior;
+    if ((rc = marg_fetch(h, s, h->pri.buf[PriorFamily::PT_LIST], (size_t)h->pri.n_pts, pt_prior)) != SRK_OK) return rc;
+    if ((rc = marg_fetch(h, s, h->pri.buf[PriorFamily::FR_LIST], (size_t)h->pri.n_frames, fr_prior)) != SRK_OK) return rc;
+    if ((rc = marg_fetch(h, s, h->jp.buf[JPriorFamily::PTR], h->jp.n > 0 ? (size_t)h->jp.n + 1 : 0, mc.set_ptr)) != SRK_OK) return rc;
+    if ((rc = marg_fetch(h, s, h->jp.buf[JPriorFamily::FRAME], h->jp.n > 0 ? (size_t)mc.set_ptr.back() : 0, mc.set_frame)) != SRK_OK) return rc;
+    SrkMargScene sc;
+    sc.N = d.N;
+    sc.M = d.M;
+    sc.row_ptr = h->row_ptr_int.data();
+    sc.obs_frame = h->mg_obs_frame.data();
+    sc.q = qt.on ? qt.q.data() : nullptr;
+    sc.perm = h->perm.data();
+    sc.frame_int = h->frame_int.empty() ? nullptr : h->frame_int.data();
+    sc.frame_user = h->frame_user.empty() ? nullptr : h->frame_user.data();
+    sc.n_pt_priors = (int64_t)pt_prior.size();
+    sc.pt_prior = pt_prior.data();
+    sc.n_fr_priors = (int32_t)fr_prior.size();
+    sc.fr_prior = fr_prior.data();
+    sc.n_rp = h->rp.n;
+    sc.rp_a = h->rp.int_a.data();
+    sc.rp_b = h->rp.int_b.data();
+    sc.n_sets = h->jp.n;
+    sc.set_ptr = mc.set_ptr.data();
+    sc.set_frame = mc.set_frame.data();
+    sc.constant_blocks = h->cst.n_pts > 0 || h->cst.n_frames > 0;
+    sc.intrinsic_groups = h->shk_G > 0;
+    sc.multi_rank = h->world > 1 || h->allreduce || h->comm;
+    const std::string why = srk_marg_plan(sc, nd, drop, np, points, mc.plan);
+    if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+    return SRK_OK;
+}
+
+static int marg_kept_out(srk_ba* h, const MargCall& mc, int32_t kept_cap, int32_t* kept, int32_t* n_kept, bool write)
+{
+    if (kept && kept_cap < mc.plan.k) {
+        h->last_error = "marginalization: " + std::to_string(mc.plan.k) + " kept frames do not fit kept_cap = " + std::to_string(kept_cap);
+        return SRK_E_ARGS;
+    }
+    if (write) {
+        copy_out(kept, mc.plan.kept);
+        if (n_kept) *n_kept = mc.plan.k;
+    }
+    return SRK_OK;
+}
+
+// A0, b0: the two kernels and their second passes on the current scene
+static int marg_device(srk_ba* h, MargCall& mc)
+{
+    const SrkDims& d = h->d;
+    const SrkMargPlan& p = mc.plan;
+    hipStream_t s = h->main_stream;
+    const int32_t ns = p.d + p.k, ldz = p.ldz(), ncols = 6 * ns;
+    const int64_t n_lm = (int64_t)p.lm.size(), n_rows = p.n_rows;
+    // the row chunks of Z: 512 rows each (128 landmarks), at most 64 of them
+    const int32_t n_chunks = (int32_t)std::min<int64_t>(64, (n_rows + 511) / 512);
+    const int64_t rows_per_chunk = n_chunks > 0 ? ((n_rows + n_chunks - 1) / n_chunks + 15) / 16 * 16 : 0;
+    int rc;
+    DevBuf* g = h->mg;
+    if ((rc = marg_put(h, s, g[srk_ba::MG_LM], p.lm)) != SRK_OK || (rc = marg_put(h, s, g[srk_ba::MG_LM_STAGE], p.lm_stage)) != SRK_OK ||
+        (rc = marg_put(h, s, g[srk_ba::MG_LM_PRIOR], p.lm_prior)) != SRK_OK || (rc = marg_put(h, s, g[srk_ba::MG_FRAME_SLOT], p.frame_slot)) != SRK_OK ||
+        (rc = marg_put(h, s, g[srk_ba::MG_SLOT_PTR], p.slot_ptr)) != SRK_OK || (rc = marg_put(h, s, g[srk_ba::MG_SLOT_ENT], p.slot_ent)) != SRK_OK)
+        return rc;
+    const size_t z_bytes = (size_t)(8 * n_rows * ldz), st_bytes = (size_t)(8 * p.n_stage * SRK_MARG_STAGE);
+    const size_t out_doubles = (size_t)ncols * ncols + (size_t)ncols;
+    if ((rc = dev_alloc(h, g[srk_ba::MG_Z], z_bytes)) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::MG_STAGE], st_bytes)) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::MG_SKIP], (size_t)(4 * n_lm))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::MG_US], (size_t)(8 * 27 * ns))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::MG_PART], (size_t)(8 * (int64_t)n_chunks * ldz * ldz))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::MG_OUT], 8 * out_doubles)) != SRK_OK)
+        return rc;
+    for (hipEvent_t& e : h->mg_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    if (z_bytes) HIPCHK(h, hipMemsetAsync(g[srk_ba::MG_Z].p, 0, z_bytes, s));
+    if (st_bytes) HIPCHK(h, hipMemsetAsync(g[srk_ba::MG_STAGE].p, 0, st_bytes, s));
+    if (n_lm) HIPCHK(h, hipMemsetAsync(g[srk_ba::MG_SKIP].p, 0, (size_t)(4 * n_lm), s));
+    SrkMargTables t{};
+    t.n_lm = (int32_t)n_lm;
+    t.n_slots = ns;
+    t.ldz = ldz;
+    t.lm = P<int32_t>(g[srk_ba::MG_LM]);
+    t.lm_stage = P<int64_t>(g[srk_ba::MG_LM_STAGE]);
+    t.lm_prior = P<int32_t>(g[srk_ba::MG_LM_PRIOR]);
+    t.frame_slot = P<int32_t>(g[srk_ba::MG_FRAME_SLOT]);
+    t.prior_val = P<double>(h->pri.buf[PriorFamily::PT_VAL]);
+    t.n_priors = h->pri.n_pts;
+    t.slot_ptr = P<int32_t>(g[srk_ba::MG_SLOT_PTR]);
+    t.slot_ent = P<int64_t>(g[srk_ba::MG_SLOT_ENT]);
+    SrkLoss Ls;
+    const SrkLoss* L = robust_loss(h, Ls);
+    const int c = h->cur;
+    HIPCHK(h, hipEventRecord(h->mg_ev[0], s));
+    srk_launch_marg_rows(s, d, P<double>(h->pts[c]), P<double>(h->cam[c]), P<int64_t>(h->row_ptr), P<int32_t>(h->obs_frame), P<double>(h->obs_uv), L,
+                         t, P<double>(g[srk_ba::MG_Z]), P<double>(g[srk_ba::MG_STAGE]), P<int32_t>(g[srk_ba::MG_SKIP]));
+    srk_launch_marg_frame_sums(s, t, P<double>(g[srk_ba::MG_STAGE]), P<double>(g[srk_ba::MG_US]));
+    HIPCHK(h, hipEventRecord(h->mg_ev[1], s));
+    HIPCHK(h, hipEventRecord(h->mg_ev[2], s));
+    srk_launch_marg_gram(s, P<double>(g[srk_ba::MG_Z]), n_rows, ldz, n_chunks, rows_per_chunk, P<double>(g[srk_ba::MG_PART]));
+    srk_launch_marg_reduce(s, P<double>(g[srk_ba::MG_PART]), n_chunks, ldz, ns, P<double>(g[srk_ba::MG_US]), P<double>(g[srk_ba::MG_OUT]),
+                           P<double>(g[srk_ba::MG_OUT]) + (size_t)ncols * ncols);
+    HIPCHK(h, hipEventRecord(h->mg_ev[3], s));
+    HIPCHK(h, hipGetLastError());
+    std::vector<double> out;
+    std::vector<int32_t> skip;
+    if ((rc = marg_fetch(h, s, g[srk_ba::MG_OUT], out_doubles, out)) != SRK_OK) return rc;
+    if ((rc = marg_fetch(h, s, g[srk_ba::MG_SKIP], (size_t)n_lm, skip)) != SRK_OK) return rc;
+    mc.A0.assign(out.begin(), out.begin() + (size_t)ncols * ncols);
+    mc.b0.assign(out.begin() + (size_t)ncols * ncols, out.end());
+    int64_t n_skip = 0;
+    for (int32_t v : skip) n_skip += v ? 1 : 0;
+    float ms0 = 0, ms1 = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms0, h->mg_ev[0], h->mg_ev[1]));
+    HIPCHK(h, hipEventElapsedTime(&ms1, h->mg_ev[2], h->mg_ev[3]));
+    mc.rep.landmarks_used = n_lm - n_skip;
+    mc.rep.landmarks_skipped = p.n_single + n_skip;
+    mc.rep.ms_rows = ms0;
+    mc.rep.ms_gram = ms1;
+    return SRK_OK;
+}
+
+// A1, b1 = A0, b0 plus the host's terms: the priors on centres of D, the relative-pose factors and the joint sets, at the current poses
+static int marg_host_terms(srk_ba* h, MargCall& mc)
+{
+    const SrkDims& d = h->d;
+    const SrkMargPlan& p = mc.plan;
+    hipStream_t s = h->main_stream;
+    const int64_t n = 6 * (int64_t)(p.d + p.k);
+    const int c = h->cur;
+    int rc;
+    if ((rc = marg_fetch(h, s, h->camR[c], (size_t)(9 * d.M), mc.R)) != SRK_OK || (rc = marg_fetch(h, s, h->camT[c], (size_t)(3 * d.M), mc.T)) != SRK_OK) return rc;
+    mc.A1 = mc.A0;
+    mc.b1 = mc.b0;
+    // H [m][m], g [m] over the pose variables of the listed internal frames, into A1, b1
+    const auto scatter = [&](int32_t nf, const int32_t* frames, const double* H, const double* gv) {
+        const int m = 6 * nf;
+        for (int a = 0; a < m; ++a) {
+            const int64_t ra = 6 * (int64_t)p.frame_slot[(size_t)frames[a / 6]] + a % 6;
+            mc.b1[(size_t)ra] += gv[a];
+            for (int b = 0; b < m; ++b) mc.A1[(size_t)(ra * n + 6 * (int64_t)p.frame_slot[(size_t)frames[b / 6]] + b % 6)] += H[a * m + b];
+        }
+    };
+    if (!p.fr_priors.empty()) {
+        std::vector<int32_t> list;
+        std::vector<double> val;
+        const size_t nf = (size_t)h->pri.n_frames;
+        if ((rc = marg_fetch(h, s, h->pri.buf[PriorFamily::FR_LIST], nf, list)) != SRK_OK || (rc = marg_fetch(h, s, h->pri.buf[PriorFamily::FR_VAL], 9 * nf, val)) != SRK_OK) return rc;
+        for (int32_t q : p.fr_priors) {
+            const int32_t f = list[(size_t)q];
+            const double* r = &mc.R[9 * (size_t)f];
+            const double* t = &mc.T[3 * (size_t)f];
+            double dx[3];
+            for (int e = 0; e < 3; ++e) dx[e] = -(r[e] * t[0] + r[3 + e] * t[1] + r[6 + e] * t[2]) - val[(size_t)e * nf + (size_t)q];
+            const double* v = val.data();
+            const double L[9] = { v[3 * nf + q], v[4 * nf + q], v[5 * nf + q], v[4 * nf + q], v[6 * nf + q], v[7 * nf + q], v[5 * nf + q], v[7 * nf + q], v[8 * nf + q] };
+            double H[36] = {}, gv[6] = {};
+            for (int a = 0; a < 3; ++a) {
+                gv[a] = L[3 * a] * dx[0] + L[3 * a + 1] * dx[1] + L[3 * a + 2] * dx[2];
+                for (int b = 0; b < 3; ++b) H[6 * a + b] = L[3 * a + b];
+            }
+            scatter(1, &f, H, gv);
+        }
+    }
+    if (!p.factors.empty()) {
+        std::vector<double> val;
+        const size_t nf = (size_t)h->rp.n;
+        if ((rc = marg_fetch(h, s, h->rp.buf[RelPoseFamily::VAL], SRK_RP_PLANES * nf, val)) != SRK_OK) return rc;
+        for (int32_t q : p.factors) {
+            const int32_t fr[2] = { h->rp.int_a[(size_t)q], h->rp.int_b[(size_t)q] };
+            double Z[9], z[3], L[36], H[144], gv[12];
+            for (int e = 0; e < 9; ++e) Z[e] = val[(size_t)e * nf + (size_t)q];
+            for (int e = 0; e < 3; ++e) z[e] = val[(size_t)(9 + e) * nf + (size_t)q];
+            int k = 12;
+            for (int r = 0; r < 6; ++r)
+                for (int cc = r; cc < 6; ++cc, ++k) L[6 * r + cc] = L[6 * cc + r] = val[(size_t)k * nf + (size_t)q];
+            srk_relpose_terms(&mc.R[9 * (size_t)fr[0]], &mc.T[3 * (size_t)fr[0]], &mc.R[9 * (size_t)fr[1]], &mc.T[3 * (size_t)fr[1]], Z, z, L, H, gv);
+            scatter(2, fr, H, gv);
+        }
+    }
+    if (!p.sets.empty()) {
+        std::vector<double> lin, mean, info;
+        std::vector<int64_t> iptr;
+        const size_t nq = mc.set_frame.size();
+        if ((rc = marg_fetch(h, s, h->jp.buf[JPriorFamily::LIN], 12 * nq, lin)) != SRK_OK || (rc = marg_fetch(h, s, h->jp.buf[JPriorFamily::MEAN], 6 * nq, mean)) != SRK_OK ||
+            (rc = marg_fetch(h, s, h->jp.buf[JPriorFamily::IPTR], (size_t)h->jp.n, iptr)) != SRK_OK)
+            return rc;
+        int64_t n_info = 0;
+        for (int32_t gq = 0; gq < h->jp.n; ++gq) {
+            const int64_t k = mc.set_ptr[(size_t)gq + 1] - mc.set_ptr[(size_t)gq];
+            n_info = std::max(n_info, iptr[(size_t)gq] + 36 * k * k);
+        }
+        if ((rc = marg_fetch(h, s, h->jp.buf[JPriorFamily::INFO], (size_t)n_info, info)) != SRK_OK) return rc;
+        for (int32_t gq : p.sets) {
+            const int32_t q0 = mc.set_ptr[(size_t)gq], k = mc.set_ptr[(size_t)gq + 1] - q0;
+            std::vector<double> Rk((size_t)(9 * k)), Tk((size_t)(3 * k)), H((size_t)(36 * k * k)), gv((size_t)(6 * k));
+            for (int32_t i = 0; i < k; ++i) {
+                const size_t f = (size_t)mc.set_frame[(size_t)(q0 + i)];
+                std::copy(&mc.R[9 * f], &mc.R[9 * f] + 9, &Rk[9 * (size_t)i]);
+                std::copy(&mc.T[3 * f], &mc.T[3 * f] + 3, &Tk[3 * (size_t)i]);
+            }
+            srk_jprior_terms(k, Rk.data(), Tk.data(), &lin[12 * (size_t)q0], &mean[6 * (size_t)q0], &info[(size_t)iptr[(size_t)gq]], H.data(), gv.data());
+            scatter(k, &mc.set_frame[(size_t)q0], H.data(), gv.data());
+        }
+    }
+    for (int64_t r = 0; r < n; ++r) // (both triangles carry the same sums up to rounding)
+        for (int64_t cc = r + 1; cc < n; ++cc) mc.A1[(size_t)(r * n + cc)] = mc.A1[(size_t)(cc * n + r)] = 0.5 * (mc.A1[(size_t)(r * n + cc)] + mc.A1[(size_t)(cc * n + r)]);
+    mc.rep.factors = (int32_t)p.factors.size();
+    mc.rep.sets = (int32_t)p.sets.size();
+    mc.rep.frame_priors = (int32_t)p.fr_priors.size();
+    return SRK_OK;
+}
+
+extern "C" {
+
+int srk_ba_marginalization_plan(srk_ba* h, int32_t n_drop, const int32_t* drop, int64_t n_points, const int64_t* points, int32_t kept_cap,
+                                int32_t* kept, srk_ba_marg_counts* counts)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    try {
+        HIPCHK(h, hipSetDevice(h->device));
+        MargCall mc;
+        int rc = marg_plan(h, n_drop, drop, n_points, points, mc);
+        if (rc != SRK_OK || (rc = marg_kept_out(h, mc, kept_cap, kept, nullptr, true)) != SRK_OK) return rc;
+        const SrkMargPlan& p = mc.plan;
+        if (counts)
+            *counts = srk_ba_marg_counts{ p.d, p.k, (int64_t)p.lm.size(), p.n_single, p.n_stage, (int32_t)p.factors.size(), (int32_t)p.sets.size(),
+                                          (int32_t)p.fr_priors.size() };
+        return SRK_OK;
+    } catch (const std::bad_alloc&) {
+        h->last_error = "marginalization_plan: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+int srk_ba_phase_marginalization(srk_ba* h, int32_t n_drop, const int32_t* drop, int64_t n_points, const int64_t* points, int32_t kept_cap,
+                                 int32_t* kept, int32_t* n_kept, double* A0, double* b0, double* A1, double* b1, srk_ba_marg_report* report)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    try {
+        HIPCHK(h, hipSetDevice(h->device));
+        MargCall mc;
+        int rc = marg_plan(h, n_drop, drop, n_points, points, mc);
+        if (rc != SRK_OK || (rc = marg_kept_out(h, mc, kept_cap, kept, n_kept, false)) != SRK_OK) return rc;
+        if ((rc = marg_device(h, mc)) != SRK_OK || (rc = marg_host_terms(h, mc)) != SRK_OK) return rc;
+        marg_kept_out(h, mc, kept_cap, kept, n_kept, true);
+        copy_out(A0, mc.A0);
+        copy_out(b0, mc.b0);
+        copy_out(A1, mc.A1);
+        copy_out(b1, mc.b1);
+        if (report) *report = mc.rep;
+        return SRK_OK;
+    } catch (const std::bad_alloc&) {
+        h->last_error = "phase_marginalization: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+int srk_ba_marginalization_prior(srk_ba* h, int32_t n_drop, const int32_t* drop, int64_t n_points, const int64_t* points, int32_t kept_cap,
+                                 int32_t* kept, int32_t* n_kept, double* lin_R, double* lin_C, double* info, double* eta, double* mean,
+                                 srk_ba_marg_report* report)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    try {
+        HIPCHK(h, hipSetDevice(h->device));
+        MargCall mc;
+        int rc = marg_plan(h, n_drop, drop, n_points, points, mc);
+        if (rc != SRK_OK || (rc = marg_kept_out(h, mc, kept_cap, kept, n_kept, false)) != SRK_OK) return rc;
+        if ((rc = marg_device(h, mc)) != SRK_OK) return rc;
+        const auto t0 = std::chrono::steady_clock::now();
+        if ((rc = marg_host_terms(h, mc)) != SRK_OK) return rc;
+        const SrkMargPlan& p = mc.plan;
+        const size_t nk = 6 * (size_t)p.k;
+        std::vector<double> Lam(nk * nk), et(nk), mn(nk), lr(9 * (size_t)p.k), lc(3 * (size_t)p.k);
+        if (srk_marg_dense(mc.A1.data(), mc.b1.data(), p.d, p.k, Lam.data(), et.data(), mn.data(), &mc.rep.defect) != 0) {
+            h->last_error = "marginalization: the block of the dropped frames is not positive definite";
+            return 1;
+        }
+        for (int32_t i = 0; i < p.k; ++i) {
+            const size_t f = (size_t)p.slot_frame[(size_t)(p.d + i)];
+            const double* r = &mc.R[9 * f];
+            const double* t = &mc.T[3 * f];
+            std::copy(r, r + 9, &lr[9 * (size_t)i]);
+            for (int e = 0; e < 3; ++e) lc[3 * (size_t)i + e] = -(r[e] * t[0] + r[3 + e] * t[1] + r[6 + e] * t[2]);
+        }
+        if (h->normalized_on_upload) srk_marg_revert(h->nrm, p.k, lr.data(), lc.data(), Lam.data(), et.data(), mn.data());
+        mc.rep.ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        marg_kept_out(h, mc, kept_cap, kept, n_kept, true);
+        copy_out(lin_R, lr);
+        copy_out(lin_C, lc);
+        copy_out(info, Lam);
+        copy_out(eta, et);
+        copy_out(mean, mn);
+        if (report) *report = mc.rep;
+        return SRK_OK;
+    } catch (const std::bad_alloc&) {
+        h->last_error = "marginalization_prior: out of host memory";
+        return SRK_E_NOMEM;
+    }
 }
 
 } // extern "C"

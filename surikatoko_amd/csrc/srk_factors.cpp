@@ -598,3 +598,98 @@ void srk_jprior_residuals(const SrkJPriorApplied& s, const double* R, const doub
         for (int c = 0; c < 6; ++c) e[c] -= s.mean[6 * q + (size_t)c];
     }
 }
+
+// ------------------------------------------------------------------ Gauss-Newton terms of one factor / one set
+// The marginalisation prior adds these on the host to the sum the device formed.  Poses in the normalised world, Log as above
+// and the inverse Jacobians on the kernels' series and thresholds (rp_jk of srk_ba_kernels.hip): must stay in step with theirs.
+
+// the coefficient of [phi]x^2 in the inverse Jacobians of SO(3) at the squared angle t2
+static double so3_jk(double t2)
+{
+    if (t2 < 1e-6) return 1.0 / 12.0 + t2 / 720.0;
+    const double t = std::sqrt(t2);
+    if (t2 >= 2.25) return 1.0 / t2 - 1.0 / (2.0 * t * std::tan(0.5 * t));
+    return 1.0 / t2 - (1.0 + std::cos(t)) / (2.0 * t * std::sin(t));
+}
+// I + sg [p]x / 2 + k [p]x^2: the inverse right Jacobian (sg = +1) or the inverse left Jacobian (sg = -1) at p
+static void so3_jinv(const double p[3], double sg, double J[9])
+{
+    const double t2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2], k = so3_jk(t2), h = 0.5 * sg;
+    J[0] = 1.0 + k * (p[0] * p[0] - t2); J[1] = -h * p[2] + k * p[0] * p[1]; J[2] = h * p[1] + k * p[0] * p[2];
+    J[3] = h * p[2] + k * p[0] * p[1]; J[4] = 1.0 + k * (p[1] * p[1] - t2); J[5] = -h * p[0] + k * p[1] * p[2];
+    J[6] = -h * p[1] + k * p[0] * p[2]; J[7] = h * p[0] + k * p[1] * p[2]; J[8] = 1.0 + k * (p[2] * p[2] - t2);
+}
+// H = J^T L J (n x n) and g = J^T L e from J [rows][n], L [rows][rows], e [rows]
+static void gn_terms(int rows, int n, const double* J, const double* L, const double* e, double* H, double* g)
+{
+    std::vector<double> LJ((size_t)rows * n, 0.0), Le((size_t)rows, 0.0);
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < rows; ++c) {
+            const double l = L[r * rows + c];
+            if (l == 0) continue;
+            Le[(size_t)r] += l * e[c];
+            for (int v = 0; v < n; ++v) LJ[(size_t)r * n + v] += l * J[c * n + v];
+        }
+    for (int a = 0; a < n; ++a) {
+        double s = 0;
+        for (int r = 0; r < rows; ++r) s += J[r * n + a] * Le[(size_t)r];
+        g[a] = s;
+        for (int v = 0; v < n; ++v) {
+            double h = 0;
+            for (int r = 0; r < rows; ++r) h += J[r * n + a] * LJ[(size_t)r * n + v];
+            H[a * n + v] = h;
+        }
+    }
+}
+
+void srk_relpose_terms(const double* Ra, const double* Ta, const double* Rb, const double* Tb, const double* Z, const double* z,
+                       const double* L, double* H, double* g)
+{
+    double Ca[3], Cb[3], d[3], e[6], Pm[9], M[9], Ji[9];
+    centre(Ra, Ta, 0, Ca);
+    centre(Rb, Tb, 0, Cb);
+    for (int c = 0; c < 3; ++c) d[c] = Cb[c] - Ca[c];
+    for (int r = 0; r < 3; ++r) e[r] = Ra[3 * r] * d[0] + Ra[3 * r + 1] * d[1] + Ra[3 * r + 2] * d[2] - z[r];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Pm[3 * r + c] = Ra[3 * r] * Rb[3 * c] + Ra[3 * r + 1] * Rb[3 * c + 1] + Ra[3 * r + 2] * Rb[3 * c + 2];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) M[3 * r + c] = Z[r] * Pm[c] + Z[3 + r] * Pm[3 + c] + Z[6 + r] * Pm[6 + c];
+    so3_log(M, e + 3);
+    so3_jinv(e + 3, 1.0, Ji);
+    // [-R_a, R_a [d]x, R_a, 0; 0, -Jr^-1 R_b, 0, Jr^-1 R_b] over [T_a W_a T_b W_b]
+    const double dx[9] = { 0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0 };
+    double J[72] = {};
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            J[12 * r + c] = -Ra[3 * r + c];
+            J[12 * r + 3 + c] = Ra[3 * r] * dx[c] + Ra[3 * r + 1] * dx[3 + c] + Ra[3 * r + 2] * dx[6 + c];
+            J[12 * r + 6 + c] = Ra[3 * r + c];
+            const double jr = Ji[3 * r] * Rb[c] + Ji[3 * r + 1] * Rb[3 + c] + Ji[3 * r + 2] * Rb[6 + c];
+            J[12 * (3 + r) + 3 + c] = -jr;
+            J[12 * (3 + r) + 9 + c] = jr;
+        }
+    gn_terms(6, 12, J, L, e, H, g);
+}
+
+void srk_jprior_terms(int32_t k, const double* R, const double* T, const double* lin, const double* mean, const double* L, double* H, double* g)
+{
+    const int n = 6 * k;
+    std::vector<double> J((size_t)n * n, 0.0), e((size_t)n);
+    for (int32_t q = 0; q < k; ++q) {
+        const double* r = R + 9 * (size_t)q;
+        const double* Rb = lin + 12 * (size_t)q;
+        double M[9], Ji[9], rr[6];
+        centre(R, T, q, rr);
+        for (int c = 0; c < 3; ++c) rr[c] -= Rb[9 + c];
+        for (int a = 0; a < 3; ++a) // M = R^T Rbar
+            for (int b = 0; b < 3; ++b) M[3 * a + b] = r[a] * Rb[b] + r[3 + a] * Rb[3 + b] + r[6 + a] * Rb[6 + b];
+        so3_log(M, rr + 3);
+        so3_jinv(rr + 3, -1.0, Ji);
+        for (int c = 0; c < 6; ++c) e[(size_t)(6 * q + c)] = rr[c] - mean[6 * q + c];
+        for (int a = 0; a < 3; ++a) {
+            J[(size_t)(6 * q + a) * n + 6 * q + a] = 1.0;
+            for (int b = 0; b < 3; ++b) J[(size_t)(6 * q + 3 + a) * n + 6 * q + 3 + b] = Ji[3 * a + b];
+        }
+    }
+    gn_terms(n, n, J.data(), L, e.data(), H, g);
+}

@@ -138,3 +138,13 @@ void srk_prior_residuals(const SrkPriorApplied& s, const double* pts, const doub
                          double* d_frames /* [n][3] or NULL */);
 void srk_relpose_residuals(const SrkRelPoseApplied& s, const double* R, const double* T, double* r_out /* [n][6] */);
 void srk_jprior_residuals(const SrkJPriorApplied& s, const double* R, const double* T, double* r_out /* [slots][6] */);
+
+// ---- the Gauss-Newton terms of one factor / one set at given poses (srk_ba_marginalization_prior adds them on the host; DESIGN.md
+// section 20): H = J^T L J and g = J^T L e, WITHOUT the factor 2 of the device's sums, over the pose variables [Tx Ty Tz Wx Wy Wz]
+// of the frames.  Poses (R world -> camera, T) and values in one coordinate system (the device tables' normalised world).  The
+// same Log, inverse-Jacobian series and thresholds as the kernels (k_relpose_add, k_jprior_form).
+// one relative-pose factor between frames a and b: Z [9], z [3], L [36] full symmetric; H [144] (a's six variables first), g [12]
+void srk_relpose_terms(const double* Ra, const double* Ta, const double* Rb, const double* Tb, const double* Z, const double* z,
+                       const double* L, double* H, double* g);
+// one joint set over k frames: R [k][9], T [k][3] the frames' poses, lin [k][12] (Rbar, Cbar), mean [6 k], L [(6 k)^2]; H [(6 k)^2], g [6 k]
+void srk_jprior_terms(int32_t k, const double* R, const double* T, const double* lin, const double* mean, const double* L, double* H, double* g);

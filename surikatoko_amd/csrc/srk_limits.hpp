@@ -25,3 +25,9 @@
 #define SRK_LONG_FB_HOST 8
 // joint Gaussian pose priors (srk_ba_set_joint_pose_priors): frames of one set; its information matrix has 6 x that many rows
 #define SRK_JP_MAX_FRAMES_HOST 16
+// marginalisation priors (srk_ba_marginalization_prior): frames dropped by one call, frames its result may
+// tie (the dense strip of k_marg_rows has 6 x (their sum) + 1 columns, padded to a multiple of 16: at most SRK_MARG_LDZ_HOST)
+#define SRK_MARG_MAX_DROP_HOST 8
+#define SRK_MARG_MAX_KEPT_HOST 32
+#define SRK_MARG_LDZ_HOST 256
+#define SRK_MARG_ROWS 4 // rows of the strip per landmark: three of L^-1 W and one of zeros (a step of the f64 MFMA takes four rows)
