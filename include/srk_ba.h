@@ -759,6 +759,65 @@ int srk_ba_marginalize_dense(const double* A, const double* b, int32_t d, int32_
 int srk_ba_revert_marginalization_prior(const srk_ba_normalizer* nrm, int32_t k, double* lin_R, double* lin_C, double* info, double* eta,
                                         double* mean);
 
+/* ---- batched landmark triangulation and refinement on the device (EXTENSION) ----
+ * The front half of a sliding window: a new keyframe brings new tracks, and a landmark has to exist before srk_ba_upload_scene
+ * can take it.  Track i owns the observations row_ptr[i] .. row_ptr[i + 1] (any length, 0 included): frame[o] in [0, n_frames),
+ * uv[o] in pixels, q[o] >= 0 its information (q NULL = all 1; q = 0 switches an observation off, and the track then has the
+ * bits of the track without it).
+ *
+ * Linear stage: the system of Triangulate3DPointByLeastSquares (cpp_impl/suriko-engine/src/obs-geom.cpp:679-727), two rows
+ * x p2 - f0 p0 and y p2 - f0 p1 per observation with P = K [R | T] built on the device, scaled by sqrt(q), solved by a streaming
+ * Givens QR factorisation (never the normal equations: relative error ~ eps cond(A), not eps cond(A)^2).  Refinement (options
+ * given, refine_attempts > 0): Levenberg-Marquardt on E(X) = sum q |uv - pi(X)|^2 in pixels from the linear result: damping factor
+ * 1e-4, x 10 on a rejected attempt, / 10 on an accepted one, each attempt solves (H + c diag H) d = -g with H = sum q J^T J, an
+ * attempt is accepted iff E decreases, the loop stops when an accepted attempt changes E by less than refine_rel_change E or
+ * after refine_attempts attempts (at most 64).  The result never has a larger E than the linear one.
+ *
+ * Outputs per track: X [3]; quality [4] = { sqrt(E / n) in pixels at X, the largest angle in degrees between the viewing ray of
+ * a weighted observation and that of the first weighted one, the 1-norm condition number of the 3 x 3 triangular factor, the
+ * number n of weighted observations }; status, a mask of SRK_TRI_*.  The library applies no threshold of its own: condition and
+ * parallax are reported, the caller decides (min_parallax_deg = 0: no gate).  With SRK_TRI_FEW_VIEWS X, quality[0] and
+ * quality[2] are NaN.  No atomics and a fixed merge order: a track's bits depend on its own observations alone.
+ *
+ * srk_triangulate_tracks takes the poses from the caller (cam_R [n_frames][9], cam_T [n_frames][3] inverse poses, K
+ * [n_frames][9] or [9] with shared_k) and, like srk_mvf_estimate_depths, leaves an uploaded scene untouched; no normalisation, no
+ * planning.  srk_ba_triangulate reads the CURRENT poses and K of the resident scene on the device (after srk_ba_optimize: the
+ * refined ones), maps the caller's frame numbers through the handle's frame order, triangulates in the normalised coordinates
+ * and, with revert_normalization = 1, returns X in the coordinates of the uploaded arrays; nothing is downloaded but the results
+ * and the resident scene is not modified.  It is refused with more than one rank and with intrinsic groups.
+ *
+ * Every index is checked on the host before anything is launched: SRK_E_ARGS (text in srk_ba_last_error) for a row_ptr that does
+ * not start at 0 or decreases, a frame outside [0, n_frames), a q that is negative or not finite, a uv that is not finite, a NULL
+ * array with a positive count, refine_attempts outside 0..64, a refine_rel_change or min_parallax_deg that is negative or not
+ * finite.  SRK_E_STATE: srk_ba_triangulate without a scene. */
+enum {
+    SRK_TRI_FEW_VIEWS = 1,      /* fewer than two observations with q > 0: X is NaN */
+    SRK_TRI_DEGENERATE = 2,     /* a zero or non-finite diagonal of the factor, or a non-finite X (srk_triangulate_least_squares returns 0) */
+    SRK_TRI_BEHIND = 4,         /* depth <= 0 in some weighted frame */
+    SRK_TRI_LOW_PARALLAX = 8,   /* quality[1] < min_parallax_deg */
+    SRK_TRI_NOT_CONVERGED = 16  /* the refinement used all its attempts */
+};
+typedef struct srk_tri_options {
+    int32_t refine_attempts;    /* 0 = linear only; at most 64 */
+    double refine_rel_change;   /* stop when an accepted attempt changes E by less than this times E */
+    double min_parallax_deg;    /* 0 = no gate */
+} srk_tri_options;
+void srk_tri_default_options(srk_tri_options*); /* { 10, 1e-9, 0 } */
+int srk_triangulate_tracks(srk_ba*, double f0, int64_t n_tracks, const int64_t* row_ptr, const int32_t* frame, const double* uv /* [O][2] */,
+                           const double* q /* [O], NULL = all 1 */, int32_t n_frames, const double* cam_R, const double* cam_T,
+                           const double* K, int shared_k, const srk_tri_options* /* NULL = linear only */, double* X /* [n][3] */,
+                           double* quality /* [n][4] */, uint32_t* status /* [n] */);
+int srk_ba_triangulate(srk_ba*, int64_t n_tracks, const int64_t* row_ptr, const int32_t* frame /* caller's numbering */, const double* uv,
+                       const double* q, const srk_tri_options*, int revert_normalization, double* X, double* quality, uint32_t* status);
+/* device ms of the two kernels (the frames' packs, the tracks) of the last of the two calls on this handle, from an event pair */
+double srk_ba_triangulate_kernel_ms(const srk_ba*);
+/* host only, no device and no handle needed: the checks of the two calls on their own.  SRK_OK, or SRK_E_ARGS with *why (may be
+ * NULL) pointing at a static text. */
+int srk_tri_check_tracks(int64_t n_tracks, const int64_t* row_ptr, const int32_t* frame, const double* uv, const double* q, int32_t n_frames,
+                         const srk_tri_options* opts, const char** why);
+/* host only: points of the normalised scene to the caller's coordinates, in place: X = R0^T (X_n / s - T0) */
+int srk_tri_revert_points(const srk_ba_normalizer* nrm, int64_t n, double* X);
+
 /* ---- marginal covariances of frames and landmarks (EXTENSION) ----
  * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
  * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior

@@ -442,6 +442,47 @@ public:
         return true;
     }
 
+    /// EXTENSION: new landmarks from corner tracks, on the device (srk_triangulate_tracks / srk_ba_triangulate; DESIGN.md
+    /// section 21; the linear system of Triangulate3DPointByLeastSquares, obs-geom.cpp:679-727, solved by a streaming QR
+    /// factorisation, with an optional Levenberg-Marquardt refinement of the reprojection error).  One result per track, in
+    /// the tracks' order; a track needs no SalientPointId.  status: SRK_TRI_* bits (0 = fine).
+    struct TriangulatedPoint {
+        Point3 X;
+        Scalar rms_pixels = 0, max_ray_angle_deg = 0, cond1 = 0;
+        size_t views = 0;
+        uint32_t status = 0;
+    };
+    /// over caller-given cameras (inverse orientations) and intrinsics; an uploaded scene is left untouched.  opts NULL:
+    /// the linear result.  Throws std::invalid_argument for every refusal of the library.
+    std::vector<TriangulatedPoint> TriangulateTracks(Scalar f0, const std::vector<CornerTrack>& tracks, const std::vector<SE3Transform>& cams,
+                                                     const Matrix3* shared_K, const std::vector<Matrix3>* Ks, const srk_tri_options* opts = nullptr) {
+        if ((shared_K != nullptr) == (Ks != nullptr)) throw std::invalid_argument("Provide either shared K or separate K for each camera frame");
+        if (Ks && Ks->size() != cams.size()) throw std::invalid_argument("triangulate: one K per camera");
+        TrackArrays a = FlattenTracks(tracks, cams.size());
+        std::vector<Scalar> R, T, K;
+        for (const SE3Transform& c : cams) {
+            R.insert(R.end(), c.R.begin(), c.R.end());
+            T.insert(T.end(), { c.T.x, c.T.y, c.T.z });
+        }
+        if (shared_K) K.assign(shared_K->begin(), shared_K->end());
+        else for (const Matrix3& k : *Ks) K.insert(K.end(), k.begin(), k.end());
+        TriOut o(tracks.size());
+        int rc = srk_triangulate_tracks(h_, f0, (int64_t)tracks.size(), a.row_ptr.data(), a.frames.data(), a.uv.data(), nullptr, (int32_t)cams.size(),
+                                        R.data(), T.data(), K.data(), shared_K ? 1 : 0, opts, o.X.data(), o.q.data(), o.st.data());
+        if (rc < 0) Raise(rc);
+        return o.Points();
+    }
+    /// over the CURRENT cameras and intrinsics of the last ComputeInplace's scene, read on the device (after the solve: the
+    /// refined ones); the points come back in the coordinates of that call's map.  The scene is not modified.
+    std::vector<TriangulatedPoint> Triangulate(const std::vector<CornerTrack>& tracks, const srk_tri_options* opts = nullptr) {
+        TrackArrays a = FlattenTracks(tracks, frames_count_);
+        TriOut o(tracks.size());
+        int rc = srk_ba_triangulate(h_, (int64_t)tracks.size(), a.row_ptr.data(), a.frames.data(), a.uv.data(), nullptr, opts, 1, o.X.data(), o.q.data(),
+                                    o.st.data());
+        if (rc < 0) Raise(rc);
+        return o.Points();
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
@@ -450,6 +491,39 @@ public:
     srk_ba* Handle() const { return h_; }
 
 private:
+    struct TrackArrays {
+        std::vector<int64_t> row_ptr{ 0 };
+        std::vector<int32_t> frames;
+        std::vector<Scalar> uv;
+    };
+    static TrackArrays FlattenTracks(const std::vector<CornerTrack>& tracks, size_t n_frames) {
+        TrackArrays a;
+        for (const CornerTrack& t : tracks) {
+            for (size_t j = 0; j < n_frames; ++j)
+                if (auto c = t.GetCorner(j)) { a.frames.push_back((int32_t)j); a.uv.push_back(c->x); a.uv.push_back(c->y); }
+            a.row_ptr.push_back((int64_t)a.frames.size());
+        }
+        a.frames.push_back(0); // never read: keeps data() valid when no track has a corner
+        a.uv.insert(a.uv.end(), { 0, 0 });
+        return a;
+    }
+    struct TriOut {
+        std::vector<Scalar> X, q;
+        std::vector<uint32_t> st;
+        explicit TriOut(size_t n) : X(3 * n + 1), q(4 * n + 1), st(n + 1) {}
+        std::vector<TriangulatedPoint> Points() const {
+            std::vector<TriangulatedPoint> out(st.size() - 1);
+            for (size_t i = 0; i < out.size(); ++i) {
+                out[i].X = Point3{ X[3 * i], X[3 * i + 1], X[3 * i + 2] };
+                out[i].rms_pixels = q[4 * i];
+                out[i].max_ray_angle_deg = q[4 * i + 1];
+                out[i].cond1 = q[4 * i + 2];
+                out[i].views = (size_t)q[4 * i + 3];
+                out[i].status = st[i];
+            }
+            return out;
+        }
+    };
     struct Flat {
         std::vector<size_t> ids;
         std::vector<Scalar> pts, R, T, K, uv;

@@ -8,5 +8,7 @@ from ._lib import lib, library_path, build_library, LibraryNotBuilt  # noqa: F40
 from .ba import (BundleAdjustmentKanatani, BundleAdjustmentKanataniTermCriteria, Report, Scene,  # noqa: F401
                  normalize_scene_inplace, check_world_is_normalized, status_string, device_count, revert_covariances,
                  revert_cross_covariances, marginalize_dense, revert_marginalization_prior, marginalization_landmarks)
+from .triangulate import (triangulate_tracks, tri_status_names, default_tri_options, TRI_FEW_VIEWS, TRI_DEGENERATE,  # noqa: F401
+                          TRI_BEHIND, TRI_LOW_PARALLAX, TRI_NOT_CONVERGED)
 from .scene import (SceneSpec, generate_scene, config_scene, drop_observations, renumber_frames, loop_scene,  # noqa: F401
                     CONFIGS)

@@ -66,6 +66,10 @@ class MargReport(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TriOptions(C.Structure):
+    _fields_ = [("refine_attempts", C.c_int32), ("refine_rel_change", C.c_double), ("min_parallax_deg", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 # every symbol include/srk_ba.h declares (checked by tests/test_abi.py)
@@ -87,6 +91,7 @@ EXPORTS = [
     "srk_ba_joint_pose_prior_pass_ms",
     "srk_ba_marginalization_plan", "srk_ba_phase_marginalization", "srk_ba_marginalization_prior", "srk_ba_marginalize_dense",
     "srk_ba_revert_marginalization_prior",
+    "srk_tri_default_options", "srk_triangulate_tracks", "srk_ba_triangulate", "srk_ba_triangulate_kernel_ms", "srk_tri_check_tracks", "srk_tri_revert_points",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
     "srk_ba_phase_cross_covariance", "srk_ba_cross_covariances", "srk_ba_revert_cross_covariances", "srk_ba_relative_pose_covariances",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
@@ -180,6 +185,16 @@ def lib():
     L.srk_ba_marginalization_prior.argtypes = _marg + [C.POINTER(C.c_int32)] + [C.c_void_p] * 5 + [C.POINTER(MargReport)]
     L.srk_ba_marginalize_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
     L.srk_ba_revert_marginalization_prior.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+    _tracks = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.srk_tri_default_options.argtypes = [C.POINTER(TriOptions)]
+    L.srk_tri_default_options.restype = None
+    L.srk_triangulate_tracks.argtypes = [C.c_void_p, C.c_double] + _tracks + [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                                              C.POINTER(TriOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.srk_ba_triangulate.argtypes = [C.c_void_p] + _tracks + [C.POINTER(TriOptions), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.srk_tri_check_tracks.argtypes = _tracks + [C.c_int32, C.POINTER(TriOptions), C.POINTER(C.c_char_p)]
+    L.srk_ba_triangulate_kernel_ms.argtypes = [C.c_void_p]
+    L.srk_ba_triangulate_kernel_ms.restype = C.c_double
+    L.srk_tri_revert_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
     L.srk_ba_phase_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.srk_ba_covariances.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.srk_ba_revert_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]

@@ -1313,6 +1313,21 @@ class BundleAdjustmentKanatani:
             out["information_metric"] = L / (float(sigma_pixels) / float(self._f0)) ** 2
         return out
 
+    def triangulate(self, row_ptr, frame, uv, q=None, refine_attempts=0, refine_rel_change=1e-9, min_parallax_deg=0.0,
+                    revert_normalization=True):
+        """New landmarks from tracks over the resident scene's CURRENT poses and intrinsics, on the device (srk_ba_triangulate;
+        after optimize(): the refined ones).  frame in the numbering of the uploaded scene.  Returns X [n][3] (in the uploaded
+        arrays' coordinates with revert_normalization), quality [n][4] and status [n]: see triangulate.triangulate_tracks.  The
+        resident scene is not modified."""
+        from .triangulate import tri_options, tri_track_args
+        n, rp, fr, m, w = tri_track_args(row_ptr, frame, uv, q)
+        X, quality, status = np.zeros((n, 3)), np.zeros((n, 4)), np.zeros(n, np.uint32)
+        opts = tri_options(refine_attempts, refine_rel_change, min_parallax_deg)
+        self._raise(self._lib.srk_ba_triangulate(C.c_void_p(self._h), C.c_int64(n), _p(rp), _p(fr), _p(m), None if w is None else _p(w),
+                                                 None if opts is None else C.byref(opts), C.c_int(int(bool(revert_normalization))), _p(X),
+                                                 _p(quality), _p(status)))
+        return X, quality, status
+
     def buffer(self, which):
         """flat download of a staged buffer; its layout follows frame_vars() (include/srk_ba.h SRK_BUF_*)"""
         n = self._lib.srk_ba_buffer_size(C.c_void_p(self._h), int(which))

@@ -13,6 +13,9 @@
 #include "srk_factors.hpp"
 #include "srk_marg.hpp"
 #include "srk_marg_dev.hpp"
+#include "srk_tri.hpp"
+#include "srk_tri_dev.hpp"
+#include "srk_tri_math.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -255,6 +258,12 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     DevBuf mg[MG_NBUF];
     hipEvent_t mg_ev[4]{};
     std::vector<int32_t> mg_obs_frame;
+    // batched triangulation (srk_triangulate_tracks, srk_ba_triangulate): the tracks, the caller's poses, the
+    // frames' packs and the results of a call, grown lazily
+    enum { TRI_ROW, TRI_FRAME, TRI_UV, TRI_Q, TRI_R, TRI_T, TRI_K, TRI_PACK, TRI_X, TRI_QUAL, TRI_STATUS, TRI_NBUF };
+    DevBuf tri[TRI_NBUF];
+    hipEvent_t tri_ev[2]{}; // around the two kernels of a call, created at the first call
+    double tri_ms = 0;      // their device time in the last call (srk_ba_triangulate_kernel_ms)
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -427,6 +436,9 @@ void srk_ba_destroy(srk_ba* h)
                       &h->cov_Y, &h->cov_grp, &h->cov_blk, &h->cov_out, &h->cov_free, &h->cov_colb, &h->cov_pairs };
     for (DevBuf* b : all) dev_free(*b);
     for (DevBuf& b : h->mg) dev_free(b);
+    for (DevBuf& b : h->tri) dev_free(b);
+    for (hipEvent_t& e : h->tri_ev)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->mg_ev)
         if (e) hipEventDestroy(e);
     for (auto& a : h->att) {
@@ -3017,6 +3029,111 @@ int srk_ba_marginalization_prior(srk_ba* h, int32_t n_drop, const int32_t* drop,
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------ batched triangulation
+// The checked tracks of a call to the device, the kernel over the given frames' poses (device pointers), the results back.
+// frame: the frames as the pose arrays number them.
+static int tri_run(srk_ba* h, double f0, int64_t n_tracks, const int64_t* row_ptr, const int32_t* frame, const double* uv, const double* q,
+                   int32_t n_frames, const double* dR, const double* dT, const double* dK, int shared_k, const srk_tri_options& o, double* X,
+                   double* quality, uint32_t* status)
+{
+    hipStream_t s = h->main_stream;
+    const int64_t O = row_ptr[n_tracks];
+    DevBuf* g = h->tri;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &g[srk_ba::TRI_ROW], row_ptr, (size_t)(8 * (n_tracks + 1)) }, { &g[srk_ba::TRI_FRAME], frame, (size_t)(4 * O) },
+        { &g[srk_ba::TRI_UV], uv, (size_t)(16 * O) },                   { &g[srk_ba::TRI_Q], q, q ? (size_t)(8 * O) : 0 },
+    };
+    for (auto& u : up) {
+        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+        if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((rc = dev_alloc(h, g[srk_ba::TRI_PACK], (size_t)(8 * SRK_TRI_PACK * (int64_t)n_frames))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::TRI_X], (size_t)(24 * n_tracks))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::TRI_QUAL], (size_t)(32 * n_tracks))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::TRI_STATUS], (size_t)(4 * n_tracks))) != SRK_OK)
+        return rc;
+    for (hipEvent_t& e : h->tri_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    HIPCHK(h, hipEventRecord(h->tri_ev[0], s));
+    srk_launch_tri_pack(s, n_frames, dR, dT, dK, shared_k, P<double>(g[srk_ba::TRI_PACK]));
+    srk_launch_tri_tracks(s, n_tracks, P<int64_t>(g[srk_ba::TRI_ROW]), P<int32_t>(g[srk_ba::TRI_FRAME]), P<double>(g[srk_ba::TRI_UV]),
+                          q ? P<double>(g[srk_ba::TRI_Q]) : nullptr, P<double>(g[srk_ba::TRI_PACK]), f0, o.refine_attempts, o.refine_rel_change,
+                          o.min_parallax_deg, P<double>(g[srk_ba::TRI_X]), P<double>(g[srk_ba::TRI_QUAL]), P<uint32_t>(g[srk_ba::TRI_STATUS]));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->tri_ev[1], s));
+    HIPCHK(h, hipMemcpyAsync(X, g[srk_ba::TRI_X].p, (size_t)(24 * n_tracks), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(quality, g[srk_ba::TRI_QUAL].p, (size_t)(32 * n_tracks), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(status, g[srk_ba::TRI_STATUS].p, (size_t)(4 * n_tracks), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->tri_ev[0], h->tri_ev[1]));
+    h->tri_ms = ms;
+    return SRK_OK;
+}
+
+extern "C" double srk_ba_triangulate_kernel_ms(const srk_ba* h) { return h ? h->tri_ms : 0.0; }
+
+extern "C" int srk_triangulate_tracks(srk_ba* h, double f0, int64_t n_tracks, const int64_t* row_ptr, const int32_t* frame, const double* uv,
+                                      const double* q, int32_t n_frames, const double* cam_R, const double* cam_T, const double* K, int shared_k,
+                                      const srk_tri_options* opts, double* X, double* quality, uint32_t* status)
+{
+    if (!h) return SRK_E_ARGS;
+    try {
+        std::string why = srk_tri_check(n_tracks, row_ptr, frame, uv, q, n_frames, opts);
+        if (why.empty() && (!cam_R || !cam_T || !K)) why = "triangulate: a NULL pose or intrinsics array";
+        if (why.empty() && (!std::isfinite(f0) || srk::is_close(0.0, f0))) why = "triangulate: f0 must be finite and not ~0";
+        if (why.empty() && n_tracks > 0 && (!X || !quality || !status)) why = "triangulate: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_tracks == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        hipStream_t s = h->main_stream;
+        DevBuf* g = h->tri;
+        int rc;
+        struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+            { &g[srk_ba::TRI_R], cam_R, (size_t)(72 * (int64_t)n_frames) }, { &g[srk_ba::TRI_T], cam_T, (size_t)(24 * (int64_t)n_frames) },
+            { &g[srk_ba::TRI_K], K, (size_t)(72 * (int64_t)(shared_k ? 1 : n_frames)) },
+        };
+        for (auto& u : up) {
+            if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+            HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+        }
+        return tri_run(h, f0, n_tracks, row_ptr, frame, uv, q, n_frames, P<double>(g[srk_ba::TRI_R]), P<double>(g[srk_ba::TRI_T]),
+                       P<double>(g[srk_ba::TRI_K]), shared_k ? 1 : 0, srk_tri_effective_options(opts), X, quality, status);
+    } catch (const std::bad_alloc&) {
+        h->last_error = "triangulate: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+extern "C" int srk_ba_triangulate(srk_ba* h, int64_t n_tracks, const int64_t* row_ptr, const int32_t* frame, const double* uv, const double* q,
+                                  const srk_tri_options* opts, int revert_normalization, double* X, double* quality, uint32_t* status)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    try {
+        std::string why;
+        if (h->world > 1 || h->allreduce || h->comm) why = "triangulate: more than one rank is not supported";
+        else if (h->shk_G > 0) why = "triangulate: intrinsic groups are not supported";
+        else why = srk_tri_check(n_tracks, row_ptr, frame, uv, q, h->d.M, opts);
+        if (why.empty() && n_tracks > 0 && (!X || !quality || !status)) why = "triangulate: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_tracks == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        for (auto& a : h->att) // nothing of an earlier call is still writing the scene
+            if (a.allocated && a.stream) HIPCHK(h, hipStreamSynchronize(a.stream));
+        std::vector<int32_t> fr;
+        srk_tri_map_frames(row_ptr[n_tracks], frame, h->frame_int.empty() ? nullptr : h->frame_int.data(), fr);
+        const int c = h->cur;
+        const int rc = tri_run(h, h->f0, n_tracks, row_ptr, fr.data(), uv, q, h->d.M, P<double>(h->camR[c]), P<double>(h->camT[c]), kbuf(h, c), 0,
+                               srk_tri_effective_options(opts), X, quality, status);
+        if (rc != SRK_OK) return rc;
+        if (revert_normalization && h->normalized_on_upload) srk_tri_revert_points(&h->nrm, n_tracks, X);
+        return SRK_OK;
+    } catch (const std::bad_alloc&) {
+        h->last_error = "triangulate: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
 
 // ------------------------------------------------------------------ the LM loop (bundle-adj-kanatani.cpp:720-893)
 

@@ -31,3 +31,8 @@
 #define SRK_MARG_MAX_KEPT_HOST 32
 #define SRK_MARG_LDZ_HOST 256
 #define SRK_MARG_ROWS 4 // rows of the strip per landmark: three of L^-1 W and one of zeros (a step of the f64 MFMA takes four rows)
+// batched triangulation (srk_triangulate_tracks): the track and observation counts are 64-bit and a track
+// may have any length; the grid holds 32 tracks a workgroup, so a call takes at most 2^31 - 1 workgroups' worth of tracks
+#define SRK_TRI_MAX_REFINE_ATTEMPTS_HOST 64
+#define SRK_TRI_TRACKS_PER_WG_HOST 32
+#define SRK_TRI_MAX_TRACKS_HOST (2147483647LL * SRK_TRI_TRACKS_PER_WG_HOST)
