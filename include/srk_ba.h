@@ -818,6 +818,85 @@ int srk_tri_check_tracks(int64_t n_tracks, const int64_t* row_ptr, const int32_t
 /* host only: points of the normalised scene to the caller's coordinates, in place: X = R0^T (X_n / s - T0) */
 int srk_tri_revert_points(const srk_ba_normalizer* nrm, int64_t n, double* X);
 
+/* ---- batched camera resection with robust pose refinement on the device (EXTENSION) ----
+ * The other half of a sliding window's front: a new keyframe needs a pose before its tracks can be triangulated and before
+ * srk_ba_upload_scene can take it, and that pose comes from 2D-3D correspondences with landmarks the map already has -- wrong
+ * matches among them.  Relocalising frames against a finished map and checking loop-closure candidates have the same shape.
+ * Frame i owns the observations row_ptr[i] .. row_ptr[i + 1] (any length, 0 included): point[o] in [0, n_points) indexes the
+ * landmarks X [n_points][3], uv[o] in pixels, q[o] >= 0 its information (q NULL = all 1, bit for bit; q = 0 switches an
+ * observation off, and the frame then has the bits of the frame without it).  The caller gives a predicted inverse pose
+ * (R0, T0) per frame (the previous keyframe, odometry, srk_mvf_relative_motion): there is no start without a pose.
+ *
+ * With x_cam = R X + T, C = -R^T T and e_o = pi(K (R X_o + T)) - uv_o in pixels, s_o = |e_o|^2, the call minimises
+ * E = sum_o rho(q_o s_o) per frame: rho none (0), Huber (1) or Cauchy (2) with delta in pixels, the formulas of
+ * srk_ba_set_robust_loss.  The six variables are the pose perturbation of the covariance and joint-prior calls, [t; w] with
+ * C <- C + t and R^T <- Exp(w) R^T; the Jacobian d x_cam / d [t; w] = R [ -I | [X - C]x ] is exact, and with w_o = rho'(q_o s_o)
+ * H = sum q_o w_o J_o^T J_o, g = sum q_o w_o J_o^T e_o.  Levenberg-Marquardt with the project's damping rule: factor 1e-4, x 10 on
+ * a rejected attempt, / 10 on an accepted one; an attempt solves (H + c diag H) d = -g by a written-out 6 x 6 Cholesky
+ * factorisation and walks the moved pose once; it is accepted iff E decreases (a failed factorisation or a non-finite E is a
+ * rejected attempt); the loop stops when an accepted attempt changes E by less than rel_change E, or after `attempts` attempts
+ * (at most 64; 0 = evaluate only).  The result never has a larger E than the start.
+ *
+ * Outputs per frame: R [9], T [3] the inverse pose (the rotation is a product of rotations, never a sum); quality [6] =
+ * { sqrt(E / n) in pixels, the number n of observations with q > 0, sum w_o / n (the effective inlier share; 1 without a loss),
+ * cond_1 of the Jacobi-scaled H_s = D^-1/2 H D^-1/2, the smallest depth of a weighted observation, the attempts used };
+ * info [36] = H / f0^2 at the result, undamped, row-major; status, a mask of SRK_RESECT_*; and optionally w_out [O], the robust
+ * weight rho'(q s) of every observation at the result (0 where q = 0; NULL = not wanted), from which the caller reads the wrong
+ * matches.  The library applies no threshold of its own.
+ *
+ * info is in the units of srk_ba_set_joint_pose_priors: with pixel noise sigma_px the covariance of the six variables is
+ * Sigma = sigma_px^2 H^-1; the library's energies are in units of (pixels / f0)^2, in which the observations' noise is
+ * (sigma_px / f0)^2, so the information that reproduces this frame's observations as a prior term (r - m)^T L (r - m) is
+ * L = (sigma_px / f0)^2 Sigma^-1 = H / f0^2.  With the result as linearisation pose and a zero mean it is a one-frame set as it
+ * comes.
+ *
+ * srk_resect_frames takes landmarks and poses from the caller and leaves an uploaded scene untouched.  srk_ba_resect reads the
+ * CURRENT landmarks of the resident scene on the device (after srk_ba_optimize: the refined ones), maps the caller's landmark
+ * numbers through the handle's landmark order, maps the start poses into the normalised coordinates (R_n = R R0^T,
+ * T_n = s (T - R_n T0)), refines there and, with revert_normalization = 1, returns poses and info in the coordinates of the
+ * uploaded arrays (info by the inverse of what srk_ba_revert_covariances does to a pose covariance; quality[3] is then taken
+ * again from that info and quality[4] divided by the scale, so that both are those of the returned coordinates).  Nothing is
+ * downloaded but the results and no buffer of the scene is written.  It is refused with more than one rank.
+ *
+ * Every index is checked on the host before anything is launched: SRK_E_ARGS (text in srk_ba_last_error) for a row_ptr that does
+ * not start at 0 or decreases, a point outside [0, n_points), a q that is negative or not finite, a uv, X, K, R0 or T0 entry that
+ * is not finite, an R0 that is not a rotation to 1e-9 (the joint-prior setter's rule), attempts outside 0..64, a negative or
+ * non-finite rel_change, a loss kind outside 0..2, a loss with delta <= 0, a NULL array with a positive count.  SRK_E_STATE:
+ * srk_ba_resect without a scene. */
+enum {
+    SRK_RESECT_FEW_POINTS = 1,    /* fewer than three observations with q > 0: the pose is the start, quality[3] is NaN */
+    SRK_RESECT_DEGENERATE = 2,    /* the scaled H at the result is not positive definite, or something is not finite */
+    SRK_RESECT_BEHIND = 4,        /* a weighted observation at depth <= 0 at the result */
+    SRK_RESECT_NOT_CONVERGED = 8  /* the loop used all its attempts */
+};
+typedef struct srk_resect_options {
+    int32_t attempts;           /* 0 = evaluate only; at most 64 */
+    double rel_change;          /* stop when an accepted attempt changes E by less than this times E */
+    int32_t loss_kind;          /* 0 none, 1 Huber, 2 Cauchy */
+    double loss_delta_pixels;   /* > 0 with a loss */
+} srk_resect_options;
+void srk_resect_default_options(srk_resect_options*); /* { 10, 1e-9, 0, 0 } */
+int srk_resect_frames(srk_ba*, double f0, int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv /* [O][2] */,
+                      const double* q /* [O], NULL = all 1 */, int64_t n_points, const double* X /* [n_points][3] */,
+                      const double* K /* [n_frames][9], or [9] with shared_k */, int shared_k, const double* R0 /* [n][9] */,
+                      const double* T0 /* [n][3] */, const srk_resect_options* /* NULL = the defaults */, double* R /* [n][9] */,
+                      double* T /* [n][3] */, double* quality /* [n][6] */, double* info /* [n][36] */, uint32_t* status /* [n] */,
+                      double* w_out /* [O] or NULL */);
+int srk_ba_resect(srk_ba*, int32_t n_frames, const int64_t* row_ptr, const int32_t* point /* caller's landmark numbering */,
+                  const double* uv, const double* q, const double* K, int shared_k, const double* R0, const double* T0,
+                  const srk_resect_options*, int revert_normalization, double* R, double* T, double* quality, double* info,
+                  uint32_t* status, double* w_out);
+/* device ms of the two kernels (the start poses' packs, the frames) of the last of the two calls on this handle, from an event pair */
+double srk_ba_resect_kernel_ms(const srk_ba*);
+/* host only, no device and no handle needed: the checks of srk_resect_frames on their own.  SRK_OK, or SRK_E_ARGS with *why (may
+ * be NULL) pointing at a static text. */
+int srk_resect_check_frames(int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv, const double* q, int64_t n_points,
+                            const double* X, const double* K, int shared_k, const double* R0, const double* T0, const srk_resect_options* opts,
+                            const char** why);
+/* host only: results of the normalised scene to the caller's coordinates, in place: R = R_n R0, T = T_n / s + R_n T0,
+ * info = D^T info_n D with D = diag(s R0, R0); R and T together or both NULL, info may be NULL */
+int srk_resect_revert(const srk_ba_normalizer* nrm, int32_t n, double* R, double* T, double* info);
+
 /* ---- marginal covariances of frames and landmarks (EXTENSION) ----
  * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
  * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior

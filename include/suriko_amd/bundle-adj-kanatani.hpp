@@ -483,6 +483,51 @@ public:
         return o.Points();
     }
 
+    /// EXTENSION: the poses of frames from 2D-3D correspondences with known landmarks and a predicted pose each, on the device
+    /// (srk_resect_frames / srk_ba_resect; DESIGN.md section 22: Levenberg-Marquardt on the reprojection error per frame, with
+    /// an optional Huber or Cauchy loss).  One result per frame, in the frames' order.  status: SRK_RESECT_* bits (0 = fine).
+    struct ResectObservation {
+        size_t point = 0;       ///< index into the landmarks
+        Point2f uv;             ///< pixels
+        Scalar information = 1; ///< q >= 0; 0 switches the observation off
+    };
+    struct ResectedFrame {
+        SE3Transform pose;                ///< inverse orientation
+        Scalar rms_pixels = 0, inlier_share = 0, cond1 = 0, min_depth = 0;
+        size_t points = 0, attempts = 0;
+        std::array<Scalar, 36> info{};    ///< H / f0^2, row-major: a one-frame set of SetJointPosePriors as it comes
+        uint32_t status = 0;
+        std::vector<Scalar> weights;      ///< the robust weight of every observation (with want_weights)
+    };
+    /// over caller-given landmarks; an uploaded scene is left untouched.  opts NULL: the defaults (10 attempts, 1e-9, no loss).
+    /// Throws std::invalid_argument for every refusal of the library.
+    std::vector<ResectedFrame> ResectFrames(Scalar f0, const std::vector<std::vector<ResectObservation>>& frames, const std::vector<Point3>& landmarks,
+                                            const std::vector<SE3Transform>& start, const Matrix3* shared_K, const std::vector<Matrix3>* Ks,
+                                            const srk_resect_options* opts = nullptr, bool want_weights = false) {
+        ResectArrays a(frames, start, shared_K, Ks, want_weights);
+        std::vector<Scalar> X;
+        for (const Point3& p : landmarks) X.insert(X.end(), { p.x, p.y, p.z });
+        X.push_back(0); // never read: keeps data() valid without landmarks
+        int rc = srk_resect_frames(h_, f0, (int32_t)frames.size(), a.row_ptr.data(), a.point.data(), a.uv.data(), a.q.data(), (int64_t)landmarks.size(),
+                                   X.data(), a.K.data(), shared_K ? 1 : 0, a.R0.data(), a.T0.data(), opts, a.R.data(), a.T.data(), a.ql.data(),
+                                   a.info.data(), a.st.data(), want_weights ? a.w.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        return a.Frames(want_weights);
+    }
+    /// over the CURRENT landmarks of the last ComputeInplace's scene, read on the device (after the solve: the refined ones);
+    /// point is the landmark's index in that scene (the order of the tracks that have a SalientPointId).  start, the poses and
+    /// info are in the coordinates of that call's map.  The scene is not modified.
+    std::vector<ResectedFrame> Resect(const std::vector<std::vector<ResectObservation>>& frames, const std::vector<SE3Transform>& start,
+                                      const Matrix3* shared_K, const std::vector<Matrix3>* Ks, const srk_resect_options* opts = nullptr,
+                                      bool want_weights = false) {
+        ResectArrays a(frames, start, shared_K, Ks, want_weights);
+        int rc = srk_ba_resect(h_, (int32_t)frames.size(), a.row_ptr.data(), a.point.data(), a.uv.data(), a.q.data(), a.K.data(), shared_K ? 1 : 0,
+                               a.R0.data(), a.T0.data(), opts, 1, a.R.data(), a.T.data(), a.ql.data(), a.info.data(), a.st.data(),
+                               want_weights ? a.w.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        return a.Frames(want_weights);
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
@@ -520,6 +565,57 @@ private:
                 out[i].cond1 = q[4 * i + 2];
                 out[i].views = (size_t)q[4 * i + 3];
                 out[i].status = st[i];
+            }
+            return out;
+        }
+    };
+    struct ResectArrays {
+        std::vector<int64_t> row_ptr{ 0 };
+        std::vector<int32_t> point;
+        std::vector<Scalar> uv, q, K, R0, T0, R, T, ql, info, w;
+        std::vector<uint32_t> st;
+        ResectArrays(const std::vector<std::vector<ResectObservation>>& frames, const std::vector<SE3Transform>& start, const Matrix3* shared_K,
+                     const std::vector<Matrix3>* Ks, bool want_weights) {
+            if ((shared_K != nullptr) == (Ks != nullptr)) throw std::invalid_argument("Provide either shared K or separate K for each camera frame");
+            if (start.size() != frames.size() || (Ks && Ks->size() != frames.size())) throw std::invalid_argument("resect: one start pose and one K per frame");
+            for (const std::vector<ResectObservation>& f : frames) {
+                for (const ResectObservation& o : f) {
+                    if (o.point > 2147483647u) throw std::invalid_argument("resect: a landmark index is beyond the landmarks");
+                    point.push_back((int32_t)o.point);
+                    uv.insert(uv.end(), { o.uv.x, o.uv.y });
+                    q.push_back(o.information);
+                }
+                row_ptr.push_back((int64_t)point.size());
+            }
+            for (const SE3Transform& c : start) {
+                R0.insert(R0.end(), c.R.begin(), c.R.end());
+                T0.insert(T0.end(), { c.T.x, c.T.y, c.T.z });
+            }
+            if (shared_K) K.assign(shared_K->begin(), shared_K->end());
+            else for (const Matrix3& k : *Ks) K.insert(K.end(), k.begin(), k.end());
+            const size_t n = frames.size(), O = point.size();
+            point.push_back(0); // never read: keep data() valid without observations or frames
+            uv.insert(uv.end(), { 0, 0 });
+            q.push_back(0);
+            for (std::vector<Scalar>* v : { &K, &R0, &T0 }) v->push_back(0);
+            R.resize(9 * n + 1), T.resize(3 * n + 1), ql.resize(6 * n + 1), info.resize(36 * n + 1), st.resize(n + 1);
+            w.resize(want_weights ? O + 1 : 1);
+        }
+        std::vector<ResectedFrame> Frames(bool want_weights) const {
+            std::vector<ResectedFrame> out(st.size() - 1);
+            for (size_t i = 0; i < out.size(); ++i) {
+                ResectedFrame& f = out[i];
+                for (size_t e = 0; e < 9; ++e) f.pose.R[e] = R[9 * i + e];
+                f.pose.T = Point3{ T[3 * i], T[3 * i + 1], T[3 * i + 2] };
+                f.rms_pixels = ql[6 * i];
+                f.points = (size_t)ql[6 * i + 1];
+                f.inlier_share = ql[6 * i + 2];
+                f.cond1 = ql[6 * i + 3];
+                f.min_depth = ql[6 * i + 4];
+                f.attempts = (size_t)ql[6 * i + 5];
+                for (size_t e = 0; e < 36; ++e) f.info[e] = info[36 * i + e];
+                f.status = st[i];
+                if (want_weights) f.weights.assign(w.begin() + row_ptr[i], w.begin() + row_ptr[i + 1]);
             }
             return out;
         }

@@ -10,5 +10,7 @@ from .ba import (BundleAdjustmentKanatani, BundleAdjustmentKanataniTermCriteria,
                  revert_cross_covariances, marginalize_dense, revert_marginalization_prior, marginalization_landmarks)
 from .triangulate import (triangulate_tracks, tri_status_names, default_tri_options, TRI_FEW_VIEWS, TRI_DEGENERATE,  # noqa: F401
                           TRI_BEHIND, TRI_LOW_PARALLAX, TRI_NOT_CONVERGED)
+from .resect import (resect_frames, resect_status_names, default_resect_options, RESECT_FEW_POINTS, RESECT_DEGENERATE,  # noqa: F401
+                     RESECT_BEHIND, RESECT_NOT_CONVERGED)
 from .scene import (SceneSpec, generate_scene, config_scene, drop_observations, renumber_frames, loop_scene,  # noqa: F401
                     CONFIGS)

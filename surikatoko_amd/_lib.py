@@ -70,6 +70,10 @@ class TriOptions(C.Structure):
     _fields_ = [("refine_attempts", C.c_int32), ("refine_rel_change", C.c_double), ("min_parallax_deg", C.c_double)]
 
 
+class ResectOptions(C.Structure):
+    _fields_ = [("attempts", C.c_int32), ("rel_change", C.c_double), ("loss_kind", C.c_int32), ("loss_delta_pixels", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 # every symbol include/srk_ba.h declares (checked by tests/test_abi.py)
@@ -92,6 +96,7 @@ EXPORTS = [
     "srk_ba_marginalization_plan", "srk_ba_phase_marginalization", "srk_ba_marginalization_prior", "srk_ba_marginalize_dense",
     "srk_ba_revert_marginalization_prior",
     "srk_tri_default_options", "srk_triangulate_tracks", "srk_ba_triangulate", "srk_ba_triangulate_kernel_ms", "srk_tri_check_tracks", "srk_tri_revert_points",
+    "srk_resect_default_options", "srk_resect_frames", "srk_ba_resect", "srk_ba_resect_kernel_ms", "srk_resect_check_frames", "srk_resect_revert",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
     "srk_ba_phase_cross_covariance", "srk_ba_cross_covariances", "srk_ba_revert_cross_covariances", "srk_ba_relative_pose_covariances",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
@@ -195,6 +200,16 @@ def lib():
     L.srk_ba_triangulate_kernel_ms.argtypes = [C.c_void_p]
     L.srk_ba_triangulate_kernel_ms.restype = C.c_double
     L.srk_tri_revert_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    _frames = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]   # n_frames, row_ptr, point, uv, q
+    _poses = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ResectOptions)]   # K, shared_k, R0, T0, options
+    L.srk_resect_default_options.argtypes = [C.POINTER(ResectOptions)]
+    L.srk_resect_default_options.restype = None
+    L.srk_resect_frames.argtypes = [C.c_void_p, C.c_double] + _frames + [C.c_int64, C.c_void_p] + _poses + [C.c_void_p] * 6
+    L.srk_ba_resect.argtypes = [C.c_void_p] + _frames + _poses + [C.c_int] + [C.c_void_p] * 6
+    L.srk_resect_check_frames.argtypes = _frames + [C.c_int64, C.c_void_p] + _poses + [C.POINTER(C.c_char_p)]
+    L.srk_ba_resect_kernel_ms.argtypes = [C.c_void_p]
+    L.srk_ba_resect_kernel_ms.restype = C.c_double
+    L.srk_resect_revert.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.srk_ba_phase_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.srk_ba_covariances.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.srk_ba_revert_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]

@@ -1328,6 +1328,21 @@ class BundleAdjustmentKanatani:
                                                  _p(quality), _p(status)))
         return X, quality, status
 
+    def resect(self, row_ptr, point, uv, K, R0, T0, q=None, attempts=10, rel_change=1e-9, loss=None, delta=None, want_weights=False,
+               revert_normalization=True):
+        """The poses of new frames from their observations of the resident scene's CURRENT landmarks, on the device
+        (srk_ba_resect; after optimize(): the refined ones).  point in the landmark numbering of the uploaded scene; K, R0, T0
+        the new frames' intrinsics and predicted inverse poses in the uploaded arrays' coordinates.  Returns R, T, quality, info,
+        status (and the robust weights with want_weights): see resect.resect_frames.  The resident scene is not modified."""
+        from .resect import _outputs, _result, resect_frame_args, resect_options
+        n, rp, pt, m, w, Kc, shared_k, R, T = resect_frame_args(row_ptr, point, uv, q, K, R0, T0)
+        opts = resect_options(attempts, rel_change, loss, delta)
+        out = _outputs(n, max(int(rp.max()), 0), want_weights)
+        self._raise(self._lib.srk_ba_resect(C.c_void_p(self._h), C.c_int32(n), _p(rp), _p(pt), _p(m), None if w is None else _p(w), _p(Kc),
+                                            C.c_int(int(shared_k)), _p(R), _p(T), C.byref(opts), C.c_int(int(bool(revert_normalization))),
+                                            *[None if a is None else _p(a) for a in out]))
+        return _result(out, want_weights)
+
     def buffer(self, which):
         """flat download of a staged buffer; its layout follows frame_vars() (include/srk_ba.h SRK_BUF_*)"""
         n = self._lib.srk_ba_buffer_size(C.c_void_p(self._h), int(which))

@@ -16,6 +16,9 @@
 #include "srk_tri.hpp"
 #include "srk_tri_dev.hpp"
 #include "srk_tri_math.hpp"
+#include "srk_resect.hpp"
+#include "srk_resect_dev.hpp"
+#include "srk_resect_math.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -264,6 +267,12 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     DevBuf tri[TRI_NBUF];
     hipEvent_t tri_ev[2]{}; // around the two kernels of a call, created at the first call
     double tri_ms = 0;      // their device time in the last call (srk_ba_triangulate_kernel_ms)
+    // batched camera resection (srk_resect_frames, srk_ba_resect): the frames' observations, the caller's
+    // landmarks, intrinsics and start poses, the packs and the results, grown lazily
+    enum { RS_ROW, RS_POINT, RS_UV, RS_Q, RS_X, RS_K, RS_R0, RS_T0, RS_PACK, RS_R, RS_T, RS_QUAL, RS_INFO, RS_STATUS, RS_W, RS_NBUF };
+    DevBuf rs[RS_NBUF];
+    hipEvent_t rs_ev[2]{}; // around the two kernels of a call, created at the first call
+    double rs_ms = 0;      // their device time in the last call (srk_ba_resect_kernel_ms)
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -437,6 +446,9 @@ void srk_ba_destroy(srk_ba* h)
     for (DevBuf* b : all) dev_free(*b);
     for (DevBuf& b : h->mg) dev_free(b);
     for (DevBuf& b : h->tri) dev_free(b);
+    for (DevBuf& b : h->rs) dev_free(b);
+    for (hipEvent_t& e : h->rs_ev)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->tri_ev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->mg_ev)
@@ -3131,6 +3143,132 @@ extern "C" int srk_ba_triangulate(srk_ba* h, int64_t n_tracks, const int64_t* ro
         return SRK_OK;
     } catch (const std::bad_alloc&) {
         h->last_error = "triangulate: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+// ------------------------------------------------------------------ batched camera resection
+// The checked frames of a call to the device, the two kernels over the given landmarks (a device pointer), the results back.
+// point: the landmarks as dX numbers them.  K, R0, T0: host arrays in the coordinates of dX.
+static int resect_run(srk_ba* h, double f0, int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv, const double* q,
+                      const double* dX, const double* K, int shared_k, const double* R0, const double* T0, const srk_resect_options& o, double* R,
+                      double* T, double* quality, double* info, uint32_t* status, double* w_out)
+{
+    hipStream_t s = h->main_stream;
+    const int64_t O = row_ptr[n_frames], n = n_frames;
+    DevBuf* g = h->rs;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &g[srk_ba::RS_ROW], row_ptr, (size_t)(8 * (n + 1)) }, { &g[srk_ba::RS_POINT], point, (size_t)(4 * O) },
+        { &g[srk_ba::RS_UV], uv, (size_t)(16 * O) },            { &g[srk_ba::RS_Q], q, q ? (size_t)(8 * O) : 0 },
+        { &g[srk_ba::RS_K], K, (size_t)(72 * (shared_k ? 1 : n)) }, { &g[srk_ba::RS_R0], R0, (size_t)(72 * n) },
+        { &g[srk_ba::RS_T0], T0, (size_t)(24 * n) },
+    };
+    for (auto& u : up) {
+        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+        if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((rc = dev_alloc(h, g[srk_ba::RS_PACK], (size_t)(8 * SRK_RESECT_PACK * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::RS_R], (size_t)(72 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::RS_T], (size_t)(24 * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::RS_QUAL], (size_t)(48 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::RS_INFO], (size_t)(288 * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::RS_STATUS], (size_t)(4 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::RS_W], w_out ? (size_t)(8 * O) : 0)) != SRK_OK)
+        return rc;
+    for (hipEvent_t& e : h->rs_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    HIPCHK(h, hipEventRecord(h->rs_ev[0], s));
+    srk_launch_resect_pack(s, n_frames, P<double>(g[srk_ba::RS_R0]), P<double>(g[srk_ba::RS_T0]), P<double>(g[srk_ba::RS_K]), shared_k,
+                           P<double>(g[srk_ba::RS_PACK]));
+    srk_launch_resect_frames(s, n_frames, P<int64_t>(g[srk_ba::RS_ROW]), P<int32_t>(g[srk_ba::RS_POINT]), P<double>(g[srk_ba::RS_UV]),
+                             q ? P<double>(g[srk_ba::RS_Q]) : nullptr, dX, P<double>(g[srk_ba::RS_K]), shared_k, P<double>(g[srk_ba::RS_R0]),
+                             P<double>(g[srk_ba::RS_T0]), P<double>(g[srk_ba::RS_PACK]), f0, o.attempts, o.rel_change, o.loss_kind,
+                             o.loss_delta_pixels, P<double>(g[srk_ba::RS_R]), P<double>(g[srk_ba::RS_T]), P<double>(g[srk_ba::RS_QUAL]),
+                             P<double>(g[srk_ba::RS_INFO]), P<uint32_t>(g[srk_ba::RS_STATUS]), w_out && O > 0 ? P<double>(g[srk_ba::RS_W]) : nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->rs_ev[1], s));
+    HIPCHK(h, hipMemcpyAsync(R, g[srk_ba::RS_R].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(T, g[srk_ba::RS_T].p, (size_t)(24 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(quality, g[srk_ba::RS_QUAL].p, (size_t)(48 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(info, g[srk_ba::RS_INFO].p, (size_t)(288 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(status, g[srk_ba::RS_STATUS].p, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+    if (w_out && O > 0) HIPCHK(h, hipMemcpyAsync(w_out, g[srk_ba::RS_W].p, (size_t)(8 * O), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->rs_ev[0], h->rs_ev[1]));
+    h->rs_ms = ms;
+    return SRK_OK;
+}
+
+extern "C" double srk_ba_resect_kernel_ms(const srk_ba* h) { return h ? h->rs_ms : 0.0; }
+
+extern "C" int srk_resect_frames(srk_ba* h, double f0, int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv,
+                                 const double* q, int64_t n_points, const double* X, const double* K, int shared_k, const double* R0,
+                                 const double* T0, const srk_resect_options* opts, double* R, double* T, double* quality, double* info,
+                                 uint32_t* status, double* w_out)
+{
+    if (!h) return SRK_E_ARGS;
+    try {
+        std::string why = srk_resect_check(n_frames, row_ptr, point, uv, q, n_points, X, K, shared_k, R0, T0, opts);
+        if (why.empty() && n_points > 0 && !X) why = "resect: the landmark array is NULL";
+        if (why.empty() && (!std::isfinite(f0) || srk::is_close(0.0, f0))) why = "resect: f0 must be finite and not ~0";
+        if (why.empty() && n_frames > 0 && (!R || !T || !quality || !info || !status)) why = "resect: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_frames == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        DevBuf& gx = h->rs[srk_ba::RS_X];
+        int rc;
+        if ((rc = dev_alloc(h, gx, (size_t)(24 * n_points))) != SRK_OK) return rc;
+        if (n_points > 0) HIPCHK(h, hipMemcpyAsync(gx.p, X, (size_t)(24 * n_points), hipMemcpyHostToDevice, h->main_stream));
+        return resect_run(h, f0, n_frames, row_ptr, point, uv, q, P<double>(gx), K, shared_k ? 1 : 0, R0, T0, srk_resect_effective_options(opts), R, T,
+                          quality, info, status, w_out);
+    } catch (const std::bad_alloc&) {
+        h->last_error = "resect: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+extern "C" int srk_ba_resect(srk_ba* h, int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv, const double* q,
+                             const double* K, int shared_k, const double* R0, const double* T0, const srk_resect_options* opts,
+                             int revert_normalization, double* R, double* T, double* quality, double* info, uint32_t* status, double* w_out)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    try {
+        std::string why;
+        std::vector<int32_t> pt;
+        if (h->world > 1 || h->allreduce || h->comm) why = "resect: more than one rank is not supported";
+        else {
+            std::vector<int64_t> pt_int((size_t)h->d.N); // the caller's landmark -> its place in the handle's landmark order
+            for (int64_t i = 0; i < h->d.N; ++i) pt_int[(size_t)h->perm[(size_t)i]] = i;
+            why = srk_resect_check(n_frames, row_ptr, point, uv, q, h->d.N, nullptr, K, shared_k, R0, T0, opts, pt_int.data(), &pt);
+        }
+        if (why.empty() && n_frames > 0 && (!R || !T || !quality || !info || !status)) why = "resect: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_frames == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        for (auto& a : h->att) // nothing of an earlier call is still writing the scene
+            if (a.allocated && a.stream) HIPCHK(h, hipStreamSynchronize(a.stream));
+        std::vector<double> Rn((size_t)(9 * (int64_t)n_frames)), Tn((size_t)(3 * (int64_t)n_frames));
+        if (h->normalized_on_upload) srk_resect_normalize_poses(h->nrm, n_frames, R0, T0, Rn.data(), Tn.data());
+        else {
+            std::memcpy(Rn.data(), R0, Rn.size() * 8);
+            std::memcpy(Tn.data(), T0, Tn.size() * 8);
+        }
+        const int rc = resect_run(h, h->f0, n_frames, row_ptr, pt.data(), uv, q, P<double>(h->pts[h->cur]), K, shared_k ? 1 : 0, Rn.data(), Tn.data(),
+                                  srk_resect_effective_options(opts), R, T, quality, info, status, w_out);
+        if (rc != SRK_OK) return rc;
+        if (revert_normalization && h->normalized_on_upload) {
+            std::vector<char> moved((size_t)n_frames);
+            for (int32_t i = 0; i < n_frames; ++i)
+                moved[(size_t)i] = std::memcmp(R + 9 * (int64_t)i, &Rn[(size_t)(9 * (int64_t)i)], 72) != 0 || std::memcmp(T + 3 * (int64_t)i, &Tn[(size_t)(3 * (int64_t)i)], 24) != 0;
+            srk_resect_revert_poses(h->nrm, n_frames, R, T, info, quality);
+            for (int32_t i = 0; i < n_frames; ++i) // a pose that did not move is the caller's start bit for bit, not its round trip
+                if (!moved[(size_t)i]) {
+                    std::memcpy(R + 9 * (int64_t)i, R0 + 9 * (int64_t)i, 72);
+                    std::memcpy(T + 3 * (int64_t)i, T0 + 3 * (int64_t)i, 24);
+                }
+        }
+        return SRK_OK;
+    } catch (const std::bad_alloc&) {
+        h->last_error = "resect: out of host memory";
         return SRK_E_NOMEM;
     }
 }

@@ -36,3 +36,8 @@
 #define SRK_TRI_MAX_REFINE_ATTEMPTS_HOST 64
 #define SRK_TRI_TRACKS_PER_WG_HOST 32
 #define SRK_TRI_MAX_TRACKS_HOST (2147483647LL * SRK_TRI_TRACKS_PER_WG_HOST)
+// batched camera resection (srk_resect_frames): one wave per frame and four frames a workgroup; a frame may
+// have any number of observations (64-bit counts), landmarks are indexed by int32
+#define SRK_RESECT_MAX_ATTEMPTS_HOST 64
+#define SRK_RESECT_FRAMES_PER_WG_HOST 4
+#define SRK_RESECT_MAX_FRAMES_HOST (1 << 22)
