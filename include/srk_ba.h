@@ -897,6 +897,79 @@ int srk_resect_check_frames(int32_t n_frames, const int64_t* row_ptr, const int3
  * info = D^T info_n D with D = diag(s R0, R0); R and T together or both NULL, info may be NULL */
 int srk_resect_revert(const srk_ba_normalizer* nrm, int32_t n, double* R, double* T, double* info);
 
+/* ---- resection without a start pose: P3P hypotheses scored on the device (EXTENSION) ----
+ * srk_resect_frames needs a predicted pose, and that is missing exactly where resection matters most: relocalisation after
+ * tracking is lost, loop-closure candidates, the first frame against a finished map, unordered image sets.  "locate" finds the
+ * pose of each frame from its 2D-3D correspondences alone, wrong matches among them, by hypothesise-and-verify (the reference's
+ * GetMaxSubsetInConsensus / RansacIterationsCount, py_proto/suriko/mvg.py), and can hand it to the refinement of section 22
+ * without leaving the device.
+ *
+ * Observations as in srk_resect_frames: CSR by frame, q >= 0 (NULL = all 1, bit for bit; q = 0 = the frame without that
+ * observation, bit for bit).  Everything works on the frame's n weighted observations, numbered by rank 0 .. n - 1 in ascending o.
+ *
+ * Sampler (counter-based, no state): mix(seed, h, k) = the splitmix64 finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ * z *= 0x94D049BB133111EB; z ^= z >> 31) of seed + 0x9E3779B97F4A7C15 (4 h + k + 1) mod 2^64.  Draw k = 0..3 of hypothesis h is
+ * r = umulhi64(mix, n - k), then for the earlier picks s in ascending order: if (r >= s) ++r.  Four distinct ranks; the key holds
+ * neither the frame's place in the batch nor the batch size.
+ *
+ * Hypothesis: bearings b ~ K^-1 (u, v, f0), normalised (K a general 3 x 3, inverted by its adjugate).  P3P on picks 0-2 gives up
+ * to four poses (R, T), x_cam = R X + T; those with a depth <= 0 at any of the four sample points are dropped and the one with the
+ * smallest squared pixel error at pick 3 is the hypothesis' pose (a tie: the earlier root).  R is a product of two orthonormal
+ * frames, so it passes the rotation check of srk_resect_frames.
+ *
+ * Score (MSAC): score(h) = sum over the ranks in ascending order of min(q s, tau^2), s the squared pixel error; an observation at
+ * depth <= 0 counts tau^2; a hypothesis without a pose scores +inf.  The smallest score wins, an equal score goes to the smaller h.
+ *
+ * Outputs per frame: R [9], T [3]; located [6] = { sqrt(score / n) in pixels, n, the inlier count at the located pose, the winning
+ * h, the number of hypotheses that produced a pose, the reprojection error in pixels of the winning sample's fourth point };
+ * located_status, a mask of SRK_LOCATE_*: then the pose is (I, 0), located[0], [3], [5] are NaN and located[2] is 0.  inlier_out [O]
+ * (may be NULL): 1 iff q_o > 0, the depth is positive and q_o s_o < tau^2 at the located pose, before any refinement.
+ *
+ * With refine != NULL the located poses stay on the device and are the R0, T0 of the kernels of srk_resect_frames: R, T, quality,
+ * info, status and w_out are then bit for bit what srk_resect_frames returns from the located poses (a frame that was not located
+ * is refined from (I, 0) like any other; its located_status says not to trust the result), and located, located_status and
+ * inlier_out are the same with and without.  Without refine, R and T are the located poses and the last four may be NULL.
+ *
+ * srk_ba_locate reads the CURRENT landmarks of the resident scene on the device through the handle's landmark order, locates in
+ * the normalised coordinates and, with revert_normalization = 1, maps poses and info back with the maps of srk_ba_resect.  It
+ * writes no scene buffer and is refused with more than one rank.
+ *
+ * Host checks before any launch (SRK_E_ARGS with a text): everything srk_resect_check_frames checks except the start poses,
+ * hypotheses outside 1..4096, inlier_pixels not finite or <= 0, a K that is singular, NULL outputs, and more than 2^22 waves of
+ * hypotheses (frames x ceil(hypotheses / 64)) in one call: split the batch, a frame's bits do not depend on it. */
+enum {
+    SRK_LOCATE_FEW_POINTS = 1, /* fewer than four observations with q > 0 */
+    SRK_LOCATE_NO_MODEL = 2    /* no sample gave a pose with positive depths */
+};
+typedef struct srk_locate_options {
+    int32_t hypotheses;   /* samples per frame, 1 .. 4096 */
+    double inlier_pixels; /* tau > 0: the truncation of the score and the inlier test */
+    uint64_t seed;
+} srk_locate_options;
+void srk_locate_default_options(srk_locate_options*); /* { 256, 4.0, 1 } */
+int srk_locate_frames(srk_ba*, double f0, int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv /* [O][2] */,
+                      const double* q /* [O], NULL = all 1 */, int64_t n_points, const double* X /* [n_points][3] */,
+                      const double* K /* [n_frames][9], or [9] with shared_k */, int shared_k, const srk_locate_options* /* NULL = the defaults */,
+                      const srk_resect_options* refine /* NULL = no refinement */, double* R /* [n][9] */, double* T /* [n][3] */,
+                      double* located /* [n][6] */, uint32_t* located_status /* [n] */, uint8_t* inlier_out /* [O] or NULL */,
+                      double* quality, double* info, uint32_t* status, double* w_out /* the four of srk_resect_frames, used with refine */);
+int srk_ba_locate(srk_ba*, int32_t n_frames, const int64_t* row_ptr, const int32_t* point /* caller's landmark numbering */,
+                  const double* uv, const double* q, const double* K, int shared_k, const srk_locate_options*,
+                  const srk_resect_options* refine, int revert_normalization, double* R, double* T, double* located,
+                  uint32_t* located_status, uint8_t* inlier_out, double* quality, double* info, uint32_t* status, double* w_out);
+/* device ms of the last of the two calls on this handle (gather, hypotheses and scores, pick, and the refinement when asked for),
+ * from an event pair; and of the hypothesis-and-score kernel alone, from a second pair */
+double srk_ba_locate_kernel_ms(const srk_ba*);
+double srk_ba_locate_score_ms(const srk_ba*);
+/* host only, no device and no handle needed: the checks of srk_locate_frames on their own.  SRK_OK, or SRK_E_ARGS with *why (may
+ * be NULL) pointing at a static text. */
+int srk_locate_check_frames(int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv, const double* q, int64_t n_points,
+                            const double* X, const double* K, int shared_k, const srk_locate_options* opts, const srk_resect_options* refine,
+                            const char** why);
+/* the reference's RansacIterationsCount: ceil(log(1 - p) / log(1 - (1 - e)^s)) samples of size s reach, with probability p, one
+ * without a wrong match at outlier ratio e.  e = 0 gives 1; e outside [0, 1), p outside (0, 1) or s < 1 gives SRK_E_ARGS. */
+int64_t srk_ransac_hypotheses(int sample_size, double outlier_ratio, double success_probability);
+
 /* ---- marginal covariances of frames and landmarks (EXTENSION) ----
  * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
  * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior

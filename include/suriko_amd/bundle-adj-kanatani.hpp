@@ -528,6 +528,49 @@ public:
         return a.Frames(want_weights);
     }
 
+    /// EXTENSION: the poses of frames from 2D-3D correspondences alone, without a predicted pose and with wrong matches among them,
+    /// on the device (srk_locate_frames / srk_ba_locate; DESIGN.md section 23: P3P hypotheses from a counter-based sampler, each
+    /// scored on every observation, the best one optionally refined by the kernels of ResectFrames).  One result per frame.
+    struct LocatedFrame {
+        SE3Transform pose;                ///< the located pose, or the refined one with refine (inverse orientation)
+        Scalar rms_pixels = 0;            ///< sqrt(score / points) of the truncated score; NaN when not located
+        Scalar fourth_point_pixels = 0;   ///< the winning sample's fourth-point error
+        size_t points = 0, inlier_count = 0, hypotheses_with_pose = 0;
+        int64_t winner = -1;              ///< the winning hypothesis, -1 when not located
+        uint32_t located_status = 0;      ///< SRK_LOCATE_* bits (0 = located)
+        std::vector<uint8_t> inliers;     ///< per observation, at the located pose (with want_inliers)
+        ResectedFrame refined;            ///< the refinement's outputs (with refine)
+    };
+    /// over caller-given landmarks; an uploaded scene is left untouched.  opts NULL: the defaults (256 hypotheses, 4 px, seed 1);
+    /// refine NULL: no refinement.  Throws std::invalid_argument for every refusal of the library.
+    std::vector<LocatedFrame> LocateFrames(Scalar f0, const std::vector<std::vector<ResectObservation>>& frames, const std::vector<Point3>& landmarks,
+                                           const Matrix3* shared_K, const std::vector<Matrix3>* Ks, const srk_locate_options* opts = nullptr,
+                                           const srk_resect_options* refine = nullptr, bool want_inliers = false, bool want_weights = false) {
+        ResectArrays a(frames, std::vector<SE3Transform>(frames.size()), shared_K, Ks, want_weights);
+        LocateOut o(frames.size(), a.point.size(), want_inliers);
+        std::vector<Scalar> X;
+        for (const Point3& p : landmarks) X.insert(X.end(), { p.x, p.y, p.z });
+        X.push_back(0); // never read: keeps data() valid without landmarks
+        int rc = srk_locate_frames(h_, f0, (int32_t)frames.size(), a.row_ptr.data(), a.point.data(), a.uv.data(), a.q.data(), (int64_t)landmarks.size(),
+                                   X.data(), a.K.data(), shared_K ? 1 : 0, opts, refine, a.R.data(), a.T.data(), o.located.data(), o.st.data(),
+                                   want_inliers ? o.inl.data() : nullptr, a.ql.data(), a.info.data(), a.st.data(), want_weights ? a.w.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        return o.Frames(a, refine != nullptr, want_inliers, want_weights);
+    }
+    /// over the CURRENT landmarks of the last ComputeInplace's scene, read on the device; point is the landmark's index in that
+    /// scene.  The poses and info are in the coordinates of that call's map.  The scene is not modified.
+    std::vector<LocatedFrame> Locate(const std::vector<std::vector<ResectObservation>>& frames, const Matrix3* shared_K, const std::vector<Matrix3>* Ks,
+                                     const srk_locate_options* opts = nullptr, const srk_resect_options* refine = nullptr, bool want_inliers = false,
+                                     bool want_weights = false) {
+        ResectArrays a(frames, std::vector<SE3Transform>(frames.size()), shared_K, Ks, want_weights);
+        LocateOut o(frames.size(), a.point.size(), want_inliers);
+        int rc = srk_ba_locate(h_, (int32_t)frames.size(), a.row_ptr.data(), a.point.data(), a.uv.data(), a.q.data(), a.K.data(), shared_K ? 1 : 0, opts,
+                               refine, 1, a.R.data(), a.T.data(), o.located.data(), o.st.data(), want_inliers ? o.inl.data() : nullptr, a.ql.data(),
+                               a.info.data(), a.st.data(), want_weights ? a.w.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        return o.Frames(a, refine != nullptr, want_inliers, want_weights);
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
@@ -616,6 +659,32 @@ private:
                 for (size_t e = 0; e < 36; ++e) f.info[e] = info[36 * i + e];
                 f.status = st[i];
                 if (want_weights) f.weights.assign(w.begin() + row_ptr[i], w.begin() + row_ptr[i + 1]);
+            }
+            return out;
+        }
+    };
+    struct LocateOut {
+        std::vector<Scalar> located;
+        std::vector<uint32_t> st;
+        std::vector<uint8_t> inl;
+        LocateOut(size_t n, size_t padded_obs, bool want_inliers) : located(6 * n + 1), st(n + 1), inl(want_inliers ? padded_obs : 1) {}
+        std::vector<LocatedFrame> Frames(const ResectArrays& a, bool refined, bool want_inliers, bool want_weights) const {
+            std::vector<LocatedFrame> out(st.size() - 1);
+            std::vector<ResectedFrame> fine;
+            if (refined) fine = a.Frames(want_weights);
+            for (size_t i = 0; i < out.size(); ++i) {
+                LocatedFrame& f = out[i];
+                for (size_t e = 0; e < 9; ++e) f.pose.R[e] = a.R[9 * i + e];
+                f.pose.T = Point3{ a.T[3 * i], a.T[3 * i + 1], a.T[3 * i + 2] };
+                f.rms_pixels = located[6 * i];
+                f.points = (size_t)located[6 * i + 1];
+                f.inlier_count = (size_t)located[6 * i + 2];
+                f.winner = st[i] ? -1 : (int64_t)located[6 * i + 3];
+                f.hypotheses_with_pose = (size_t)located[6 * i + 4];
+                f.fourth_point_pixels = located[6 * i + 5];
+                f.located_status = st[i];
+                if (want_inliers) f.inliers.assign(inl.begin() + a.row_ptr[i], inl.begin() + a.row_ptr[i + 1]);
+                if (refined) f.refined = fine[i];
             }
             return out;
         }

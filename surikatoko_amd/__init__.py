@@ -12,5 +12,7 @@ from .triangulate import (triangulate_tracks, tri_status_names, default_tri_opti
                           TRI_BEHIND, TRI_LOW_PARALLAX, TRI_NOT_CONVERGED)
 from .resect import (resect_frames, resect_status_names, default_resect_options, RESECT_FEW_POINTS, RESECT_DEGENERATE,  # noqa: F401
                      RESECT_BEHIND, RESECT_NOT_CONVERGED)
+from .locate import (locate_frames, locate_status_names, default_locate_options, ransac_hypotheses, LocateResult,  # noqa: F401
+                     LOCATE_FEW_POINTS, LOCATE_NO_MODEL)
 from .scene import (SceneSpec, generate_scene, config_scene, drop_observations, renumber_frames, loop_scene,  # noqa: F401
                     CONFIGS)

@@ -74,6 +74,10 @@ class ResectOptions(C.Structure):
     _fields_ = [("attempts", C.c_int32), ("rel_change", C.c_double), ("loss_kind", C.c_int32), ("loss_delta_pixels", C.c_double)]
 
 
+class LocateOptions(C.Structure):
+    _fields_ = [("hypotheses", C.c_int32), ("inlier_pixels", C.c_double), ("seed", C.c_uint64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 # every symbol include/srk_ba.h declares (checked by tests/test_abi.py)
@@ -97,6 +101,8 @@ EXPORTS = [
     "srk_ba_revert_marginalization_prior",
     "srk_tri_default_options", "srk_triangulate_tracks", "srk_ba_triangulate", "srk_ba_triangulate_kernel_ms", "srk_tri_check_tracks", "srk_tri_revert_points",
     "srk_resect_default_options", "srk_resect_frames", "srk_ba_resect", "srk_ba_resect_kernel_ms", "srk_resect_check_frames", "srk_resect_revert",
+    "srk_locate_default_options", "srk_locate_frames", "srk_ba_locate", "srk_ba_locate_kernel_ms", "srk_ba_locate_score_ms", "srk_locate_check_frames",
+    "srk_ransac_hypotheses",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
     "srk_ba_phase_cross_covariance", "srk_ba_cross_covariances", "srk_ba_revert_cross_covariances", "srk_ba_relative_pose_covariances",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
@@ -210,6 +216,18 @@ def lib():
     L.srk_ba_resect_kernel_ms.argtypes = [C.c_void_p]
     L.srk_ba_resect_kernel_ms.restype = C.c_double
     L.srk_resect_revert.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    _hyp = [C.c_void_p, C.c_int, C.POINTER(LocateOptions), C.POINTER(ResectOptions)]   # K, shared_k, options, refine
+    L.srk_locate_default_options.argtypes = [C.POINTER(LocateOptions)]
+    L.srk_locate_default_options.restype = None
+    L.srk_locate_frames.argtypes = [C.c_void_p, C.c_double] + _frames + [C.c_int64, C.c_void_p] + _hyp + [C.c_void_p] * 9
+    L.srk_ba_locate.argtypes = [C.c_void_p] + _frames + _hyp + [C.c_int] + [C.c_void_p] * 9
+    L.srk_locate_check_frames.argtypes = _frames + [C.c_int64, C.c_void_p] + _hyp + [C.POINTER(C.c_char_p)]
+    L.srk_ba_locate_kernel_ms.argtypes = [C.c_void_p]
+    L.srk_ba_locate_kernel_ms.restype = C.c_double
+    L.srk_ba_locate_score_ms.argtypes = [C.c_void_p]
+    L.srk_ba_locate_score_ms.restype = C.c_double
+    L.srk_ransac_hypotheses.argtypes = [C.c_int, C.c_double, C.c_double]
+    L.srk_ransac_hypotheses.restype = C.c_int64
     L.srk_ba_phase_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.srk_ba_covariances.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.srk_ba_revert_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]

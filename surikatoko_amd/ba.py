@@ -1343,6 +1343,18 @@ class BundleAdjustmentKanatani:
                                             *[None if a is None else _p(a) for a in out]))
         return _result(out, want_weights)
 
+    def locate(self, row_ptr, point, uv, K, q=None, hypotheses=256, inlier_pixels=4.0, seed=1, refine=None, want_inliers=False,
+               want_weights=False, revert_normalization=True):
+        """The poses of new frames from their observations of the resident scene's CURRENT landmarks alone, without a predicted
+        pose, on the device (srk_ba_locate): P3P hypotheses scored on every observation, the best one optionally refined.  point
+        in the landmark numbering of the uploaded scene; K the new frames' intrinsics.  Returns a locate.LocateResult: see
+        locate.locate_frames.  The resident scene is not modified."""
+        from .locate import LocateResult, _prepare
+        frames, hyp, out, _keep = _prepare(row_ptr, point, uv, K, q, hypotheses, inlier_pixels, seed, refine, want_inliers, want_weights)
+        self._raise(self._lib.srk_ba_locate(C.c_void_p(self._h), *frames, *hyp, C.c_int(int(bool(revert_normalization))),
+                                            *[None if a is None else _p(a) for a in out]))
+        return LocateResult(*out)
+
     def buffer(self, which):
         """flat download of a staged buffer; its layout follows frame_vars() (include/srk_ba.h SRK_BUF_*)"""
         n = self._lib.srk_ba_buffer_size(C.c_void_p(self._h), int(which))

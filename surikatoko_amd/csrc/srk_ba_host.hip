@@ -19,6 +19,9 @@
 #include "srk_resect.hpp"
 #include "srk_resect_dev.hpp"
 #include "srk_resect_math.hpp"
+#include "srk_locate.hpp"
+#include "srk_locate_dev.hpp"
+#include "srk_locate_math.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -273,6 +276,13 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     DevBuf rs[RS_NBUF];
     hipEvent_t rs_ev[2]{}; // around the two kernels of a call, created at the first call
     double rs_ms = 0;      // their device time in the last call (srk_ba_resect_kernel_ms)
+    // resection without a start pose (srk_locate_frames, srk_ba_locate): the gathered strip, the frames'
+    // weighted counts, the waves' slots and the located outputs, grown lazily.  The observations, intrinsics and every buffer of
+    // the refinement are the resection's (rs): the located poses are written into RS_R0 / RS_T0, where its kernels read their starts
+    enum { LC_STRIP, LC_COUNT, LC_SLOTS, LC_LOCATED, LC_LSTATUS, LC_INL, LC_NBUF };
+    DevBuf lc[LC_NBUF];
+    hipEvent_t lc_ev[4]{};           // the call, and the hypothesis-and-score kernel inside it; created at the first call
+    double lc_ms = 0, lc_score_ms = 0; // srk_ba_locate_kernel_ms, srk_ba_locate_score_ms
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -447,6 +457,9 @@ void srk_ba_destroy(srk_ba* h)
     for (DevBuf& b : h->mg) dev_free(b);
     for (DevBuf& b : h->tri) dev_free(b);
     for (DevBuf& b : h->rs) dev_free(b);
+    for (DevBuf& b : h->lc) dev_free(b);
+    for (hipEvent_t& e : h->lc_ev)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->rs_ev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->tri_ev)
@@ -3269,6 +3282,166 @@ extern "C" int srk_ba_resect(srk_ba* h, int32_t n_frames, const int64_t* row_ptr
         return SRK_OK;
     } catch (const std::bad_alloc&) {
         h->last_error = "resect: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+// ------------------------------------------------------------------ resection without a start pose
+// The checked frames of a call to the device, gather / hypotheses and scores / pick over the given landmarks (a device pointer),
+// the refinement's two kernels from the located poses when asked for, the results back.  point: the landmarks as dX numbers them.
+static int locate_run(srk_ba* h, double f0, int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv, const double* q,
+                      const double* dX, const double* K, int shared_k, const srk_locate_options& lo, const srk_resect_options* refine, double* R,
+                      double* T, double* located, uint32_t* located_status, uint8_t* inlier_out, double* quality, double* info, uint32_t* status,
+                      double* w_out)
+{
+    hipStream_t s = h->main_stream;
+    const int64_t O = row_ptr[n_frames], n = n_frames;
+    const int64_t waves = (lo.hypotheses + SRK_LOCATE_LANES - 1) / SRK_LOCATE_LANES;
+    DevBuf* g = h->rs;
+    DevBuf* l = h->lc;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &g[srk_ba::RS_ROW], row_ptr, (size_t)(8 * (n + 1)) }, { &g[srk_ba::RS_POINT], point, (size_t)(4 * O) },
+        { &g[srk_ba::RS_UV], uv, (size_t)(16 * O) },            { &g[srk_ba::RS_Q], q, q ? (size_t)(8 * O) : 0 },
+        { &g[srk_ba::RS_K], K, (size_t)(72 * (shared_k ? 1 : n)) },
+    };
+    for (auto& u : up) {
+        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+        if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    const bool want_w = refine && w_out && O > 0, want_inl = inlier_out && O > 0;
+    if ((rc = dev_alloc(h, l[srk_ba::LC_STRIP], (size_t)(8 * SRK_LOCATE_STRIP * O))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::LC_COUNT], (size_t)(8 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::LC_SLOTS], (size_t)(8 * SRK_LOCATE_SLOT * n * waves))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::LC_LOCATED], (size_t)(48 * n))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::LC_LSTATUS], (size_t)(4 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::LC_INL], want_inl ? (size_t)O : 0)) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::RS_R0], (size_t)(72 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::RS_T0], (size_t)(24 * n))) != SRK_OK)
+        return rc;
+    if (refine &&
+        ((rc = dev_alloc(h, g[srk_ba::RS_PACK], (size_t)(8 * SRK_RESECT_PACK * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::RS_R], (size_t)(72 * n))) != SRK_OK ||
+         (rc = dev_alloc(h, g[srk_ba::RS_T], (size_t)(24 * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::RS_QUAL], (size_t)(48 * n))) != SRK_OK ||
+         (rc = dev_alloc(h, g[srk_ba::RS_INFO], (size_t)(288 * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::RS_STATUS], (size_t)(4 * n))) != SRK_OK ||
+         (rc = dev_alloc(h, g[srk_ba::RS_W], want_w ? (size_t)(8 * O) : 0)) != SRK_OK))
+        return rc;
+    for (hipEvent_t& e : h->lc_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    const int64_t* d_row = P<int64_t>(g[srk_ba::RS_ROW]);
+    const int32_t* d_point = P<int32_t>(g[srk_ba::RS_POINT]);
+    const double* d_uv = P<double>(g[srk_ba::RS_UV]);
+    const double* d_q = q ? P<double>(g[srk_ba::RS_Q]) : nullptr;
+    const double* d_K = P<double>(g[srk_ba::RS_K]);
+    double* d_R0 = P<double>(g[srk_ba::RS_R0]);
+    double* d_T0 = P<double>(g[srk_ba::RS_T0]);
+    HIPCHK(h, hipEventRecord(h->lc_ev[0], s));
+    srk_launch_locate_gather(s, n_frames, d_row, d_point, d_uv, d_q, dX, P<double>(l[srk_ba::LC_STRIP]), P<int64_t>(l[srk_ba::LC_COUNT]));
+    HIPCHK(h, hipEventRecord(h->lc_ev[1], s));
+    srk_launch_locate_score(s, n_frames, lo.hypotheses, lo.seed, lo.inlier_pixels, f0, d_row, P<double>(l[srk_ba::LC_STRIP]),
+                            P<int64_t>(l[srk_ba::LC_COUNT]), d_K, shared_k, P<double>(l[srk_ba::LC_SLOTS]));
+    HIPCHK(h, hipEventRecord(h->lc_ev[2], s));
+    srk_launch_locate_pick(s, n_frames, lo.hypotheses, lo.inlier_pixels, f0, d_row, d_point, d_uv, d_q, dX, d_K, shared_k, P<int64_t>(l[srk_ba::LC_COUNT]),
+                           P<double>(l[srk_ba::LC_SLOTS]), d_R0, d_T0, P<double>(l[srk_ba::LC_LOCATED]), P<uint32_t>(l[srk_ba::LC_LSTATUS]),
+                           want_inl ? P<uint8_t>(l[srk_ba::LC_INL]) : nullptr);
+    if (refine) { // the located poses never leave the device: they are the starts of the resection's own kernels
+        srk_launch_resect_pack(s, n_frames, d_R0, d_T0, d_K, shared_k, P<double>(g[srk_ba::RS_PACK]));
+        srk_launch_resect_frames(s, n_frames, d_row, d_point, d_uv, d_q, dX, d_K, shared_k, d_R0, d_T0, P<double>(g[srk_ba::RS_PACK]), f0,
+                                 refine->attempts, refine->rel_change, refine->loss_kind, refine->loss_delta_pixels, P<double>(g[srk_ba::RS_R]),
+                                 P<double>(g[srk_ba::RS_T]), P<double>(g[srk_ba::RS_QUAL]), P<double>(g[srk_ba::RS_INFO]),
+                                 P<uint32_t>(g[srk_ba::RS_STATUS]), want_w ? P<double>(g[srk_ba::RS_W]) : nullptr);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->lc_ev[3], s));
+    HIPCHK(h, hipMemcpyAsync(R, refine ? g[srk_ba::RS_R].p : g[srk_ba::RS_R0].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(T, refine ? g[srk_ba::RS_T].p : g[srk_ba::RS_T0].p, (size_t)(24 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(located, l[srk_ba::LC_LOCATED].p, (size_t)(48 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(located_status, l[srk_ba::LC_LSTATUS].p, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+    if (want_inl) HIPCHK(h, hipMemcpyAsync(inlier_out, l[srk_ba::LC_INL].p, (size_t)O, hipMemcpyDeviceToHost, s));
+    if (refine) {
+        HIPCHK(h, hipMemcpyAsync(quality, g[srk_ba::RS_QUAL].p, (size_t)(48 * n), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(info, g[srk_ba::RS_INFO].p, (size_t)(288 * n), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(status, g[srk_ba::RS_STATUS].p, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+        if (want_w) HIPCHK(h, hipMemcpyAsync(w_out, g[srk_ba::RS_W].p, (size_t)(8 * O), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
+    float ms = 0, score_ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->lc_ev[0], h->lc_ev[3]));
+    HIPCHK(h, hipEventElapsedTime(&score_ms, h->lc_ev[1], h->lc_ev[2]));
+    h->lc_ms = ms;
+    h->lc_score_ms = score_ms;
+    return SRK_OK;
+}
+
+extern "C" double srk_ba_locate_kernel_ms(const srk_ba* h) { return h ? h->lc_ms : 0.0; }
+extern "C" double srk_ba_locate_score_ms(const srk_ba* h) { return h ? h->lc_score_ms : 0.0; }
+
+static std::string locate_outputs_missing(int32_t n_frames, const srk_resect_options* refine, const double* R, const double* T, const double* located,
+                                          const uint32_t* located_status, const double* quality, const double* info, const uint32_t* status)
+{
+    if (n_frames > 0 && (!R || !T || !located || !located_status)) return "locate: a NULL output array";
+    if (n_frames > 0 && refine && (!quality || !info || !status)) return "locate: a NULL output array of the refinement";
+    return std::string();
+}
+
+extern "C" int srk_locate_frames(srk_ba* h, double f0, int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv,
+                                 const double* q, int64_t n_points, const double* X, const double* K, int shared_k, const srk_locate_options* opts,
+                                 const srk_resect_options* refine, double* R, double* T, double* located, uint32_t* located_status,
+                                 uint8_t* inlier_out, double* quality, double* info, uint32_t* status, double* w_out)
+{
+    if (!h) return SRK_E_ARGS;
+    try {
+        std::string why = srk_locate_check(n_frames, row_ptr, point, uv, q, n_points, X, K, shared_k, opts, refine);
+        if (why.empty() && n_points > 0 && !X) why = "locate: the landmark array is NULL";
+        if (why.empty() && (!std::isfinite(f0) || srk::is_close(0.0, f0))) why = "locate: f0 must be finite and not ~0";
+        if (why.empty()) why = locate_outputs_missing(n_frames, refine, R, T, located, located_status, quality, info, status);
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_frames == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        DevBuf& gx = h->rs[srk_ba::RS_X];
+        int rc;
+        if ((rc = dev_alloc(h, gx, (size_t)(24 * n_points))) != SRK_OK) return rc;
+        if (n_points > 0) HIPCHK(h, hipMemcpyAsync(gx.p, X, (size_t)(24 * n_points), hipMemcpyHostToDevice, h->main_stream));
+        return locate_run(h, f0, n_frames, row_ptr, point, uv, q, P<double>(gx), K, shared_k ? 1 : 0, srk_locate_effective_options(opts), refine, R, T,
+                          located, located_status, inlier_out, quality, info, status, w_out);
+    } catch (const std::bad_alloc&) {
+        h->last_error = "locate: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+extern "C" int srk_ba_locate(srk_ba* h, int32_t n_frames, const int64_t* row_ptr, const int32_t* point, const double* uv, const double* q,
+                             const double* K, int shared_k, const srk_locate_options* opts, const srk_resect_options* refine,
+                             int revert_normalization, double* R, double* T, double* located, uint32_t* located_status, uint8_t* inlier_out,
+                             double* quality, double* info, uint32_t* status, double* w_out)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    try {
+        std::string why;
+        std::vector<int32_t> pt;
+        if (h->world > 1 || h->allreduce || h->comm) why = "locate: more than one rank is not supported";
+        else {
+            std::vector<int64_t> pt_int((size_t)h->d.N); // the caller's landmark -> its place in the handle's landmark order
+            for (int64_t i = 0; i < h->d.N; ++i) pt_int[(size_t)h->perm[(size_t)i]] = i;
+            why = srk_locate_check(n_frames, row_ptr, point, uv, q, h->d.N, nullptr, K, shared_k, opts, refine, pt_int.data(), &pt);
+        }
+        if (why.empty()) why = locate_outputs_missing(n_frames, refine, R, T, located, located_status, quality, info, status);
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_frames == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        for (auto& a : h->att) // nothing of an earlier call is still writing the scene
+            if (a.allocated && a.stream) HIPCHK(h, hipStreamSynchronize(a.stream));
+        const int rc = locate_run(h, h->f0, n_frames, row_ptr, pt.data(), uv, q, P<double>(h->pts[h->cur]), K, shared_k ? 1 : 0,
+                                  srk_locate_effective_options(opts), refine, R, T, located, located_status, inlier_out, quality, info, status, w_out);
+        if (rc != SRK_OK) return rc;
+        if (revert_normalization && h->normalized_on_upload) {
+            srk_resect_revert_poses(h->nrm, n_frames, R, T, refine ? info : nullptr, refine ? quality : nullptr);
+            if (!refine)
+                for (int32_t i = 0; i < n_frames; ++i) // a frame that was not located keeps (I, 0) in every coordinate system
+                    if (located_status[i]) {
+                        for (int e = 0; e < 9; ++e) R[9 * (int64_t)i + e] = (e % 4 == 0) ? 1.0 : 0.0;
+                        for (int e = 0; e < 3; ++e) T[3 * (int64_t)i + e] = 0.0;
+                    }
+        }
+        return SRK_OK;
+    } catch (const std::bad_alloc&) {
+        h->last_error = "locate: out of host memory";
         return SRK_E_NOMEM;
     }
 }

@@ -41,3 +41,8 @@
 #define SRK_RESECT_MAX_ATTEMPTS_HOST 64
 #define SRK_RESECT_FRAMES_PER_WG_HOST 4
 #define SRK_RESECT_MAX_FRAMES_HOST (1 << 22)
+// resection without a start pose (srk_locate_frames): a wave scores 64 hypotheses of one frame; a call holds
+// one slot of 160 bytes per wave, so frames x ceil(hypotheses / 64) is capped (640 MiB of slots at the cap)
+#define SRK_LOCATE_MAX_HYPOTHESES_HOST 4096
+#define SRK_LOCATE_LANES_HOST 64
+#define SRK_LOCATE_MAX_WAVES_HOST (1 << 22)
