@@ -970,6 +970,73 @@ int srk_locate_check_frames(int32_t n_frames, const int64_t* row_ptr, const int3
  * without a wrong match at outlier ratio e.  e = 0 gives 1; e outside [0, 1), p outside (0, 1) or s < 1 gives SRK_E_ARGS. */
 int64_t srk_ransac_hypotheses(int sample_size, double outlier_ratio, double success_probability);
 
+/* ---- two-view relative pose: five-point hypotheses scored on the device (EXTENSION) ----
+ * Triangulation, resection and locate all need a map or a pose to start from; "relate" produces the first one.  From the 2D-2D
+ * matches of two images, wrong matches among them, it finds the rotation and the direction of the translation between the two
+ * cameras by hypothesise-and-verify (the reference's FindRelativeMotion, py_proto/suriko/mvg.py: the five-point method, the
+ * Sampson distance, the decomposition of the essential matrix and its GetMaxSubsetInConsensus loop).  The five-point method is not
+ * degenerate on planar scenes, where the eight-point method is.
+ *
+ * Conventions: frame a is (I, 0), frame b is (R, T) with x_b ~ R x_a + T and |T| = 1 (the R X + T of srk_resect_frames).  E = [T]x R
+ * exactly as returned, and x^_b^T E x^_a = 0 for the rays x^ = K^-1 (u, v, f0).  K and f0 as in srk_locate_frames.  Pairs in CSR
+ * form with any number of matches; q >= 0 the optional information of a match (NULL = all 1, bit for bit; q = 0 = the pair without
+ * that match, bit for bit).  Everything works on the pair's n weighted matches, numbered by rank 0 .. n - 1 in ascending o.
+ *
+ * Sampler (counter-based, no state, a stream of its own): mix(seed, h, k) = the splitmix64 finaliser of
+ * seed + 0xD1B54A32D192ED03 (8 h + k + 1) mod 2^64.  Draw k = 0..5 of hypothesis h is r = umulhi64(mix, n - k), then for the
+ * earlier picks s in ascending order: if (r >= s) ++r.  Six distinct ranks that depend on seed, h and k alone.
+ *
+ * Hypothesis: picks 0-4 give up to ten essential matrices (Nister's route: the null space of the 5 x 9 epipolar matrix, the ten
+ * cubic constraints det E = 0 and 2 E E^T E - tr(E E^T) E = 0 eliminated to a 3 x 3 matrix B(z), the real roots of det B, a
+ * polynomial of degree 10, by the derivative chain, each solution polished by Gauss-Newton steps on the constraints); pick 5
+ * chooses the one with the smallest Sampson error, an equal error goes to the smaller root.
+ *
+ * Score (MSAC): score(h) = sum over the ranks in ascending order of min(q s, tau^2), s the squared Sampson distance in pixels of
+ * F = K_b^-T E K_a^-1; a hypothesis without a model scores +inf.  The smallest score wins, an equal score goes to the smaller h.
+ *
+ * Pose: for the winner only (the four poses of an E have one score).  T is the unit vector along the largest cross product of two
+ * columns of E, R1 = Cof(E) - [T]x E, R2 = Cof(E) + [T]x E; the four poses in the order (R1, T), (R1, -T), (R2, T), (R2, -T).  The
+ * one with the most inliers at a positive distance along both rays is returned; a tie goes to the earlier in that order.
+ *
+ * Outputs per pair: R [9], T [3] (unit), E [9]; related [8] = { sqrt(score / n) in pixels, n, the inlier count, the winning h, the
+ * number of hypotheses that gave a model, the sixth-match Sampson error in pixels, the number of inliers in front of both cameras
+ * under the returned pose, the mean angle in radians between the two rays of those inliers (the parallax, summed per lane in
+ * ascending rank and merged in a fixed tree) }.  The library has no threshold of its own: pure rotation and low parallax are read
+ * from related[6] and related[7].  status, a mask of SRK_RELATE_*: then the pose is (I, 0), E is zero, related[0], [3], [5], [7] are
+ * NaN and related[2], [6] are 0.  inlier_out [O] (may be NULL): 1 iff q_o > 0 and q_o s_o < tau^2 at the winner.
+ *
+ * Host checks before any launch (SRK_E_ARGS with a text): a descending or negative row_ptr, uv or K that is not finite, q negative
+ * or not finite, a singular K, hypotheses outside 1..4096, inlier_pixels not finite or <= 0, NULL outputs, and more than 2^22
+ * waves (pairs x ceil(hypotheses / 64)) in one call: split the batch, a pair's bits do not depend on it.  Nothing is allocated or
+ * launched unless srk_relate_frames is called.  Absent: an adaptive early stop, refinement inside the call (two-frame bundle
+ * adjustment after triangulating the inliers is the refinement), several ranks. */
+enum {
+    SRK_RELATE_FEW_POINTS = 1, /* fewer than six matches with q > 0 */
+    SRK_RELATE_NO_MODEL = 2    /* no sample gave an essential matrix */
+};
+typedef struct srk_relate_options {
+    int32_t hypotheses;   /* samples per pair, 1 .. 4096 */
+    double inlier_pixels; /* tau > 0: the truncation of the score and the inlier test */
+    uint64_t seed;
+} srk_relate_options;
+void srk_relate_default_options(srk_relate_options*); /* { 256, 2.0, 1 } */
+int srk_relate_frames(srk_ba*, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a /* [O][2] */, const double* uv_b /* [O][2] */,
+                      const double* q /* [O], NULL = all 1 */, const double* K_a, const double* K_b /* [n_pairs][9], or [9] with shared_k */,
+                      int shared_k, const srk_relate_options* /* NULL = the defaults */, double* R /* [n][9] */, double* T /* [n][3], unit */,
+                      double* E /* [n][9] */, double* related /* [n][8] */, uint32_t* status /* [n] */, uint8_t* inlier_out /* [O] or NULL */);
+/* device ms of the last srk_relate_frames on this handle (gather, solve, score, pick) from an event pair, and of the score kernel
+ * alone from a second pair: the difference is, but for the gather and the pick, the five-point solve */
+double srk_ba_relate_kernel_ms(const srk_ba*);
+double srk_ba_relate_score_ms(const srk_ba*);
+/* host only, no device and no handle needed: the checks of srk_relate_frames on their own.  SRK_OK, or SRK_E_ARGS with *why (may
+ * be NULL) pointing at a static text. */
+int srk_relate_check_pairs(int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q, const double* K_a,
+                           const double* K_b, int shared_k, const srk_relate_options* opts, const char** why);
+/* host only: one pair of n_obs matches in the kernels' own order of operations (the same statements, compiled for the host).
+ * Returns the status bits, or SRK_E_ARGS (negative) when the checks refuse the pair. */
+int srk_relate_host_pair(int64_t n_obs, const double* uv_a, const double* uv_b, const double* q, const double* K_a, const double* K_b, double f0,
+                         const srk_relate_options* opts, double* R, double* T, double* E, double* related, uint8_t* inlier_out);
+
 /* ---- marginal covariances of frames and landmarks (EXTENSION) ----
  * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
  * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior

@@ -571,6 +571,77 @@ public:
         return o.Frames(a, refine != nullptr, want_inliers, want_weights);
     }
 
+    /// EXTENSION: the relative pose of pairs of images from their 2D-2D matches, wrong matches among them, on the device
+    /// (srk_relate_frames; DESIGN.md section 24: five-point hypotheses from a counter-based sampler, each scored on every match by
+    /// its Sampson distance; the reference's FindRelativeMotion).  One result per pair: frame a is (I, 0), frame b is `pose` with
+    /// x_b ~ R x_a + T and |T| = 1.
+    struct Match {
+        Point2f a, b;           ///< pixels in the two images
+        Scalar information = 1; ///< q >= 0; 0 switches the match off
+    };
+    struct RelatedPair {
+        SE3Transform pose;                ///< (R, T) of frame b; (I, 0) when not related
+        std::array<Scalar, 9> E{};        ///< [T]x R, row-major; zero when not related
+        Scalar rms_pixels = 0;            ///< sqrt(score / matches) of the truncated score; NaN when not related
+        Scalar sixth_match_pixels = 0;    ///< the winning sample's sixth-match Sampson error
+        Scalar parallax_rad = 0;          ///< the mean angle between the two rays of the inliers in front of both cameras
+        size_t matches = 0, inlier_count = 0, hypotheses_with_model = 0, in_front = 0;
+        int64_t winner = -1;              ///< the winning hypothesis, -1 when not related
+        uint32_t status = 0;              ///< SRK_RELATE_* bits (0 = related)
+        std::vector<uint8_t> inliers;     ///< per match, at the winner (with want_inliers)
+    };
+    /// shared_Ka / shared_Kb for all pairs, or Kas / Kbs with one matrix per pair.  opts NULL: the defaults (256 hypotheses, 2 px,
+    /// seed 1).  An uploaded scene is left untouched.  Throws std::invalid_argument for every refusal of the library.
+    std::vector<RelatedPair> RelateFrames(Scalar f0, const std::vector<std::vector<Match>>& pairs, const Matrix3* shared_Ka, const Matrix3* shared_Kb,
+                                          const std::vector<Matrix3>* Kas, const std::vector<Matrix3>* Kbs, const srk_relate_options* opts = nullptr,
+                                          bool want_inliers = false) {
+        const bool shared = shared_Ka && shared_Kb;
+        if (shared == (Kas && Kbs) || (!shared && (shared_Ka || shared_Kb)))
+            throw std::invalid_argument("Provide either shared intrinsics or separate intrinsics for each pair, for both cameras");
+        if (!shared && (Kas->size() != pairs.size() || Kbs->size() != pairs.size())) throw std::invalid_argument("relate: one K_a and one K_b per pair");
+        std::vector<int64_t> row_ptr{ 0 };
+        std::vector<Scalar> ua, ub, q, Ka, Kb;
+        for (const std::vector<Match>& p : pairs) {
+            for (const Match& m : p) {
+                ua.insert(ua.end(), { m.a.x, m.a.y });
+                ub.insert(ub.end(), { m.b.x, m.b.y });
+                q.push_back(m.information);
+            }
+            row_ptr.push_back((int64_t)q.size());
+        }
+        if (shared) Ka.assign(shared_Ka->begin(), shared_Ka->end()), Kb.assign(shared_Kb->begin(), shared_Kb->end());
+        else
+            for (size_t i = 0; i < pairs.size(); ++i) {
+                Ka.insert(Ka.end(), (*Kas)[i].begin(), (*Kas)[i].end());
+                Kb.insert(Kb.end(), (*Kbs)[i].begin(), (*Kbs)[i].end());
+            }
+        const size_t n = pairs.size(), O = q.size();
+        for (std::vector<Scalar>* v : { &ua, &ub, &q, &Ka, &Kb }) v->push_back(0); // never read: keep data() valid without matches or pairs
+        std::vector<Scalar> R(9 * n + 1), T(3 * n + 1), E(9 * n + 1), rel(8 * n + 1);
+        std::vector<uint32_t> st(n + 1);
+        std::vector<uint8_t> inl(want_inliers ? O + 1 : 1);
+        int rc = srk_relate_frames(h_, f0, (int32_t)n, row_ptr.data(), ua.data(), ub.data(), q.data(), Ka.data(), Kb.data(), shared ? 1 : 0, opts, R.data(),
+                                   T.data(), E.data(), rel.data(), st.data(), want_inliers ? inl.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        std::vector<RelatedPair> out(n);
+        for (size_t i = 0; i < n; ++i) {
+            RelatedPair& p = out[i];
+            for (size_t e = 0; e < 9; ++e) p.pose.R[e] = R[9 * i + e], p.E[e] = E[9 * i + e];
+            p.pose.T = Point3{ T[3 * i], T[3 * i + 1], T[3 * i + 2] };
+            p.rms_pixels = rel[8 * i];
+            p.matches = (size_t)rel[8 * i + 1];
+            p.inlier_count = (size_t)rel[8 * i + 2];
+            p.status = st[i];
+            p.winner = st[i] ? -1 : (int64_t)rel[8 * i + 3];
+            p.hypotheses_with_model = (size_t)rel[8 * i + 4];
+            p.sixth_match_pixels = rel[8 * i + 5];
+            p.in_front = (size_t)rel[8 * i + 6];
+            p.parallax_rad = rel[8 * i + 7];
+            if (want_inliers) p.inliers.assign(inl.begin() + row_ptr[i], inl.begin() + row_ptr[i + 1]);
+        }
+        return out;
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }

@@ -14,5 +14,7 @@ from .resect import (resect_frames, resect_status_names, default_resect_options,
                      RESECT_BEHIND, RESECT_NOT_CONVERGED)
 from .locate import (locate_frames, locate_status_names, default_locate_options, ransac_hypotheses, LocateResult,  # noqa: F401
                      LOCATE_FEW_POINTS, LOCATE_NO_MODEL)
+from .relate import (relate_frames, relate_status_names, default_relate_options, two_view_scene, RelateResult, TwoViewScene,  # noqa: F401
+                     RELATE_FEW_POINTS, RELATE_NO_MODEL)
 from .scene import (SceneSpec, generate_scene, config_scene, drop_observations, renumber_frames, loop_scene,  # noqa: F401
                     CONFIGS)

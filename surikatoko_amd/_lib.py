@@ -78,6 +78,10 @@ class LocateOptions(C.Structure):
     _fields_ = [("hypotheses", C.c_int32), ("inlier_pixels", C.c_double), ("seed", C.c_uint64)]
 
 
+class RelateOptions(C.Structure):
+    _fields_ = [("hypotheses", C.c_int32), ("inlier_pixels", C.c_double), ("seed", C.c_uint64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 # every symbol include/srk_ba.h declares (checked by tests/test_abi.py)
@@ -103,6 +107,7 @@ EXPORTS = [
     "srk_resect_default_options", "srk_resect_frames", "srk_ba_resect", "srk_ba_resect_kernel_ms", "srk_resect_check_frames", "srk_resect_revert",
     "srk_locate_default_options", "srk_locate_frames", "srk_ba_locate", "srk_ba_locate_kernel_ms", "srk_ba_locate_score_ms", "srk_locate_check_frames",
     "srk_ransac_hypotheses",
+    "srk_relate_default_options", "srk_relate_frames", "srk_ba_relate_kernel_ms", "srk_ba_relate_score_ms", "srk_relate_check_pairs", "srk_relate_host_pair",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
     "srk_ba_phase_cross_covariance", "srk_ba_cross_covariances", "srk_ba_revert_cross_covariances", "srk_ba_relative_pose_covariances",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
@@ -226,6 +231,17 @@ def lib():
     L.srk_ba_locate_kernel_ms.restype = C.c_double
     L.srk_ba_locate_score_ms.argtypes = [C.c_void_p]
     L.srk_ba_locate_score_ms.restype = C.c_double
+    # n_pairs, row_ptr, uv_a, uv_b, q, K_a, K_b, shared_k, options
+    _pairs = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RelateOptions)]
+    L.srk_relate_default_options.argtypes = [C.POINTER(RelateOptions)]
+    L.srk_relate_default_options.restype = None
+    L.srk_relate_frames.argtypes = [C.c_void_p, C.c_double] + _pairs + [C.c_void_p] * 6
+    L.srk_relate_check_pairs.argtypes = _pairs + [C.POINTER(C.c_char_p)]
+    L.srk_relate_host_pair.argtypes = [C.c_int64] + [C.c_void_p] * 5 + [C.c_double, C.POINTER(RelateOptions)] + [C.c_void_p] * 5
+    L.srk_ba_relate_kernel_ms.argtypes = [C.c_void_p]
+    L.srk_ba_relate_kernel_ms.restype = C.c_double
+    L.srk_ba_relate_score_ms.argtypes = [C.c_void_p]
+    L.srk_ba_relate_score_ms.restype = C.c_double
     L.srk_ransac_hypotheses.argtypes = [C.c_int, C.c_double, C.c_double]
     L.srk_ransac_hypotheses.restype = C.c_int64
     L.srk_ba_phase_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -22,6 +22,9 @@
 #include "srk_locate.hpp"
 #include "srk_locate_dev.hpp"
 #include "srk_locate_math.hpp"
+#include "srk_relate.hpp"
+#include "srk_relate_dev.hpp"
+#include "srk_relate_math.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -283,6 +286,12 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     DevBuf lc[LC_NBUF];
     hipEvent_t lc_ev[4]{};           // the call, and the hypothesis-and-score kernel inside it; created at the first call
     double lc_ms = 0, lc_score_ms = 0; // srk_ba_locate_kernel_ms, srk_ba_locate_score_ms
+    // two-view relative pose (srk_relate_frames): the pairs' matches and intrinsics, the gathered strip, the
+    // pairs' weighted counts, the hypotheses' records, the waves' slots and the outputs, grown lazily
+    enum { RL_ROW, RL_UVA, RL_UVB, RL_Q, RL_KA, RL_KB, RL_STRIP, RL_COUNT, RL_HYP, RL_SLOTS, RL_R, RL_T, RL_E, RL_RELATED, RL_STATUS, RL_INL, RL_NBUF };
+    DevBuf rl[RL_NBUF];
+    hipEvent_t rl_ev[4]{};           // the call, and the score kernel inside it; created at the first call
+    double rl_ms = 0, rl_score_ms = 0; // srk_ba_relate_kernel_ms, srk_ba_relate_score_ms
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -458,6 +467,9 @@ void srk_ba_destroy(srk_ba* h)
     for (DevBuf& b : h->tri) dev_free(b);
     for (DevBuf& b : h->rs) dev_free(b);
     for (DevBuf& b : h->lc) dev_free(b);
+    for (DevBuf& b : h->rl) dev_free(b);
+    for (hipEvent_t& e : h->rl_ev)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->lc_ev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->rs_ev)
@@ -3442,6 +3454,93 @@ extern "C" int srk_ba_locate(srk_ba* h, int32_t n_frames, const int64_t* row_ptr
         return SRK_OK;
     } catch (const std::bad_alloc&) {
         h->last_error = "locate: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+// ------------------------------------------------------------------ two-view relative pose
+// The checked pairs of a call to the device, gather / solve / score / pick, the results back.
+static int relate_run(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
+                      const double* K_a, const double* K_b, int shared_k, const srk_relate_options& lo, double* R, double* T, double* E,
+                      double* related, uint32_t* status, uint8_t* inlier_out)
+{
+    hipStream_t s = h->main_stream;
+    const int64_t O = row_ptr[n_pairs], n = n_pairs;
+    const int64_t waves = (lo.hypotheses + SRK_RELATE_LANES - 1) / SRK_RELATE_LANES;
+    DevBuf* l = h->rl;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &l[srk_ba::RL_ROW], row_ptr, (size_t)(8 * (n + 1)) }, { &l[srk_ba::RL_UVA], uv_a, (size_t)(16 * O) },
+        { &l[srk_ba::RL_UVB], uv_b, (size_t)(16 * O) },         { &l[srk_ba::RL_Q], q, q ? (size_t)(8 * O) : 0 },
+        { &l[srk_ba::RL_KA], K_a, (size_t)(72 * (shared_k ? 1 : n)) }, { &l[srk_ba::RL_KB], K_b, (size_t)(72 * (shared_k ? 1 : n)) },
+    };
+    for (auto& u : up) {
+        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+        if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    const bool want_inl = inlier_out && O > 0;
+    if ((rc = dev_alloc(h, l[srk_ba::RL_STRIP], (size_t)(8 * SRK_RELATE_STRIP * O))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::RL_COUNT], (size_t)(8 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::RL_HYP], (size_t)(8 * SRK_RELATE_HYP * n * lo.hypotheses))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::RL_SLOTS], (size_t)(8 * SRK_RELATE_SLOT * n * waves))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::RL_R], (size_t)(72 * n))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::RL_T], (size_t)(24 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::RL_E], (size_t)(72 * n))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::RL_RELATED], (size_t)(64 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::RL_STATUS], (size_t)(4 * n))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::RL_INL], want_inl ? (size_t)O : 0)) != SRK_OK)
+        return rc;
+    for (hipEvent_t& e : h->rl_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    const int64_t* d_row = P<int64_t>(l[srk_ba::RL_ROW]);
+    const double* d_q = q ? P<double>(l[srk_ba::RL_Q]) : nullptr;
+    const double* d_strip = P<double>(l[srk_ba::RL_STRIP]);
+    const int64_t* d_count = P<int64_t>(l[srk_ba::RL_COUNT]);
+    HIPCHK(h, hipEventRecord(h->rl_ev[0], s));
+    srk_launch_relate_gather(s, n_pairs, d_row, P<double>(l[srk_ba::RL_UVA]), P<double>(l[srk_ba::RL_UVB]), d_q, P<double>(l[srk_ba::RL_STRIP]),
+                             P<int64_t>(l[srk_ba::RL_COUNT]));
+    srk_launch_relate_solve(s, n_pairs, lo.hypotheses, lo.seed, f0, d_row, d_strip, d_count, P<double>(l[srk_ba::RL_KA]), P<double>(l[srk_ba::RL_KB]),
+                            shared_k, P<double>(l[srk_ba::RL_HYP]));
+    HIPCHK(h, hipEventRecord(h->rl_ev[1], s));
+    srk_launch_relate_score(s, n_pairs, lo.hypotheses, lo.inlier_pixels, f0, d_row, d_strip, d_count, P<double>(l[srk_ba::RL_HYP]),
+                            P<double>(l[srk_ba::RL_SLOTS]));
+    HIPCHK(h, hipEventRecord(h->rl_ev[2], s));
+    srk_launch_relate_pick(s, n_pairs, lo.hypotheses, lo.inlier_pixels, f0, d_row, d_q, d_strip, d_count, P<double>(l[srk_ba::RL_KA]),
+                           P<double>(l[srk_ba::RL_KB]), shared_k, P<double>(l[srk_ba::RL_HYP]), P<double>(l[srk_ba::RL_SLOTS]), P<double>(l[srk_ba::RL_R]),
+                           P<double>(l[srk_ba::RL_T]), P<double>(l[srk_ba::RL_E]), P<double>(l[srk_ba::RL_RELATED]), P<uint32_t>(l[srk_ba::RL_STATUS]),
+                           want_inl ? P<uint8_t>(l[srk_ba::RL_INL]) : nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->rl_ev[3], s));
+    HIPCHK(h, hipMemcpyAsync(R, l[srk_ba::RL_R].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(T, l[srk_ba::RL_T].p, (size_t)(24 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(E, l[srk_ba::RL_E].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(related, l[srk_ba::RL_RELATED].p, (size_t)(64 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(status, l[srk_ba::RL_STATUS].p, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+    if (want_inl) HIPCHK(h, hipMemcpyAsync(inlier_out, l[srk_ba::RL_INL].p, (size_t)O, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    float ms = 0, score_ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->rl_ev[0], h->rl_ev[3]));
+    HIPCHK(h, hipEventElapsedTime(&score_ms, h->rl_ev[1], h->rl_ev[2]));
+    h->rl_ms = ms;
+    h->rl_score_ms = score_ms;
+    return SRK_OK;
+}
+
+extern "C" double srk_ba_relate_kernel_ms(const srk_ba* h) { return h ? h->rl_ms : 0.0; }
+extern "C" double srk_ba_relate_score_ms(const srk_ba* h) { return h ? h->rl_score_ms : 0.0; }
+
+extern "C" int srk_relate_frames(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
+                                 const double* K_a, const double* K_b, int shared_k, const srk_relate_options* opts, double* R, double* T, double* E,
+                                 double* related, uint32_t* status, uint8_t* inlier_out)
+{
+    if (!h) return SRK_E_ARGS;
+    try {
+        std::string why = srk_relate_check(n_pairs, row_ptr, uv_a, uv_b, q, K_a, K_b, shared_k, opts);
+        if (why.empty() && (!std::isfinite(f0) || srk::is_close(0.0, f0))) why = "relate: f0 must be finite and not ~0";
+        if (why.empty() && n_pairs > 0 && (!R || !T || !E || !related || !status)) why = "relate: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_pairs == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        return relate_run(h, f0, n_pairs, row_ptr, uv_a, uv_b, q, K_a, K_b, shared_k ? 1 : 0, srk_relate_effective_options(opts), R, T, E, related, status,
+                          inlier_out);
+    } catch (const std::bad_alloc&) {
+        h->last_error = "relate: out of host memory";
         return SRK_E_NOMEM;
     }
 }

@@ -46,3 +46,8 @@
 #define SRK_LOCATE_MAX_HYPOTHESES_HOST 4096
 #define SRK_LOCATE_LANES_HOST 64
 #define SRK_LOCATE_MAX_WAVES_HOST (1 << 22)
+// two-view relative pose (srk_relate_frames): a wave scores 64 hypotheses of one pair; a call holds one record
+// of 160 bytes per hypothesis and one slot per wave, so pairs x ceil(hypotheses / 64) is capped like locate's
+#define SRK_RELATE_MAX_HYPOTHESES_HOST 4096
+#define SRK_RELATE_LANES_HOST 64
+#define SRK_RELATE_MAX_WAVES_HOST (1 << 22)
