@@ -1037,6 +1037,88 @@ int srk_relate_check_pairs(int32_t n_pairs, const int64_t* row_ptr, const double
 int srk_relate_host_pair(int64_t n_obs, const double* uv_a, const double* uv_b, const double* q, const double* K_a, const double* K_b, double f0,
                          const srk_relate_options* opts, double* R, double* T, double* E, double* related, uint8_t* inlier_out);
 
+/* ---- map alignment: similarity hypotheses scored on the device (EXTENSION) ----
+ * relate is 2D-2D and locate 2D-3D; "align" is the 3D-3D member: the similarity b ~ s R a + t (s > 0, R a proper rotation) between
+ * two sets of corresponding points, wrong correspondences among them.  It brings one map into the coordinates of another: a
+ * bootstrapped or relocalised sub-map into the main map, the two ends of a monocular loop (where the scale has drifted), a
+ * free-gauge solve near surveyed coordinates before srk_ba_set_position_priors(..., keep_gauge = 0).  The reference has no such
+ * function.
+ *
+ * Sets in CSR form (row_ptr [n_sets + 1], a [O][3], b [O][3]) with any number of correspondences; q >= 0 the optional information
+ * of a correspondence (NULL = all 1, bit for bit; q = 0 = the set without that correspondence, bit for bit).  Everything works on
+ * the set's n weighted correspondences, numbered by rank 0 .. n - 1 in ascending o.
+ *
+ * Sampler (counter-based, no state, a stream of its own): mix(seed, h, k) = the splitmix64 finaliser of
+ * seed + 0xA0761D6478BD642F (4 h + k + 1) mod 2^64.  Draw k = 0..2 of hypothesis h is r = umulhi64(mix, n - k), then for the
+ * earlier picks s in ascending order: if (r >= s) ++r.  Three distinct ranks that depend on seed, h and k alone.
+ *
+ * Hypothesis (Horn's three-point construction): on each side d1 = p1 - p0, d2 = p2 - p0, c = d1 x d2; no model when
+ * |c|^2 <= 1e-12 |d1|^2 |d2|^2 on either side or anything is not finite.  Otherwise the orthonormal frames A = [d1^, c^ x d1^, c^]
+ * and B likewise, R = B A^T, s = sqrt(sum |b_k - bm|^2 / sum |a_k - am|^2) over the three (1 with with_scale = 0), t = bm - s R am.
+ *
+ * Score (MSAC): score(h) = sum over the ranks in ascending order of min(q |b - (s R a + t)|^2, tau^2), tau = inlier_distance in
+ * the units of b; a hypothesis without a model scores +inf.  The smallest score wins, an equal score goes to the smaller h.
+ *
+ * Local optimisation: up to refine_rounds rounds from the winner.  The inliers (q r^2 < tau^2) of the current model, at least
+ * three; their weighted centroids, then M = sum q (b - bm)(a - am)^T and sum q |a - am|^2 (each lane of the wave sums the ranks
+ * l, l + 64, .. in ascending order, the lanes merge in a fixed tree); R maximises tr(R^T M), the eigenvector of the largest
+ * eigenvalue of Horn's symmetric 4 x 4 matrix by cyclic Jacobi (a proper rotation on mirrored and on coplanar sets);
+ * s = tr(R^T M) / sum q |a - am|^2 (1 with with_scale = 0), t = bm - s R am; accepted only when its score over all n is strictly
+ * smaller, else the rounds stop: the result is never worse than the winning hypothesis.
+ *
+ * Outputs per set: s, R [9], t [3]; aligned [8] = { sqrt(score / n) in the units of b, n, the inlier count, the winning h, the
+ * number of hypotheses with a model, the rounds accepted, (lambda1 - lambda2) / |lambda1| of the last accepted closed form (NaN
+ * when none was accepted; 0 = the inliers are collinear; the library sets no threshold on it), the RMS distance of the inliers };
+ * status, a mask of SRK_ALIGN_*: then the model is (1, I, 0), aligned[0], [3], [6], [7] are NaN and aligned[2], [5] are 0.
+ * inlier_out [O] (may be NULL): 1 iff q_o > 0 and q_o r_o^2 < tau^2 at the returned model.
+ *
+ * srk_ba_align: a is the CURRENT landmark point[o] (caller's numbering) of the resident scene, read on the device through the
+ * handle's landmark order; target = b.  The kernels work in the normalised coordinates X_n = s_n (R0 X + T0); with
+ * revert_normalization = 1 the result (sigma, Q, tau) comes back as (sigma s_n, Q R0, sigma s_n Q T0 + tau), which maps the
+ * uploaded arrays' coordinates to b.  It writes no scene buffer and is refused with more than one rank.
+ *
+ * Host checks before any allocation or launch (SRK_E_ARGS with a text): a descending or negative row_ptr, a, b or q that is not
+ * finite, a negative q, hypotheses outside 1..4096, inlier_distance not finite or <= 0 (it has no default: the 0 of
+ * srk_align_default_options is refused), refine_rounds outside 0..16, with_scale not 0 or 1, NULL outputs, a point beyond the
+ * map, and more than 2^22 waves (sets x ceil(hypotheses / 64)) in one call: split the batch, a set's bits do not depend on it.
+ * Absent: an information matrix of the similarity, Sim(3) factors in the solver, transforming the resident scene in place, an
+ * adaptive early stop, several ranks. */
+enum {
+    SRK_ALIGN_FEW_POINTS = 1, /* fewer than three correspondences with q > 0 */
+    SRK_ALIGN_NO_MODEL = 2    /* no sample gave a similarity (every triple collinear) */
+};
+typedef struct srk_align_options {
+    int32_t hypotheses;     /* samples per set, 1 .. 4096; srk_ransac_hypotheses(3, ...) gives the count for an outlier ratio */
+    double inlier_distance; /* tau > 0 in the units of b: the truncation of the score and the inlier test */
+    uint64_t seed;
+    int32_t with_scale;     /* 1: a similarity; 0: a rigid motion, s = 1 */
+    int32_t refine_rounds;  /* rounds of local optimisation, 0 .. 16 */
+} srk_align_options;
+void srk_align_default_options(srk_align_options*); /* { 256, 0 (must be set), 1, 1, 2 } */
+int srk_align_points(srk_ba*, int32_t n_sets, const int64_t* row_ptr, const double* a /* [O][3] */, const double* b /* [O][3] */,
+                     const double* q /* [O], NULL = all 1 */, const srk_align_options*, double* s /* [n] */, double* R /* [n][9] */,
+                     double* t /* [n][3] */, double* aligned /* [n][8] */, uint32_t* status /* [n] */, uint8_t* inlier_out /* [O] or NULL */);
+int srk_ba_align(srk_ba*, int32_t n_sets, const int64_t* row_ptr, const int32_t* point /* caller's landmark numbering */,
+                 const double* target /* [O][3] */, const double* q, const srk_align_options*, int revert_normalization, double* s, double* R,
+                 double* t, double* aligned, uint32_t* status, uint8_t* inlier_out);
+/* device ms of the last of the two calls on this handle (gather, hypotheses and scores, pick with its rounds) from an event pair;
+ * and of the hypothesis-and-score kernel alone, from a second pair */
+double srk_ba_align_kernel_ms(const srk_ba*);
+double srk_ba_align_score_ms(const srk_ba*);
+/* host only, no device and no handle needed: the checks of srk_align_points (point NULL) or srk_ba_align (point and n_points, a
+ * may be NULL) on their own.  SRK_OK, or SRK_E_ARGS with *why (may be NULL) pointing at a static text. */
+int srk_align_check_sets(int32_t n_sets, const int64_t* row_ptr, const int32_t* point, int64_t n_points, const double* a, const double* b,
+                         const double* q, const srk_align_options* opts, const double* s, const double* R, const double* t, const double* aligned,
+                         const uint32_t* status, const char** why);
+/* host only: one set of n_obs correspondences in the kernels' own order of operations (the same statements, compiled for the
+ * host).  Returns the status bits, or SRK_E_ARGS (negative) when the checks refuse the set. */
+int srk_align_host_set(int64_t n_obs, const double* a, const double* b, const double* q, const srk_align_options* opts, double* s, double* R, double* t,
+                       double* aligned, uint8_t* inlier_out);
+/* host only, in place: a scene under the similarity X' = s R X + t.  Points X [n_points][3]; poses (x_cam = R_c X + T_c):
+ * R_c' = R_c R^T, T_c' = s T_c - R_c' t -- the camera frame is scaled by s, so every projection is unchanged.  Either group may be
+ * NULL (cam_R and cam_T together). */
+int srk_similarity_apply(double s, const double* R, const double* t, int64_t n_points, double* X, int64_t n_frames, double* cam_R, double* cam_T);
+
 /* ---- marginal covariances of frames and landmarks (EXTENSION) ----
  * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
  * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior

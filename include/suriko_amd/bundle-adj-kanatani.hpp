@@ -642,6 +642,86 @@ public:
         return out;
     }
 
+    /// EXTENSION: the similarity b ~ s R a + t between sets of corresponding 3D points, wrong correspondences among them, on the
+    /// device (srk_align_points / srk_ba_align; DESIGN.md section 25: three-point hypotheses from a counter-based sampler, each
+    /// scored on every correspondence, the winner refined by a closed-form least-squares similarity on its inliers).  One result
+    /// per set.
+    struct Correspondence {
+        Point3 a, b;            ///< the point in the two maps
+        Scalar information = 1; ///< q >= 0; 0 switches the correspondence off
+    };
+    struct MapCorrespondence {
+        size_t point = 0;       ///< the landmark's index in the last ComputeInplace's scene
+        Point3 target;          ///< where it lies in the other map
+        Scalar information = 1;
+    };
+    struct AlignedSet {
+        Scalar scale = 1;                 ///< s
+        Matrix3 R{ 1, 0, 0, 0, 1, 0, 0, 0, 1 };
+        Point3 t;                         ///< (1, I, 0) when not aligned
+        Scalar rms_distance = 0;          ///< sqrt(score / points) of the truncated score; NaN when not aligned
+        Scalar inlier_rms_distance = 0;   ///< the RMS distance of the inliers
+        Scalar eigen_gap = 0;             ///< (lambda1 - lambda2) / |lambda1| of the last accepted closed form; NaN without one; 0: collinear inliers
+        size_t points = 0, inlier_count = 0, hypotheses_with_model = 0, rounds = 0;
+        int64_t winner = -1;              ///< the winning hypothesis, -1 when not aligned
+        uint32_t status = 0;              ///< SRK_ALIGN_* bits (0 = aligned)
+        std::vector<uint8_t> inliers;     ///< per correspondence, at the returned model (with want_inliers)
+    };
+    /// over caller-given points; an uploaded scene is left untouched.  opts.inlier_distance must be set (it has no default).
+    /// Throws std::invalid_argument with the text of the check for every refusal of the library.
+    std::vector<AlignedSet> AlignPoints(const std::vector<std::vector<Correspondence>>& sets, const srk_align_options& opts, bool want_inliers = false) {
+        AlignArrays v(sets.size());
+        for (const std::vector<Correspondence>& set : sets) {
+            for (const Correspondence& c : set) {
+                v.a.insert(v.a.end(), { c.a.x, c.a.y, c.a.z });
+                v.b.insert(v.b.end(), { c.b.x, c.b.y, c.b.z });
+                v.q.push_back(c.information);
+            }
+            v.row_ptr.push_back((int64_t)v.q.size());
+        }
+        v.Pad(want_inliers);
+        int rc = srk_align_points(h_, (int32_t)sets.size(), v.row_ptr.data(), v.a.data(), v.b.data(), v.q.data(), &opts, v.s.data(), v.R.data(), v.t.data(),
+                                  v.al.data(), v.st.data(), want_inliers ? v.inl.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        return v.Sets(want_inliers);
+    }
+    /// over the CURRENT landmarks of the last ComputeInplace's scene, read on the device (after the solve: the refined ones); the
+    /// similarity maps the coordinates of that call's map to the targets'.  The scene is not modified.
+    std::vector<AlignedSet> Align(const std::vector<std::vector<MapCorrespondence>>& sets, const srk_align_options& opts, bool want_inliers = false) {
+        AlignArrays v(sets.size());
+        for (const std::vector<MapCorrespondence>& set : sets) {
+            for (const MapCorrespondence& c : set) {
+                if (c.point > 2147483647u) throw std::invalid_argument("align: a landmark index is beyond the map");
+                v.point.push_back((int32_t)c.point);
+                v.b.insert(v.b.end(), { c.target.x, c.target.y, c.target.z });
+                v.q.push_back(c.information);
+            }
+            v.row_ptr.push_back((int64_t)v.q.size());
+        }
+        v.Pad(want_inliers);
+        int rc = srk_ba_align(h_, (int32_t)sets.size(), v.row_ptr.data(), v.point.data(), v.b.data(), v.q.data(), &opts, 1, v.s.data(), v.R.data(),
+                              v.t.data(), v.al.data(), v.st.data(), want_inliers ? v.inl.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        return v.Sets(want_inliers);
+    }
+    /// host only: a map under the similarity X' = s R X + t, in place.  Poses are inverse orientations (x_cam = R_c X + T_c): the
+    /// camera frame is scaled by s, so every projection is unchanged.  Either group may be NULL.
+    static void ApplySimilarity(Scalar s, const Matrix3& R, const Point3& t, std::vector<Point3>* points, std::vector<SE3Transform>* cams) {
+        const Scalar tv[3] = { t.x, t.y, t.z };
+        std::vector<Scalar> X, cR, cT;
+        if (points) for (const Point3& p : *points) X.insert(X.end(), { p.x, p.y, p.z });
+        if (cams) for (const SE3Transform& c : *cams) { cR.insert(cR.end(), c.R.begin(), c.R.end()); cT.insert(cT.end(), { c.T.x, c.T.y, c.T.z }); }
+        const size_t n = points ? points->size() : 0, m = cams ? cams->size() : 0;
+        for (std::vector<Scalar>* v : { &X, &cR, &cT }) v->push_back(0); // never read: keep data() valid
+        if (srk_similarity_apply(s, R.data(), tv, (int64_t)n, X.data(), (int64_t)m, cR.data(), cT.data()) < 0)
+            throw std::invalid_argument("ApplySimilarity: s must be finite and > 0");
+        for (size_t i = 0; i < n; ++i) (*points)[i] = Point3{ X[3 * i], X[3 * i + 1], X[3 * i + 2] };
+        for (size_t j = 0; j < m; ++j) {
+            for (size_t e = 0; e < 9; ++e) (*cams)[j].R[e] = cR[9 * j + e];
+            (*cams)[j].T = Point3{ cT[3 * j], cT[3 * j + 1], cT[3 * j + 2] };
+        }
+    }
+
     size_t VarsCount() const { return 3 * points_count_ + (size_t)srk_ba_frame_vars(h_) * frames_count_; }
     size_t NormalizedVarsCount() const { return VarsCount() - 7; }
     const std::string& OptimizationStatusString() const { return status_; }
@@ -756,6 +836,39 @@ private:
                 f.located_status = st[i];
                 if (want_inliers) f.inliers.assign(inl.begin() + a.row_ptr[i], inl.begin() + a.row_ptr[i + 1]);
                 if (refined) f.refined = fine[i];
+            }
+            return out;
+        }
+    };
+    struct AlignArrays {
+        std::vector<int64_t> row_ptr{ 0 };
+        std::vector<int32_t> point;
+        std::vector<Scalar> a, b, q, s, R, t, al;
+        std::vector<uint32_t> st;
+        std::vector<uint8_t> inl;
+        explicit AlignArrays(size_t n) : s(n + 1), R(9 * n + 1), t(3 * n + 1), al(8 * n + 1), st(n + 1) {}
+        void Pad(bool want_inliers) { // never read: keep data() valid without correspondences or sets
+            inl.resize(want_inliers ? q.size() + 1 : 1);
+            point.push_back(0);
+            for (std::vector<Scalar>* v : { &a, &b, &q }) v->push_back(0);
+        }
+        std::vector<AlignedSet> Sets(bool want_inliers) const {
+            std::vector<AlignedSet> out(st.size() - 1);
+            for (size_t i = 0; i < out.size(); ++i) {
+                AlignedSet& f = out[i];
+                f.scale = s[i];
+                for (size_t e = 0; e < 9; ++e) f.R[e] = R[9 * i + e];
+                f.t = Point3{ t[3 * i], t[3 * i + 1], t[3 * i + 2] };
+                f.rms_distance = al[8 * i];
+                f.points = (size_t)al[8 * i + 1];
+                f.inlier_count = (size_t)al[8 * i + 2];
+                f.status = st[i];
+                f.winner = st[i] ? -1 : (int64_t)al[8 * i + 3];
+                f.hypotheses_with_model = (size_t)al[8 * i + 4];
+                f.rounds = (size_t)al[8 * i + 5];
+                f.eigen_gap = al[8 * i + 6];
+                f.inlier_rms_distance = al[8 * i + 7];
+                if (want_inliers) f.inliers.assign(inl.begin() + row_ptr[i], inl.begin() + row_ptr[i + 1]);
             }
             return out;
         }

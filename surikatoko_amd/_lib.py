@@ -82,6 +82,11 @@ class RelateOptions(C.Structure):
     _fields_ = [("hypotheses", C.c_int32), ("inlier_pixels", C.c_double), ("seed", C.c_uint64)]
 
 
+class AlignOptions(C.Structure):
+    _fields_ = [("hypotheses", C.c_int32), ("inlier_distance", C.c_double), ("seed", C.c_uint64), ("with_scale", C.c_int32),
+                ("refine_rounds", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 # every symbol include/srk_ba.h declares (checked by tests/test_abi.py)
@@ -108,6 +113,8 @@ EXPORTS = [
     "srk_locate_default_options", "srk_locate_frames", "srk_ba_locate", "srk_ba_locate_kernel_ms", "srk_ba_locate_score_ms", "srk_locate_check_frames",
     "srk_ransac_hypotheses",
     "srk_relate_default_options", "srk_relate_frames", "srk_ba_relate_kernel_ms", "srk_ba_relate_score_ms", "srk_relate_check_pairs", "srk_relate_host_pair",
+    "srk_align_default_options", "srk_align_points", "srk_ba_align", "srk_ba_align_kernel_ms", "srk_ba_align_score_ms", "srk_align_check_sets",
+    "srk_align_host_set", "srk_similarity_apply",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
     "srk_ba_phase_cross_covariance", "srk_ba_cross_covariances", "srk_ba_revert_cross_covariances", "srk_ba_relative_pose_covariances",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
@@ -242,6 +249,18 @@ def lib():
     L.srk_ba_relate_kernel_ms.restype = C.c_double
     L.srk_ba_relate_score_ms.argtypes = [C.c_void_p]
     L.srk_ba_relate_score_ms.restype = C.c_double
+    L.srk_align_default_options.argtypes = [C.POINTER(AlignOptions)]
+    L.srk_align_default_options.restype = None
+    L.srk_align_points.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.POINTER(AlignOptions)] + [C.c_void_p] * 6
+    L.srk_ba_align.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.POINTER(AlignOptions), C.c_int] + [C.c_void_p] * 6
+    L.srk_align_check_sets.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.POINTER(AlignOptions)] + [C.c_void_p] * 5 + [
+        C.POINTER(C.c_char_p)]
+    L.srk_align_host_set.argtypes = [C.c_int64] + [C.c_void_p] * 3 + [C.POINTER(AlignOptions)] + [C.c_void_p] * 5
+    L.srk_similarity_apply.argtypes = [C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.srk_ba_align_kernel_ms.argtypes = [C.c_void_p]
+    L.srk_ba_align_kernel_ms.restype = C.c_double
+    L.srk_ba_align_score_ms.argtypes = [C.c_void_p]
+    L.srk_ba_align_score_ms.restype = C.c_double
     L.srk_ransac_hypotheses.argtypes = [C.c_int, C.c_double, C.c_double]
     L.srk_ransac_hypotheses.restype = C.c_int64
     L.srk_ba_phase_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

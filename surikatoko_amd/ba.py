@@ -1355,6 +1355,27 @@ class BundleAdjustmentKanatani:
                                             *[None if a is None else _p(a) for a in out]))
         return LocateResult(*out)
 
+    def align(self, point, target, row_ptr=None, q=None, hypotheses=256, inlier_distance=None, seed=1, with_scale=True, refine_rounds=2,
+              want_inliers=False, revert_normalization=True):
+        """The similarity target ~ s R X + t between the resident scene's CURRENT landmarks `point` (the landmark numbering of the
+        uploaded scene) and their targets [O][3] in another map, wrong correspondences among them, on the device (srk_ba_align;
+        after optimize(): the refined landmarks).  row_ptr None: one set.  With revert_normalization the similarity maps the
+        uploaded arrays' coordinates to the targets'.  Returns an align.AlignResult: see align.align_points.  The resident scene
+        is not modified."""
+        from .align import AlignResult, _options, _outputs
+        pt = np.ascontiguousarray(point, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(target, dtype=np.float64).reshape(-1, 3)
+        w = None if q is None else np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+        rp = np.ascontiguousarray([0, pt.size] if row_ptr is None else row_ptr, dtype=np.int64).reshape(-1)
+        n_obs = max(int(rp.max()), 0) if rp.size else 0
+        if rp.size < 1 or pt.size < n_obs or b.shape[0] < n_obs or (w is not None and w.size < n_obs):
+            raise ValueError("align: the correspondence arrays are shorter than row_ptr says")
+        opts = _options(hypotheses, inlier_distance, seed, with_scale, refine_rounds)
+        out = _outputs(rp.size - 1, n_obs, want_inliers)
+        self._raise(self._lib.srk_ba_align(C.c_void_p(self._h), C.c_int32(rp.size - 1), _p(rp), _p(pt), _p(b), None if w is None else _p(w),
+                                           C.byref(opts), C.c_int(int(bool(revert_normalization))), *[None if a is None else _p(a) for a in out]))
+        return AlignResult(*out)
+
     def buffer(self, which):
         """flat download of a staged buffer; its layout follows frame_vars() (include/srk_ba.h SRK_BUF_*)"""
         n = self._lib.srk_ba_buffer_size(C.c_void_p(self._h), int(which))

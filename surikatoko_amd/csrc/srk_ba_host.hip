@@ -19,6 +19,9 @@
 #include "srk_resect.hpp"
 #include "srk_resect_dev.hpp"
 #include "srk_resect_math.hpp"
+#include "srk_align.hpp"
+#include "srk_align_dev.hpp"
+#include "srk_align_math.hpp"
 #include "srk_locate.hpp"
 #include "srk_locate_dev.hpp"
 #include "srk_locate_math.hpp"
@@ -292,6 +295,12 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     DevBuf rl[RL_NBUF];
     hipEvent_t rl_ev[4]{};           // the call, and the score kernel inside it; created at the first call
     double rl_ms = 0, rl_score_ms = 0; // srk_ba_relate_kernel_ms, srk_ba_relate_score_ms
+    // map alignment (srk_align_points, srk_ba_align): the sets' correspondences, the gathered strip, the sets'
+    // weighted counts, the waves' slots and the outputs, grown lazily
+    enum { AL_ROW, AL_POINT, AL_A, AL_B, AL_Q, AL_STRIP, AL_COUNT, AL_SLOTS, AL_S, AL_R, AL_T, AL_ALIGNED, AL_STATUS, AL_INL, AL_NBUF };
+    DevBuf al[AL_NBUF];
+    hipEvent_t al_ev[4]{};           // the call, and the hypothesis-and-score kernel inside it; created at the first call
+    double al_ms = 0, al_score_ms = 0; // srk_ba_align_kernel_ms, srk_ba_align_score_ms
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -468,6 +477,9 @@ void srk_ba_destroy(srk_ba* h)
     for (DevBuf& b : h->rs) dev_free(b);
     for (DevBuf& b : h->lc) dev_free(b);
     for (DevBuf& b : h->rl) dev_free(b);
+    for (DevBuf& b : h->al) dev_free(b);
+    for (hipEvent_t& e : h->al_ev)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->rl_ev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->lc_ev)
@@ -3541,6 +3553,124 @@ extern "C" int srk_relate_frames(srk_ba* h, double f0, int32_t n_pairs, const in
                           inlier_out);
     } catch (const std::bad_alloc&) {
         h->last_error = "relate: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+// ------------------------------------------------------------------ map alignment
+// The checked sets of a call to the device, gather / hypotheses and scores / pick with its rounds, the results back.  The sources
+// are a (host, [O][3]) or, with point != NULL, the landmarks dX (a device pointer) as point numbers them.
+static int align_run(srk_ba* h, int32_t n_sets, const int64_t* row_ptr, const int32_t* point, const double* a, const double* dX, const double* b,
+                     const double* q, const srk_align_options& lo, double* sc, double* R, double* t, double* aligned, uint32_t* status,
+                     uint8_t* inlier_out)
+{
+    hipStream_t s = h->main_stream;
+    const int64_t O = row_ptr[n_sets], n = n_sets;
+    const int64_t waves = (lo.hypotheses + SRK_ALIGN_LANES - 1) / SRK_ALIGN_LANES;
+    DevBuf* l = h->al;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &l[srk_ba::AL_ROW], row_ptr, (size_t)(8 * (n + 1)) }, { &l[srk_ba::AL_POINT], point, point ? (size_t)(4 * O) : 0 },
+        { &l[srk_ba::AL_A], a, point ? 0 : (size_t)(24 * O) },  { &l[srk_ba::AL_B], b, (size_t)(24 * O) },
+        { &l[srk_ba::AL_Q], q, q ? (size_t)(8 * O) : 0 },
+    };
+    for (auto& u : up) {
+        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+        if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    const bool want_inl = inlier_out && O > 0;
+    if ((rc = dev_alloc(h, l[srk_ba::AL_STRIP], (size_t)(8 * SRK_ALIGN_STRIP * O))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::AL_COUNT], (size_t)(8 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::AL_SLOTS], (size_t)(8 * SRK_ALIGN_SLOT * n * waves))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::AL_S], (size_t)(8 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::AL_R], (size_t)(72 * n))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::AL_T], (size_t)(24 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::AL_ALIGNED], (size_t)(64 * n))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::AL_STATUS], (size_t)(4 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::AL_INL], want_inl ? (size_t)O : 0)) != SRK_OK)
+        return rc;
+    for (hipEvent_t& e : h->al_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    const int64_t* d_row = P<int64_t>(l[srk_ba::AL_ROW]);
+    const int32_t* d_point = point ? P<int32_t>(l[srk_ba::AL_POINT]) : nullptr;
+    const double* d_a = point ? dX : P<double>(l[srk_ba::AL_A]);
+    const double* d_b = P<double>(l[srk_ba::AL_B]);
+    const double* d_q = q ? P<double>(l[srk_ba::AL_Q]) : nullptr;
+    const double* d_strip = P<double>(l[srk_ba::AL_STRIP]);
+    const int64_t* d_count = P<int64_t>(l[srk_ba::AL_COUNT]);
+    HIPCHK(h, hipEventRecord(h->al_ev[0], s));
+    srk_launch_align_gather(s, n_sets, d_row, d_point, d_a, d_b, d_q, P<double>(l[srk_ba::AL_STRIP]), P<int64_t>(l[srk_ba::AL_COUNT]));
+    HIPCHK(h, hipEventRecord(h->al_ev[1], s));
+    srk_launch_align_score(s, n_sets, lo.hypotheses, lo.seed, lo.inlier_distance, lo.with_scale, d_row, d_strip, d_count, P<double>(l[srk_ba::AL_SLOTS]));
+    HIPCHK(h, hipEventRecord(h->al_ev[2], s));
+    srk_launch_align_pick(s, n_sets, lo.hypotheses, lo.inlier_distance, lo.with_scale, lo.refine_rounds, d_row, d_point, d_a, d_b, d_q, d_strip, d_count,
+                          P<double>(l[srk_ba::AL_SLOTS]), P<double>(l[srk_ba::AL_S]), P<double>(l[srk_ba::AL_R]), P<double>(l[srk_ba::AL_T]),
+                          P<double>(l[srk_ba::AL_ALIGNED]), P<uint32_t>(l[srk_ba::AL_STATUS]), want_inl ? P<uint8_t>(l[srk_ba::AL_INL]) : nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->al_ev[3], s));
+    HIPCHK(h, hipMemcpyAsync(sc, l[srk_ba::AL_S].p, (size_t)(8 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(R, l[srk_ba::AL_R].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(t, l[srk_ba::AL_T].p, (size_t)(24 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(aligned, l[srk_ba::AL_ALIGNED].p, (size_t)(64 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(status, l[srk_ba::AL_STATUS].p, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+    if (want_inl) HIPCHK(h, hipMemcpyAsync(inlier_out, l[srk_ba::AL_INL].p, (size_t)O, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    float ms = 0, score_ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->al_ev[0], h->al_ev[3]));
+    HIPCHK(h, hipEventElapsedTime(&score_ms, h->al_ev[1], h->al_ev[2]));
+    h->al_ms = ms;
+    h->al_score_ms = score_ms;
+    return SRK_OK;
+}
+
+extern "C" double srk_ba_align_kernel_ms(const srk_ba* h) { return h ? h->al_ms : 0.0; }
+extern "C" double srk_ba_align_score_ms(const srk_ba* h) { return h ? h->al_score_ms : 0.0; }
+
+extern "C" int srk_align_points(srk_ba* h, int32_t n_sets, const int64_t* row_ptr, const double* a, const double* b, const double* q,
+                                const srk_align_options* opts, double* s, double* R, double* t, double* aligned, uint32_t* status, uint8_t* inlier_out)
+{
+    if (!h) return SRK_E_ARGS;
+    try {
+        std::string why = srk_align_check(n_sets, row_ptr, nullptr, 0, a, b, q, opts);
+        if (why.empty() && n_sets > 0 && (!s || !R || !t || !aligned || !status)) why = "align: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_sets == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        return align_run(h, n_sets, row_ptr, nullptr, a, nullptr, b, q, srk_align_effective_options(opts), s, R, t, aligned, status, inlier_out);
+    } catch (const std::bad_alloc&) {
+        h->last_error = "align: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+extern "C" int srk_ba_align(srk_ba* h, int32_t n_sets, const int64_t* row_ptr, const int32_t* point, const double* target, const double* q,
+                            const srk_align_options* opts, int revert_normalization, double* s, double* R, double* t, double* aligned,
+                            uint32_t* status, uint8_t* inlier_out)
+{
+    if (!h || !h->have_scene) return SRK_E_STATE;
+    try {
+        std::string why;
+        std::vector<int32_t> pt;
+        if (h->world > 1 || h->allreduce || h->comm) why = "align: more than one rank is not supported";
+        else if (n_sets >= 0 && row_ptr && row_ptr[n_sets] > 0 && !point) why = "align: a NULL correspondence array";
+        else {
+            std::vector<int64_t> pt_int((size_t)h->d.N); // the caller's landmark -> its place in the handle's landmark order
+            for (int64_t i = 0; i < h->d.N; ++i) pt_int[(size_t)h->perm[(size_t)i]] = i;
+            static const int32_t none = 0; // an empty call still takes the map's branch of the checks
+            why = srk_align_check(n_sets, row_ptr, point ? point : &none, h->d.N, nullptr, target, q, opts, pt_int.data(), &pt);
+        }
+        if (why.empty() && n_sets > 0 && (!s || !R || !t || !aligned || !status)) why = "align: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_sets == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        for (auto& a : h->att) // nothing of an earlier call is still writing the scene
+            if (a.allocated && a.stream) HIPCHK(h, hipStreamSynchronize(a.stream));
+        pt.push_back(0); // never read: keeps data() valid without correspondences
+        const int rc = align_run(h, n_sets, row_ptr, pt.data(), nullptr, P<double>(h->pts[h->cur]), target, q, srk_align_effective_options(opts), s, R, t,
+                                 aligned, status, inlier_out);
+        if (rc != SRK_OK) return rc;
+        if (revert_normalization && h->normalized_on_upload)
+            for (int32_t i = 0; i < n_sets; ++i) // a set that was not aligned keeps (1, I, 0) in every coordinate system
+                if (!status[i]) srk_align_revert(h->nrm, 1, s + i, R + 9 * (int64_t)i, t + 3 * (int64_t)i);
+        return SRK_OK;
+    } catch (const std::bad_alloc&) {
+        h->last_error = "align: out of host memory";
         return SRK_E_NOMEM;
     }
 }

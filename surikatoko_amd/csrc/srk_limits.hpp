@@ -51,3 +51,9 @@
 #define SRK_RELATE_MAX_HYPOTHESES_HOST 4096
 #define SRK_RELATE_LANES_HOST 64
 #define SRK_RELATE_MAX_WAVES_HOST (1 << 22)
+// map alignment (srk_align_points): a wave scores 64 hypotheses of one set; a call holds one slot of 160 bytes
+// per wave, so sets x ceil(hypotheses / 64) is capped like locate's
+#define SRK_ALIGN_MAX_HYPOTHESES_HOST 4096
+#define SRK_ALIGN_LANES_HOST 64
+#define SRK_ALIGN_MAX_WAVES_HOST (1 << 22)
+#define SRK_ALIGN_MAX_ROUNDS_HOST 16
