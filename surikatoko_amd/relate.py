@@ -116,7 +116,10 @@ def two_view_scene(ba, f0, uv_a, uv_b, K_a, K_b, q=None, hypotheses=256, inlier_
     """The two-view bootstrap: relate the pair of images from its matches uv_a, uv_b [M][2], triangulate the inliers from (I, 0)
     and (R, T) (triangulate_tracks, refined), drop the tracks that lie behind a camera, and return a TwoViewScene: poses, points and
     point-major observations as Scene(points, cam_R, cam_T, K, shared_k, row_ptr, obs_frame, obs_uv) takes them, in the scale
-    |T| = 1.  Raises ValueError when the pair was not related (TwoViewScene.relate.status would be non-zero)."""
+    |T| = 1.  Raises ValueError when the pair was not related (TwoViewScene.relate.status would be non-zero).
+    To bundle-adjust the result, give Scene the intrinsics as K * f0 (the same cameras, K(2,2) = f0): with K / f0 the adjuster's pose
+    derivatives are not those of the error and it moves the scene little or, with two different cameras, not
+    at all."""
     a = np.ascontiguousarray(uv_a, dtype=np.float64).reshape(-1, 2)
     b = np.ascontiguousarray(uv_b, dtype=np.float64).reshape(-1, 2)
     rel = relate_frames(ba, f0, [0, a.shape[0]], a, b, np.reshape(K_a, (1, 9)), np.reshape(K_b, (1, 9)), q=q, hypotheses=hypotheses,

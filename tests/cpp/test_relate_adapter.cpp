@@ -8,6 +8,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "distinct_intrinsics.hpp"
 #include "suriko_amd/bundle-adj-kanatani.hpp"
 using namespace suriko_amd;
 
@@ -30,6 +31,8 @@ int main()
     std::vector<int32_t> fr(O);
     if (srk_scene_generate(&spec, pts.data(), nullptr, R.data(), T.data(), nullptr, nullptr, K.data(), row_ptr.data(),
                            fr.data(), uv.data()) != 0) return 10;
+    distinct_intrinsics(M, spec.f0, K, fr, uv); // every frame its own fx, fy, u0, v0: the adapter must hand each frame's own K on
+    if (!intrinsics_are_distinct(M, K)) return 10;
     using BA = BundleAdjustmentKanatani;
     const int32_t fa[2] = { 0, 2 }, fb[2] = { 5, 9 };
     std::vector<std::vector<BA::Match>> pairs(2);
@@ -102,12 +105,21 @@ int main()
         std::printf("pair %d: rotation %.3e rad, direction %.3e rad from the generated pose, %zu inliers\n", p, angle, dir, r.inlier_count);
     }
 
-    // shared intrinsics: the generated cameras share one K, so the bits are the same
+    // shared intrinsics (K_a != K_b): the bits of the call that repeats the two matrices per pair.  The frames carry distinct K, so
+    // pair 1 of that call is not pair 1 above, and pair 0 is
+    if (std::memcmp(Kas[0].data(), Kas[1].data(), 72) == 0 || std::memcmp(Kbs[0].data(), Kbs[1].data(), 72) == 0 ||
+        std::memcmp(Kas[0].data(), Kbs[0].data(), 72) == 0) return 21;
+    const std::vector<Matrix3> Ka0(2, Kas[0]), Kb0(2, Kbs[0]);
     const std::vector<BA::RelatedPair> sh = ba.RelateFrames(600.0, pairs, &Kas[0], &Kbs[0], nullptr, nullptr, &lo);
-    for (int p = 0; p < 2; ++p)
-        if (std::memcmp(Kas[(size_t)p].data(), Kas[0].data(), 72) == 0 && std::memcmp(Kbs[(size_t)p].data(), Kbs[0].data(), 72) == 0 &&
-            (std::memcmp(sh[(size_t)p].pose.R.data(), res[(size_t)p].pose.R.data(), 72) || sh[(size_t)p].winner != res[(size_t)p].winner || !sh[(size_t)p].inliers.empty()))
+    const std::vector<BA::RelatedPair> rep = ba.RelateFrames(600.0, pairs, nullptr, nullptr, &Ka0, &Kb0, &lo);
+    for (int p = 0; p < 2; ++p) {
+        const BA::RelatedPair &s = sh[(size_t)p], &r = rep[(size_t)p];
+        if (std::memcmp(s.pose.R.data(), r.pose.R.data(), 72) || std::memcmp(s.E.data(), r.E.data(), 72) || std::memcmp(&s.rms_pixels, &r.rms_pixels, 8) ||
+            s.winner != r.winner || s.inlier_count != r.inlier_count || s.status != r.status || !s.inliers.empty())
             return 22;
+    }
+    if (std::memcmp(sh[0].pose.R.data(), res[0].pose.R.data(), 72) || sh[0].winner != res[0].winner) return 22;
+    if (std::memcmp(sh[1].pose.R.data(), res[1].pose.R.data(), 72) == 0) return 22;   // pair 1 with pair 0's cameras is another problem
 
     std::vector<Matrix3> one(1);
     if (!throws_invalid([&] { ba.RelateFrames(600.0, pairs, nullptr, nullptr, &one, &Kbs); })) return 23;       // one K_a for two pairs

@@ -8,6 +8,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "distinct_intrinsics.hpp"
 #include "suriko_amd/bundle-adj-kanatani.hpp"
 using namespace suriko_amd;
 
@@ -30,6 +31,8 @@ int main()
     std::vector<int32_t> fr(O);
     if (srk_scene_generate(&spec, pts.data(), nullptr, R.data(), T.data(), nullptr, nullptr, K.data(), row_ptr.data(),
                            fr.data(), uv.data()) != 0) return 10;
+    distinct_intrinsics(M, spec.f0, K, fr, uv); // every frame its own fx, fy, u0, v0: the adapter must hand each frame's own K on
+    if (!intrinsics_are_distinct(M, K)) return 10;
     using BA = BundleAdjustmentKanatani;
     FragmentMap map; CornerTrackRepository rep; std::vector<SE3Transform> cams((size_t)used), start((size_t)held);
     std::vector<Matrix3> Ks((size_t)used), Kh((size_t)held);

@@ -250,23 +250,34 @@ def pose_gap(R, T, y):
 
 
 @functools.lru_cache(maxsize=None)
-def host_floor():
+def _own_host_floor():
+    return host_floor(tuple((small(holes), small_yardstick(holes, H), H, SAMPLER_SEED[H]) for holes in (False, True) for H in HYPOTHESES))
+
+
+def host_floor(cases=None):
     """The largest pose distance between the host walk and the yardstick over the located frames of the small ragged batches at
     every hypothesis count: what the two implementations of the same formulas differ by in double precision (the closed-form
-    roots against the companion matrix's, the triangle's frame against the SVD).  The GPU tests allow ten times this."""
+    roots against the companion matrix's, the triangle's frame against the SVD).  The GPU tests allow ten times this.
+    cases: other batches, as (batch, its yardstick results, hypotheses, seed) each."""
+    if cases is None:
+        return _own_host_floor()
     worst = 0.0
-    for holes in (False, True):
-        b = small(holes)
-        for H in HYPOTHESES:
-            got, ys = host_walk(b, H, SAMPLER_SEED[H]), small_yardstick(holes, H)
-            worst = max([worst] + [pose_gap(got.R[i], got.T[i], y) for i, y in enumerate(ys) if y["status"] == 0])
+    for b, ys, H, seed in cases:
+        got = host_walk(b, H, seed)
+        worst = max([worst] + [pose_gap(got.R[i], got.T[i], y) for i, y in (ys.items() if isinstance(ys, dict) else enumerate(ys))
+                               if y["status"] == 0])
     return worst
 
 
 @functools.lru_cache(maxsize=None)
-def accuracy_floor():
-    """the host walk's largest distance from the truth on the noise-free cases at 64 hypotheses (a CPU run)"""
-    b = accuracy()
+def _own_accuracy_floor():
+    return accuracy_floor(accuracy())
+
+
+def accuracy_floor(b=None):
+    """the host walk's largest distance from the truth on the noise-free cases (or on the batch b) at 64 hypotheses (a CPU run)"""
+    if b is None:
+        return _own_accuracy_floor()
     got = host_walk(b, 64, 1)
     return max(max(pose_error(got.R[i], got.T[i], f)) for i, f in enumerate(b.frames))
 

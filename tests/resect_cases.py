@@ -242,6 +242,51 @@ def accuracy_yardstick():
     return ys, max(accuracy_units(y["R"], y["T"], b.frames[i], y["H"]) for i, y in enumerate(ys))
 
 
+@functools.lru_cache(maxsize=None)
+def host_program():
+    """tests/cpp/test_resect_host.cpp with csrc/srk_resect.cpp, built once per process into a temporary directory"""
+    import os
+    import shutil
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx is not None, "no host C++ compiler"
+    exe = os.path.join(tempfile.mkdtemp(prefix="resect_bin"), "test_resect_host")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", os.path.join(root, "tests", "cpp", "test_resect_host.cpp"),
+                        os.path.join(root, "surikatoko_amd", "csrc", "srk_resect.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+def host_walk(b, attempts, rel_change):
+    """every frame of the batch in the kernel's own order of operations on the host: R, T, quality, info, status, logs, w"""
+    import os
+    import subprocess
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        src, dst = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+        write_host_input(src, b, attempts=attempts, rel_change=rel_change)
+        r = subprocess.run([host_program(), "frames", src, dst], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        return read_host_output(dst, b)
+
+
+def host_walk_floor(cases=None):
+    """The largest distance, in Newton-step units, between the yardstick and the kernel's order of operations walked on the host
+    (host_walk), over the two ragged batches: computed on the CPU, the device is held to ten times this.  cases: other batches,
+    as (batch, its yardstick results, attempts, rel_change) each."""
+    if cases is None:
+        cases = [(ragged(holes), ragged_yardstick(holes)) + RAGGED_OPTIONS[holes] for holes in (False, True)]
+    worst = 0.0
+    for b, ys, attempts, rel_change in cases:
+        R, T = host_walk(b, attempts, rel_change)[:2]
+        for i, y in (ys.items() if isinstance(ys, dict) else enumerate(ys)):
+            if not y["status"] & ref.FEW_POINTS:
+                worst = max(worst, pose_units(R[i], T[i], y))
+    return worst
+
+
 def write_host_input(path, b, attempts=10, rel_change=1e-9, kind=0, delta=0.0, want_weights=False):
     """the input file of tests/cpp/test_resect_host.cpp's `frames` mode"""
     with open(path, "wb") as f:

@@ -14,6 +14,7 @@ import surikatoko_amd as sa
 from surikatoko_amd import _lib
 from surikatoko_amd import ba as B
 from surikatoko_amd import locate as LC
+import hetero_cases
 import locate_cases as lc
 import locate_ref as ref
 
@@ -214,11 +215,15 @@ def test_one_hypothesis_of_wrong_matches(h):
 
 
 # ------------------------------------------------------------------ the resident scene
-def _held_out(reorder, n_extra=2, share=0.3):
+def _held_out(reorder, n_extra=2, share=0.3, hetero=False):
     """An all-visible scene; its last n_extra frames are held out: their observations, `share` of them moved by 20 .. 60 px,
-    become the frames to locate"""
+    become the frames to locate.  hetero: the full scene gets per-frame intrinsics before it is split, so the held-out frames carry
+    K distinct from each other and from the resident frames."""
     spec = sa.SceneSpec(n_frames=12, grid_nx=12, grid_ny=9, vis_window=0, noise_uv_pix=0.3)
     full = sa.generate_scene(spec)
+    if hetero:
+        full = hetero_cases.per_frame_intrinsics(full, spec.f0)
+        assert min(hetero_cases.distinct_intrinsics(full)) == full.M
     M = full.M - n_extra
     lm = np.repeat(np.arange(full.N), np.diff(full.row_ptr))
     inside = full.obs_frame < M
@@ -251,7 +256,17 @@ SCENE_BUFFERS = (B.BUF_POINTS, B.BUF_CAM_R, B.BUF_CAM_T)
 def test_resident_scene_equals_the_downloaded_landmarks(h, reorder):
     """ba.locate in the normalised coordinates against locate_frames on the downloaded landmarks: the same winner and inlier
     count; the poses within ten times the distance between the yardstick's own runs in the two coordinate systems (a CPU run)"""
-    g, sc, f0, e = _held_out(reorder)
+    _equals_the_downloaded_landmarks(h, reorder, False)
+
+
+@pytest.mark.parametrize("reorder", [False, True])
+def test_resident_scene_with_per_frame_intrinsics_equals_the_downloaded_landmarks(h, reorder):
+    _equals_the_downloaded_landmarks(h, reorder, True)
+
+
+def _equals_the_downloaded_landmarks(h, reorder, hetero):
+    g, sc, f0, e = _held_out(reorder, hetero=hetero)
+    assert not hetero or len(np.unique(e["K"][:, 1, 2])) == len(e["K"])
     try:
         before = [g.buffer(w).copy() for w in SCENE_BUFFERS]
         kw = dict(hypotheses=128, seed=5, want_inliers=True)

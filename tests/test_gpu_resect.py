@@ -12,6 +12,7 @@ import surikatoko_amd as sa
 from surikatoko_amd import _lib
 from surikatoko_amd import ba as B
 from surikatoko_amd import resect as RS
+import hetero_cases
 import resect_cases as rc
 import resect_ref as ref
 
@@ -36,28 +37,10 @@ def _same_bits(a, b):
 
 
 @pytest.fixture(scope="module")
-def host_walk_floor(tmp_path_factory):
+def host_walk_floor():
     """the largest distance, in Newton-step units, between the yardstick and the kernel's order of operations walked on the host
     (tests/cpp/test_resect_host.cpp), over the two ragged batches: computed on the CPU, the device is held to ten times this"""
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx is not None, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("resect_floor")
-    exe = d / "test_resect_host"
-    r = subprocess.run([cxx, "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "test_resect_host.cpp"),
-                        os.path.join(ROOT, "surikatoko_amd", "csrc", "srk_resect.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    worst = 0.0
-    for holes in (False, True):
-        b = rc.ragged(holes)
-        attempts, rel_change = rc.RAGGED_OPTIONS[holes]
-        rc.write_host_input(str(d / "in.bin"), b, attempts=attempts, rel_change=rel_change)
-        r = subprocess.run([str(exe), "frames", str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        R, T, _, _, status, _, _ = rc.read_host_output(str(d / "out.bin"), b)
-        for i, y in enumerate(rc.ragged_yardstick(holes)):
-            if not y["status"] & ref.FEW_POINTS:
-                worst = max(worst, rc.pose_units(R[i], T[i], y))
-    return worst
+    return rc.host_walk_floor()
 
 
 def _agree(got, ys, b, bound, kind=ref.NONE, delta=None):
@@ -271,12 +254,16 @@ def test_info_is_a_one_frame_joint_prior(h):
 
 
 # ------------------------------------------------------------------ the resident scene
-def _held_out(reorder, aligned=False, n_extra=2):
+def _held_out(reorder, aligned=False, n_extra=2, hetero=False):
     """An all-visible scene; its last n_extra frames are held out: their observations become the frames to resect, from starts
     2 degrees and 0.05 units off the generated poses.  aligned: the world is moved so that frame 0 of the uploaded scene has the
-    pose (I, 0); the upload's normalisation is then a scale alone."""
+    pose (I, 0); the upload's normalisation is then a scale alone.  hetero: the full scene gets per-frame intrinsics before it is
+    split, so the held-out frames carry K distinct from each other and from the resident frames."""
     spec = sa.SceneSpec(n_frames=12, grid_nx=12, grid_ny=9, vis_window=0, noise_uv_pix=0.3)
     full = sa.generate_scene(spec)
+    if hetero:
+        full = hetero_cases.per_frame_intrinsics(full, spec.f0)
+        assert min(hetero_cases.distinct_intrinsics(full)) == full.M
     M = full.M - n_extra
     lm = np.repeat(np.arange(full.N), np.diff(full.row_ptr))
     inside = full.obs_frame < M
@@ -338,7 +325,17 @@ def test_resident_scene_evaluated_in_both_coordinates(h, reorder):
     """attempts = 0 on a scene whose normalisation turns, moves and scales the world: the start comes back bit for bit from both
     calls, and E, quality (cond_1 and the smallest depth mapped back with the pose) and info, evaluated once in the normalised
     coordinates and mapped and once in the caller's, agree to the issue's bounds"""
-    g, sc, f0, e = _held_out(reorder)
+    _evaluated_in_both_coordinates(h, reorder, False)
+
+
+@pytest.mark.parametrize("reorder", [False, True])
+def test_resident_scene_with_per_frame_intrinsics_evaluated_in_both_coordinates(h, reorder):
+    _evaluated_in_both_coordinates(h, reorder, True)
+
+
+def _evaluated_in_both_coordinates(h, reorder, hetero):
+    g, sc, f0, e = _held_out(reorder, hetero=hetero)
+    assert not hetero or len(np.unique(e["K"][:, 1, 2])) == len(e["K"])
     try:
         res, own, _ = _both(h, g, sc, f0, e, attempts=0)
         assert _same_bits(res[:2], [e["R0"], e["T0"]]) and _same_bits(own[:2], [e["R0"], e["T0"]])
@@ -362,7 +359,16 @@ def test_resident_scene_equals_the_downloaded_landmarks(h, host_walk_floor, reor
     host walk's distance from the yardstick in the Newton-step unit of the ragged test.  Two attempts at rel_change 0 from
     starts 2 degrees off: both are accepted by margins the yardstick's log shows (checked below), and the Newton step that
     remains is far above rounding, so the unit means something."""
-    g, sc, f0, e = _held_out(reorder, aligned=True)
+    _equals_the_downloaded_landmarks(h, host_walk_floor, reorder, False)
+
+
+@pytest.mark.parametrize("reorder", [False, True])
+def test_resident_scene_with_per_frame_intrinsics_equals_the_downloaded_landmarks(h, host_walk_floor, reorder):
+    _equals_the_downloaded_landmarks(h, host_walk_floor, reorder, True)
+
+
+def _equals_the_downloaded_landmarks(h, host_walk_floor, reorder, hetero):
+    g, sc, f0, e = _held_out(reorder, aligned=True, hetero=hetero)
     try:
         opts = dict(attempts=2, rel_change=0.0)
         res, own, points = _both(h, g, sc, f0, e, **opts)

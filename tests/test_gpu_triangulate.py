@@ -10,6 +10,7 @@ from surikatoko_amd import _lib
 from surikatoko_amd import ba as B
 from surikatoko_amd import io as sio
 from surikatoko_amd import triangulate as T
+import hetero_cases
 import triangulate_cases as tc
 import triangulate_ref as ref
 
@@ -233,8 +234,13 @@ def test_not_converged_exactly_where_the_yardstick_hits_the_cap(h, attempts, rel
 SPEC = sa.SceneSpec(n_frames=10, grid_nx=12, grid_ny=9, vis_window=5)
 
 
-def _resident(reorder):
+def _resident(reorder, hetero=False):
+    """hetero: every frame with its own fx, fy, u0 and v0 (zero skew: what the resident core takes), so that a resident K that did not
+    travel with its renumbered frame would be seen"""
     sc = sa.generate_scene(SPEC)
+    if hetero:
+        sc = hetero_cases.per_frame_intrinsics(sc, SPEC.f0)
+        assert min(hetero_cases.distinct_intrinsics(sc)) == sc.M
     if reorder:
         sc = sa.renumber_frames(sc, np.random.default_rng(3).permutation(sc.M))
     g = sa.BundleAdjustmentKanatani(0)
@@ -247,7 +253,18 @@ def _resident(reorder):
 
 @pytest.mark.parametrize("reorder", [False, True])
 def test_resident_scene_equals_the_downloaded_poses(h, reorder):
-    g, sc = _resident(reorder)
+    _resident_scene_equals_the_downloaded_poses(h, reorder, False)
+
+
+@pytest.mark.parametrize("reorder", [False, True])
+def test_resident_scene_with_per_frame_intrinsics_equals_the_downloaded_poses(h, reorder):
+    """intrinsic corrections are never applied, so the scene's K is the resident K: triangulate_tracks gets the
+    scene's per-frame K in the caller's frame order"""
+    _resident_scene_equals_the_downloaded_poses(h, reorder, True)
+
+
+def _resident_scene_equals_the_downloaded_poses(h, reorder, hetero):
+    g, sc = _resident(reorder, hetero)
     try:
         before = [g.buffer(w).copy() for w in (B.BUF_POINTS, B.BUF_CAM_R, B.BUF_CAM_T)]
         X, quality, status = g.triangulate(sc.row_ptr, sc.obs_frame, sc.obs_uv, revert_normalization=True)
