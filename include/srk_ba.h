@@ -1008,8 +1008,8 @@ int64_t srk_ransac_hypotheses(int sample_size, double outlier_ratio, double succ
  * Host checks before any launch (SRK_E_ARGS with a text): a descending or negative row_ptr, uv or K that is not finite, q negative
  * or not finite, a singular K, hypotheses outside 1..4096, inlier_pixels not finite or <= 0, NULL outputs, and more than 2^22
  * waves (pairs x ceil(hypotheses / 64)) in one call: split the batch, a pair's bits do not depend on it.  Nothing is allocated or
- * launched unless srk_relate_frames is called.  Absent: an adaptive early stop, refinement inside the call (two-frame bundle
- * adjustment after triangulating the inliers is the refinement), several ranks. */
+ * launched unless srk_relate_frames is called.  Absent: an adaptive early stop, several ranks.  The refinement of the winner over all
+ * its matches is srk_relate_frames_refined, below. */
 enum {
     SRK_RELATE_FEW_POINTS = 1, /* fewer than six matches with q > 0 */
     SRK_RELATE_NO_MODEL = 2    /* no sample gave an essential matrix */
@@ -1036,6 +1036,102 @@ int srk_relate_check_pairs(int32_t n_pairs, const int64_t* row_ptr, const double
  * Returns the status bits, or SRK_E_ARGS (negative) when the checks refuse the pair. */
 int srk_relate_host_pair(int64_t n_obs, const double* uv_a, const double* uv_b, const double* q, const double* K_a, const double* K_b, double f0,
                          const srk_relate_options* opts, double* R, double* T, double* E, double* related, uint8_t* inlier_out);
+
+/* ---- two-view pose refinement: robust Sampson LM per pair on the device (EXTENSION) ----
+ * srk_relate_frames returns the essential matrix of five matches, chosen by a sixth.  "refine pairs" is the step after it (the
+ * reference's RefineFundMat, py_proto/suriko/mvg.py, minimises the Sampson distance from a start): per pair a Levenberg-Marquardt
+ * loop on the robust Sampson error of all its matches over the five degrees of freedom of (R, unit T), one wave a pair, from a
+ * start pose or chained behind relate without leaving the device, with the information of the result in the form
+ * srk_ba_set_relative_pose_factors takes (srk_pair_factor).
+ *
+ * Conventions: relate's.  Frame a is (I, 0), frame b is (R, T) with x_b ~ R x_a + T and |T| = 1; E = [T]x R, F = K_b^-T E K_a^-1
+ * (K a general 3 x 3, inverted by its adjugate), p = (u, v, f0).  The signed Sampson residual of a match is
+ *     r = p_b^T F p_a / sqrt((F p_a)_0^2 + (F p_a)_1^2 + (F^T p_b)_0^2 + (F^T p_b)_1^2)   in pixels,   s = r^2,
+ * the s of relate's score.  Pairs in CSR form; q >= 0 the optional information of a match (NULL = all 1, bit for bit; q = 0 = the
+ * pair without that match, bit for bit).  Everything works on the pair's n weighted matches, numbered by rank in ascending o.
+ *
+ * Objective: E_pair = sum_o rho(q_o s_o), rho none, Huber or Cauchy with delta in pixels (the formulas of srk_ba_set_robust_loss).
+ *
+ * Variables d = [w (3); beta (2)]: R <- R Exp(w)^T, a product of rotations (as in srk_resect_frames), and T on the unit sphere,
+ * T <- (T + b1 beta_1 + b2 beta_2) / |T + b1 beta_1 + b2 beta_2|.  The tangent basis is fixed by rule and recomputed from the
+ * current T at every linearisation: k the index of the smallest |T_k| (a tie: the smaller k), b1 = (e_k x T) / |e_k x T|,
+ * b2 = T x b1.
+ *
+ * Jacobian, exact: dE/dw_i = -[T]x R [e_i]x, dE/dbeta_j = [b_j]x R, dF_k = K_b^-T (dE/dd_k) K_a^-1, and dr by the quotient rule,
+ * the derivative of the denominator included.  With w_o = rho'(q_o s_o): H = sum q_o w_o J_o^T J_o (5 x 5), g = sum q_o w_o J_o r_o.
+ *
+ * Loop: the rule of srk_resect_frames.  The damping factor c starts at 1e-4; an attempt solves (H + c diag H) d = -g by a
+ * written-out 5 x 5 Cholesky factorisation, walks the moved pose once and is accepted iff E_pair decreases (c /= 10; otherwise, and
+ * after a failed factorisation or a value that is not finite, c *= 10).  The loop stops when an accepted attempt changes E_pair by
+ * less than rel_change E_pair, or after `attempts` attempts (0 .. 64; 0 = evaluate only: R0 and T0 come back bit for bit).  The
+ * result never has a larger E_pair than the start.
+ *
+ * Outputs per pair: R [9], T [3] (unit), E [9] = [T]x R exactly as returned; quality [6] = { sqrt(E_pair / n) in pixels, n,
+ * sum w_o / n, cond_1 of the Jacobi-scaled H (NaN when it is not positive definite), the number of weighted matches at a positive
+ * distance along both rays at the result (the depth rule of relate's vote), the attempts used }; info [25] = H / f0^2 at the
+ * result, undamped, row-major, in the order [w; beta]; basis [6] = b1, b2 at the result; status, a mask of SRK_PAIR_*; w_out [O]
+ * (may be NULL): the robust weight of every match at the result, 0 where q = 0.  With FEW_POINTS the pose is the start, quality is
+ * { NaN, n, NaN, NaN, NaN, 0 } and info is zero.  The library applies no threshold of its own: pure rotation (T not observable)
+ * shows as a large quality[3].
+ *
+ * srk_relate_frames_refined runs relate's kernels unchanged; the related poses stay on the device and are the R0, T0 of the
+ * refinement.  related, related_status and inlier_out are bit for bit those of srk_relate_frames; R, T, E, quality, info, basis,
+ * status and w_out are bit for bit those of srk_refine_pairs from the related poses.  With inliers_only = 1 the refinement uses
+ * q_o * inlier_o, the winner's inlier flags, formed on the device and frozen for the loop: the outputs are those of
+ * srk_refine_pairs called with that product.  A pair that was not related is refined from (I, (1, 0, 0)) like any other; its
+ * related_status says not to trust the result.
+ *
+ * Host checks before any allocation or launch (SRK_E_ARGS with a text): a row_ptr that does not start at 0 or decreases; a uv, K,
+ * R0 or T0 entry that is not finite; a negative or not finite q; a singular K; an R0 that is not a rotation to 1e-9 (the rule of
+ * srk_ba_set_joint_pose_priors); a T0 whose length is not 1 to 1e-9; attempts outside 0..64; a negative or not finite rel_change;
+ * a loss kind outside 0..2; a loss with delta <= 0; inliers_only not 0 or 1 (and not 0 in srk_refine_pairs, where it has no
+ * meaning); a NULL array with a positive count; NULL outputs (w_out may be NULL). */
+enum {
+    SRK_PAIR_FEW_POINTS = 1,   /* fewer than five matches with q > 0: the pose is the start */
+    SRK_PAIR_DEGENERATE = 2,   /* the scaled H at the result is not positive definite, or something is not finite */
+    SRK_PAIR_NOT_CONVERGED = 8 /* every attempt was used */
+};
+typedef struct srk_pair_options {
+    int32_t attempts;         /* 0 .. 64; 0 = evaluate only */
+    double rel_change;        /* stop when an accepted attempt changes E_pair by less than rel_change E_pair */
+    int32_t loss_kind;        /* 0 none, 1 Huber, 2 Cauchy */
+    double loss_delta_pixels; /* > 0 with a loss */
+    int32_t inliers_only;     /* srk_relate_frames_refined: refine on the winner's inliers only; 0 elsewhere */
+} srk_pair_options;
+void srk_pair_default_options(srk_pair_options*); /* { 10, 1e-9, 0, 0, 0 } */
+int srk_refine_pairs(srk_ba*, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a /* [O][2] */, const double* uv_b /* [O][2] */,
+                     const double* q /* [O], NULL = all 1 */, const double* K_a, const double* K_b /* [n_pairs][9], or [9] with shared_k */,
+                     int shared_k, const double* R0 /* [n][9] */, const double* T0 /* [n][3], unit */,
+                     const srk_pair_options* /* NULL = the defaults */, double* R /* [n][9] */, double* T /* [n][3], unit */, double* E /* [n][9] */,
+                     double* quality /* [n][6] */, double* info /* [n][25] */, double* basis /* [n][6] */, uint32_t* status /* [n] */,
+                     double* w_out /* [O] or NULL */);
+int srk_relate_frames_refined(srk_ba*, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
+                              const double* K_a, const double* K_b, int shared_k, const srk_relate_options* /* NULL = the defaults */,
+                              const srk_pair_options* refine /* not NULL */, double* R, double* T, double* E, double* related /* [n][8] */,
+                              uint32_t* related_status /* [n] */, uint8_t* inlier_out /* [O] or NULL */, double* quality, double* info,
+                              double* basis, uint32_t* status, double* w_out /* [O] or NULL */);
+/* device ms of the refinement's kernels (the inverses of K, the product with the inlier flags, the pairs) in the last of the two
+ * calls on this handle, from an event pair; the chained call leaves relate's own time in srk_ba_relate_kernel_ms */
+double srk_ba_pair_kernel_ms(const srk_ba*);
+/* host only, no device and no handle needed: the checks of srk_refine_pairs on their own.  SRK_OK, or SRK_E_ARGS with *why (may be
+ * NULL) pointing at a static text. */
+int srk_pair_check_pairs(int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q, const double* K_a,
+                         const double* K_b, int shared_k, const double* R0, const double* T0, const srk_pair_options* opts, const char** why);
+/* host only: one pair of n_obs matches in the kernel's own order of operations (the same statements, compiled for the host; the
+ * same deal of the weighted matches to 64 lanes, the same merge tree).  grad [5] (may be NULL): g at the result.  log (may be
+ * NULL) receives (accepted, E_cur, E_cand) per attempt, [attempts][3], E_cand NaN when the factorisation failed, and *log_count
+ * their number.  Returns the status bits, or SRK_E_ARGS (negative) when the checks refuse the pair. */
+int srk_pair_host_pair(int64_t n_obs, const double* uv_a, const double* uv_b, const double* q, const double* K_a, const double* K_b, double f0,
+                       const double* R0, const double* T0, const srk_pair_options* opts, double* R, double* T, double* E, double* quality,
+                       double* info, double* basis, double* w_out, double* grad, double* log, int32_t* log_count);
+/* host only: from a refined pair to the factor srk_ba_set_relative_pose_factors takes for the frames (a, b), at a baseline length
+ * lambda > 0 that the caller knows (two views do not): rel_R = Z = R^T, rel_t = z = -lambda R^T T, and info21 the upper triangle
+ * (row by row, order [t; r]) of L = M^T info M with the 5 x 6 matrix M = [[0, R^T], [-(1 / lambda) B^T R, B^T [T]x]], B = [b1 b2]:
+ * to first order the factor's residual [e_t; e_r] moves the refinement's variables by w = R^T e_r and
+ * beta = -(1 / lambda) B^T R e_t + B^T [T]x e_r.  L is positive semi-definite of rank at most 5; its null direction [z; 0] is the
+ * scale.  SRK_E_ARGS for a NULL pointer, a value that is not finite or lambda <= 0. */
+int srk_pair_factor(const double* R, const double* T, const double* info /* [25] */, const double* basis /* [6] */, double baseline,
+                    double* rel_R /* [9] */, double* rel_t /* [3] */, double* info21 /* [21] */);
 
 /* ---- map alignment: similarity hypotheses scored on the device (EXTENSION) ----
  * relate is 2D-2D and locate 2D-3D; "align" is the 3D-3D member: the similarity b ~ s R a + t (s > 0, R a proper rotation) between

@@ -642,6 +642,91 @@ public:
         return out;
     }
 
+    /// EXTENSION: the refinement of two-view poses over all the matches of each pair, on the device (srk_refine_pairs,
+    /// srk_relate_frames_refined; DESIGN.md section 26: per pair a Levenberg-Marquardt loop on the robust Sampson error over the five
+    /// degrees of freedom of (R, unit T), one wave a pair).  One result per pair.
+    struct RefinedPair {
+        SE3Transform pose;                ///< (R, T) of frame b, |T| = 1; the start when status has SRK_PAIR_FEW_POINTS
+        std::array<Scalar, 9> E{};        ///< [T]x R, row-major
+        Scalar rms_pixels = 0;            ///< sqrt(E_pair / matches)
+        Scalar mean_weight = 0;           ///< the mean robust weight at the result
+        Scalar condition = 0;             ///< cond_1 of the Jacobi-scaled H; large for a pure rotation, NaN when not positive definite
+        size_t matches = 0, in_front = 0, attempts = 0;
+        std::array<Scalar, 25> info{};    ///< H / f0^2 at the result over [w; beta], row-major
+        std::array<Scalar, 6> basis{};    ///< b1, b2: the tangent basis of T that beta refers to
+        uint32_t status = 0;              ///< SRK_PAIR_* bits
+        std::vector<Scalar> weights;      ///< per match, at the result (with want_weights)
+    };
+    /// from the start poses `starts` (one per pair; |T| = 1).  opts NULL: the defaults (10 attempts, 1e-9, no loss).  Throws
+    /// std::invalid_argument for every refusal of the library.
+    std::vector<RefinedPair> RefinePairs(Scalar f0, const std::vector<std::vector<Match>>& pairs, const Matrix3* shared_Ka, const Matrix3* shared_Kb,
+                                         const std::vector<Matrix3>* Kas, const std::vector<Matrix3>* Kbs, const std::vector<SE3Transform>& starts,
+                                         const srk_pair_options* opts = nullptr, bool want_weights = false) {
+        if (starts.size() != pairs.size()) throw std::invalid_argument("pair: one start pose per pair");
+        PairArrays a(pairs, shared_Ka, shared_Kb, Kas, Kbs, want_weights);
+        std::vector<Scalar> R0(9 * a.n + 1), T0(3 * a.n + 1);
+        for (size_t i = 0; i < a.n; ++i) {
+            for (size_t e = 0; e < 9; ++e) R0[9 * i + e] = starts[i].R[e];
+            T0[3 * i] = starts[i].T.x, T0[3 * i + 1] = starts[i].T.y, T0[3 * i + 2] = starts[i].T.z;
+        }
+        int rc = srk_refine_pairs(h_, f0, (int32_t)a.n, a.row_ptr.data(), a.ua.data(), a.ub.data(), a.q.data(), a.Ka.data(), a.Kb.data(), a.shared ? 1 : 0,
+                                  R0.data(), T0.data(), opts, a.R.data(), a.T.data(), a.E.data(), a.ql.data(), a.info.data(), a.basis.data(), a.st.data(),
+                                  want_weights ? a.w.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        return a.Pairs(want_weights);
+    }
+    /// RelateFrames with the refinement chained behind it on the device: `related` (may be NULL) receives what RelateFrames returns
+    /// except that RelatedPair::pose and RelatedPair::E are the REFINED pose (the C call has one set of pose outputs; the five-point
+    /// winner itself is what RelateFrames returns).  refine.inliers_only = 1 refines on the winner's inliers alone.
+    std::vector<RefinedPair> RelateFramesRefined(Scalar f0, const std::vector<std::vector<Match>>& pairs, const Matrix3* shared_Ka, const Matrix3* shared_Kb,
+                                                 const std::vector<Matrix3>* Kas, const std::vector<Matrix3>* Kbs, const srk_relate_options* opts,
+                                                 const srk_pair_options& refine, std::vector<RelatedPair>* related = nullptr, bool want_inliers = false,
+                                                 bool want_weights = false) {
+        PairArrays a(pairs, shared_Ka, shared_Kb, Kas, Kbs, want_weights);
+        std::vector<Scalar> rel(8 * a.n + 1);
+        std::vector<uint32_t> rst(a.n + 1);
+        std::vector<uint8_t> inl(want_inliers ? a.q.size() : 1);
+        int rc = srk_relate_frames_refined(h_, f0, (int32_t)a.n, a.row_ptr.data(), a.ua.data(), a.ub.data(), a.q.data(), a.Ka.data(), a.Kb.data(),
+                                           a.shared ? 1 : 0, opts, &refine, a.R.data(), a.T.data(), a.E.data(), rel.data(), rst.data(),
+                                           want_inliers ? inl.data() : nullptr, a.ql.data(), a.info.data(), a.basis.data(), a.st.data(),
+                                           want_weights ? a.w.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        std::vector<RefinedPair> out = a.Pairs(want_weights);
+        if (related) {
+            related->assign(a.n, RelatedPair());
+            for (size_t i = 0; i < a.n; ++i) {
+                RelatedPair& p = (*related)[i];
+                p.pose = out[i].pose;
+                p.E = out[i].E;
+                p.rms_pixels = rel[8 * i];
+                p.matches = (size_t)rel[8 * i + 1];
+                p.inlier_count = (size_t)rel[8 * i + 2];
+                p.status = rst[i];
+                p.winner = rst[i] ? -1 : (int64_t)rel[8 * i + 3];
+                p.hypotheses_with_model = (size_t)rel[8 * i + 4];
+                p.sixth_match_pixels = rel[8 * i + 5];
+                p.in_front = (size_t)rel[8 * i + 6];
+                p.parallax_rad = rel[8 * i + 7];
+                if (want_inliers) p.inliers.assign(inl.begin() + a.row_ptr[i], inl.begin() + a.row_ptr[i + 1]);
+            }
+        }
+        return out;
+    }
+    /// The relative-pose factor of a refined pair at a baseline length the caller knows (srk_pair_factor; host only), as
+    /// SetRelativePoseFactors takes it for the cameras (frame_a, frame_b): rel_R = R^T, rel_t = -baseline R^T T and the 21
+    /// upper-triangle entries of the 6 x 6 information over [t; r].  Its null direction [rel_t; 0] is the scale.
+    static RelativePoseFactor PairFactor(const RefinedPair& p, Scalar baseline, size_t frame_a = 0, size_t frame_b = 1) {
+        RelativePoseFactor f;
+        f.frame_a = frame_a, f.frame_b = frame_b;
+        const Scalar T[3] = { p.pose.T.x, p.pose.T.y, p.pose.T.z };
+        Scalar R[9], z[3];
+        for (size_t e = 0; e < 9; ++e) R[e] = p.pose.R[e];
+        if (srk_pair_factor(R, T, p.info.data(), p.basis.data(), baseline, f.rel_R.data(), z, f.info.data()) != SRK_OK)
+            throw std::invalid_argument("PairFactor: a value that is not finite, or a baseline <= 0");
+        f.rel_t = Point3{ z[0], z[1], z[2] };
+        return f;
+    }
+
     /// EXTENSION: the similarity b ~ s R a + t between sets of corresponding 3D points, wrong correspondences among them, on the
     /// device (srk_align_points / srk_ba_align; DESIGN.md section 25: three-point hypotheses from a counter-based sampler, each
     /// scored on every correspondence, the winner refined by a closed-form least-squares similarity on its inliers).  One result
@@ -759,6 +844,59 @@ private:
                 out[i].cond1 = q[4 * i + 2];
                 out[i].views = (size_t)q[4 * i + 3];
                 out[i].status = st[i];
+            }
+            return out;
+        }
+    };
+    struct PairArrays {
+        std::vector<int64_t> row_ptr{ 0 };
+        std::vector<Scalar> ua, ub, q, Ka, Kb, R, T, E, ql, info, basis, w;
+        std::vector<uint32_t> st;
+        size_t n = 0;
+        bool shared = false;
+        PairArrays(const std::vector<std::vector<Match>>& pairs, const Matrix3* shared_Ka, const Matrix3* shared_Kb, const std::vector<Matrix3>* Kas,
+                   const std::vector<Matrix3>* Kbs, bool want_weights) {
+            shared = shared_Ka && shared_Kb;
+            if (shared == (Kas && Kbs) || (!shared && (shared_Ka || shared_Kb)))
+                throw std::invalid_argument("Provide either shared intrinsics or separate intrinsics for each pair, for both cameras");
+            if (!shared && (Kas->size() != pairs.size() || Kbs->size() != pairs.size())) throw std::invalid_argument("pair: one K_a and one K_b per pair");
+            for (const std::vector<Match>& p : pairs) {
+                for (const Match& m : p) {
+                    ua.insert(ua.end(), { m.a.x, m.a.y });
+                    ub.insert(ub.end(), { m.b.x, m.b.y });
+                    q.push_back(m.information);
+                }
+                row_ptr.push_back((int64_t)q.size());
+            }
+            if (shared) Ka.assign(shared_Ka->begin(), shared_Ka->end()), Kb.assign(shared_Kb->begin(), shared_Kb->end());
+            else
+                for (size_t i = 0; i < pairs.size(); ++i) {
+                    Ka.insert(Ka.end(), (*Kas)[i].begin(), (*Kas)[i].end());
+                    Kb.insert(Kb.end(), (*Kbs)[i].begin(), (*Kbs)[i].end());
+                }
+            n = pairs.size();
+            const size_t O = q.size();
+            for (std::vector<Scalar>* v : { &ua, &ub, &q, &Ka, &Kb }) v->push_back(0); // never read: keep data() valid without matches or pairs
+            R.resize(9 * n + 1), T.resize(3 * n + 1), E.resize(9 * n + 1), ql.resize(6 * n + 1), info.resize(25 * n + 1), basis.resize(6 * n + 1);
+            st.resize(n + 1);
+            w.resize(want_weights ? O + 1 : 1);
+        }
+        std::vector<RefinedPair> Pairs(bool want_weights) const {
+            std::vector<RefinedPair> out(n);
+            for (size_t i = 0; i < n; ++i) {
+                RefinedPair& p = out[i];
+                for (size_t e = 0; e < 9; ++e) p.pose.R[e] = R[9 * i + e], p.E[e] = E[9 * i + e];
+                p.pose.T = Point3{ T[3 * i], T[3 * i + 1], T[3 * i + 2] };
+                p.rms_pixels = ql[6 * i];
+                p.matches = (size_t)ql[6 * i + 1];
+                p.mean_weight = ql[6 * i + 2];
+                p.condition = ql[6 * i + 3];
+                p.in_front = ql[6 * i + 4] > 0 ? (size_t)ql[6 * i + 4] : 0; // NaN with FEW_POINTS
+                p.attempts = (size_t)ql[6 * i + 5];
+                for (size_t e = 0; e < 25; ++e) p.info[e] = info[25 * i + e];
+                for (size_t e = 0; e < 6; ++e) p.basis[e] = basis[6 * i + e];
+                p.status = st[i];
+                if (want_weights) p.weights.assign(w.begin() + row_ptr[i], w.begin() + row_ptr[i + 1]);
             }
             return out;
         }

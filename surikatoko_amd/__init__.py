@@ -16,6 +16,8 @@ from .locate import (locate_frames, locate_status_names, default_locate_options,
                      LOCATE_FEW_POINTS, LOCATE_NO_MODEL)
 from .relate import (relate_frames, relate_status_names, default_relate_options, two_view_scene, RelateResult, TwoViewScene,  # noqa: F401
                      RELATE_FEW_POINTS, RELATE_NO_MODEL)
+from .pair import (refine_pairs, relative_pose_factor, pair_status_names, default_pair_options, PairResult,  # noqa: F401
+                   PAIR_FEW_POINTS, PAIR_DEGENERATE, PAIR_NOT_CONVERGED)
 from .align import (align_points, apply_similarity, align_status_names, default_align_options, AlignResult,  # noqa: F401
                     ALIGN_FEW_POINTS, ALIGN_NO_MODEL)
 from .scene import (SceneSpec, generate_scene, config_scene, drop_observations, renumber_frames, loop_scene,  # noqa: F401

@@ -82,6 +82,11 @@ class RelateOptions(C.Structure):
     _fields_ = [("hypotheses", C.c_int32), ("inlier_pixels", C.c_double), ("seed", C.c_uint64)]
 
 
+class PairOptions(C.Structure):
+    _fields_ = [("attempts", C.c_int32), ("rel_change", C.c_double), ("loss_kind", C.c_int32), ("loss_delta_pixels", C.c_double),
+                ("inliers_only", C.c_int32)]
+
+
 class AlignOptions(C.Structure):
     _fields_ = [("hypotheses", C.c_int32), ("inlier_distance", C.c_double), ("seed", C.c_uint64), ("with_scale", C.c_int32),
                 ("refine_rounds", C.c_int32)]
@@ -113,6 +118,8 @@ EXPORTS = [
     "srk_locate_default_options", "srk_locate_frames", "srk_ba_locate", "srk_ba_locate_kernel_ms", "srk_ba_locate_score_ms", "srk_locate_check_frames",
     "srk_ransac_hypotheses",
     "srk_relate_default_options", "srk_relate_frames", "srk_ba_relate_kernel_ms", "srk_ba_relate_score_ms", "srk_relate_check_pairs", "srk_relate_host_pair",
+    "srk_pair_default_options", "srk_refine_pairs", "srk_relate_frames_refined", "srk_ba_pair_kernel_ms", "srk_pair_check_pairs", "srk_pair_host_pair",
+    "srk_pair_factor",
     "srk_align_default_options", "srk_align_points", "srk_ba_align", "srk_ba_align_kernel_ms", "srk_ba_align_score_ms", "srk_align_check_sets",
     "srk_align_host_set", "srk_similarity_apply",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
@@ -249,6 +256,18 @@ def lib():
     L.srk_ba_relate_kernel_ms.restype = C.c_double
     L.srk_ba_relate_score_ms.argtypes = [C.c_void_p]
     L.srk_ba_relate_score_ms.restype = C.c_double
+    L.srk_pair_default_options.argtypes = [C.POINTER(PairOptions)]
+    L.srk_pair_default_options.restype = None
+    # ... the pairs without relate's options, then R0, T0, options
+    _starts = _pairs[:-1] + [C.c_void_p, C.c_void_p, C.POINTER(PairOptions)]
+    L.srk_refine_pairs.argtypes = [C.c_void_p, C.c_double] + _starts + [C.c_void_p] * 8
+    L.srk_relate_frames_refined.argtypes = [C.c_void_p, C.c_double] + _pairs + [C.POINTER(PairOptions)] + [C.c_void_p] * 11
+    L.srk_pair_check_pairs.argtypes = _starts + [C.POINTER(C.c_char_p)]
+    L.srk_pair_host_pair.argtypes = [C.c_int64] + [C.c_void_p] * 5 + [C.c_double, C.c_void_p, C.c_void_p, C.POINTER(PairOptions)] + [C.c_void_p] * 9 + [
+        C.POINTER(C.c_int32)]
+    L.srk_pair_factor.argtypes = [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 3
+    L.srk_ba_pair_kernel_ms.argtypes = [C.c_void_p]
+    L.srk_ba_pair_kernel_ms.restype = C.c_double
     L.srk_align_default_options.argtypes = [C.POINTER(AlignOptions)]
     L.srk_align_default_options.restype = None
     L.srk_align_points.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.POINTER(AlignOptions)] + [C.c_void_p] * 6

@@ -28,6 +28,9 @@
 #include "srk_relate.hpp"
 #include "srk_relate_dev.hpp"
 #include "srk_relate_math.hpp"
+#include "srk_pair.hpp"
+#include "srk_pair_dev.hpp"
+#include "srk_pair_math.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -301,6 +304,13 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     DevBuf al[AL_NBUF];
     hipEvent_t al_ev[4]{};           // the call, and the hypothesis-and-score kernel inside it; created at the first call
     double al_ms = 0, al_score_ms = 0; // srk_ba_align_kernel_ms, srk_ba_align_score_ms
+    // two-view pose refinement (srk_refine_pairs, srk_relate_frames_refined): the pairs' matches, intrinsics
+    // and start poses of srk_refine_pairs (the chained call reads relate's buffers instead), the inverses of K, the product of q
+    // with the inlier flags and the outputs, grown lazily
+    enum { PR_ROW, PR_UVA, PR_UVB, PR_Q, PR_KA, PR_KB, PR_R0, PR_T0, PR_KINV, PR_QE, PR_R, PR_T, PR_E, PR_QUAL, PR_INFO, PR_BASIS, PR_STATUS, PR_W, PR_NBUF };
+    DevBuf pr[PR_NBUF];
+    hipEvent_t pr_ev[2]{}; // around the refinement's kernels, created at the first call
+    double pr_ms = 0;      // their device time in the last call (srk_ba_pair_kernel_ms)
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -478,6 +488,9 @@ void srk_ba_destroy(srk_ba* h)
     for (DevBuf& b : h->lc) dev_free(b);
     for (DevBuf& b : h->rl) dev_free(b);
     for (DevBuf& b : h->al) dev_free(b);
+    for (DevBuf& b : h->pr) dev_free(b);
+    for (hipEvent_t& e : h->pr_ev)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->al_ev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->rl_ev)
@@ -3471,10 +3484,23 @@ extern "C" int srk_ba_locate(srk_ba* h, int32_t n_frames, const int64_t* row_ptr
 }
 
 // ------------------------------------------------------------------ two-view relative pose
-// The checked pairs of a call to the device, gather / solve / score / pick, the results back.
+// the refinement of section 26, defined below: its kernels over pairs that are on the device, and the copies back
+static int pair_device(srk_ba* h, double f0, int32_t n_pairs, int64_t O, const int64_t* d_row, const double* d_uva, const double* d_uvb, const double* d_q,
+                       const double* d_ka, const double* d_kb, int shared_k, const double* d_R0, const double* d_T0, const uint32_t* d_related_status,
+                       const uint8_t* d_inlier, const srk_pair_options& o, bool want_w);
+static int pair_download(srk_ba* h, int32_t n_pairs, int64_t O, double* R, double* T, double* E, double* quality, double* info, double* basis,
+                         uint32_t* status, double* w_out);
+struct RelateRefine {
+    const srk_pair_options* opts;
+    double *R, *T, *E, *quality, *info, *basis, *w_out;
+    uint32_t* status;
+};
+// The checked pairs of a call to the device, gather / solve / score / pick, the results back.  refine (srk_relate_frames_refined): the
+// refinement follows on the same stream before anything is copied back, R, T and E are the refined ones (the three of this call
+// are not used), and with inliers_only the inlier flags are formed on the device even when the caller does not ask for them.
 static int relate_run(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
                       const double* K_a, const double* K_b, int shared_k, const srk_relate_options& lo, double* R, double* T, double* E,
-                      double* related, uint32_t* status, uint8_t* inlier_out)
+                      double* related, uint32_t* status, uint8_t* inlier_out, const RelateRefine* refine = nullptr)
 {
     hipStream_t s = h->main_stream;
     const int64_t O = row_ptr[n_pairs], n = n_pairs;
@@ -3490,7 +3516,8 @@ static int relate_run(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_
         if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
         if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
     }
-    const bool want_inl = inlier_out && O > 0;
+    const bool keep_inl = refine && refine->opts->inliers_only && O > 0;
+    const bool want_inl = (inlier_out && O > 0) || keep_inl;
     if ((rc = dev_alloc(h, l[srk_ba::RL_STRIP], (size_t)(8 * SRK_RELATE_STRIP * O))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::RL_COUNT], (size_t)(8 * n))) != SRK_OK ||
         (rc = dev_alloc(h, l[srk_ba::RL_HYP], (size_t)(8 * SRK_RELATE_HYP * n * lo.hypotheses))) != SRK_OK ||
         (rc = dev_alloc(h, l[srk_ba::RL_SLOTS], (size_t)(8 * SRK_RELATE_SLOT * n * waves))) != SRK_OK ||
@@ -3519,13 +3546,26 @@ static int relate_run(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_
                            want_inl ? P<uint8_t>(l[srk_ba::RL_INL]) : nullptr);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->rl_ev[3], s));
-    HIPCHK(h, hipMemcpyAsync(R, l[srk_ba::RL_R].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(T, l[srk_ba::RL_T].p, (size_t)(24 * n), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(E, l[srk_ba::RL_E].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+    if (refine) { // the related poses never leave the device: they are the starts of the refinement
+        if ((rc = pair_device(h, f0, n_pairs, O, d_row, P<double>(l[srk_ba::RL_UVA]), P<double>(l[srk_ba::RL_UVB]), d_q, P<double>(l[srk_ba::RL_KA]),
+                              P<double>(l[srk_ba::RL_KB]), shared_k, P<double>(l[srk_ba::RL_R]), P<double>(l[srk_ba::RL_T]),
+                              P<uint32_t>(l[srk_ba::RL_STATUS]), keep_inl ? P<uint8_t>(l[srk_ba::RL_INL]) : nullptr, *refine->opts,
+                              refine->w_out != nullptr)) != SRK_OK)
+            return rc;
+    } else {
+        HIPCHK(h, hipMemcpyAsync(R, l[srk_ba::RL_R].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(T, l[srk_ba::RL_T].p, (size_t)(24 * n), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(E, l[srk_ba::RL_E].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(h, hipMemcpyAsync(related, l[srk_ba::RL_RELATED].p, (size_t)(64 * n), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(status, l[srk_ba::RL_STATUS].p, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
-    if (want_inl) HIPCHK(h, hipMemcpyAsync(inlier_out, l[srk_ba::RL_INL].p, (size_t)O, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
+    if (inlier_out && O > 0) HIPCHK(h, hipMemcpyAsync(inlier_out, l[srk_ba::RL_INL].p, (size_t)O, hipMemcpyDeviceToHost, s));
+    if (refine) { // copies, the synchronisation and the refinement's own time
+        if ((rc = pair_download(h, n_pairs, O, refine->R, refine->T, refine->E, refine->quality, refine->info, refine->basis, refine->status,
+                                refine->w_out)) != SRK_OK)
+            return rc;
+    } else
+        HIPCHK(h, hipStreamSynchronize(s));
     float ms = 0, score_ms = 0;
     HIPCHK(h, hipEventElapsedTime(&ms, h->rl_ev[0], h->rl_ev[3]));
     HIPCHK(h, hipEventElapsedTime(&score_ms, h->rl_ev[1], h->rl_ev[2]));
@@ -3553,6 +3593,129 @@ extern "C" int srk_relate_frames(srk_ba* h, double f0, int32_t n_pairs, const in
                           inlier_out);
     } catch (const std::bad_alloc&) {
         h->last_error = "relate: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+// ------------------------------------------------------------------ two-view pose refinement
+// The refinement's kernels over pairs that are on the device already (every pointer a device pointer): the inverses of K, with
+// d_inlier the product q * inlier, then one wave a pair.  Nothing is copied back and nothing is waited for.
+static int pair_device(srk_ba* h, double f0, int32_t n_pairs, int64_t O, const int64_t* d_row, const double* d_uva, const double* d_uvb, const double* d_q,
+                       const double* d_ka, const double* d_kb, int shared_k, const double* d_R0, const double* d_T0, const uint32_t* d_related_status,
+                       const uint8_t* d_inlier, const srk_pair_options& o, bool want_w)
+{
+    hipStream_t s = h->main_stream;
+    const int64_t n = n_pairs;
+    DevBuf* g = h->pr;
+    int rc;
+    if ((rc = dev_alloc(h, g[srk_ba::PR_KINV], (size_t)(8 * SRK_PAIR_KINV * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::PR_QE], d_inlier ? (size_t)(8 * O) : 0)) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::PR_R], (size_t)(72 * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::PR_T], (size_t)(24 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::PR_E], (size_t)(72 * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::PR_QUAL], (size_t)(48 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::PR_INFO], (size_t)(200 * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::PR_BASIS], (size_t)(48 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, g[srk_ba::PR_STATUS], (size_t)(4 * n))) != SRK_OK || (rc = dev_alloc(h, g[srk_ba::PR_W], want_w && O > 0 ? (size_t)(8 * O) : 0)) != SRK_OK)
+        return rc;
+    for (hipEvent_t& e : h->pr_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    HIPCHK(h, hipEventRecord(h->pr_ev[0], s));
+    srk_launch_pair_pack(s, n_pairs, d_ka, d_kb, shared_k, P<double>(g[srk_ba::PR_KINV]));
+    if (d_inlier) {
+        srk_launch_pair_mask(s, O, d_q, d_inlier, P<double>(g[srk_ba::PR_QE]));
+        d_q = P<double>(g[srk_ba::PR_QE]);
+    }
+    srk_launch_pair_refine(s, n_pairs, d_row, d_uva, d_uvb, d_q, P<double>(g[srk_ba::PR_KINV]), d_R0, d_T0, d_related_status, f0, o.attempts, o.rel_change,
+                           o.loss_kind, o.loss_delta_pixels, P<double>(g[srk_ba::PR_R]), P<double>(g[srk_ba::PR_T]), P<double>(g[srk_ba::PR_E]),
+                           P<double>(g[srk_ba::PR_QUAL]), P<double>(g[srk_ba::PR_INFO]), P<double>(g[srk_ba::PR_BASIS]), P<uint32_t>(g[srk_ba::PR_STATUS]),
+                           want_w && O > 0 ? P<double>(g[srk_ba::PR_W]) : nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->pr_ev[1], s));
+    return SRK_OK;
+}
+
+// the results of pair_device back, the synchronisation and the kernels' time
+static int pair_download(srk_ba* h, int32_t n_pairs, int64_t O, double* R, double* T, double* E, double* quality, double* info, double* basis,
+                         uint32_t* status, double* w_out)
+{
+    hipStream_t s = h->main_stream;
+    const int64_t n = n_pairs;
+    DevBuf* g = h->pr;
+    HIPCHK(h, hipMemcpyAsync(R, g[srk_ba::PR_R].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(T, g[srk_ba::PR_T].p, (size_t)(24 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(E, g[srk_ba::PR_E].p, (size_t)(72 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(quality, g[srk_ba::PR_QUAL].p, (size_t)(48 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(info, g[srk_ba::PR_INFO].p, (size_t)(200 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(basis, g[srk_ba::PR_BASIS].p, (size_t)(48 * n), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(status, g[srk_ba::PR_STATUS].p, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+    if (w_out && O > 0) HIPCHK(h, hipMemcpyAsync(w_out, g[srk_ba::PR_W].p, (size_t)(8 * O), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->pr_ev[0], h->pr_ev[1]));
+    h->pr_ms = ms;
+    return SRK_OK;
+}
+
+extern "C" double srk_ba_pair_kernel_ms(const srk_ba* h) { return h ? h->pr_ms : 0.0; }
+
+extern "C" int srk_refine_pairs(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
+                                const double* K_a, const double* K_b, int shared_k, const double* R0, const double* T0, const srk_pair_options* opts,
+                                double* R, double* T, double* E, double* quality, double* info, double* basis, uint32_t* status, double* w_out)
+{
+    if (!h) return SRK_E_ARGS;
+    try {
+        std::string why = srk_pair_check(n_pairs, row_ptr, uv_a, uv_b, q, K_a, K_b, shared_k, R0, T0, opts);
+        if (why.empty() && (!std::isfinite(f0) || srk::is_close(0.0, f0))) why = "pair: f0 must be finite and not ~0";
+        if (why.empty() && n_pairs > 0 && (!R || !T || !E || !quality || !info || !basis || !status)) why = "pair: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_pairs == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        hipStream_t s = h->main_stream;
+        const int64_t O = row_ptr[n_pairs], n = n_pairs;
+        const int sk = shared_k ? 1 : 0;
+        DevBuf* g = h->pr;
+        int rc;
+        struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+            { &g[srk_ba::PR_ROW], row_ptr, (size_t)(8 * (n + 1)) }, { &g[srk_ba::PR_UVA], uv_a, (size_t)(16 * O) },
+            { &g[srk_ba::PR_UVB], uv_b, (size_t)(16 * O) },         { &g[srk_ba::PR_Q], q, q ? (size_t)(8 * O) : 0 },
+            { &g[srk_ba::PR_KA], K_a, (size_t)(72 * (sk ? 1 : n)) }, { &g[srk_ba::PR_KB], K_b, (size_t)(72 * (sk ? 1 : n)) },
+            { &g[srk_ba::PR_R0], R0, (size_t)(72 * n) },            { &g[srk_ba::PR_T0], T0, (size_t)(24 * n) },
+        };
+        for (auto& u : up) {
+            if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+            if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+        }
+        if ((rc = pair_device(h, f0, n_pairs, O, P<int64_t>(g[srk_ba::PR_ROW]), P<double>(g[srk_ba::PR_UVA]), P<double>(g[srk_ba::PR_UVB]),
+                              q ? P<double>(g[srk_ba::PR_Q]) : nullptr, P<double>(g[srk_ba::PR_KA]), P<double>(g[srk_ba::PR_KB]), sk,
+                              P<double>(g[srk_ba::PR_R0]), P<double>(g[srk_ba::PR_T0]), nullptr, nullptr, srk_pair_effective_options(opts),
+                              w_out != nullptr)) != SRK_OK)
+            return rc;
+        return pair_download(h, n_pairs, O, R, T, E, quality, info, basis, status, w_out);
+    } catch (const std::bad_alloc&) {
+        h->last_error = "pair: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+extern "C" int srk_relate_frames_refined(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b,
+                                         const double* q, const double* K_a, const double* K_b, int shared_k, const srk_relate_options* opts,
+                                         const srk_pair_options* refine, double* R, double* T, double* E, double* related, uint32_t* related_status,
+                                         uint8_t* inlier_out, double* quality, double* info, double* basis, uint32_t* status, double* w_out)
+{
+    if (!h) return SRK_E_ARGS;
+    try {
+        std::string why = srk_relate_check(n_pairs, row_ptr, uv_a, uv_b, q, K_a, K_b, shared_k, opts);
+        if (why.empty() && !refine) why = "pair: the refinement's options are NULL (srk_relate_frames is the call without)";
+        if (why.empty()) why = srk_pair_check_options(refine, true);
+        if (why.empty() && n_pairs > SRK_PAIR_MAX_PAIRS_HOST) why = "pair: too many pairs in one call";
+        if (why.empty() && (!std::isfinite(f0) || srk::is_close(0.0, f0))) why = "relate: f0 must be finite and not ~0";
+        if (why.empty() && n_pairs > 0 && (!R || !T || !E || !related || !related_status || !quality || !info || !basis || !status))
+            why = "pair: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_pairs == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        const RelateRefine rf = { refine, R, T, E, quality, info, basis, w_out, status };
+        return relate_run(h, f0, n_pairs, row_ptr, uv_a, uv_b, q, K_a, K_b, shared_k ? 1 : 0, srk_relate_effective_options(opts), nullptr, nullptr, nullptr,
+                          related, related_status, inlier_out, &rf);
+    } catch (const std::bad_alloc&) {
+        h->last_error = "pair: out of host memory";
         return SRK_E_NOMEM;
     }
 }

@@ -18,7 +18,8 @@ RELATE_STATUS_NAMES = {RELATE_FEW_POINTS: "FEW_POINTS", RELATE_NO_MODEL: "NO_MOD
 
 # R [n][3][3], T [n][3] (unit): x_b ~ R x_a + T; E [n][3][3] = [T]x R; related [n][8] (RMS truncated Sampson error in pixels,
 # weighted matches, inliers, winning hypothesis, hypotheses with a model, the winning sample's sixth-match error in pixels, inliers
-# in front of both cameras, their mean parallax in radians); status [n]; inliers [O] uint8 or None
+# in front of both cameras, their mean parallax in radians); status [n]; inliers [O] uint8 or None.  From relate_frames(..., refine=...)
+# R, T, E are the REFINED pose (the C call has one set of pose outputs); the five-point winner itself is what the call without refine returns
 RelateResult = namedtuple("RelateResult", "R T E related status inliers")
 
 # cam_R [2][3][3], cam_T [2][3] (frame 0 = (I, 0), |cam_T[1]| = 1), points [N][3], and the observations point-major as Scene takes
@@ -70,13 +71,27 @@ def _call_args(row_ptr, uv_a, uv_b, K_a, K_b, q, hypotheses, inlier_pixels, seed
     return n, max(int(rp.max()), 0), [C.c_int32(n), _d(rp), _d(a), _d(b), _d(w), _d(Ka), _d(Kb), C.c_int(int(shared_k)), C.byref(lo)], keep
 
 
-def relate_frames(ba, f0, row_ptr, uv_a, uv_b, K_a, K_b, q=None, hypotheses=256, inlier_pixels=2.0, seed=1, want_inliers=False):
+def relate_frames(ba, f0, row_ptr, uv_a, uv_b, K_a, K_b, q=None, hypotheses=256, inlier_pixels=2.0, seed=1, want_inliers=False, refine=None):
     """srk_relate_frames: pairs in CSR form (row_ptr [n + 1], uv_a, uv_b [O][2] pixels of the two images, q [O] information or None)
     and the intrinsics of the two cameras ([n][3][3] each, or one 3 x 3 each for all).  `hypotheses` samples per pair (1 .. 4096;
     ransac_hypotheses(share, p, sample_size=5) gives the count for an outlier ratio), inlier_pixels the truncation of the score and the
     inlier test, seed the sampler's.  Returns a RelateResult; with want_inliers its inliers [O] mark the matches within inlier_pixels
-    of the winner's epipolar geometry.  An uploaded scene of `ba` is left untouched."""
+    of the winner's epipolar geometry.  An uploaded scene of `ba` is left untouched.
+    refine: None, or a dict of the refinement's options (the keywords of pair.pair_options: attempts, rel_change, loss, delta,
+    inliers_only; and want_weights): srk_relate_frames_refined, which refines every related pose over all the pair's matches (or,
+    with inliers_only, the winner's inliers) without leaving the device, and returns (RelateResult, PairResult).  The RelateResult's
+    R, T, E are then the refined ones."""
     n, n_obs, args, _keep = _call_args(row_ptr, uv_a, uv_b, K_a, K_b, q, hypotheses, inlier_pixels, seed)
+    if refine is not None:
+        from .pair import PairResult, pair_options, pair_outputs
+        kw = dict(refine)
+        want_weights = bool(kw.pop("want_weights", False))
+        opts = pair_options(**kw)
+        po = pair_outputs(n, n_obs, want_weights)
+        related, status, inl = np.zeros((n, 8)), np.zeros(n, np.uint32), np.zeros(n_obs, np.uint8) if want_inliers else None
+        ba._raise(lib().srk_relate_frames_refined(C.c_void_p(ba._h), C.c_double(f0), *args, C.byref(opts), _d(po[0]), _d(po[1]), _d(po[2]), _d(related),
+                                                  _d(status), _d(inl), *[_d(a) for a in po[3:]]))
+        return RelateResult(po[0], po[1], po[2], related, status, inl), PairResult(*po)
     out = (np.zeros((n, 3, 3)), np.zeros((n, 3)), np.zeros((n, 3, 3)), np.zeros((n, 8)), np.zeros(n, np.uint32),
            np.zeros(n_obs, np.uint8) if want_inliers else None)
     ba._raise(lib().srk_relate_frames(C.c_void_p(ba._h), C.c_double(f0), *args, *[_d(a) for a in out]))
@@ -112,18 +127,22 @@ def host_pair(f0, uv_a, uv_b, K_a, K_b, q=None, hypotheses=256, inlier_pixels=2.
     return RelateResult(out[0], out[1], out[2], out[3], np.array([rc], np.uint32), out[4])
 
 
-def two_view_scene(ba, f0, uv_a, uv_b, K_a, K_b, q=None, hypotheses=256, inlier_pixels=2.0, seed=1, refine_attempts=10):
+def two_view_scene(ba, f0, uv_a, uv_b, K_a, K_b, q=None, hypotheses=256, inlier_pixels=2.0, seed=1, refine_attempts=10, refine=None):
     """The two-view bootstrap: relate the pair of images from its matches uv_a, uv_b [M][2], triangulate the inliers from (I, 0)
     and (R, T) (triangulate_tracks, refined), drop the tracks that lie behind a camera, and return a TwoViewScene: poses, points and
     point-major observations as Scene(points, cam_R, cam_T, K, shared_k, row_ptr, obs_frame, obs_uv) takes them, in the scale
     |T| = 1.  Raises ValueError when the pair was not related (TwoViewScene.relate.status would be non-zero).
+    refine (None, or the dict relate_frames takes): the pose is refined over the pair's matches before the inliers are triangulated
+    from it; TwoViewScene.relate then holds the refined R, T, E.
     To bundle-adjust the result, give Scene the intrinsics as K * f0 (the same cameras, K(2,2) = f0): with K / f0 the adjuster's pose
     derivatives are not those of the error and it moves the scene little or, with two different cameras, not
     at all."""
     a = np.ascontiguousarray(uv_a, dtype=np.float64).reshape(-1, 2)
     b = np.ascontiguousarray(uv_b, dtype=np.float64).reshape(-1, 2)
     rel = relate_frames(ba, f0, [0, a.shape[0]], a, b, np.reshape(K_a, (1, 9)), np.reshape(K_b, (1, 9)), q=q, hypotheses=hypotheses,
-                        inlier_pixels=inlier_pixels, seed=seed, want_inliers=True)
+                        inlier_pixels=inlier_pixels, seed=seed, want_inliers=True, refine=refine)
+    if refine is not None:
+        rel = rel[0]
     if rel.status[0]:
         raise ValueError(f"two_view_scene: the pair was not related ({', '.join(relate_status_names(rel.status[0]))})")
     match = np.flatnonzero(rel.inliers)
