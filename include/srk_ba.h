@@ -1215,6 +1215,81 @@ int srk_align_host_set(int64_t n_obs, const double* a, const double* b, const do
  * NULL (cam_R and cam_T together). */
 int srk_similarity_apply(double s, const double* R, const double* t, int64_t n_points, double* X, int64_t n_frames, double* cam_R, double* cam_T);
 
+/* ---- two-view homography: four-point hypotheses scored on the device (EXTENSION) ----
+ * The member of the family for planar scenes and for pure rotation, the two cases in which srk_relate_frames cannot answer: the
+ * homography p_b ~ G p_a between the 2D-2D matches of a pair of images, wrong matches among them.  Inputs as srk_relate_frames:
+ * pairs in CSR form, K_a, K_b [n_pairs][9] (or [9] with shared_k), f0; homogeneous pixels are p = (u, v, f0); everything works on
+ * the pair's n weighted matches (q > 0) numbered by rank in ascending o.  G is the pixel homography, returned with Frobenius norm 1
+ * and signed so that (G p_a)_3 > 0 for its inliers; H = K_b^-1 G K_a relates the rays x = K^-1 p.
+ *
+ * Gather, then hypothesis and score, then pick with local optimisation, as srk_align_points.  The sampler is the project's
+ * counter-based one on a stream of its own (four distinct ranks per hypothesis).  A hypothesis is closed form through the
+ * projective basis: on each side [p0 p1 p2] lambda = p3 by the adjugate, A = [lambda_k p_k], G = B adj(A); no model when three of
+ * the four points are collinear (a determinant below 1e-9 of the product of its columns' norms), the four (G p_ak)_3 differ in
+ * sign, |det G| <= 1e-12 at norm 1, or anything is not finite.  The score is MSAC, sum min(q s, tau^2), with s the symmetric transfer
+ * error in pixels squared, |pi(G p_a) - uv_b|^2 + |pi(G^-1 p_b) - uv_a|^2, pi(y) = f0 y_xy / y_3; a match behind either image counts
+ * tau^2 and is no inlier; the smallest score wins, an equal score goes to the smaller h.  Then up to refine_rounds Gauss-Newton steps
+ * on the symmetric transfer error of the current model's inliers, q-weighted, G <- G (I + sum d_k B_k) over a fixed basis of the eight
+ * traceless matrices, each accepted only when the score over all n gets strictly smaller: never worse than the winner.
+ *
+ * inlier_pixels (tau), default 6.0: with noise sigma per coordinate in both images each one-way distance carries both images'
+ * noise, so s is about 2 sigma^2 chi^2_4, and P(chi^2_4 > t) = e^(-t/2) (1 + t/2): at sigma = 1, tau = 6 gives t = 18 and cuts
+ * e^-9 (1 + 9) = 0.12 % of the true matches.
+ *
+ * The returned model is decomposed (Ma, Soatto, Kosecka, Sastry, algorithm 5.2): H over its middle singular value, signed so that
+ * sum q x_b^T H x_a > 0 over the inliers, then the two poses of the plane, H = R + (T/d) N^T, each R passed through the nearest
+ * rotation, N flipped so that at least half of the inliers have N^T x_a > 0.  Both are returned, the one with more inliers in front
+ * first (a tie: u_1); the library does not choose between the twins.  When w1 - w3 <= 1e-10 of the normalised H^T H (a rotation, or
+ * the plane at infinity) one candidate is returned: the rotation nearest to H, T/d = 0, N = 0.
+ *
+ * Outputs per pair: G [9]; H [9] normalised and signed; n_poses (0, 1 or 2); R [2][9], T [2][3] (= t/d), N [2][3], front [2] (the
+ * inliers with N^T x_a > 0), unused entries zero; homog [8] = { sqrt(score / n) in pixels, n, the inlier count, the winning h, the
+ * number of hypotheses with a model, the rounds accepted, w1 - w3, the RMS symmetric error of the inliers (0 when a model without an
+ * inlier wins, as a huge q or a tiny tau allows) }; status, a mask of
+ * SRK_HOMOGRAPHY_*: then G = H = I, n_poses = 0, homog[0], [3], [6], [7] are NaN and homog[2], [5] are 0.  inlier_out [O] (may be
+ * NULL): 1 iff q > 0 and q s < tau^2 at the returned model.  The library sets no threshold between this model and the essential
+ * matrix of srk_relate_frames: both deliver inlier counts and RMS figures to be compared by the caller.
+ *
+ * Host checks before any allocation or launch (SRK_E_ARGS with a text), as srk_relate_frames: a descending or negative row_ptr, uv
+ * or K not finite, q negative or not finite, a singular K, hypotheses outside 1..4096, inlier_pixels not finite or <= 0,
+ * refine_rounds outside 0..16, NULL outputs, and more than 2^22 waves (pairs x ceil(hypotheses / 64)) in one call.
+ * Absent: a robust loss in the rounds, an information matrix, a library choice between the twins or between E and H, an adaptive
+ * early stop, several ranks. */
+enum {
+    SRK_HOMOGRAPHY_FEW_POINTS = 1, /* fewer than four matches with q > 0 */
+    SRK_HOMOGRAPHY_NO_MODEL = 2    /* no sample gave a homography */
+};
+typedef struct srk_homography_options {
+    int32_t hypotheses;    /* samples per pair, 1 .. 4096; srk_ransac_hypotheses with a sample of 4 gives the count for an outlier ratio */
+    double inlier_pixels;  /* tau > 0 in pixels: the truncation of the score and the inlier test */
+    uint64_t seed;
+    int32_t refine_rounds; /* rounds of local optimisation, 0 .. 16 */
+} srk_homography_options;
+void srk_homography_default_options(srk_homography_options*); /* { 256, 6.0, 1, 4 } */
+int srk_relate_homography(srk_ba*, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a /* [O][2] */, const double* uv_b /* [O][2] */,
+                          const double* q /* [O], NULL = all 1 */, const double* K_a, const double* K_b, int shared_k, const srk_homography_options*,
+                          double* G /* [n][9] */, double* H /* [n][9] */, int32_t* n_poses /* [n] */, double* R /* [n][2][9] */,
+                          double* T /* [n][2][3] */, double* N /* [n][2][3] */, int32_t* front /* [n][2] */, double* homog /* [n][8] */,
+                          uint32_t* status /* [n] */, uint8_t* inlier_out /* [O] or NULL */);
+/* device ms of the last call on this handle (gather, hypotheses and scores, pick with its rounds and the decomposition) from an
+ * event pair; and of the hypothesis-and-score kernel alone, from a second pair */
+double srk_ba_homography_kernel_ms(const srk_ba*);
+double srk_ba_homography_score_ms(const srk_ba*);
+/* host only, no device and no handle needed: the checks of srk_relate_homography on their own (f0 and the outputs excepted).
+ * SRK_OK, or SRK_E_ARGS with *why (may be NULL) pointing at a static text. */
+int srk_homography_check_pairs(int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q, const double* K_a,
+                               const double* K_b, int shared_k, const srk_homography_options* opts, const char** why);
+/* host only: one pair of n_obs matches in the kernels' own order of operations (the same statements, compiled for the host).
+ * Returns the status bits, or SRK_E_ARGS (negative) when the checks refuse the pair. */
+int srk_homography_host_pair(int64_t n_obs, const double* uv_a, const double* uv_b, const double* q, const double* K_a, const double* K_b, double f0,
+                             const srk_homography_options* opts, double* G, double* H, int32_t* n_poses, double* R, double* T, double* N,
+                             int32_t* front, double* homog, uint8_t* inlier_out);
+/* host only: the decomposition on its own.  H_in [9] at any scale and sign, the rays x_a, x_b [n][3] of its inliers (q [n] or NULL
+ * = all 1).  H_out [9], R [2][9], T [2][3], N [2][3], front [2], *gap = w1 - w3.  Returns n_poses (1 or 2), or SRK_E_ARGS (a NULL
+ * argument, an H that is not finite or has no middle singular value) with nothing written. */
+int srk_homography_decompose(const double* H_in, int64_t n, const double* x_a, const double* x_b, const double* q, double* H_out, double* R, double* T,
+                             double* N, int32_t* front, double* gap);
+
 /* ---- marginal covariances of frames and landmarks (EXTENSION) ----
  * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
  * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior

@@ -727,6 +727,67 @@ public:
         return f;
     }
 
+    /// EXTENSION: the homography p_b ~ G p_a between the matches of pairs of images, wrong matches among them, on the device
+    /// (srk_relate_homography; DESIGN.md section 27: four-point hypotheses from a counter-based sampler, each scored on every match
+    /// by the symmetric transfer error, the winner refined by Gauss-Newton rounds on its inliers, then decomposed).  The member for
+    /// planar scenes and pure rotation, where RelateFrames cannot answer.  One result per pair.
+    struct PlanePose {
+        SE3Transform pose;  ///< R and T / d (the translation over the plane's distance from camera a)
+        Point3 normal;      ///< N in camera a; zero for a pure rotation
+        size_t in_front = 0; ///< the inliers with N^T x_a > 0
+    };
+    struct HomographyPair {
+        Matrix3 G{ 1, 0, 0, 0, 1, 0, 0, 0, 1 }; ///< pixels (u, v, f0), Frobenius norm 1; I when there is none
+        Matrix3 H{ 1, 0, 0, 0, 1, 0, 0, 0, 1 }; ///< K_b^-1 G K_a over its middle singular value
+        std::vector<PlanePose> poses;           ///< none, the rotation alone, or both poses of the plane: the library does not choose
+        Scalar rms_pixels = 0;                  ///< sqrt(score / matches) of the truncated score; NaN without a model
+        Scalar inlier_rms_pixels = 0;           ///< the RMS symmetric transfer error of the inliers
+        Scalar singular_gap = 0;                ///< w1 - w3 of the normalised H^T H; <= 1e-10: a rotation
+        size_t matches = 0, inlier_count = 0, hypotheses_with_model = 0, rounds = 0;
+        int64_t winner = -1;                    ///< the winning hypothesis, -1 without a model
+        uint32_t status = 0;                    ///< SRK_HOMOGRAPHY_* bits (0 = a model)
+        std::vector<uint8_t> inliers;           ///< per match, at the returned model (with want_inliers)
+    };
+    /// shared_Ka / shared_Kb for all pairs, or Kas / Kbs with one matrix per pair.  opts NULL: the defaults (256 hypotheses, 6 px,
+    /// seed 1, 4 rounds).  An uploaded scene is left untouched.  Throws std::invalid_argument for every refusal of the library.
+    std::vector<HomographyPair> RelateHomography(Scalar f0, const std::vector<std::vector<Match>>& pairs, const Matrix3* shared_Ka, const Matrix3* shared_Kb,
+                                                 const std::vector<Matrix3>* Kas, const std::vector<Matrix3>* Kbs,
+                                                 const srk_homography_options* opts = nullptr, bool want_inliers = false) {
+        PairArrays a(pairs, shared_Ka, shared_Kb, Kas, Kbs, false);
+        const size_t n = a.n, O = a.q.size() - 1;
+        std::vector<Scalar> G(9 * n + 1), H(9 * n + 1), R(18 * n + 1), T(6 * n + 1), N(6 * n + 1), hg(8 * n + 1);
+        std::vector<int32_t> poses(n + 1), front(2 * n + 1);
+        std::vector<uint8_t> inl(want_inliers ? O + 1 : 1);
+        int rc = srk_relate_homography(h_, f0, (int32_t)n, a.row_ptr.data(), a.ua.data(), a.ub.data(), a.q.data(), a.Ka.data(), a.Kb.data(), a.shared ? 1 : 0,
+                                       opts, G.data(), H.data(), poses.data(), R.data(), T.data(), N.data(), front.data(), hg.data(), a.st.data(),
+                                       want_inliers ? inl.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        std::vector<HomographyPair> out(n);
+        for (size_t i = 0; i < n; ++i) {
+            HomographyPair& p = out[i];
+            for (size_t e = 0; e < 9; ++e) p.G[e] = G[9 * i + e], p.H[e] = H[9 * i + e];
+            for (int32_t k = 0; k < poses[i]; ++k) {
+                PlanePose c;
+                for (size_t e = 0; e < 9; ++e) c.pose.R[e] = R[18 * i + 9 * k + e];
+                c.pose.T = Point3{ T[6 * i + 3 * k], T[6 * i + 3 * k + 1], T[6 * i + 3 * k + 2] };
+                c.normal = Point3{ N[6 * i + 3 * k], N[6 * i + 3 * k + 1], N[6 * i + 3 * k + 2] };
+                c.in_front = (size_t)front[2 * i + k];
+                p.poses.push_back(c);
+            }
+            p.rms_pixels = hg[8 * i];
+            p.matches = (size_t)hg[8 * i + 1];
+            p.inlier_count = (size_t)hg[8 * i + 2];
+            p.status = a.st[i];
+            p.winner = a.st[i] ? -1 : (int64_t)hg[8 * i + 3];
+            p.hypotheses_with_model = (size_t)hg[8 * i + 4];
+            p.rounds = (size_t)hg[8 * i + 5];
+            p.singular_gap = hg[8 * i + 6];
+            p.inlier_rms_pixels = hg[8 * i + 7];
+            if (want_inliers) p.inliers.assign(inl.begin() + a.row_ptr[i], inl.begin() + a.row_ptr[i + 1]);
+        }
+        return out;
+    }
+
     /// EXTENSION: the similarity b ~ s R a + t between sets of corresponding 3D points, wrong correspondences among them, on the
     /// device (srk_align_points / srk_ba_align; DESIGN.md section 25: three-point hypotheses from a counter-based sampler, each
     /// scored on every correspondence, the winner refined by a closed-form least-squares similarity on its inliers).  One result

@@ -20,5 +20,7 @@ from .pair import (refine_pairs, relative_pose_factor, pair_status_names, defaul
                    PAIR_FEW_POINTS, PAIR_DEGENERATE, PAIR_NOT_CONVERGED)
 from .align import (align_points, apply_similarity, align_status_names, default_align_options, AlignResult,  # noqa: F401
                     ALIGN_FEW_POINTS, ALIGN_NO_MODEL)
+from .homography import (relate_homography, apply_homography, decompose_homography, homography_status_names,  # noqa: F401
+                         default_homography_options, HomographyResult, HomographyPoses, HOMOGRAPHY_FEW_POINTS, HOMOGRAPHY_NO_MODEL)
 from .scene import (SceneSpec, generate_scene, config_scene, drop_observations, renumber_frames, loop_scene,  # noqa: F401
                     CONFIGS)

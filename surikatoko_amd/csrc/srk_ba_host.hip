@@ -22,6 +22,9 @@
 #include "srk_align.hpp"
 #include "srk_align_dev.hpp"
 #include "srk_align_math.hpp"
+#include "srk_homog.hpp"
+#include "srk_homog_dev.hpp"
+#include "srk_homog_math.hpp"
 #include "srk_locate.hpp"
 #include "srk_locate_dev.hpp"
 #include "srk_locate_math.hpp"
@@ -311,6 +314,12 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     DevBuf pr[PR_NBUF];
     hipEvent_t pr_ev[2]{}; // around the refinement's kernels, created at the first call
     double pr_ms = 0;      // their device time in the last call (srk_ba_pair_kernel_ms)
+    // two-view homography (srk_relate_homography): the pairs' matches and intrinsics, the gathered strip, the
+    // pairs' weighted counts, the waves' slots and the outputs, grown lazily
+    enum { HG_ROW, HG_UVA, HG_UVB, HG_Q, HG_KA, HG_KB, HG_STRIP, HG_COUNT, HG_SLOTS, HG_G, HG_H, HG_POSES, HG_R, HG_T, HG_N, HG_FRONT, HG_HOMOG, HG_STATUS, HG_INL, HG_NBUF };
+    DevBuf hg[HG_NBUF];
+    hipEvent_t hg_ev[4]{};           // the call, and the hypothesis-and-score kernel inside it; created at the first call
+    double hg_ms = 0, hg_score_ms = 0; // srk_ba_homography_kernel_ms, srk_ba_homography_score_ms
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -489,6 +498,9 @@ void srk_ba_destroy(srk_ba* h)
     for (DevBuf& b : h->rl) dev_free(b);
     for (DevBuf& b : h->al) dev_free(b);
     for (DevBuf& b : h->pr) dev_free(b);
+    for (DevBuf& b : h->hg) dev_free(b);
+    for (hipEvent_t& e : h->hg_ev)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->pr_ev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->al_ev)
@@ -3834,6 +3846,94 @@ extern "C" int srk_ba_align(srk_ba* h, int32_t n_sets, const int64_t* row_ptr, c
         return SRK_OK;
     } catch (const std::bad_alloc&) {
         h->last_error = "align: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+// ------------------------------------------------------------------ two-view homography
+// The checked pairs of a call to the device, gather / hypotheses and scores / pick with its rounds and the decomposition, the
+// results back.
+static int homog_run(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
+                     const double* K_a, const double* K_b, int shared_k, const srk_homography_options& lo, double* G, double* H, int32_t* n_poses,
+                     double* R, double* T, double* N, int32_t* front, double* homog, uint32_t* status, uint8_t* inlier_out)
+{
+    hipStream_t s = h->main_stream;
+    const int64_t O = row_ptr[n_pairs], n = n_pairs;
+    const int64_t waves = (lo.hypotheses + SRK_HOMOG_LANES - 1) / SRK_HOMOG_LANES;
+    DevBuf* l = h->hg;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &l[srk_ba::HG_ROW], row_ptr, (size_t)(8 * (n + 1)) }, { &l[srk_ba::HG_UVA], uv_a, (size_t)(16 * O) },
+        { &l[srk_ba::HG_UVB], uv_b, (size_t)(16 * O) },         { &l[srk_ba::HG_Q], q, q ? (size_t)(8 * O) : 0 },
+        { &l[srk_ba::HG_KA], K_a, (size_t)(72 * (shared_k ? 1 : n)) }, { &l[srk_ba::HG_KB], K_b, (size_t)(72 * (shared_k ? 1 : n)) },
+    };
+    for (auto& u : up) {
+        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+        if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    const bool want_inl = inlier_out && O > 0;
+    struct { int buf; size_t bytes; void* dst; } outs[] = {
+        { srk_ba::HG_G, (size_t)(72 * n), G },       { srk_ba::HG_H, (size_t)(72 * n), H },         { srk_ba::HG_POSES, (size_t)(4 * n), n_poses },
+        { srk_ba::HG_R, (size_t)(144 * n), R },      { srk_ba::HG_T, (size_t)(48 * n), T },         { srk_ba::HG_N, (size_t)(48 * n), N },
+        { srk_ba::HG_FRONT, (size_t)(8 * n), front }, { srk_ba::HG_HOMOG, (size_t)(64 * n), homog }, { srk_ba::HG_STATUS, (size_t)(4 * n), status },
+        { srk_ba::HG_INL, want_inl ? (size_t)O : 0, inlier_out },
+    };
+    if ((rc = dev_alloc(h, l[srk_ba::HG_STRIP], (size_t)(8 * SRK_HOMOG_STRIP * O))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::HG_COUNT], (size_t)(8 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::HG_SLOTS], (size_t)(8 * SRK_HOMOG_SLOT * n * waves))) != SRK_OK)
+        return rc;
+    for (auto& o : outs)
+        if ((rc = dev_alloc(h, l[o.buf], o.bytes)) != SRK_OK) return rc;
+    for (hipEvent_t& e : h->hg_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    const int64_t* d_row = P<int64_t>(l[srk_ba::HG_ROW]);
+    const double* d_uva = P<double>(l[srk_ba::HG_UVA]);
+    const double* d_uvb = P<double>(l[srk_ba::HG_UVB]);
+    const double* d_q = q ? P<double>(l[srk_ba::HG_Q]) : nullptr;
+    const double* d_strip = P<double>(l[srk_ba::HG_STRIP]);
+    const int64_t* d_count = P<int64_t>(l[srk_ba::HG_COUNT]);
+    HIPCHK(h, hipEventRecord(h->hg_ev[0], s));
+    srk_launch_homog_gather(s, n_pairs, d_row, d_uva, d_uvb, d_q, P<double>(l[srk_ba::HG_STRIP]), P<int64_t>(l[srk_ba::HG_COUNT]));
+    HIPCHK(h, hipEventRecord(h->hg_ev[1], s));
+    srk_launch_homog_score(s, n_pairs, lo.hypotheses, lo.seed, lo.inlier_pixels, f0, d_row, d_strip, d_count, P<double>(l[srk_ba::HG_SLOTS]));
+    HIPCHK(h, hipEventRecord(h->hg_ev[2], s));
+    srk_launch_homog_pick(s, n_pairs, lo.hypotheses, lo.inlier_pixels, f0, lo.refine_rounds, d_row, d_uva, d_uvb, d_q, d_strip, d_count,
+                          P<double>(l[srk_ba::HG_KA]), P<double>(l[srk_ba::HG_KB]), shared_k, P<double>(l[srk_ba::HG_SLOTS]), P<double>(l[srk_ba::HG_G]),
+                          P<double>(l[srk_ba::HG_H]), P<int32_t>(l[srk_ba::HG_POSES]), P<double>(l[srk_ba::HG_R]), P<double>(l[srk_ba::HG_T]),
+                          P<double>(l[srk_ba::HG_N]), P<int32_t>(l[srk_ba::HG_FRONT]), P<double>(l[srk_ba::HG_HOMOG]), P<uint32_t>(l[srk_ba::HG_STATUS]),
+                          want_inl ? P<uint8_t>(l[srk_ba::HG_INL]) : nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->hg_ev[3], s));
+    for (auto& o : outs)
+        if (o.bytes) HIPCHK(h, hipMemcpyAsync(o.dst, l[o.buf].p, o.bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    float ms = 0, score_ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->hg_ev[0], h->hg_ev[3]));
+    HIPCHK(h, hipEventElapsedTime(&score_ms, h->hg_ev[1], h->hg_ev[2]));
+    h->hg_ms = ms;
+    h->hg_score_ms = score_ms;
+    return SRK_OK;
+}
+
+extern "C" double srk_ba_homography_kernel_ms(const srk_ba* h) { return h ? h->hg_ms : 0.0; }
+extern "C" double srk_ba_homography_score_ms(const srk_ba* h) { return h ? h->hg_score_ms : 0.0; }
+
+extern "C" int srk_relate_homography(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
+                                     const double* K_a, const double* K_b, int shared_k, const srk_homography_options* opts, double* G, double* H,
+                                     int32_t* n_poses, double* R, double* T, double* N, int32_t* front, double* homog, uint32_t* status,
+                                     uint8_t* inlier_out)
+{
+    if (!h) return SRK_E_ARGS;
+    try {
+        std::string why = srk_homog_check(n_pairs, row_ptr, uv_a, uv_b, q, K_a, K_b, shared_k, opts);
+        if (why.empty() && (!std::isfinite(f0) || srk::is_close(0.0, f0))) why = "homography: f0 must be finite and not ~0";
+        if (why.empty() && n_pairs > 0 && (!G || !H || !n_poses || !R || !T || !N || !front || !homog || !status)) why = "homography: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_pairs == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        return homog_run(h, f0, n_pairs, row_ptr, uv_a, uv_b, q, K_a, K_b, shared_k ? 1 : 0, srk_homog_effective_options(opts), G, H, n_poses, R, T, N,
+                         front, homog, status, inlier_out);
+    } catch (const std::bad_alloc&) {
+        h->last_error = "homography: out of host memory";
         return SRK_E_NOMEM;
     }
 }

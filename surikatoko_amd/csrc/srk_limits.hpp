@@ -57,3 +57,9 @@
 #define SRK_ALIGN_LANES_HOST 64
 #define SRK_ALIGN_MAX_WAVES_HOST (1 << 22)
 #define SRK_ALIGN_MAX_ROUNDS_HOST 16
+// two-view homography (srk_relate_homography): a wave scores 64 hypotheses of one pair; a call holds one slot
+// of 128 bytes per wave, so pairs x ceil(hypotheses / 64) is capped like align's
+#define SRK_HOMOG_MAX_HYPOTHESES_HOST 4096
+#define SRK_HOMOG_LANES_HOST 64
+#define SRK_HOMOG_MAX_WAVES_HOST (1 << 22)
+#define SRK_HOMOG_MAX_ROUNDS_HOST 16
