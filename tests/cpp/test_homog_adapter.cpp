@@ -1,7 +1,8 @@
 // Runtime test of BundleAdjustmentKanatani::RelateHomography (include/suriko_amd/bundle-adj-kanatani.hpp): a planar pair with a
-// fifth of the targets wrong and a pure rotation give the C ABI's bits on the same handle, mark no wrong match an inlier, return
-// the plane's two poses with one of them the truth and the rotation alone; refusals of the library throw std::invalid_argument
-// with the check's text.
+// fifth of the targets wrong and a pure rotation, each pair seen through its own K_a and K_b (per-pair vectors), give the C ABI's
+// bits on the same handle, mark no wrong match an inlier, return the plane's two poses with one of them the truth and the rotation
+// alone; the shared form gives the bits of the call that repeats the two matrices per pair; refusals of the library throw
+// std::invalid_argument with the check's text, and mismatched intrinsics arguments throw.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -29,7 +30,14 @@ int main()
 {
     using BA = BundleAdjustmentKanatani;
     const double f0 = 600.0, c = std::cos(0.15), sn = std::sin(0.15);
-    const Matrix3 Ka{ 1.25, 0, 0.53, 0, 1.3, 0.4, 0, 0, 1 }, Kb{ 1.1, 0.01, 0.5, 0, 1.15, 0.42, 0, 0, 1 };
+    // every pair its own fx, fy, skew, u0 and v0 on either side: the adapter must hand each pair's own two matrices on
+    const std::vector<Matrix3> Kas{ Matrix3{ 1.25, 0, 0.53, 0, 1.3, 0.4, 0, 0, 1 }, Matrix3{ 1.12, -0.015, 0.61, 0, 1.41, 0.33, 0, 0, 1 } };
+    const std::vector<Matrix3> Kbs{ Matrix3{ 1.1, 0.01, 0.5, 0, 1.15, 0.42, 0, 0, 1 }, Matrix3{ 1.31, 0.02, 0.44, 0, 1.02, 0.49, 0, 0, 1 } };
+    for (int e : { 0, 1, 2, 4, 5 })
+        if (Kas[0][(size_t)e] == Kas[1][(size_t)e] || Kbs[0][(size_t)e] == Kbs[1][(size_t)e] || Kas[0][(size_t)e] == Kbs[0][(size_t)e] ||
+            Kas[1][(size_t)e] == Kbs[1][(size_t)e] || Kas[0][(size_t)e] == Kbs[1][(size_t)e] || Kas[1][(size_t)e] == Kbs[0][(size_t)e])
+            return 10;
+    const Matrix3 &Ka = Kas[0], &Kb = Kbs[0];
     const Matrix3 Rt{ c, 0, sn, 0, 1, 0, -sn, 0, c };
     const double Tt[2][3] = { { 0.6, -0.2, 0.3 }, { 0, 0, 0 } };
     const double nn = std::sqrt(0.2 * 0.2 + 0.1 * 0.1 + 1.0), Nt[3] = { -0.2 / nn, 0.1 / nn, 1.0 / nn }, d = 6.0 / nn;
@@ -42,8 +50,8 @@ int main()
             if (p == 0) X[2] = 6 + 0.2 * X[0] - 0.1 * X[1];
             for (int r = 0; r < 3; ++r) Y[r] = Rt[3 * r] * X[0] + Rt[3 * r + 1] * X[1] + Rt[3 * r + 2] * X[2] + Tt[p][r];
             BA::Match m;
-            m.a = pixel(Ka, X, f0);
-            m.b = pixel(Kb, Y, f0);
+            m.a = pixel(Kas[(size_t)p], X, f0);
+            m.b = pixel(Kbs[(size_t)p], Y, f0);
             if (i % 5 == p) m.b.y += 40.0; // a wrong match
             pairs[(size_t)p].push_back(m);
         }
@@ -53,12 +61,12 @@ int main()
     lo.hypotheses = 128;
     lo.inlier_pixels = 0.01;
     BA ba;
-    const std::vector<BA::HomographyPair> res = ba.RelateHomography(f0, pairs, &Ka, &Kb, nullptr, nullptr, &lo, true);
+    const std::vector<BA::HomographyPair> res = ba.RelateHomography(f0, pairs, nullptr, nullptr, &Kas, &Kbs, &lo, true);
     if (res.size() != 2) return 12;
 
     // the C ABI on the same handle: the same bits
     std::vector<int64_t> rp{ 0 };
-    std::vector<double> ua, ub, q, G(18), H(18), R(36), T(12), N(12), hg(16);
+    std::vector<double> ua, ub, q, cKa, cKb, G(18), H(18), R(36), T(12), N(12), hg(16);
     std::vector<int32_t> poses(2), front(4);
     std::vector<uint32_t> st(2);
     for (int p = 0; p < 2; ++p) {
@@ -68,9 +76,11 @@ int main()
             q.push_back(m.information);
         }
         rp.push_back((int64_t)q.size());
+        cKa.insert(cKa.end(), Kas[(size_t)p].begin(), Kas[(size_t)p].end());
+        cKb.insert(cKb.end(), Kbs[(size_t)p].begin(), Kbs[(size_t)p].end());
     }
     std::vector<uint8_t> ci(q.size());
-    if (srk_relate_homography(ba.Handle(), f0, 2, rp.data(), ua.data(), ub.data(), q.data(), Ka.data(), Kb.data(), 1, &lo, G.data(), H.data(), poses.data(),
+    if (srk_relate_homography(ba.Handle(), f0, 2, rp.data(), ua.data(), ub.data(), q.data(), cKa.data(), cKb.data(), 0, &lo, G.data(), H.data(), poses.data(),
                               R.data(), T.data(), N.data(), front.data(), hg.data(), st.data(), ci.data()) != 0)
         return 13;
     for (int p = 0; p < 2; ++p) {
@@ -109,6 +119,32 @@ int main()
     for (size_t e = 0; e < 9; ++e) dr = std::fmax(dr, std::fabs(res[1].poses[0].pose.R[e] - Rt[e]));
     std::printf("rotation: |R - R_true| %.3e, gap %.3e\n", dr, res[1].singular_gap);
     if (dr > 1e-9 || res[1].poses[0].pose.T.x != 0 || res[1].poses[0].normal.z != 0) return 23;
+
+    // shared intrinsics (K_a != K_b): the bits of the call that repeats the two matrices per pair.  The pairs carry distinct K, so
+    // pair 0 of that call is pair 0 above, and pair 1 keeps its G (which lives in pixels) and gets another H = K_b^-1 G K_a
+    const std::vector<Matrix3> Ka0(2, Ka), Kb0(2, Kb);
+    const std::vector<BA::HomographyPair> sh = ba.RelateHomography(f0, pairs, &Ka, &Kb, nullptr, nullptr, &lo, true);
+    const std::vector<BA::HomographyPair> rep = ba.RelateHomography(f0, pairs, nullptr, nullptr, &Ka0, &Kb0, &lo, true);
+    if (sh.size() != 2 || rep.size() != 2) return 30;
+    for (int p = 0; p < 2; ++p) {
+        const BA::HomographyPair &s = sh[(size_t)p], &r = rep[(size_t)p];
+        if (std::memcmp(s.G.data(), r.G.data(), 72) || std::memcmp(s.H.data(), r.H.data(), 72) || s.poses.size() != r.poses.size() ||
+            std::memcmp(&s.rms_pixels, &r.rms_pixels, 8) || std::memcmp(&s.singular_gap, &r.singular_gap, 8) || s.winner != r.winner ||
+            s.inlier_count != r.inlier_count || s.status != r.status || s.inliers != r.inliers)
+            return 31;
+        for (size_t k = 0; k < s.poses.size(); ++k)
+            if (std::memcmp(s.poses[k].pose.R.data(), r.poses[k].pose.R.data(), 72) || std::memcmp(&s.poses[k].pose.T, &r.poses[k].pose.T, sizeof(Point3)) ||
+                std::memcmp(&s.poses[k].normal, &r.poses[k].normal, sizeof(Point3)) || s.poses[k].in_front != r.poses[k].in_front)
+                return 32;
+    }
+    if (std::memcmp(sh[0].G.data(), res[0].G.data(), 72) || std::memcmp(sh[0].H.data(), res[0].H.data(), 72) || sh[0].poses.size() != 2 ||
+        std::memcmp(sh[0].poses[0].pose.R.data(), res[0].poses[0].pose.R.data(), 72))
+        return 33;
+    if (std::memcmp(sh[1].G.data(), res[1].G.data(), 72) || std::memcmp(sh[1].H.data(), res[1].H.data(), 72) == 0) return 34;
+    std::vector<Matrix3> one(1, Ka);
+    if (!throws_invalid([&] { ba.RelateHomography(f0, pairs, nullptr, nullptr, &one, &Kbs, &lo); })) return 35;     // one K_a for two pairs
+    if (!throws_invalid([&] { ba.RelateHomography(f0, pairs, &Ka, nullptr, nullptr, &Kbs, &lo); })) return 36;      // shared and separate mixed
+    if (!throws_invalid([&] { ba.RelateHomography(f0, pairs, nullptr, nullptr, nullptr, nullptr, &lo); })) return 37; // no intrinsics
 
     // refusals of the library carry the check's text
     srk_homography_options bad = lo;
