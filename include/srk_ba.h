@@ -1290,6 +1290,71 @@ int srk_homography_host_pair(int64_t n_obs, const double* uv_a, const double* uv
 int srk_homography_decompose(const double* H_in, int64_t n, const double* x_a, const double* x_b, const double* q, double* H_out, double* R, double* T,
                              double* N, int32_t* front, double* gap);
 
+/* ---- two-view fundamental matrix: seven-point hypotheses scored on the device (EXTENSION) ----
+ * The member of the family that needs no intrinsics: the fundamental matrix p_b^T F p_a = 0 between the 2D-2D matches of a pair of
+ * images, wrong matches among them -- geometric verification of matches when K is a guess (an EXIF focal length, an unordered image
+ * set).  Inputs as srk_relate_frames without K_a, K_b, shared_k: pairs in CSR form, f0; homogeneous pixels are p = (u, v, f0) and
+ * the solver works on p / f0; everything works on the pair's n weighted matches (q > 0) numbered by rank in ascending o.  The F
+ * returned has Frobenius norm 1, rank exactly 2 by construction, F = U diag(1, sigma, 0) V^T / sqrt(1 + sigma^2) with proper
+ * rotations U, V and 0 <= sigma <= 1, and is signed so that its entry of largest magnitude is positive (a tie: the first row by
+ * row).  The epipoles are the third columns: F v_3 = 0, F^T u_3 = 0, homogeneous in (u, v, f0).
+ *
+ * Gather, solve, score, then pick with local optimisation.  The sampler is the project's counter-based one on a stream of its own
+ * (eight distinct ranks per hypothesis).  Picks 0-6 give the 7 x 9 matrix of rows p_b (x) p_a; its null space F1, F2 by Gauss-Jordan
+ * elimination with complete pivoting (a last pivot at most 1e-12 of the first: the rows are dependent, no model -- seven points of
+ * a plane, a pure rotation: srk_relate_homography's cases); the cubic det(F1 + z F2), its real roots by the derivative chain; pick 7
+ * chooses the root with the smallest Sampson error (an equal error: the smaller root).  The score is relate's: MSAC,
+ * sum min(q s, tau^2), s the squared Sampson distance in pixels; the smallest score wins, an equal score goes to the smaller h.
+ * The winner is brought into the representation above (the smallest singular value dropped), and that model is the current one.
+ * Then up to refine_rounds Levenberg-Marquardt attempts on the Sampson error of the current model's inliers, q-weighted, over
+ * d = [a; b; delta]: U <- U Exp(a), V <- V Exp(b), sigma <- sigma + delta, exact Jacobian, (H + c diag H) d = -g with c from 1e-4,
+ * the candidate re-scored over all n matches and accepted iff its score is strictly smaller (c /= 10, else c *= 10).  The loop ends
+ * after refine_rounds attempts, with fewer than eight inliers, with sums that are not finite, or after the first attempt whose
+ * candidate score differs from the current one by at most 1e-9 of it.
+ *
+ * Outputs per pair: F [9]; U [9], V [9], sigma; fund [12] = { sqrt(score / n) in pixels, n, the inlier count, the winning h, the
+ * hypotheses with a model, the eighth-match Sampson error in pixels, attempts accepted, attempts used, the inliers' RMS Sampson
+ * distance, sigma, cond_1 of the Jacobi-scaled H at the result (NaN when it is not positive definite; sigma = 1, an essential
+ * matrix, makes the rotations of U and V about their third axes one direction, and cond_1 reports it: the library sets no
+ * threshold), the number of real roots of the winning sample }; info [49] = the undamped H = sum q J^T J over the inliers at the
+ * result with r in pixels, row-major in the order [a; b; delta]: with pixel noise sigma_px the covariance of d is about
+ * sigma_px^2 H^-1; status, a mask of SRK_FUNDAMENTAL_*: then F = 0, U = V = I, sigma = 0, info = 0, fund[0], [3], [5], [8], [10]
+ * are NaN and the counts are 0.  inlier_out [O] (may be NULL): 1 iff q > 0 and q s < tau^2 at the returned model.
+ *
+ * Host checks before any allocation or launch (SRK_E_ARGS with a text), relate's minus K: a descending or negative row_ptr, uv not
+ * finite, q negative or not finite, hypotheses outside 1..4096, inlier_pixels not finite or <= 0, refine_rounds outside 0..16, NULL
+ * outputs, and more than 2^22 waves (pairs x ceil(hypotheses / 64)) in one call.
+ * Absent: a robust loss in the attempts, a stand-alone refinement from a given start, focal lengths from F, a library choice
+ * between F, E and H, an adaptive early stop, several ranks. */
+enum {
+    SRK_FUNDAMENTAL_FEW_POINTS = 1, /* fewer than eight matches with q > 0 */
+    SRK_FUNDAMENTAL_NO_MODEL = 2    /* no sample gave a fundamental matrix */
+};
+typedef struct srk_fundamental_options {
+    int32_t hypotheses;    /* samples per pair, 1 .. 4096; srk_ransac_hypotheses with a sample of 7 gives the count for an outlier ratio */
+    double inlier_pixels;  /* tau > 0 in pixels: the truncation of the score and the inlier test */
+    uint64_t seed;
+    int32_t refine_rounds; /* Levenberg-Marquardt attempts, 0 .. 16 */
+} srk_fundamental_options;
+void srk_fundamental_default_options(srk_fundamental_options*); /* { 256, 2.0, 1, 8 } */
+int srk_relate_uncalibrated(srk_ba*, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a /* [O][2] */, const double* uv_b /* [O][2] */,
+                            const double* q /* [O], NULL = all 1 */, const srk_fundamental_options*, double* F /* [n][9] */, double* U /* [n][9] */,
+                            double* V /* [n][9] */, double* sigma /* [n] */, double* fund /* [n][12] */, double* info /* [n][49] */,
+                            uint32_t* status /* [n] */, uint8_t* inlier_out /* [O] or NULL */);
+/* device ms of the last call on this handle (gather, solve, score, pick with its attempts) from an event pair; of the score
+ * kernel alone, from a second pair; and of the solve kernel alone, from a third */
+double srk_ba_fundamental_kernel_ms(const srk_ba*);
+double srk_ba_fundamental_score_ms(const srk_ba*);
+double srk_ba_fundamental_solve_ms(const srk_ba*);
+/* host only, no device and no handle needed: the checks of srk_relate_uncalibrated on their own (f0 and the outputs excepted).
+ * SRK_OK, or SRK_E_ARGS with *why (may be NULL) pointing at a static text. */
+int srk_fundamental_check_pairs(int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
+                                const srk_fundamental_options* opts, const char** why);
+/* host only: one pair of n_obs matches in the kernels' own order of operations (the same statements, compiled for the host).
+ * Returns the status bits, or SRK_E_ARGS (negative) when the checks refuse the pair. */
+int srk_fundamental_host_pair(int64_t n_obs, const double* uv_a, const double* uv_b, const double* q, double f0, const srk_fundamental_options* opts,
+                              double* F, double* U, double* V, double* sigma, double* fund, double* info, uint8_t* inlier_out);
+
 /* ---- marginal covariances of frames and landmarks (EXTENSION) ----
  * "How well is frame 37 determined?", "how good is this landmark?": the diagonal blocks of the covariance of the estimate, for
  * gating a loop closure, choosing keyframes to marginalise, weighting the map in a later stage or a chi-square test of a prior

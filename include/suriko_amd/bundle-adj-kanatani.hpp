@@ -788,6 +788,73 @@ public:
         return out;
     }
 
+    /// EXTENSION: the fundamental matrix p_b^T F p_a = 0 between the matches of pairs of images, wrong matches among them, on the
+    /// device and without intrinsics (srk_relate_uncalibrated; DESIGN.md section 28: seven-point hypotheses from a counter-based
+    /// sampler, each scored on every match by its Sampson distance, the winner refined by Levenberg-Marquardt attempts over
+    /// F = U diag(1, sigma, 0) V^T).  The member for cameras whose K is a guess.  One result per pair.
+    struct UncalibratedPair {
+        Matrix3 F{};                          ///< pixels (u, v, f0), Frobenius norm 1, rank 2, its largest entry positive; zero without a model
+        Matrix3 U{ 1, 0, 0, 0, 1, 0, 0, 0, 1 }; ///< proper rotations with F = U diag(1, sigma, 0) V^T / sqrt(1 + sigma^2)
+        Matrix3 V{ 1, 0, 0, 0, 1, 0, 0, 0, 1 };
+        Scalar sigma = 0;
+        Point3 epipole_a, epipole_b;          ///< the third columns of V and U, homogeneous in (u, v, f0): F e_a = 0, F^T e_b = 0
+        std::array<Scalar, 49> information{}; ///< sum q J^T J over the inliers in the order [a; b; delta], pixels^-2
+        Scalar rms_pixels = 0;                ///< sqrt(score / matches) of the truncated score; NaN without a model
+        Scalar inlier_rms_pixels = 0;         ///< the RMS Sampson distance of the inliers
+        Scalar eighth_match_pixels = 0;       ///< the winning sample's eighth-match Sampson error
+        Scalar condition = 0;                 ///< cond_1 of the Jacobi-scaled information; NaN when it is not positive definite
+        size_t matches = 0, inlier_count = 0, hypotheses_with_model = 0, attempts_accepted = 0, attempts_used = 0, real_roots = 0;
+        int64_t winner = -1;                  ///< the winning hypothesis, -1 without a model
+        uint32_t status = 0;                  ///< SRK_FUNDAMENTAL_* bits (0 = a model)
+        std::vector<uint8_t> inliers;         ///< per match, at the returned model (with want_inliers)
+    };
+    /// opts NULL: the defaults (256 hypotheses, 2 px, seed 1, 8 attempts).  An uploaded scene is left untouched.  Throws
+    /// std::invalid_argument for every refusal of the library.
+    std::vector<UncalibratedPair> RelateUncalibrated(Scalar f0, const std::vector<std::vector<Match>>& pairs, const srk_fundamental_options* opts = nullptr,
+                                                     bool want_inliers = false) {
+        std::vector<int64_t> row_ptr{ 0 };
+        std::vector<Scalar> ua, ub, q;
+        for (const std::vector<Match>& p : pairs) {
+            for (const Match& m : p) {
+                ua.insert(ua.end(), { m.a.x, m.a.y });
+                ub.insert(ub.end(), { m.b.x, m.b.y });
+                q.push_back(m.information);
+            }
+            row_ptr.push_back((int64_t)q.size());
+        }
+        const size_t n = pairs.size(), O = q.size();
+        for (std::vector<Scalar>* v : { &ua, &ub, &q }) v->push_back(0); // never read: keep data() valid without matches or pairs
+        std::vector<Scalar> F(9 * n + 1), U(9 * n + 1), V(9 * n + 1), sg(n + 1), fd(12 * n + 1), info(49 * n + 1);
+        std::vector<uint32_t> st(n + 1);
+        std::vector<uint8_t> inl(want_inliers ? O + 1 : 1);
+        int rc = srk_relate_uncalibrated(h_, f0, (int32_t)n, row_ptr.data(), ua.data(), ub.data(), q.data(), opts, F.data(), U.data(), V.data(), sg.data(),
+                                         fd.data(), info.data(), st.data(), want_inliers ? inl.data() : nullptr);
+        if (rc < 0) Raise(rc);
+        std::vector<UncalibratedPair> out(n);
+        for (size_t i = 0; i < n; ++i) {
+            UncalibratedPair& p = out[i];
+            for (size_t e = 0; e < 9; ++e) p.F[e] = F[9 * i + e], p.U[e] = U[9 * i + e], p.V[e] = V[9 * i + e];
+            for (size_t e = 0; e < 49; ++e) p.information[e] = info[49 * i + e];
+            p.sigma = sg[i];
+            p.epipole_a = Point3{ p.V[2], p.V[5], p.V[8] };
+            p.epipole_b = Point3{ p.U[2], p.U[5], p.U[8] };
+            p.rms_pixels = fd[12 * i];
+            p.matches = (size_t)fd[12 * i + 1];
+            p.inlier_count = (size_t)fd[12 * i + 2];
+            p.status = st[i];
+            p.winner = st[i] ? -1 : (int64_t)fd[12 * i + 3];
+            p.hypotheses_with_model = (size_t)fd[12 * i + 4];
+            p.eighth_match_pixels = fd[12 * i + 5];
+            p.attempts_accepted = (size_t)fd[12 * i + 6];
+            p.attempts_used = (size_t)fd[12 * i + 7];
+            p.inlier_rms_pixels = fd[12 * i + 8];
+            p.condition = fd[12 * i + 10];
+            p.real_roots = (size_t)fd[12 * i + 11];
+            if (want_inliers) p.inliers.assign(inl.begin() + row_ptr[i], inl.begin() + row_ptr[i + 1]);
+        }
+        return out;
+    }
+
     /// EXTENSION: the similarity b ~ s R a + t between sets of corresponding 3D points, wrong correspondences among them, on the
     /// device (srk_align_points / srk_ba_align; DESIGN.md section 25: three-point hypotheses from a counter-based sampler, each
     /// scored on every correspondence, the winner refined by a closed-form least-squares similarity on its inliers).  One result

@@ -22,5 +22,7 @@ from .align import (align_points, apply_similarity, align_status_names, default_
                     ALIGN_FEW_POINTS, ALIGN_NO_MODEL)
 from .homography import (relate_homography, apply_homography, decompose_homography, homography_status_names,  # noqa: F401
                          default_homography_options, HomographyResult, HomographyPoses, HOMOGRAPHY_FEW_POINTS, HOMOGRAPHY_NO_MODEL)
+from .fundamental import (relate_uncalibrated, epipolar_lines, pose_from_fundamental, fundamental_status_names,  # noqa: F401
+                          default_fundamental_options, FundamentalResult, FUNDAMENTAL_FEW_POINTS, FUNDAMENTAL_NO_MODEL)
 from .scene import (SceneSpec, generate_scene, config_scene, drop_observations, renumber_frames, loop_scene,  # noqa: F401
                     CONFIGS)

@@ -96,6 +96,10 @@ class HomographyOptions(C.Structure):
     _fields_ = [("hypotheses", C.c_int32), ("inlier_pixels", C.c_double), ("seed", C.c_uint64), ("refine_rounds", C.c_int32)]
 
 
+class FundamentalOptions(C.Structure):
+    _fields_ = [("hypotheses", C.c_int32), ("inlier_pixels", C.c_double), ("seed", C.c_uint64), ("refine_rounds", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 # every symbol include/srk_ba.h declares (checked by tests/test_abi.py)
@@ -128,6 +132,9 @@ EXPORTS = [
     "srk_align_host_set", "srk_similarity_apply",
     "srk_homography_default_options", "srk_relate_homography", "srk_ba_homography_kernel_ms", "srk_ba_homography_score_ms",
     "srk_homography_check_pairs", "srk_homography_host_pair", "srk_homography_decompose",
+    "srk_fundamental_default_options", "srk_relate_uncalibrated", "srk_ba_fundamental_kernel_ms", "srk_ba_fundamental_score_ms",
+    "srk_ba_fundamental_solve_ms",
+    "srk_fundamental_check_pairs", "srk_fundamental_host_pair",
     "srk_ba_phase_covariance", "srk_ba_covariances", "srk_ba_revert_covariances", "srk_ba_set_covariance_batch",
     "srk_ba_phase_cross_covariance", "srk_ba_cross_covariances", "srk_ba_revert_cross_covariances", "srk_ba_relative_pose_covariances",
     "srk_ba_normalize_scene", "srk_ba_revert_normalization", "srk_ba_check_world_is_normalized",
@@ -298,6 +305,19 @@ def lib():
     L.srk_ba_homography_kernel_ms.restype = C.c_double
     L.srk_ba_homography_score_ms.argtypes = [C.c_void_p]
     L.srk_ba_homography_score_ms.restype = C.c_double
+    # n_pairs, row_ptr, uv_a, uv_b, q, options
+    _fpairs = [C.c_int32] + [C.c_void_p] * 4 + [C.POINTER(FundamentalOptions)]
+    L.srk_fundamental_default_options.argtypes = [C.POINTER(FundamentalOptions)]
+    L.srk_fundamental_default_options.restype = None
+    L.srk_relate_uncalibrated.argtypes = [C.c_void_p, C.c_double] + _fpairs + [C.c_void_p] * 8
+    L.srk_fundamental_check_pairs.argtypes = _fpairs + [C.POINTER(C.c_char_p)]
+    L.srk_fundamental_host_pair.argtypes = [C.c_int64] + [C.c_void_p] * 3 + [C.c_double, C.POINTER(FundamentalOptions)] + [C.c_void_p] * 7
+    L.srk_ba_fundamental_kernel_ms.argtypes = [C.c_void_p]
+    L.srk_ba_fundamental_kernel_ms.restype = C.c_double
+    L.srk_ba_fundamental_score_ms.argtypes = [C.c_void_p]
+    L.srk_ba_fundamental_score_ms.restype = C.c_double
+    L.srk_ba_fundamental_solve_ms.argtypes = [C.c_void_p]
+    L.srk_ba_fundamental_solve_ms.restype = C.c_double
     L.srk_ransac_hypotheses.argtypes = [C.c_int, C.c_double, C.c_double]
     L.srk_ransac_hypotheses.restype = C.c_int64
     L.srk_ba_phase_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

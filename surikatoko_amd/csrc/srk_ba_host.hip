@@ -25,6 +25,9 @@
 #include "srk_homog.hpp"
 #include "srk_homog_dev.hpp"
 #include "srk_homog_math.hpp"
+#include "srk_fund.hpp"
+#include "srk_fund_dev.hpp"
+#include "srk_fund_math.hpp"
 #include "srk_locate.hpp"
 #include "srk_locate_dev.hpp"
 #include "srk_locate_math.hpp"
@@ -320,6 +323,12 @@ struct srk_ba : SrkPlanKept { // (the base: what the last upload's plan decided,
     DevBuf hg[HG_NBUF];
     hipEvent_t hg_ev[4]{};           // the call, and the hypothesis-and-score kernel inside it; created at the first call
     double hg_ms = 0, hg_score_ms = 0; // srk_ba_homography_kernel_ms, srk_ba_homography_score_ms
+    // two-view fundamental matrix (srk_relate_uncalibrated): the pairs' matches, the gathered strip, the pairs'
+    // weighted counts, the hypotheses' records, the waves' slots and the outputs, grown lazily
+    enum { FD_ROW, FD_UVA, FD_UVB, FD_Q, FD_STRIP, FD_COUNT, FD_HYP, FD_SLOTS, FD_F, FD_U, FD_V, FD_SIGMA, FD_FUND, FD_INFO, FD_STATUS, FD_INL, FD_NBUF };
+    DevBuf fd[FD_NBUF];
+    hipEvent_t fd_ev[5]{};           // the call, the score kernel and the solve kernel inside it; created at the first call
+    double fd_ms = 0, fd_score_ms = 0, fd_solve_ms = 0; // srk_ba_fundamental_kernel_ms, _score_ms, _solve_ms
 };
 
 // librccl.so is opened on first use: the library itself carries no link-time dependency on it (a single-GPU caller
@@ -500,6 +509,9 @@ void srk_ba_destroy(srk_ba* h)
     for (DevBuf& b : h->pr) dev_free(b);
     for (DevBuf& b : h->hg) dev_free(b);
     for (hipEvent_t& e : h->hg_ev)
+        if (e) hipEventDestroy(e);
+    for (DevBuf& b : h->fd) dev_free(b);
+    for (hipEvent_t& e : h->fd_ev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t& e : h->pr_ev)
         if (e) hipEventDestroy(e);
@@ -3934,6 +3946,94 @@ extern "C" int srk_relate_homography(srk_ba* h, double f0, int32_t n_pairs, cons
                          front, homog, status, inlier_out);
     } catch (const std::bad_alloc&) {
         h->last_error = "homography: out of host memory";
+        return SRK_E_NOMEM;
+    }
+}
+
+// ------------------------------------------------------------------ two-view fundamental matrix
+// The checked pairs of a call to the device, gather / solve / score / pick with its attempts, the results back.
+static int fund_run(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
+                    const srk_fundamental_options& lo, double* F, double* U, double* V, double* sigma, double* fund, double* info, uint32_t* status,
+                    uint8_t* inlier_out)
+{
+    hipStream_t s = h->main_stream;
+    const int64_t O = row_ptr[n_pairs], n = n_pairs;
+    const int64_t waves = (lo.hypotheses + SRK_FUND_LANES - 1) / SRK_FUND_LANES;
+    DevBuf* l = h->fd;
+    int rc;
+    struct { DevBuf* b; const void* src; size_t bytes; } up[] = {
+        { &l[srk_ba::FD_ROW], row_ptr, (size_t)(8 * (n + 1)) }, { &l[srk_ba::FD_UVA], uv_a, (size_t)(16 * O) },
+        { &l[srk_ba::FD_UVB], uv_b, (size_t)(16 * O) },         { &l[srk_ba::FD_Q], q, q ? (size_t)(8 * O) : 0 },
+    };
+    for (auto& u : up) {
+        if ((rc = dev_alloc(h, *u.b, u.bytes)) != SRK_OK) return rc;
+        if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    const bool want_inl = inlier_out && O > 0;
+    struct { int buf; size_t bytes; void* dst; } outs[] = {
+        { srk_ba::FD_F, (size_t)(72 * n), F },        { srk_ba::FD_U, (size_t)(72 * n), U },        { srk_ba::FD_V, (size_t)(72 * n), V },
+        { srk_ba::FD_SIGMA, (size_t)(8 * n), sigma }, { srk_ba::FD_FUND, (size_t)(96 * n), fund },  { srk_ba::FD_INFO, (size_t)(392 * n), info },
+        { srk_ba::FD_STATUS, (size_t)(4 * n), status }, { srk_ba::FD_INL, want_inl ? (size_t)O : 0, inlier_out },
+    };
+    if ((rc = dev_alloc(h, l[srk_ba::FD_STRIP], (size_t)(8 * SRK_FUND_STRIP * O))) != SRK_OK || (rc = dev_alloc(h, l[srk_ba::FD_COUNT], (size_t)(8 * n))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::FD_HYP], (size_t)(8 * SRK_FUND_HYP * n * lo.hypotheses))) != SRK_OK ||
+        (rc = dev_alloc(h, l[srk_ba::FD_SLOTS], (size_t)(8 * SRK_FUND_SLOT * n * waves))) != SRK_OK)
+        return rc;
+    for (auto& o : outs)
+        if ((rc = dev_alloc(h, l[o.buf], o.bytes)) != SRK_OK) return rc;
+    for (hipEvent_t& e : h->fd_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    const int64_t* d_row = P<int64_t>(l[srk_ba::FD_ROW]);
+    const double* d_uva = P<double>(l[srk_ba::FD_UVA]);
+    const double* d_uvb = P<double>(l[srk_ba::FD_UVB]);
+    const double* d_q = q ? P<double>(l[srk_ba::FD_Q]) : nullptr;
+    const double* d_strip = P<double>(l[srk_ba::FD_STRIP]);
+    const int64_t* d_count = P<int64_t>(l[srk_ba::FD_COUNT]);
+    HIPCHK(h, hipEventRecord(h->fd_ev[0], s));
+    srk_launch_fund_gather(s, n_pairs, d_row, d_uva, d_uvb, d_q, P<double>(l[srk_ba::FD_STRIP]), P<int64_t>(l[srk_ba::FD_COUNT]));
+    HIPCHK(h, hipEventRecord(h->fd_ev[4], s));
+    srk_launch_fund_solve(s, n_pairs, lo.hypotheses, lo.seed, f0, d_row, d_strip, d_count, P<double>(l[srk_ba::FD_HYP]));
+    HIPCHK(h, hipEventRecord(h->fd_ev[1], s));
+    srk_launch_fund_score(s, n_pairs, lo.hypotheses, lo.inlier_pixels, f0, d_row, d_strip, d_count, P<double>(l[srk_ba::FD_HYP]), P<double>(l[srk_ba::FD_SLOTS]));
+    HIPCHK(h, hipEventRecord(h->fd_ev[2], s));
+    srk_launch_fund_pick(s, n_pairs, lo.hypotheses, lo.inlier_pixels, f0, lo.refine_rounds, d_row, d_uva, d_uvb, d_q, d_strip, d_count,
+                         P<double>(l[srk_ba::FD_HYP]), P<double>(l[srk_ba::FD_SLOTS]), P<double>(l[srk_ba::FD_F]), P<double>(l[srk_ba::FD_U]),
+                         P<double>(l[srk_ba::FD_V]), P<double>(l[srk_ba::FD_SIGMA]), P<double>(l[srk_ba::FD_FUND]), P<double>(l[srk_ba::FD_INFO]),
+                         P<uint32_t>(l[srk_ba::FD_STATUS]), want_inl ? P<uint8_t>(l[srk_ba::FD_INL]) : nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->fd_ev[3], s));
+    for (auto& o : outs)
+        if (o.bytes) HIPCHK(h, hipMemcpyAsync(o.dst, l[o.buf].p, o.bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    float ms = 0, score_ms = 0, solve_ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->fd_ev[0], h->fd_ev[3]));
+    HIPCHK(h, hipEventElapsedTime(&score_ms, h->fd_ev[1], h->fd_ev[2]));
+    HIPCHK(h, hipEventElapsedTime(&solve_ms, h->fd_ev[4], h->fd_ev[1]));
+    h->fd_ms = ms;
+    h->fd_score_ms = score_ms;
+    h->fd_solve_ms = solve_ms;
+    return SRK_OK;
+}
+
+extern "C" double srk_ba_fundamental_kernel_ms(const srk_ba* h) { return h ? h->fd_ms : 0.0; }
+extern "C" double srk_ba_fundamental_score_ms(const srk_ba* h) { return h ? h->fd_score_ms : 0.0; }
+extern "C" double srk_ba_fundamental_solve_ms(const srk_ba* h) { return h ? h->fd_solve_ms : 0.0; }
+
+extern "C" int srk_relate_uncalibrated(srk_ba* h, double f0, int32_t n_pairs, const int64_t* row_ptr, const double* uv_a, const double* uv_b, const double* q,
+                                       const srk_fundamental_options* opts, double* F, double* U, double* V, double* sigma, double* fund, double* info,
+                                       uint32_t* status, uint8_t* inlier_out)
+{
+    if (!h) return SRK_E_ARGS;
+    try {
+        std::string why = srk_fund_check(n_pairs, row_ptr, uv_a, uv_b, q, opts);
+        if (why.empty() && (!std::isfinite(f0) || srk::is_close(0.0, f0))) why = "fundamental: f0 must be finite and not ~0";
+        if (why.empty() && n_pairs > 0 && (!F || !U || !V || !sigma || !fund || !info || !status)) why = "fundamental: a NULL output array";
+        if (!why.empty()) { h->last_error = why; return SRK_E_ARGS; }
+        if (n_pairs == 0) return SRK_OK;
+        HIPCHK(h, hipSetDevice(h->device));
+        return fund_run(h, f0, n_pairs, row_ptr, uv_a, uv_b, q, srk_fund_effective_options(opts), F, U, V, sigma, fund, info, status, inlier_out);
+    } catch (const std::bad_alloc&) {
+        h->last_error = "fundamental: out of host memory";
         return SRK_E_NOMEM;
     }
 }

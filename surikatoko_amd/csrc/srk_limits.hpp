@@ -63,3 +63,9 @@
 #define SRK_HOMOG_LANES_HOST 64
 #define SRK_HOMOG_MAX_WAVES_HOST (1 << 22)
 #define SRK_HOMOG_MAX_ROUNDS_HOST 16
+// two-view fundamental matrix (srk_relate_uncalibrated): a wave scores 64 hypotheses of one pair; a call holds
+// one record of 96 bytes per hypothesis and one slot per wave, so pairs x ceil(hypotheses / 64) is capped like relate's
+#define SRK_FUND_MAX_HYPOTHESES_HOST 4096
+#define SRK_FUND_LANES_HOST 64
+#define SRK_FUND_MAX_WAVES_HOST (1 << 22)
+#define SRK_FUND_MAX_ROUNDS_HOST 16
